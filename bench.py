@@ -1,16 +1,26 @@
 #!/usr/bin/env python
 """bench.py — VisRAG-Ret corpus embedding + retrieval on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps K --warmup W --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = one pass of the hot path over one batch of synthetic input already resident in
 HBM: 32 page images (448x448x3 uint8) -> vr_encode (SigLIP ViT + resampler + MiniCPM-2B
 decoder + wmean pool + L2 norm) -> 32 fp32 embeddings appended to the HBM-resident index.
 Workload at N=1 = BASELINE.json configs[1] (bf16 encode, batch 32 pages); pages are sharded
-across ranks with no data-path collective (weak scaling).  The same JSON line also carries
-the retrieval half of the metric (configs[2]/[3]): 1k queries top-10 over a 100k-row index
-sharded over the N ranks, local fused search + ONE RCCL all-gather of [nq,k] + device merge.
+across ranks with no data-path collective (weak scaling).
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value` =
+pages/s, `ms_per_step`).  `--dump-outputs DIR` also writes the last timed step's embeddings
+(rank 0: DIR/embeddings.npy, float32 [batch, 2304]); the inputs and weights are seeded, so
+two builds can be compared output for output.  `--full` adds everything else to the same
+line: per-kernel-class phases and the roofline (extra passes, a rocprofv3 --pmc child run),
+two batches in flight, the retrieval half of the metric (configs[2]/[3]: 1k queries top-10
+over a 100k-row index sharded over the N ranks, local fused search + ONE RCCL all-gather of
+[nq,k] + device merge), PIL / sliced pages, EVisRAG generation, the CPU baseline and the
+reference-parity legs.  `--corpus-pages`, `--search-steps`, `--pipelined`, `--cpu-pages` and the
+`--no-*` switches shape that `--full` run.
 
 Full model dims, random-init (deterministic synthetic) weights, synthetic pages: there is no
 network for checkpoints or datasets.
@@ -43,6 +53,11 @@ def main():
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's embeddings (rank 0) to DIR/embeddings.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure (phases, roofline, search, extras, CPU baseline, "
+                         "reference parity); off by default")
     ap.add_argument("--index-rows", type=int, default=100_000)
     ap.add_argument("--corpus-pages", type=int, default=100_000,
                     help="DISTINCT synthetic pages embedded by the model into the retrieval index, whole job (BASELINE configs[2]: "
@@ -52,7 +67,7 @@ def main():
     ap.add_argument("--search-steps", type=int, default=20)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--pipelined", action="store_true",
-                    help="measure encode with two batches in flight (vr_model_clone + two HIP streams) even with --no-extras; "
+                    help="--full: measure encode with two batches in flight (vr_model_clone + two HIP streams) even with --no-extras; "
                          "reported under \"pipelined\", never as `value`")
     ap.add_argument("--cpu-pages", type=int, default=16,
                     help="pages of the CPU baseline sample (one reference-sized batch of 16 by default; 64 = all of "
@@ -60,6 +75,8 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the PIL-input and sliced-page measurements")
     ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 --pmc measurement of the dominant kernel's HBM traffic")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -126,6 +143,43 @@ def main():
         step(i)
     barrier()
     dt = time.perf_counter() - t0
+
+    def max_over_ranks(x: float) -> float:
+        t = torch.tensor([x], dtype=torch.float64, device="cpu" if shared else dev)
+        if world > 1:
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        return float(t.item())
+
+    dt = max_over_ranks(dt)
+    pages_per_s = world * args.steps * B / dt
+    ms_per_step = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path receives from its last step: the batch's L2-normalised fp32 embeddings
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "embeddings.npy"), out.cpu().numpy().astype(np.float32))
+    f_page = cfg.flops_page(1024, len(items[0].input_ids))
+    result = {
+        "metric": "page-images embedded/sec (VisRAG-Ret encode, 448x448, bf16 MFMA) "
+                  "+ queries/sec@top-10 over 100k-page index",
+        "value": round(pages_per_s, 2), "unit": "pages/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+        "config": {"workload": "VisRAG-Ret (SigLIP-so400m 26 blk + resampler + MiniCPM-2B 40 layers) bf16 "
+                               f"encode batch={B} page images 448x448 per GPU; index {args.index_rows} rows x 2304 "
+                               f"sharded {world} way(s), {args.queries} queries top-{args.topk}",
+                   "batch_per_gpu": B, "global_batch": B * world, "tokens_per_page": len(items[0].input_ids),
+                   "flops_per_page": f_page, "parallelism": f"dp{world} (pages sharded, no data-path collective)"},
+        "model_tflops": round(pages_per_s * f_page / 1e12 / world, 1),
+        "model_frac_of_mfma_peak": round(pages_per_s * f_page / 1e12 / world / PEAK_BF16_TFLOPS, 4),
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything below is outside `value`
     # per-kernel-class HIP events (roofline, phases) in a SECOND pass of the same steps: outside `value`
     enc.set_profile(True)
     for i in range(args.steps):
@@ -141,15 +195,6 @@ def main():
     barrier()
     prof.update({k: v for k, v in enc.get_profile().items() if k.startswith("dec_")})
     enc.set_profile(False)
-    def max_over_ranks(x: float) -> float:
-        t = torch.tensor([x], dtype=torch.float64, device="cpu" if shared else dev)
-        if world > 1:
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        return float(t.item())
-
-    dt = max_over_ranks(dt)
-    pages_per_s = world * args.steps * B / dt
-    ms_per_step = dt / args.steps * 1e3
 
     # ---- optional: two batches in flight (own workspace + stream each, shared weights); outside `value`
     pipelined = None
@@ -474,20 +519,7 @@ def main():
     phases = {k: {"ms_per_step": round(v["ms"] / args.steps, 3),
                   "tflops": round(v["flops"] / max(v["ms"], 1e-9) / 1e9, 1)} for k, v in prof.items()}
     # (dec_* = the decoder phase split by events BETWEEN its kernels, taken in a pass of their own; "decoder" is the undisturbed total)
-    f_page = cfg.flops_page(1024, len(items[0].input_ids))
-    result = {
-        "metric": "page-images embedded/sec (VisRAG-Ret encode, 448x448, bf16 MFMA) "
-                  "+ queries/sec@top-10 over 100k-page index",
-        "value": round(pages_per_s, 2), "unit": "pages/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-        "config": {"workload": "VisRAG-Ret (SigLIP-so400m 26 blk + resampler + MiniCPM-2B 40 layers) bf16 "
-                               f"encode batch={B} page images 448x448 per GPU; index {args.index_rows} rows x 2304 "
-                               f"sharded {world} way(s), {args.queries} queries top-{args.topk}",
-                   "batch_per_gpu": B, "global_batch": B * world, "tokens_per_page": len(items[0].input_ids),
-                   "flops_per_page": f_page, "parallelism": f"dp{world} (pages sharded, no data-path collective)"},
-        "model_tflops": round(pages_per_s * f_page / 1e12 / world, 1),
-        "model_frac_of_mfma_peak": round(pages_per_s * f_page / 1e12 / world / PEAK_BF16_TFLOPS, 4),
+    result.update({
         "queries_per_sec": round(search_qps, 1),
         # the retrieval half on the index BASELINE configs[2] words: model-embedded pages, model-encoded queries
         # (index_kind "filler" only when the corpus embed was skipped with --corpus-pages 0)
@@ -504,7 +536,7 @@ def main():
         "phases": phases,
         "pipelined": pipelined,
         "box": box_id(),
-    }
+    })
 
     # ---- extras (outside `value`): what the reference's own entry point sees, and real-document pages
     if world == 1 and not args.no_extras:

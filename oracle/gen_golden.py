@@ -12,6 +12,8 @@ deterministic synthetic checkpoint (visrag_amd/synth.py) and stand-in tokenizer.
     python oracle/gen_golden.py --config1sep # the same chain over a corpus of 51 slide decks x 10 pages + the four
                                            # reference images, 1022 + 2 queries: the fixture whose top-10 cut falls BETWEEN
                                            # decks (strict id parity on hundreds of queries; ~25 min on 8 cores, resumable)
+    python oracle/gen_golden.py --evaldriver # what the reference's driver/eval.py leaves behind (eval_driver.npz)
+    python oracle/gen_golden.py --evalmrr  # the reference's eval_mrr on fixed random cases (eval_mrr.json)
 
 Runs only in the build container (the reference tree does not travel to the GPU box);
 the resulting fixtures are committed.
@@ -354,12 +356,49 @@ def eval_driver_fixture():
     ref_harness.install_shims()
     sys.modules["pytrec_eval"] = T.shim
     ref_eval = importlib.import_module("openmatch.driver.eval")
+    import io
+    from contextlib import redirect_stdout
     with tempfile.TemporaryDirectory() as d:
         qrels = T._write_case(d, GOLD)
-        trec, log, lines = T._run_driver(ref_eval, d, qrels, "cpu")
+        data_args = types.SimpleNamespace(from_hf_repo=False, qrels_path=qrels)
+        enc = types.SimpleNamespace(output_dir=d, process_index=0, world_size=1, retrieve_depth=10, trec_save_path=None, device="cpu")
+        buf = io.StringIO()
+        with redirect_stdout(buf):
+            ref_eval.retrieve(data_args, enc)
+        trec = open(os.path.join(d, "test.0.trec"), "rb").read()
+        log = open(os.path.join(d, "test_result.log"), "rb").read()
+        lines = [ln for ln in buf.getvalue().splitlines() if not ln.startswith("loading")]
         np.savez_compressed(os.path.join(GOLD, "eval_driver.npz"), trec=np.array(trec.decode()), log=np.array(log.decode()),
                             lines=np.array(lines), qrels=np.array(open(qrels).read()))
     print("eval_driver:", lines)
+
+
+def eval_mrr_fixture():
+    """The reference's `openmatch.utils.eval_mrr` on the cases tests/test_cpu_eval_dropin.py replays: the verdict's example,
+    40 seeded random qrels / runs at four cutoffs each, and an empty run (which raises: the result is the exception's
+    name).  Inputs and outputs are stored in order, as JSON (floats round-trip exactly), so that the test needs no
+    reference tree."""
+    import json
+    ref_harness.install_shims()
+    from openmatch.utils import eval_mrr as ref_mrr
+    cases = []
+    qrel = {"q1": {"d1": 1}, "q2": {"d9": 1}}
+    run = {"q1": {"d0": .9, "d1": .5}, "q3": {"d1": 1.0}}
+    cases.append({"qrel": qrel, "run": run, "results": [[10, ref_mrr(qrel, run, 10)]]})
+    rng = np.random.default_rng(3)
+    for trial in range(40):
+        docs = [f"d{j}" for j in range(30)]
+        qrel = {f"q{i}": {d: int(rng.integers(0, 3)) for d in rng.choice(docs, 6, replace=False)} for i in range(8)}
+        run = {f"q{i}": {d: float(np.float32(rng.standard_normal())) for d in rng.choice(docs, 15, replace=False)} for i in range(2, 11)}
+        cases.append({"qrel": qrel, "run": run, "results": [[cutoff, ref_mrr(qrel, run, cutoff)] for cutoff in (None, 1, 3, 10)]})
+    try:
+        ref_mrr({"q": {"d": 1}}, {}, 10)
+        raise AssertionError("the reference's eval_mrr accepted an empty run")
+    except ZeroDivisionError:
+        cases.append({"qrel": {"q": {"d": 1}}, "run": {}, "results": [[10, "ZeroDivisionError"]]})
+    with open(os.path.join(GOLD, "eval_mrr.json"), "w") as f:
+        json.dump(cases, f)
+    print("eval_mrr:", len(cases), "cases")
 
 
 def main():
@@ -369,6 +408,7 @@ def main():
     ap.add_argument("--config1xl", action="store_true")
     ap.add_argument("--config1sep", action="store_true")
     ap.add_argument("--evaldriver", action="store_true")
+    ap.add_argument("--evalmrr", action="store_true")
     a = ap.parse_args()
     os.makedirs(GOLD, exist_ok=True)
     torch.set_grad_enabled(False)
@@ -380,6 +420,8 @@ def main():
         return config1sep()
     if a.evaldriver:
         return eval_driver_fixture()
+    if a.evalmrr:
+        return eval_mrr_fixture()
 
     # ---- tiny dims: 4 single-slice pages (112x112), 2 sliced pages, 3 queries ----------
     cfg = tiny_config()

@@ -437,9 +437,11 @@ def test_corpus_sharded_retrieve_behind_the_kept_api_world2_gloo(tmp_path):
     from visrag_amd.utils import shard_name, write_shard
     rng = np.random.default_rng(7)
     dim = 16
-    C = rng.standard_normal((260, dim)).astype(np.float32)
+    # entries on a 2^-6 grid: every dot product is exact in fp32 whatever the host's summation order, so the duplicated rows
+    # below tie exactly in every shard layout
+    C = (np.round(rng.standard_normal((260, dim)) * 64) / 64).astype(np.float32)
     C[250] = C[20]; C[130] = C[20]                         # exact ties across files and ranks
-    Q = rng.standard_normal((9, dim)).astype(np.float32)
+    Q = (np.round(rng.standard_normal((9, dim)) * 64) / 64).astype(np.float32)
     out = tmp_path / "emb"; out.mkdir()
     docs = [f"doc{i}" for i in range(260)]
     write_shard(str(out / shard_name("corpus", 0, 0, 120)), C[:120], docs[:120])

@@ -9,5 +9,5 @@ VISRAG_TEST_CORPUS_PAGES=3200 timeout 1500 python -m pytest tests -q -m gpu > $O
 tail -3 $O/r06_gpu_tests.log
 bash tools/round_profiles.sh 06 > $O/round_profiles.log 2>&1
 tail -25 $O/round_profiles.log
-timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 4 --warmup 1 --corpus-pages 640 --no-extras --no-cpu-baseline > $O/r06_bench_n2_one_gpu.json 2> $O/n2.err
+timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 4 --warmup 1 --full --corpus-pages 640 --no-extras --no-cpu-baseline > $O/r06_bench_n2_one_gpu.json 2> $O/n2.err
 tail -c 1500 $O/r06_bench_n2_one_gpu.json

@@ -5,10 +5,10 @@
 #   bash tools/round_profiles.sh 03        then copy gpurun_out/round/* to profiles/
 N=${1:-03}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/round; mkdir -p $O
-cd $R && timeout 1500 python bench.py --steps 20 --warmup 5 > $O/r${N}_bench_n1.json 2> $O/bench.err     # the driver's command line (100k-page corpus embed included)
+cd $R && timeout 1500 python bench.py --steps 20 --warmup 5 --full > $O/r${N}_bench_n1.json 2> $O/bench.err     # the driver's command line (100k-page corpus embed included)
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/rp1 /tmp/rp2 /tmp/rp3 /tmp/rp4
-rocprofv3 --kernel-trace --stats -d /tmp/rp1 -o b -- python $R/bench.py --no-cpu-baseline --no-extras --corpus-pages 3200 > /tmp/rp1.log 2>&1   # (the full corpus embed is 1.5 M launches of the same kernels: 3 200 pages here)
+rocprofv3 --kernel-trace --stats -d /tmp/rp1 -o b -- python $R/bench.py --full --no-cpu-baseline --no-extras --corpus-pages 3200 > /tmp/rp1.log 2>&1   # (the full corpus embed is 1.5 M launches of the same kernels: 3 200 pages here)
 python $R/tools/prof_summary.py $(find /tmp/rp1 -name '*.db' | head -1) $O/r${N}_bench_kernel_trace.txt
 rocprofv3 --kernel-trace --stats -d /tmp/rp2 -o e -- python $R/tools/encode_only.py 4 > /tmp/rp2.log 2>&1
 python $R/tools/prof_summary.py $(find /tmp/rp2 -name '*.db' | head -1) $O/r${N}_encode_only_kernel_trace.txt

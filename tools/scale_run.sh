@@ -2,7 +2,7 @@
 # The 1 / 2 / 4 / 8-GPU scaling curve of BASELINE.json configs[3], unattended, on one node:
 #   bash tools/scale_run.sh [OUTDIR] [STEPS] [WARMUP]
 # For every N that the node has GPUs for it runs bench.py exactly as the driver does —
-#   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+#   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N --full
 # (one process per GPU, backend "nccl" = RCCL over xGMI; pages sharded over the ranks with no data-path
 # collective, index rows sharded, ONE all-gather of the packed [nq, k] keys per search) — and prints, per N, what
 # RCCL saw (backend, world size), `value` (pages/s, whole job), queries_per_sec and the all-gather's own time.
@@ -23,10 +23,10 @@ for N in 1 2 4 8; do
   if [ "$N" -gt "$NGPU" ]; then echo "N=$N: skipped ($NGPU GPU(s) here)"; continue; fi
   PORT=$((29500 + N))
   if [ "$N" -eq 1 ]; then
-    timeout 1800 python bench.py --gpus 1 --steps "$STEPS" --warmup "$WARMUP" --no-extras > "$OUT/bench_n$N.json" 2> "$OUT/bench_n$N.err"
+    timeout 1800 python bench.py --gpus 1 --steps "$STEPS" --warmup "$WARMUP" --full --no-extras > "$OUT/bench_n$N.json" 2> "$OUT/bench_n$N.err"
   else
     timeout 1800 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port "$PORT" \
-      bench.py --gpus "$N" --steps "$STEPS" --warmup "$WARMUP" --no-extras --no-cpu-baseline > "$OUT/bench_n$N.json" 2> "$OUT/bench_n$N.err"
+      bench.py --gpus "$N" --steps "$STEPS" --warmup "$WARMUP" --full --no-extras --no-cpu-baseline > "$OUT/bench_n$N.json" 2> "$OUT/bench_n$N.err"
   fi
   python - "$OUT/bench_n$N.json" "$N" <<'PY'
 import json, sys
