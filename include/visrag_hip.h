@@ -181,6 +181,58 @@ int vr_model_set_profile(vr_model_t m, int32_t enable);
 int vr_model_get_profile(vr_model_t m, int32_t cls, double* total_ms, int64_t* launches,
                          double* total_flops);
 
+/* ---- chat: MiniCPM-V 2.0 answer generation on the model's weights ------------------- */
+/* Reference: MiniCPMV.generate / chat (src/openmatch/modeling/modeling_minicpmv/modeling_minicpmv.py:218-237, 276-400) over
+ * MiniCPMForCausalLM (modeling_minicpm.py:1411-1412: logits = lm_head(h / (hidden_size / dim_model_base))), driven by HF
+ * generate; visrag_amd/generation.py holds the decoding loop.  A chat handle shares the weights of a finalised model (like
+ * vr_model_clone: the model must outlive it) and owns its KV cache and workspace; the model's own vr_encode is unaffected.
+ * Cache: a prompt SLOT keeps the rope'd K / V of one prompt, a ROW keeps the K / V of the tokens it generated (its tail)
+ * and its seen-id set; the beams of a prompt are rows that share the slot.  Device memory: the caches, layers x 2 x
+ * (max_slots x max_len + max_rows x max_new) x hidden_size bf16, the logits (2 max_rows x vocab f32), and a second
+ * encode workspace for the prefill (a vr_model_clone of the model, sized by the model's vr_config_t). */
+typedef struct vr_chat_s* vr_chat_t;
+typedef struct vr_chat_config {
+    int32_t max_len;        /* positions of a sequence: prompt + generated tokens (a prompt has at most max_len - 1) */
+    int32_t max_rows;       /* rows of one step (prompts x beams), 1..16 */
+    float   dim_model_base; /* 256 for MiniCPM-V 2.0 (config.json) */
+    int32_t max_slots;      /* prompts held at once, 1..max_rows (one per prompt of a step: max_rows / num_beams) */
+    int32_t max_new;        /* generated tokens a row can hold, 1..max_len - 1 (max_new_tokens) */
+} vr_chat_config_t;
+#define VR_CHAT_GREEDY 0    /* repetition penalty on the raw logits, then argmax (ties: lowest id) */
+#define VR_CHAT_BEAM 1      /* log_softmax, penalty, + beam score; top-k over the group's rows x vocab */
+#define VR_CHAT_SAMPLE 2    /* penalty, / temperature, top_k filter, softmax, one draw from counter noise */
+int vr_chat_create(vr_model_t m, const vr_chat_config_t* cfg, vr_chat_t* out);
+int vr_chat_destroy(vr_chat_t ch);
+/* llm.lm_head.weight [vocab_size][hidden_size] (tied embeddings: pass llm.model.embed_tokens.weight); dtype / on_device as
+ * in vr_model_load_weight.  Stored as padded bf16 for the decode step's weight streamer. */
+int vr_chat_load_head(vr_chat_t ch, const void* data, const int64_t* shape, int32_t ndim, int32_t dtype, int32_t on_device);
+/* Run ONE prompt (the arguments of vr_encode for a single item: T tokens) through tower, resampler and decoder on the bf16
+ * route, keep every layer's K / V in `slot`, and leave the last token's logits on row `row`, which becomes the slot's first
+ * row with an empty tail and an empty seen set (generation starts from inputs_embeds: only generated ids are penalised).
+ * Rows that continued the slot before lose their tails.  T >= max_len: VR_ERR_CAPACITY. */
+int vr_chat_prefill(vr_chat_t ch, int32_t slot, int32_t row, const uint8_t* const* slices, const int32_t* slice_hw,
+                    int32_t n_slices, int32_t slices_on_device, const int32_t* input_ids, int32_t T,
+                    const int32_t* vision_rows, void* stream);
+/* Append tokens[i] to row rows[i] of prompt slot slots[i] (the rows of one slot adjacent) and compute each row's logits:
+ * one pass over the weights for all n rows.  The token joins the row's seen set.  A row with an empty tail may start on any
+ * slot.  n > max_rows, or a row past max_len or max_new: VR_ERR_CAPACITY, nothing changed. */
+int vr_chat_step(vr_chat_t ch, int32_t n, const int32_t* slots, const int32_t* rows, const int32_t* tokens, void* stream);
+/* Next-token candidates from the current logits of rows[] grouped by group_offsets [n_groups + 1] (beam search: one group
+ * per prompt; greedy / sampling: one row per group).  Host outputs [n_groups][k]: score, token, parent (row index within the
+ * group), best first; missing candidates are (-inf, -1, -1).
+ *   VR_CHAT_GREEDY: score = penalised logit;  VR_CHAT_BEAM: score = penalised log-prob + beam_scores[i];
+ *   VR_CHAT_SAMPLE: k = 1, top_k candidates (1..64), temperature > 0, noise selected by (seed, step, token). */
+int vr_chat_select(vr_chat_t ch, int32_t mode, int32_t n_groups, const int32_t* group_offsets, const int32_t* rows,
+                   const float* beam_scores, int32_t k, float repetition_penalty, float temperature, int32_t top_k,
+                   uint64_t seed, int32_t step, float* out_scores, int32_t* out_tokens, int32_t* out_parents, void* stream);
+/* Row rows[i] becomes a copy of row parents[i] (slot, tail, seen set), all read before any is written; the prompt's K / V
+ * are never copied. */
+int vr_chat_reorder(vr_chat_t ch, int32_t n, const int32_t* rows, const int32_t* parents, void* stream);
+/* The current logits of `row` (f32 [vocab_size]) to the host — tests. */
+int vr_chat_logits(vr_chat_t ch, int32_t row, float* out, void* stream);
+/* The prompt slot of `row` (-1: none) and the number of tokens in its tail. */
+int vr_chat_row_len(vr_chat_t ch, int32_t row, int32_t* slot, int32_t* generated);
+
 /* ---- index: replaces torch.matmul + torch.topk over pickle shards -------------------- */
 /* Reference: _retrieve_one_shard / distributed_parallel_retrieve
  * (src/openmatch/retriever/dense_retriever.py:13-97); demo answer.py:26-35. */

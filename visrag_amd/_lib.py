@@ -28,6 +28,11 @@ class VRConfig(C.Structure):
     ]
 
 
+class VRChatConfig(C.Structure):   # vr_chat_config_t (include/visrag_hip.h)
+    _fields_ = [("max_len", C.c_int32), ("max_rows", C.c_int32), ("dim_model_base", C.c_float), ("max_slots", C.c_int32),
+                ("max_new", C.c_int32)]
+
+
 class VGConfig(C.Structure):       # vg_config_t (include/visrag_gen.h)
     _fields_ = [
         ("hidden_size", C.c_int32), ("num_layers", C.c_int32), ("num_heads", C.c_int32), ("num_kv_heads", C.c_int32),
@@ -94,6 +99,17 @@ SIGNATURES = {
     "vr_op_norm": (C.c_int, [C.c_int, _i32, _vp, _i32, _i32, _vp, _vp, _f32, _vp, _i32, _vp]),
     "vr_op_attention": (C.c_int, [C.c_int, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32,
                                   _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
+    "vr_chat_create": (C.c_int, [_vp, C.POINTER(VRChatConfig), C.POINTER(_vp)]),
+    "vr_chat_destroy": (C.c_int, [_vp]),
+    "vr_chat_load_head": (C.c_int, [_vp, _vp, C.POINTER(_i64), _i32, _i32, _i32]),
+    "vr_chat_prefill": (C.c_int, [_vp, _i32, _i32, C.POINTER(_vp), C.POINTER(_i32), _i32, _i32, C.POINTER(_i32), _i32,
+                                  C.POINTER(_i32), _vp]),
+    "vr_chat_step": (C.c_int, [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp]),
+    "vr_chat_select": (C.c_int, [_vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_f32), _i32, _f32, _f32, _i32,
+                                 C.c_uint64, _i32, C.POINTER(_f32), C.POINTER(_i32), C.POINTER(_i32), _vp]),
+    "vr_chat_reorder": (C.c_int, [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32), _vp]),
+    "vr_chat_logits": (C.c_int, [_vp, _i32, _vp, _vp]),
+    "vr_chat_row_len": (C.c_int, [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
 }
 # every symbol include/visrag_gen.h declares (the EVisRAG generator's language model)
 GEN_SIGNATURES = {

@@ -41,6 +41,18 @@ static inline int fail(int code, const char* fmt, ...) {
         if (r_ != VR_OK) return r_; \
     } while (0)
 
+// split-K factor of a weight-streaming GEMM (gemm_skinny.hip) for n output columns and k inputs: the most workgroups that
+// still fit one round of 256 CUs, with at least 4 K-steps each and no empty split (at most max_split)
+static inline int skinny_ksplit(int n, int k, int max_split) {
+    const int tiles = (n + 255) / 256, nk = k / 64;
+    int best = 1;
+    for (int d = 2; d <= max_split && tiles * d <= 256; ++d) {
+        const int per = (nk + d - 1) / d;
+        if (per >= 4 && (d - 1) * per < nk) best = d;
+    }
+    return best;
+}
+
 static inline int pad128(int x) { return (x + 127) / 128 * 128; }
 static inline int64_t pad128l(int64_t x) { return (x + 127) / 128 * 128; }
 static inline int pad256(int x) { return (x + 255) / 256 * 256; }

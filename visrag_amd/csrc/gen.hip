@@ -39,16 +39,7 @@ static void drop_graph(vg_model_s* m) {
 #define VR_KS_GU 0
 #define VR_KS_DOWN 0
 #endif
-static int choose_ksplit(int n, int k, int forced = 0) {
-    if (forced > 0) return forced;
-    const int tiles = (n + 255) / 256, nk = k / 64;
-    int best = 1;
-    for (int d = 2; d <= GEN_KS_MAX && tiles * d <= 256; ++d) {
-        const int per = (nk + d - 1) / d;
-        if (per >= 4 && (d - 1) * per < nk) best = d;
-    }
-    return best;
-}
+static int choose_ksplit(int n, int k, int forced = 0) { return forced > 0 ? forced : skinny_ksplit(n, k, GEN_KS_MAX); }
 
 // The persistent layer kernel of the decode step (gen_persist.hip): decide whether this model / device takes it and build
 // its layer table for the CURRENT slot (the caches are per slot).  It is OPT-IN — VR_DECODE_PERSIST=1 in the environment

@@ -97,6 +97,43 @@ struct AttnArgs {
 };
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
 
+// ---- MiniCPM-V 2.0 answer generation (chat_kernels.hip; host side vr_chat_* in engine.hip) ------
+constexpr int CHAT_MAX_ROWS = 16;   // rows (prompts x beams) of one decode step
+constexpr int CHAT_ATT_SPLITS = 8;  // most prompt-key ranges of one (prompt, head) in the decode attention
+constexpr int CHAT_KEYS = 256;      // keys per chunk of the decode attention (one per thread)
+constexpr int CHAT_SEL_WGS = 64;    // workgroups of the candidate pass per group
+constexpr int CHAT_TOPK_MAX = 64;   // most candidates per group
+enum ChatSelMode { CHAT_SEL_GREEDY = 0, CHAT_SEL_BEAM = 1, CHAT_SEL_SAMPLE = 2 };
+// one decode step, passed by value: step row i appends `token[i]` to tail row `row[i]` (at tail index tail[i], position
+// pos[i]); rows [g_lo[g], g_lo[g + 1]) share prompt slot slot[g_lo[g]] of plen[g] tokens
+struct ChatStep {
+    int n, groups;
+    int row[CHAT_MAX_ROWS], slot[CHAT_MAX_ROWS], tail[CHAT_MAX_ROWS], pos[CHAT_MAX_ROWS], token[CHAT_MAX_ROWS];
+    int g_lo[CHAT_MAX_ROWS + 1], plen[CHAT_MAX_ROWS];
+    int gsplit[CHAT_MAX_ROWS], rsplit[CHAT_MAX_ROWS];   // prompt-key ranges of the attention per group / per row (its group's)
+};
+// cache geometry: prompt planes [slots][len][E], tail planes [rows][tail][E] per (layer, K|V)
+struct ChatCaps { int slots, len, rows, tail; };
+// beam reordering: row dst[i] receives the first len[i] tail rows and the seen set of row src[i]
+struct ChatMove { int n; int src[CHAT_MAX_ROWS], dst[CHAT_MAX_ROWS], len[CHAT_MAX_ROWS]; };
+// selection: selected row i reads logits row lrow[i] and seen set srow[i]; rows [g_lo[g], g_lo[g + 1]) form group g
+struct ChatSel {
+    int n, groups;
+    int lrow[CHAT_MAX_ROWS], srow[CHAT_MAX_ROWS], g_lo[CHAT_MAX_ROWS + 1];
+    float bscore[CHAT_MAX_ROWS];
+};
+hipError_t launch_chat_embed(const ChatStep& st, const void* table, int E, float scale, float* h, unsigned* seen, int words, hipStream_t s);
+hipError_t launch_chat_qkv(const ChatStep& st, const float* parts, int n_parts, size_t plane, int ldp, const float* rope, int E, int heads,
+                           void* q_out, void* tails, int l, int max_rows, int max_new, hipStream_t s);
+hipError_t launch_chat_attn(const ChatStep& st, const void* q, const void* prompt, const void* tails, int l, int E, int heads,
+                            const ChatCaps& cap, int S_max, float* po, float* pml, void* att, hipStream_t s);
+hipError_t launch_chat_prompt_kv(const void* qkv, int ld, int T, int E, void* kdst, void* vdst, hipStream_t s);
+hipError_t launch_chat_move(const ChatMove& mv, void* tails, void* scratch, int layers, int max_rows, int max_new, int E, int max_tail,
+                            unsigned* seen, unsigned* seen_scratch, int words, hipStream_t s);
+hipError_t launch_chat_select(const ChatSel& sel, int mode, const float* logits, int ld, int V, const unsigned* seen, int words, float pen,
+                              float temperature, int K, int kout, unsigned long long seed, unsigned step, float* lse,
+                              unsigned long long* part, float* o_score, int* o_tok, int* o_par, hipStream_t s);
+
 // ---- EVisRAG generator (gen_kernels.hip) ---------------------------------------------------
 constexpr int GEN_ATT_SPLITS = 16;  // most KV ranges one decode step's attention is cut into
 // What a decode step needs beyond the caches, resident on the device so that consecutive steps need no host round trip

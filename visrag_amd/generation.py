@@ -1,0 +1,366 @@
+"""MiniCPM-V 2.0 answer generation (the generator VisRAG pairs with its retriever) on the VisRAG-Ret weights.
+
+Mirrors the reference's `MiniCPMV.generate` / `chat` (src/openmatch/modeling/modeling_minicpmv/modeling_minicpmv.py:218-237,
+276-400) and the HF generate rules they rely on (the reference pins transformers==4.40.2):
+
+* beam search (`chat(sampling=False)`: num_beams=3, repetition_penalty=1.2): per row log_softmax, then the repetition
+  penalty (negative scores * penalty, positive / penalty) on that beam's GENERATED ids, plus the beam score; the top
+  2 * num_beams of num_beams x vocab per prompt.  An eos among the first num_beams candidates closes a hypothesis with score
+  sum_logprobs / generated_len ** length_penalty, where generated_len counts the eos (4.40.2 `process` adds with
+  cur_len = generated tokens + 1; 5.x `_update_finished_beams` divides by cur_len + 1 - prompt_len: the same).  length_penalty
+  1.0, early_stopping=False: an item is done when it holds num_beams hypotheses and worst_score >= best candidate score /
+  cur_len.  After max_new_tokens the running beams join the hypotheses (length = max_new_tokens); the best hypothesis wins
+  (ties: the one added last, like `sorted(...).pop()`), followed by one eos when shorter than max_new_tokens.  The 5.x
+  `n_tokens_to_keep` / `beams_to_keep` cut is the same 2 * num_beams with one eos id.  Initial beam scores are 0 for beam 0
+  and -1e9 for the others: the first step's candidates all come from beam 0, so it is run on that one row.
+* greedy (num_beams=1, do_sample=False): penalty on the raw logits, argmax (lowest id on ties), stop after eos.
+* sampling (`chat(sampling=True)`: temperature 0.7, repetition_penalty 1.02): penalty, / temperature, top_k 50 (HF's
+  default), softmax, one draw — here from counter-based noise selected by (seed, step), so a seed reproduces a run; the
+  reference draws from torch's global generator.
+* Generation starts from `inputs_embeds` (modeling_minicpmv.py:218-226), so HF starts `input_ids` EMPTY: the repetition
+  penalty only ever sees generated tokens, never the prompt.
+
+Batches: every item is generated independently — an item's output is a function of the item alone.  The reference
+right-pads a batch (`_process_list(padding_side="right")`) and a shorter item then continues after pad rows of the longer
+ones; that behaviour is NOT reproduced (parity is defined per item).
+
+The decoding rules are generators of `select` / `advance` requests: `run_rule` drives one against any backend (the tests
+replay recorded log-probs), `generate_items` serves the requests of all items of a batch in one device call per phase.
+Options HF would accept but this generator does not implement (top_p, length_penalty, beam sampling, ...) raise
+NotImplementedError instead of being dropped.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import json
+import os
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+
+EOS_ID, PAD_ID, BOS_ID = 2, 0, 1
+GREEDY, BEAM, SAMPLE = 0, 1, 2
+
+
+# ------------------------------------------------------------------------------------------ config ---
+@dataclass
+class GenerationConfig:
+    """The MiniCPM-V 2.0 checkpoint fields the generator needs beyond VisRAGRetConfig (config.json)."""
+    dim_model_base: float = 256.0
+    tie_word_embeddings: bool = False
+    eos_token_id: int = EOS_ID
+    pad_token_id: int = PAD_ID
+
+
+def generation_config_from_checkpoint(path: str) -> GenerationConfig:
+    with open(os.path.join(path, "config.json")) as f:
+        j = json.load(f)
+    g = GenerationConfig()
+    g.dim_model_base = float(j.get("dim_model_base", g.dim_model_base))
+    g.tie_word_embeddings = bool(j.get("tie_word_embeddings", g.tie_word_embeddings))
+    return g
+
+
+def chat_generation_config(sampling: bool, kwargs: Dict) -> Dict:
+    """modeling_minicpmv.py:369-383: the defaults of the mode, and only THEIR keys overridden from kwargs."""
+    if sampling:
+        cfg = {"temperature": 0.7, "do_sample": True, "repetition_penalty": 1.02}
+    else:
+        cfg = {"num_beams": 3, "repetition_penalty": 1.2}
+    cfg.update((k, kwargs[k]) for k in cfg.keys() & kwargs.keys())
+    return cfg
+
+
+def decode_text(result_ids: Sequence[Sequence[int]], tokenizer) -> List[str]:
+    """modeling_minicpmv.py:228-237: drop 0s, a leading bos and a trailing eos, decode, strip."""
+    out = []
+    for result in result_ids:
+        r = [int(t) for t in result if int(t) != 0]
+        if r and r[0] == tokenizer.bos_id:
+            r = r[1:]
+        if r and r[-1] == tokenizer.eos_id:
+            r = r[:-1]
+        out.append(tokenizer.decode(r).strip())
+    return out
+
+
+# ------------------------------------------------------------------------------------- decode rules ---
+class _Hyps:
+    """BeamHypotheses of HF 4.40.2 (length_penalty, early_stopping=False)."""
+
+    def __init__(self, num_beams: int, length_penalty: float = 1.0):
+        self.n, self.lp = num_beams, length_penalty
+        self.beams: List[Tuple[float, List[int]]] = []
+        self.worst = 1e9
+
+    def add(self, tokens: List[int], sum_logprobs: float, generated_len: int) -> None:
+        score = sum_logprobs / (generated_len ** self.lp)
+        if len(self.beams) < self.n or score > self.worst:
+            self.beams.append((score, list(tokens)))
+            if len(self.beams) > self.n:
+                order = sorted((s, i) for i, (s, _) in enumerate(self.beams))
+                del self.beams[order[0][1]]
+                self.worst = order[1][0]
+            else:
+                self.worst = min(score, self.worst)
+
+    def is_done(self, best_sum_logprobs: float, cur_len: int) -> bool:
+        if len(self.beams) < self.n:
+            return False
+        return self.worst >= best_sum_logprobs / (cur_len ** self.lp)
+
+    def best(self) -> Tuple[float, List[int]]:
+        return sorted(self.beams, key=lambda x: x[0]).pop()
+
+
+def beam_rule(num_beams: int, max_new_tokens: int, eos: int = EOS_ID, length_penalty: float = 1.0):
+    """One item's beam search as a generator of requests: yields ("select", n_rows, beam_scores, k) and receives the
+    candidates [(score, token, parent)] best first over the first n_rows beams; yields ("advance", parents, tokens) (beam i
+    continues beam parents[i] with tokens[i]) and receives None.  Returns {"tokens": output ids (one eos appended when
+    shorter than max_new_tokens), "score": the best hypothesis score, "steps": [(candidates, next beams)] per step}."""
+    hyps = _Hyps(num_beams, length_penalty)
+    seqs: List[List[int]] = [[]]
+    scores = [0.0]
+    done = False
+    steps = []
+    for step in range(max_new_tokens):
+        cand = yield ("select", len(seqs), list(scores), 2 * num_beams)
+        cur_len = step + 1
+        nxt = []
+        for rank, (s, tok, par) in enumerate(cand):
+            if tok == eos:
+                if rank >= num_beams:
+                    continue
+                hyps.add(seqs[par], s, cur_len)
+            else:
+                nxt.append((s, tok, par))
+            if len(nxt) == num_beams:
+                break
+        steps.append((list(cand), list(nxt)))
+        done = hyps.is_done(cand[0][0], cur_len)
+        if done:
+            break
+        seqs = [seqs[p] + [t] for _, t, p in nxt]
+        scores = [s for s, _, _ in nxt]
+        if step + 1 == max_new_tokens:
+            break
+        yield ("advance", [p for _, _, p in nxt], [t for _, t, _ in nxt])
+    if not done:
+        for s, q in zip(scores, seqs):
+            hyps.add(q, s, len(q))
+    score, best = hyps.best()
+    tokens = best + ([eos] if len(best) < max_new_tokens else [])
+    return {"tokens": tokens, "score": score, "steps": steps}
+
+
+def greedy_rule(max_new_tokens: int, eos: int = EOS_ID):
+    """One item, greedy search or sampling (the draw is the device's select with k = 1): the request protocol of beam_rule."""
+    tokens, steps = [], []
+    for step in range(max_new_tokens):
+        s, tok, _ = (yield ("select", 1, [0.0], 1))[0]
+        tokens.append(tok)
+        steps.append(s)
+        if tok == eos or step + 1 == max_new_tokens:
+            break
+        yield ("advance", [0], [tok])
+    return {"tokens": tokens, "scores": steps}
+
+
+def run_rule(rule, backend) -> Dict:
+    """Drive one rule against a backend with select(n_rows, beam_scores, k) and advance(parents, tokens)."""
+    try:
+        req = next(rule)
+        while True:
+            if req[0] == "select":
+                req = rule.send(backend.select(req[1], req[2], req[3]))
+            else:
+                backend.advance(req[1], req[2])
+                req = rule.send(None)
+    except StopIteration as stop:
+        return stop.value
+
+
+def beam_search(backend, num_beams: int, max_new_tokens: int, eos: int = EOS_ID, length_penalty: float = 1.0) -> Dict:
+    return run_rule(beam_rule(num_beams, max_new_tokens, eos, length_penalty), backend)
+
+
+def greedy_search(backend, max_new_tokens: int, eos: int = EOS_ID) -> Dict:
+    return run_rule(greedy_rule(max_new_tokens, eos), backend)
+
+
+# ------------------------------------------------------------------------------------------ device ---
+class HipChat:
+    """Owner of a vr_chat_t: prompt slots, beam rows, KV cache and the logits processing on the device."""
+
+    def __init__(self, encoder, max_len: int, max_rows: int = 3, dim_model_base: float = 256.0, max_slots: Optional[int] = None,
+                 max_new: Optional[int] = None):
+        """max_len: positions of a sequence (prompt + generated); max_rows: rows of a step (prompts x beams); max_slots:
+        prompts held at once (default max_rows); max_new: generated tokens a row holds (default max_len - 1)."""
+        self.lib, self.enc = _lib.load(), encoder
+        self.device = encoder.device
+        self.max_len, self.max_rows = int(max_len), int(max_rows)
+        self.max_slots = int(max_slots) if max_slots else self.max_rows
+        self.max_new = int(max_new) if max_new else self.max_len - 1
+        self.V = encoder.cfg.vocab_size
+        c = _lib.VRChatConfig(max_len=self.max_len, max_rows=self.max_rows, dim_model_base=float(dim_model_base),
+                              max_slots=self.max_slots, max_new=self.max_new)
+        self._h = C.c_void_p()
+        _lib.check(self.lib.vr_chat_create(encoder._h, C.byref(c), C.byref(self._h)), "vr_chat_create")
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self.lib.vr_chat_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        return C.c_void_p(int(torch.cuda.current_stream(self.device).cuda_stream))
+
+    def load_head(self, t: torch.Tensor) -> None:
+        dt = _lib.VR_DTYPE_BF16 if t.dtype == torch.bfloat16 else _lib.VR_DTYPE_F32
+        t = (t if dt == _lib.VR_DTYPE_BF16 else t.to(torch.float32)).contiguous()
+        shape = (C.c_int64 * 2)(*t.shape)
+        _lib.check(self.lib.vr_chat_load_head(self._h, C.c_void_p(t.data_ptr()), shape, 2, dt, 1 if t.is_cuda else 0), "vr_chat_load_head")
+
+    def prefill(self, slot: int, row: int, item) -> None:
+        """One PreparedItem (token ids, image bounds, u8 slices) into prompt `slot`; its logits land on `row`."""
+        Q = self.enc.cfg.query_num
+        ids = np.ascontiguousarray(np.asarray(item.input_ids, dtype=np.int32))
+        n = len(item.slices)
+        keep = [np.ascontiguousarray(s, dtype=np.uint8) for s in item.slices]
+        if n:
+            ptrs = (C.c_void_p * n)(*[C.c_void_p(a.ctypes.data) for a in keep])
+            hw = (C.c_int32 * (2 * n))(*[v for a in keep for v in (a.shape[0], a.shape[1])])
+            rows = np.full((n, Q), -1, dtype=np.int32)
+            for k, (b0, b1) in enumerate(item.image_bound[:n]):
+                m = max(0, min(Q, b1 - b0))
+                rows[k, :m] = b0 + np.arange(m, dtype=np.int32)
+            rows = np.ascontiguousarray(rows.reshape(-1))
+            rp = rows.ctypes.data_as(C.POINTER(C.c_int32))
+        else:
+            ptrs, hw, rp = None, None, None
+        _lib.check(self.lib.vr_chat_prefill(self._h, int(slot), int(row), ptrs, hw, n, 0, ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            len(ids), rp, self._stream()), "vr_chat_prefill")
+
+    def step(self, slots: Sequence[int], rows: Sequence[int], tokens: Sequence[int]) -> None:
+        n = len(rows)
+        a = lambda v: (C.c_int32 * n)(*[int(x) for x in v])
+        _lib.check(self.lib.vr_chat_step(self._h, n, a(slots), a(rows), a(tokens), self._stream()), "vr_chat_step")
+
+    def select(self, mode: int, groups: Sequence[Sequence[int]], k: int, beam_scores: Optional[Sequence[float]] = None,
+               repetition_penalty: float = 1.0, temperature: float = 1.0, top_k: int = 50, seed: int = 0, step: int = 0):
+        """-> (scores, tokens, parents), each [len(groups)][k] numpy."""
+        rows = [int(r) for g in groups for r in g]
+        off = np.cumsum([0] + [len(g) for g in groups]).astype(np.int32)
+        G, n = len(groups), len(rows)
+        bs = (C.c_float * n)(*([float(x) for x in beam_scores] if beam_scores is not None else [0.0] * n))
+        sc = np.zeros((G, k), dtype=np.float32)
+        tk = np.zeros((G, k), dtype=np.int32)
+        pa = np.zeros((G, k), dtype=np.int32)
+        p32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_int32))
+        _lib.check(self.lib.vr_chat_select(self._h, int(mode), G, p32(off), (C.c_int32 * n)(*rows), bs, int(k), float(repetition_penalty),
+                                           float(temperature), int(top_k), C.c_uint64(int(seed) & (2 ** 64 - 1)), int(step),
+                                           sc.ctypes.data_as(C.POINTER(C.c_float)), p32(tk), p32(pa), self._stream()), "vr_chat_select")
+        return sc, tk, pa
+
+    def reorder(self, rows: Sequence[int], parents: Sequence[int]) -> None:
+        n = len(rows)
+        a = lambda v: (C.c_int32 * n)(*[int(x) for x in v])
+        _lib.check(self.lib.vr_chat_reorder(self._h, n, a(rows), a(parents), self._stream()), "vr_chat_reorder")
+
+    def logits(self, row: int) -> np.ndarray:
+        out = np.empty(self.V, dtype=np.float32)
+        _lib.check(self.lib.vr_chat_logits(self._h, int(row), C.c_void_p(out.ctypes.data), self._stream()), "vr_chat_logits")
+        return out
+
+    def row_state(self, row: int) -> Tuple[int, int]:
+        s, g = C.c_int32(), C.c_int32()
+        _lib.check(self.lib.vr_chat_row_len(self._h, int(row), C.byref(s), C.byref(g)), "vr_chat_row_len")
+        return int(s.value), int(g.value)
+
+
+# what HF generate would accept but this generator does not implement: refused rather than silently dropped
+_NEUTRAL = {"top_p": 1.0, "length_penalty": 1.0, "min_new_tokens": 0, "no_repeat_ngram_size": 0, "num_return_sequences": 1,
+            "early_stopping": False, "typical_p": 1.0, "num_beam_groups": 1, "diversity_penalty": 0.0}
+
+
+def generate_items(chat: HipChat, items: Sequence, max_new_tokens: int = 20, num_beams: int = 1, do_sample: bool = False,
+                   repetition_penalty: float = 1.0, temperature: float = 1.0, top_k: int = 50, seed: int = 0,
+                   eos: int = EOS_ID, details: bool = False, **kwargs) -> List:
+    """Generate every PreparedItem independently, the items of a batch in lockstep (one decode step streams the weights once
+    for all their rows).  Returns the output ids per item (HF's sequences without the empty prompt part), or with
+    details=True the rule's result per item (tokens, score, per-step candidates)."""
+    for k, v in kwargs.items():
+        if k not in _NEUTRAL or v != _NEUTRAL[k]:
+            raise NotImplementedError(f"generation option {k}={v!r} is not supported")
+    nb = int(num_beams)
+    if nb < 1:
+        raise ValueError("num_beams must be positive")
+    if do_sample and nb > 1:
+        raise NotImplementedError("beam sampling (do_sample=True with num_beams > 1) is not supported")
+    if do_sample and not (1 <= int(top_k) <= 64):
+        raise NotImplementedError(f"top_k={top_k}: sampling supports a top-k filter of 1..64 candidates")
+    if do_sample and not temperature > 0:
+        raise ValueError("temperature must be positive when sampling")
+    if nb > chat.max_rows:
+        raise ValueError(f"num_beams={nb} exceeds the chat handle's max_rows={chat.max_rows}")
+    if max_new_tokens > chat.max_new:
+        raise ValueError(f"max_new_tokens={max_new_tokens} exceeds the chat handle's max_new={chat.max_new}")
+    per = max(1, min(chat.max_rows // nb, chat.max_slots))
+    out: List[List[int]] = []
+    for lo in range(0, len(items), per):
+        res = _generate_chunk(chat, items[lo:lo + per], max_new_tokens, nb, do_sample, repetition_penalty, temperature, top_k, seed, eos)
+        out += res if details else [r["tokens"] for r in res]
+    return out
+
+
+def _generate_chunk(chat, items, max_new, nb, do_sample, pen, temp, top_k, seed, eos):
+    """Every item's rule is a generator of select / advance requests; each round serves all pending requests of one kind in
+    ONE device call (advances first: a select must see the appended token), so the items advance in lockstep."""
+    rules, rows, reqs, results = [], [], [], [None] * len(items)
+    for i, it in enumerate(items):
+        r = list(range(i * nb, (i + 1) * nb))
+        chat.prefill(i, r[0], it)
+        rule = greedy_rule(max_new, eos) if (do_sample or nb == 1) else beam_rule(nb, max_new, eos)
+        rules.append(rule); rows.append(r); reqs.append(next(rule))
+    mode = SAMPLE if do_sample else (BEAM if nb > 1 else GREEDY)
+    step = 0
+    while any(q is not None for q in reqs):
+        live = [i for i, q in enumerate(reqs) if q is not None]
+        kind = "advance" if any(reqs[i][0] == "advance" for i in live) else "select"
+        sel = [i for i in live if reqs[i][0] == kind]
+        answers = {}
+        if kind == "select":
+            k = reqs[sel[0]][3]
+            groups = [rows[i][:reqs[i][1]] for i in sel]
+            sc, tk, pa = chat.select(mode, groups, k, [s for i in sel for s in reqs[i][2]], repetition_penalty=pen,
+                                     temperature=temp, top_k=top_k, seed=seed, step=step)
+            step += 1
+            for j, i in enumerate(sel):
+                answers[i] = [(float(sc[j, q]), int(tk[j, q]), int(pa[j, q])) for q in range(k) if tk[j, q] >= 0]
+        else:
+            slots, srows, toks = [], [], []
+            for i in sel:
+                parents, tokens = reqs[i][1], reqs[i][2]
+                src = [rows[i][p] for p in parents]
+                dst = rows[i][:len(parents)]
+                if src != dst:
+                    chat.reorder(dst, src)
+                slots += [i] * len(dst); srows += dst; toks += tokens
+            chat.step(slots, srows, toks)
+            answers = {i: None for i in sel}
+        for i in sel:
+            try:
+                reqs[i] = rules[i].send(answers[i])
+            except StopIteration as stop:
+                results[i], reqs[i] = stop.value, None
+    return results

@@ -277,6 +277,126 @@ class VisRAGRet:
 
     __call__ = forward
 
+    # ---- MiniCPM-V 2.0 answer generation (the reference's MiniCPMV.generate / chat, modeling_minicpmv.py:276-400) ----------
+    def attach_generator(self, lm_head: torch.Tensor, gen_cfg=None, max_inp_length: int = 2048, max_new_tokens: int = 1024,
+                         num_beams: int = 3, batch: int = 1) -> "VisRAGRet":
+        """Give the model its LM head (`llm.lm_head.weight`; with tied embeddings the embedding matrix): the retrieval path
+        drops it at load.  The cache holds `batch` prompts of up to max_inp_length tokens, each with num_beams rows of up to
+        max_new_tokens generated tokens (chat()'s defaults: 2048, 1024, 3 beams; 2.3 GB at full dims for one prompt)."""
+        from .generation import GenerationConfig, HipChat
+        gen_cfg = gen_cfg or GenerationConfig()
+        self._gen_cfg = gen_cfg
+        self._chat = HipChat(self._owner.encoder, max_inp_length + max_new_tokens, num_beams * batch, gen_cfg.dim_model_base,
+                             max_slots=batch, max_new=max_new_tokens)
+        self._chat.load_head(lm_head)
+        return self
+
+    def generate(self, data_list=None, img_list=None, tokenizer=None, max_inp_length: Optional[int] = None,
+                 vision_hidden_states=None, return_vision_hidden_states=False, **kwargs):
+        """data_list: prompts that already hold their image placeholders; img_list: per prompt the PIL slices in placeholder
+        order.  kwargs: max_new_tokens, num_beams, do_sample, temperature, repetition_penalty, top_k, seed."""
+        from .generation import decode_text, generate_items
+        if data_list is None:
+            raise ValueError("data_list is required")
+        if vision_hidden_states is not None or return_vision_hidden_states:
+            raise NotImplementedError("vision_hidden_states are not supported")
+        if getattr(self, "_chat", None) is None:
+            raise RuntimeError("generate() needs an LM head: call attach_generator() first (or load_generator())")
+        if img_list is None:
+            img_list = [[] for _ in data_list]
+        if len(img_list) != len(data_list):
+            raise ValueError("data_list and img_list must have the same length")
+        items = [_prompt_item(t, imgs, tokenizer, max_inp_length) for t, imgs in zip(data_list, img_list)]
+        kwargs.setdefault("max_new_tokens", 20)
+        ids = generate_items(self._chat, items, eos=tokenizer.eos_id, **kwargs)
+        return decode_text(ids, tokenizer)
+
+    def chat(self, image_list, msgs_list, tokenizer, vision_hidden_states=None, max_new_tokens: int = 1024, sampling: bool = True,
+             max_inp_length: int = 2048, seed: int = 0, **kwargs):
+        """The reference's chat (modeling_minicpmv.py:321-398).  `seed` (not in the reference, whose draws come from torch's
+        global generator) selects the sampling noise: chat(sampling=True) with one seed returns the same answer each call."""
+        from .generation import chat_generation_config
+        prompts, images = [], []
+        for msgs, image in zip(msgs_list, image_list):
+            p, imgs = chat_prompt(msgs, image, tokenizer, self.config)
+            prompts.append(p)
+            images.append(imgs)
+        gen = chat_generation_config(sampling, kwargs)
+        return self.generate(data_list=prompts, img_list=images, tokenizer=tokenizer, max_inp_length=max_inp_length,
+                             vision_hidden_states=vision_hidden_states, max_new_tokens=max_new_tokens, seed=seed, **gen)
+
+
+def chat_prompt(msgs, image, tokenizer, cfg):
+    """modeling_minicpmv.py:335-367: ChatML messages + one image -> (prompt, image slices)."""
+    from .preprocess import get_grid_placeholder, image_placeholder, slice_image
+    if not isinstance(msgs, list):
+        raise NotImplementedError(f"chatml format expected, expect outmost type to be list but got {type(msgs)}")
+    prompt, images = "", []
+    for i, msg in enumerate(msgs):
+        role, content = msg["role"], msg["content"]
+        assert role in ["user", "assistant"]
+        if i == 0:
+            assert role == "user", "The role of first msg should be user"
+            if cfg.slice_mode:
+                src, patches, grid = slice_image(image, cfg.max_slice_nums, cfg.scale_resolution, cfg.patch_size)
+                images = [src] + [p for row in patches for p in row]
+                ph = image_placeholder(tokenizer, cfg.query_num)
+                if patches:
+                    ph += get_grid_placeholder(tokenizer, grid, cfg.query_num)
+            else:
+                images = [image]
+                ph = image_placeholder(tokenizer, cfg.query_num)
+            content = ph + "\n" + content
+        prompt += "<用户>" if role == "user" else "<AI>"
+        prompt += content
+    return prompt, images
+
+
+def _prompt_item(text, images, tokenizer, max_inp_length):
+    """MiniCPMV._convert_to_tensors (modeling_minicpmv.py:173-200) for a prompt that already holds its placeholders."""
+    ids = list(tokenizer.encode(text))
+    if not getattr(tokenizer, "add_bos_token", True):
+        ids = [tokenizer.bos_id] + ids
+    if max_inp_length is not None:
+        ids = ids[:max_inp_length]
+    arr = np.asarray(ids, dtype=np.int64)
+    starts = np.nonzero(arr == tokenizer.im_start_id)[0] + 1
+    ends = np.nonzero(arr == tokenizer.im_end_id)[0]
+    if len(starts) != len(ends):
+        raise ValueError("unbalanced <image> / </image> markers after truncation; raise max_inp_length")
+    bound = [(int(s), int(e)) for s, e in zip(starts, ends)]
+    slices = [np.asarray(im if im.mode == "RGB" else im.convert("RGB"), dtype=np.uint8) for im in images]
+    return PreparedItem(input_ids=ids, image_bound=bound, slices=slices)
+
+
+def load_generator(path: str, device=None, **cache) -> "VisRAGRet":
+    """A MiniCPM-V 2.0 checkpoint directory -> VisRAGRet with generate / chat (config.json: dim_model_base,
+    tie_word_embeddings; the head is llm.lm_head.weight, or the embedding matrix when tied).  `cache`: attach_generator's
+    sizes."""
+    from .generation import generation_config_from_checkpoint
+    gcfg = generation_config_from_checkpoint(path)
+    model = VisRAGRet.from_pretrained(path) if device is None else VisRAGRet.from_pretrained(path, device=device)
+    want = "llm.model.embed_tokens.weight" if gcfg.tie_word_embeddings else "llm.lm_head.weight"
+    return model.attach_generator(checkpoint_tensor(path, want), gcfg, **cache)
+
+
+def checkpoint_tensor(path: str, key: str) -> torch.Tensor:
+    """One tensor of a checkpoint directory: read from the safetensors shard that holds it (only that tensor is
+    materialised); .bin shards are loaded one at a time until the key turns up."""
+    files = sorted(f for f in os.listdir(path) if f.endswith(".safetensors"))
+    if files:
+        from safetensors import safe_open
+        for fn in files:
+            with safe_open(os.path.join(path, fn), framework="pt", device="cpu") as f:
+                if key in f.keys():
+                    return f.get_tensor(key)
+    else:
+        for fn in sorted(f for f in os.listdir(path) if f.startswith("pytorch_model") and f.endswith(".bin")):
+            sd = torch.load(os.path.join(path, fn), map_location="cpu", weights_only=True)
+            if key in sd:
+                return sd[key]
+    raise KeyError(f"{key} not found under {path}")
+
 
 def types_namespace(**kw):
     import types

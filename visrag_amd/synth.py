@@ -140,6 +140,12 @@ def synth_state_dict(cfg: VisRAGRetConfig, seed: int = 0, device="cpu") -> Dict[
     return OrderedDict(iter_synth_weights(cfg, seed, device))
 
 
+def synth_lm_head(cfg: VisRAGRetConfig, seed: int = 0, device="cpu") -> torch.Tensor:
+    """A deterministic `llm.lm_head.weight` [vocab_size, hidden_size] for the generator (the retrieval checkpoint drops the
+    head; synth_state_dict stays the retriever's key set).  Gain 4: logits of a few units at the head's scaled input."""
+    return synth_tensor("llm.lm_head.weight", (cfg.vocab_size, cfg.hidden_size), _lin_amp(cfg.hidden_size, 4.0), seed, device=device)
+
+
 def param_count(cfg: VisRAGRetConfig) -> int:
     return sum(int(math.prod(sh)) for sh, _, _ in weight_specs(cfg).values())
 
