@@ -390,7 +390,7 @@ def test_exact_pass_alone_matches_oracle(nd, nq, dim, k):
 
 def test_flagged_queries_walk_several_windows_of_the_score_buffer():
     """The fallback passes hold at most 512 MiB of fp32 score rows: `slots` = 2^27 / rows flagged queries per window, walked in
-    a loop of launches (engine.hip: vr_index_search).  300 000 rows x 500 flagged queries = two windows for the band GEMM +
+    a loop of launches (index.hip: vr_index_search).  300 000 rows x 500 flagged queries = two windows for the band GEMM +
     band selection and for the exact pass (every band is the whole index: band pass hands on to the exact pass): ids ==
     fp64 for every query, whichever window it fell into."""
     nd, nq, dim, k = 300000, 500, 64, 10

@@ -18,19 +18,12 @@ template <> struct AttnCfg<72>  { static constexpr int K32 = 2, TAIL = 1, DFRAGS
 template <> struct AttnCfg<80>  { static constexpr int K32 = 2, TAIL = 1, DFRAGS = 5, PITCH = 160; };
 template <> struct AttnCfg<128> { static constexpr int K32 = 4, TAIL = 0, DFRAGS = 8, PITCH = 288; };
 
-#ifndef VR_ATTN_TAIL16
-#define VR_ATTN_TAIL16 1
-#endif
-// the tail of head_dim 72 / 80 (d = 64..79) as ONE 16x16x16 MFMA per fragment — half the matrix-pipe time of the
-// 16x16x32 form it replaces, whose second half multiplied zeros (72: 80 instead of 96 columns of QK^T work)
-constexpr bool TAIL16 = VR_ATTN_TAIL16 != 0;
-// wave priority: raised for a tile's PV MFMAs, dropped for its softmax (1) — with three workgroups per CU the arbiter then
+// The tail of head_dim 72 / 80 (d = 64..79) is ONE 16x16x16 MFMA per fragment — half the matrix-pipe time of a 16x16x32
+// whose second half would multiply zeros (72: 80 instead of 96 columns of QK^T work).
+// Wave priority: raised for a tile's PV MFMAs, dropped for its softmax — with three workgroups per CU the arbiter then
 // prefers the wave that can feed the matrix pipe and fills in with the others' VALU work: ViT attention 738 -> 764 TF in
-// isolation, 5.28 -> 5.18 ms per step in the model.  (2: the other way round, 3 / 4: also raised for the score MFMAs, to
-// level 3 / 1: 766-783 TF in isolation, no better than 1 in the model.)
-#ifndef VR_ATTN_PRIO
-#define VR_ATTN_PRIO 1
-#endif
+// isolation, 5.28 -> 5.18 ms per step in the model.  (The other way round, or also raised for the score MFMAs: 766-783 TF
+// in isolation, no better in the model.)
 constexpr int ATT_KV = 64;          // keys per tile
 constexpr float MAX_SLACK = 8.0f;   // log2 units the running max may lag behind before O is rescaled
 
@@ -62,16 +55,16 @@ template <int HD, int PIPE> constexpr int attn_smem_bytes() { return 2 * (PIPE ?
 
 template <int HD, int QF, int PIPE, bool COH = false>
 __device__ __forceinline__ void attention_body(const AttnArgs& p, int unit, char* smem, const bf16_t* q_lds = nullptr) {
+    static_assert(PIPE == 0 || PIPE == 3, "PIPE 0: one K/V slot staged through registers; PIPE 3: two slots staged by LDS-DMA");
     using C = AttnCfg<HD>;
     constexpr int K32 = C::K32, DFRAGS = C::DFRAGS, PITCH = C::PITCH;
     constexpr bool TAIL = C::TAIL != 0;
     constexpr bool ONES = TAIL && DFRAGS * 16 > HD;    // a spare V column holds 1.0: the PV MFMA produces the row sums
-    constexpr int TAILQ = (HD - K32 * 32) / 8;         // 16-byte chunks of real data in the tail window
     constexpr int CPR = HD / 8;                   // 16-byte chunks per global row
     constexpr int QT = 64 * QF;                   // query rows per workgroup
     constexpr int NCH = (ATT_KV * CPR + 255) / 256;   // staging chunks per thread
     constexpr int NB = PIPE ? 2 : 1;              // K / V slots
-    constexpr bool DMA = PIPE >= 3;
+    constexpr bool DMA = PIPE == 3;
     constexpr int SLOT = ATT_KV * PITCH;
 
     static_assert(2 * NB * SLOT == attn_smem_bytes<HD, PIPE>(), "LDS size");   // K slots, then V slots
@@ -118,17 +111,13 @@ __device__ __forceinline__ void attention_body(const AttnArgs& p, int unit, char
             if (ok) raw = *reinterpret_cast<const u32x4*>(qbase + (size_t)q * p.ldq + ks * 32 + fq * 8);
             qf[f][ks] = __builtin_bit_cast(bf16x8, raw);
         }
-        // tail MFMA (d = 64..95 window): lanes fq == 0 carry the real d = 64..71, every other k-slot of Q
-        // is zero — so the K operand of those slots may be ANY finite LDS content (see scores())
+        // tail MFMA (16x16x16): lane (fr, fq) holds Q[q = fr][d = 64 + fq*4 .. +3] in the low half (d >= HD: zero)
         u32x4 rt = {0, 0, 0, 0};
-        if constexpr (TAIL && TAIL16) {
-            // 16x16x16 tail: lane (fr, fq) holds Q[q = fr][d = 64 + fq*4 .. +3] in the low half (d >= HD: zero)
+        if constexpr (TAIL) {
             if (ok && 64 + fq * 4 < HD) {
                 const u32x2 r2 = *reinterpret_cast<const u32x2*>(qbase + (size_t)q * p.ldq + K32 * 32 + fq * 4);
                 rt[0] = r2[0]; rt[1] = r2[1];
             }
-        } else {
-            if (TAIL && ok && fq < TAILQ) rt = *reinterpret_cast<const u32x4*>(qbase + (size_t)q * p.ldq + K32 * 32 + fq * 8);
         }
         qtail[f] = __builtin_bit_cast(bf16x8, rt);
     }
@@ -147,7 +136,7 @@ __device__ __forceinline__ void attention_body(const AttnArgs& p, int unit, char
     const int n_tiles = (kv_end + ATT_KV - 1) / ATT_KV;
     const float sc = p.scale * 1.44269504088896340736f;   // exp2 domain
 
-    // ---- staging through registers (PIPE 0..2): every thread moves NCH 16-byte chunks of K and of V
+    // ---- staging through registers (PIPE 0): every thread moves NCH 16-byte chunks of K and of V
     //      per tile (threads past the last chunk repeat it: same bytes, same address)
     constexpr int NCHR = DMA ? 1 : NCH;
     u32x4 rk[NCHR], rv[NCHR];
@@ -235,15 +224,10 @@ __device__ __forceinline__ void attention_body(const AttnArgs& p, int unit, char
             const char* kr = Kt + kf * 16 * PITCH + k_off;
 #pragma unroll
             for (int ks = 0; ks < K32; ++ks) ka[kf][ks] = *reinterpret_cast<const bf16x8*>(kr + ks * 64);
-            // tail: one b128 read per lane at d = 64 + fq*8.  fq 0: the real d 64..71; fq 1: the row's zero
-            // padding; fq 2, 3: the first bytes of the NEXT row (finite K data, or the start of the next
-            // slot / the V slots after the last row) — multiplied by Q's zero k-slots
-            if constexpr (TAIL && TAIL16) {
-                // d = 64 + fq*4 .. +3 of key row fr: 8 bytes at column byte 128 + fq*8 (72: d 72..79 is the row's zero padding)
+            if constexpr (TAIL) {
+                // tail: d = 64 + fq*4 .. +3 of key row fr: 8 bytes at column byte 128 + fq*8 (72: d 72..79 is the row's zero padding)
                 const u32x2 r2 = *reinterpret_cast<const u32x2*>(kr - fq * 16 + K32 * 64 + fq * 8);
                 kt[kf] = __builtin_bit_cast(bf16x8, u32x4{r2[0], r2[1], 0u, 0u});
-            } else if constexpr (TAIL) {
-                kt[kf] = *reinterpret_cast<const bf16x8*>(kr + K32 * 64);
             }
         }
 #pragma unroll
@@ -257,7 +241,7 @@ __device__ __forceinline__ void attention_body(const AttnArgs& p, int unit, char
 #pragma unroll
                 for (int f = 0; f < QF; ++f)
                     s[f][kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka[kf][ks], qf[f][ks], s[f][kf], 0, 0, 0);
-        if constexpr (TAIL && TAIL16) {
+        if constexpr (TAIL) {
 #pragma unroll
             for (int kf = 0; kf < 4; ++kf)
 #pragma unroll
@@ -267,12 +251,6 @@ __device__ __forceinline__ void attention_body(const AttnArgs& p, int unit, char
                     s[f][kf] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, ka4), __builtin_bit_cast(s16x4, qb4),
                                                                          s[f][kf], 0, 0, 0);
                 }
-        } else if constexpr (TAIL) {
-#pragma unroll
-            for (int kf = 0; kf < 4; ++kf)
-#pragma unroll
-                for (int f = 0; f < QF; ++f)
-                    s[f][kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kt[kf], qtail[f], s[f][kf], 0, 0, 0);
         }
     };
 
@@ -386,16 +364,12 @@ __device__ __forceinline__ void attention_body(const AttnArgs& p, int unit, char
         bf16x8 va0[DFRAGS], va1[DFRAGS], pb[QF][2];
         float neg_m[QF];
         v_frags(Vt, 0, va0);                     // issued now, consumed after the softmax
-        if constexpr (VR_ATTN_PRIO == 1 || VR_ATTN_PRIO == 3 || VR_ATTN_PRIO == 4) __builtin_amdgcn_s_setprio(0);
-        if constexpr (VR_ATTN_PRIO == 2) __builtin_amdgcn_s_setprio(2);
+        __builtin_amdgcn_s_setprio(0);
         stats(s, tile, neg_m);
         exp_pack(s, neg_m, pb);
         v_frags(Vt, 1, va1);
         v_wait(va0);
-        if constexpr (VR_ATTN_PRIO == 1) __builtin_amdgcn_s_setprio(2);
-        if constexpr (VR_ATTN_PRIO == 3) __builtin_amdgcn_s_setprio(3);
-        if constexpr (VR_ATTN_PRIO == 4) __builtin_amdgcn_s_setprio(1);
-        if constexpr (VR_ATTN_PRIO == 2) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(2);
         pv(va0, pb, 0);
         v_wait(va1);
         pv(va1, pb, 1);
@@ -421,26 +395,7 @@ __device__ __forceinline__ void attention_body(const AttnArgs& p, int unit, char
             scores(Ks, s);
             softmax_pv(s, Vs, tile);
         }
-    } else if constexpr (PIPE == 1) {
-        write_k(0); write_v(0);
-        load_k(1); load_v(1);
-        __syncthreads();
-        // (two iterations per trip so that the slot addresses are compile-time constants)
-        auto body = [&](int tile, auto cur_c) {
-            constexpr int cur = decltype(cur_c)::value;
-            write_k(cur ^ 1); write_v(cur ^ 1);   // tile+1: its slot was last read before the previous barrier
-            load_k(tile + 2); load_v(tile + 2);
-            f32x4 s[QF][4];
-            scores(Ks + cur * SLOT, s);
-            softmax_pv(s, Vs + cur * SLOT, tile);
-            __syncthreads();
-        };
-        for (int tile = 0; tile < n_tiles; tile += 2) {
-            body(tile, std::integral_constant<int, 0>{});
-            if (tile + 1 >= n_tiles) break;
-            body(tile + 1, std::integral_constant<int, 1>{});
-        }
-    } else if constexpr (PIPE == 3) {
+    } else {
         // (dsrc points at tile 0 after the setup above; every dma_tile call moves it one tile on)
         dma_tile(0, 0);
         __syncthreads();                          // (the LDS-DMA in flight makes this wait vmcnt(0) too)
@@ -448,8 +403,6 @@ __device__ __forceinline__ void attention_body(const AttnArgs& p, int unit, char
             constexpr int cur = decltype(cur_c)::value;
             if (tile + 1 < n_tiles) dma_tile(tile + 1, cur ^ 1);   // its slot was last read before the previous barrier
             f32x4 s[QF][4];
-            if constexpr (VR_ATTN_PRIO == 3) __builtin_amdgcn_s_setprio(3);
-            if constexpr (VR_ATTN_PRIO == 4) __builtin_amdgcn_s_setprio(1);
             scores(Ks + cur * SLOT, s);
             softmax_pv(s, Vs + cur * SLOT, tile);
             __syncthreads();                      // tile+1 landed (vmcnt(0) + barrier), slot `cur` free
@@ -458,74 +411,6 @@ __device__ __forceinline__ void attention_body(const AttnArgs& p, int unit, char
             body(tile, std::integral_constant<int, 0>{});
             if (tile + 1 >= n_tiles) break;
             body(tile + 1, std::integral_constant<int, 1>{});
-        }
-    } else if constexpr (PIPE == 4) {
-        // LDS-DMA staging AND scores one tile ahead: at the top of iteration t the LDS holds K[t+1]
-        // (slot (t+1)&1) and V[t] (slot t&1), s_cur = scores of tile t; the iteration requests K[t+2]
-        // and V[t+1] (rows past the end arrive as zeros)
-        dma_tile(0, 0);
-        __syncthreads();
-        dma_issue(1, 1, 0, 0);                    // K[1]; the V half re-fetches V[0] into its own slot (harmless)
-        f32x4 s_a[QF][4], s_b[QF][4];
-        scores(Ks, s_a);
-        __syncthreads();
-        auto body = [&](int tile, auto cur_c, f32x4 (&s_cur)[QF][4], f32x4 (&s_nxt)[QF][4]) {
-            constexpr int cur = decltype(cur_c)::value;
-            dma_issue(tile + 2, cur, tile + 1, cur ^ 1);
-            const char* Vt = Vs + cur * SLOT;
-            bf16x8 va0[DFRAGS], va1[DFRAGS], pb[QF][2];
-            float neg_m[QF];
-            v_frags(Vt, 0, va0);
-            stats(s_cur, tile, neg_m);
-            scores(Ks + (cur ^ 1) * SLOT, s_nxt);
-            exp_pack(s_cur, neg_m, pb);
-            v_frags(Vt, 1, va1);
-            v_wait(va0);
-            pv(va0, pb, 0);
-            v_wait(va1);
-            pv(va1, pb, 1);
-            __syncthreads();
-        };
-        for (int tile = 0; tile < n_tiles; tile += 2) {
-            body(tile, std::integral_constant<int, 0>{}, s_a, s_b);
-            if (tile + 1 >= n_tiles) break;
-            body(tile + 1, std::integral_constant<int, 1>{}, s_b, s_a);
-        }
-    } else {
-        // invariant at the top of iteration t: LDS holds K[t+1] (slot (t+1)&1) and V[t] (slot t&1),
-        // s_cur = scores of tile t, registers carry K[t+2] and V[t+1] (in flight)
-        write_k(0); write_v(0);
-        load_k(1);
-        __syncthreads();
-        f32x4 s_a[QF][4], s_b[QF][4];
-        scores(Ks, s_a);
-        write_k(1);
-        load_k(2); load_v(1);
-        __syncthreads();
-        // two iterations per trip: the two score sets swap roles (no register copies) and the slot
-        // addresses are compile-time constants
-        auto body = [&](int tile, auto cur_c, f32x4 (&s_cur)[QF][4], f32x4 (&s_nxt)[QF][4]) {
-            constexpr int cur = decltype(cur_c)::value;
-            write_k(cur); write_v(cur ^ 1);
-            load_k(tile + 3); load_v(tile + 2);
-            const char* Vt = Vs + cur * SLOT;
-            bf16x8 va0[DFRAGS], va1[DFRAGS], pb[QF][2];
-            float neg_m[QF];
-            v_frags(Vt, 0, va0);
-            stats(s_cur, tile, neg_m);
-            // one straight-line region: the score MFMAs of tile+1 (past the end: unused) run under
-            // the exp / convert VALU work of tile `tile`
-            scores(Ks + (cur ^ 1) * SLOT, s_nxt);
-            exp_pack(s_cur, neg_m, pb);
-            v_frags(Vt, 1, va1);
-            pv(va0, pb, 0);
-            pv(va1, pb, 1);
-            __syncthreads();
-        };
-        for (int tile = 0; tile < n_tiles; tile += 2) {
-            body(tile, std::integral_constant<int, 0>{}, s_a, s_b);
-            if (tile + 1 >= n_tiles) break;
-            body(tile + 1, std::integral_constant<int, 1>{}, s_b, s_a);
         }
     }
 

@@ -1,0 +1,367 @@
+// MiniCPM-V 2.0 answer generation on the model's weights (MiniCPMV.generate / chat, modeling_minicpmv.py:218-237, 276-400;
+// the decoder + head of modeling_minicpm.py:1147-1304, 1411-1412).  The prefill is the encode pass itself (bf16 route) with a
+// per-layer hook that keeps the rope'd K / V rows; a decode step streams every weight once for all its rows (gemm_skinny.hip).
+// Cache: prompt planes per prompt SLOT [layer][K|V][max_slots][max_len][E], tail planes (generated tokens) per ROW
+// [layer][K|V][max_rows][max_new][E], bf16.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "model.h"
+
+struct vr_chat_s {
+    vr_model_s* model = nullptr;
+    vr_model_t work = nullptr;            // vr_model_clone of `model`: the prefill pass's workspace
+    vr_chat_config_t c{};
+    int E = 0, H = 0, L = 0, V = 0, Vpad = 0, Ip = 0, words = 0;
+    Linear head;
+    DevBuf norm_w;                        // final norm weight * dim_model_base / hidden (the /scale of the head's input, :1411)
+    DevBuf rope;                          // f32 [max_len][64], the table of vr_model_finalize extended to max_len
+    DevBuf prompt, tails, seen;           // caches; seen-id bit sets [max_rows][words]
+    DevBuf w_h, w_xn, w_q, w_att, w_act, w_part, w_po, w_pml, w_logits, w_lse, w_sel, w_out, w_reps, w_move, w_move_seen;
+    std::vector<int> plen;                // per slot: prompt tokens (0 = none)
+    std::vector<int> row_slot, row_len;   // per row: its prompt slot (-1 = unbound), generated tokens in its tail
+    std::vector<int> lpos;                // per row: its logits row in w_logits (-1 = none)
+};
+
+static size_t chat_prompt_off(const vr_chat_s* ch, int l, int kv, int slot) {      // bytes
+    return ((((size_t)l * 2 + kv) * ch->c.max_slots + slot) * (size_t)ch->c.max_len * ch->E) * 2;
+}
+
+extern "C" int vr_chat_create(vr_model_t m, const vr_chat_config_t* cfg, vr_chat_t* out) {
+    if (!m || !cfg || !out) return fail(VR_ERR_INVALID, "NULL argument");
+    if (!m->finalized) return fail(VR_ERR_STATE, "vr_chat_create before vr_model_finalize");
+    if (cfg->max_rows < 1 || cfg->max_rows > CHAT_MAX_ROWS) return fail(VR_ERR_INVALID, "max_rows must be 1..%d", CHAT_MAX_ROWS);
+    if (cfg->max_len < 2) return fail(VR_ERR_INVALID, "max_len must be at least 2");
+    if (cfg->max_slots < 1 || cfg->max_slots > cfg->max_rows) return fail(VR_ERR_INVALID, "max_slots must be 1..max_rows");
+    if (cfg->max_new < 1 || cfg->max_new >= cfg->max_len) return fail(VR_ERR_INVALID, "max_new must be 1..max_len - 1");
+    if (!(cfg->dim_model_base > 0.f)) return fail(VR_ERR_INVALID, "dim_model_base must be positive");
+    VRCHK(set_dev(m->device));
+    vr_chat_s* ch = new vr_chat_s();
+    auto bail = [&](int rc) { if (ch->work) vr_model_destroy(ch->work); delete ch; return rc; };
+    ch->model = m;
+    ch->c = *cfg;
+    ch->E = m->E; ch->H = m->c.num_heads; ch->L = m->c.num_layers; ch->V = m->c.vocab_size; ch->Vpad = pad128(ch->V); ch->Ip = m->Ip;
+    ch->words = (ch->V + 31) / 32;
+    const int E = ch->E, R = cfg->max_rows, ML = cfg->max_len;
+    int rc = vr_model_clone(m, &ch->work);
+    if (rc) return bail(rc);
+    {   // final norm weight with the head's input scale folded in
+        std::vector<float> w(E);
+        if (hipMemcpy(w.data(), m->final_norm.v.p, (size_t)E * 4, hipMemcpyDeviceToHost) != hipSuccess) return bail(fail(VR_ERR_HIP, "norm copy"));
+        const float sc = cfg->dim_model_base / (float)E;
+        for (float& x : w) x *= sc;
+        if ((rc = ch->norm_w.alloc((size_t)E * 4))) return bail(rc);
+        if (hipMemcpy(ch->norm_w.p, w.data(), (size_t)E * 4, hipMemcpyHostToDevice) != hipSuccess) return bail(fail(VR_ERR_HIP, "norm upload"));
+    }
+    {   // RoPE table of the model (vr_model_finalize), max_len positions
+        const std::vector<float> tab = rope_table_host(m->c.rope_theta, ML);
+        if ((rc = ch->rope.alloc(tab.size() * 4))) return bail(rc);
+        if (hipMemcpy(ch->rope.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return bail(fail(VR_ERR_HIP, "rope upload"));
+    }
+    const size_t pcache = (size_t)ch->L * 2 * cfg->max_slots * ML * E * 2, tcache = (size_t)ch->L * 2 * R * cfg->max_new * E * 2;
+    size_t part = 0;
+    for (const DecLayer& l : m->layers)
+        for (const Linear* w : {&l.qkv, &l.o, &l.gu, &l.down})
+            part = std::max(part, (size_t)stream_ksplit(w->n_pad, w->k_pad) * CHAT_MAX_ROWS * w->n_pad);
+    const size_t H = ch->H;
+    if ((rc = ch->prompt.alloc(pcache)) || (rc = ch->tails.alloc(tcache)) || (rc = ch->seen.alloc((size_t)R * ch->words * 4)) ||
+        (rc = ch->w_h.alloc((size_t)CHAT_MAX_ROWS * E * 4)) || (rc = ch->w_xn.alloc((size_t)CHAT_MAX_ROWS * E * 2)) ||
+        (rc = ch->w_q.alloc((size_t)CHAT_MAX_ROWS * E * 2)) || (rc = ch->w_att.alloc((size_t)CHAT_MAX_ROWS * E * 2)) ||
+        (rc = ch->w_act.alloc((size_t)CHAT_MAX_ROWS * ch->Ip * 2)) || (rc = ch->w_part.alloc(part * 4)) ||
+        (rc = ch->w_po.alloc((size_t)CHAT_MAX_ROWS * H * CHAT_ATT_SPLITS * 64 * 4)) ||
+        (rc = ch->w_pml.alloc((size_t)CHAT_MAX_ROWS * H * CHAT_ATT_SPLITS * 2 * 4)) ||
+        (rc = ch->w_logits.alloc((size_t)2 * R * ch->Vpad * 4)) || (rc = ch->w_lse.alloc(CHAT_MAX_ROWS * 4)) ||
+        (rc = ch->w_sel.alloc((size_t)CHAT_MAX_ROWS * CHAT_SEL_WGS * CHAT_TOPK_MAX * 8)) ||
+        (rc = ch->w_out.alloc((size_t)CHAT_MAX_ROWS * CHAT_TOPK_MAX * 12)) || (rc = ch->w_reps.alloc((size_t)E * 4)) ||
+        (rc = ch->w_move_seen.alloc((size_t)CHAT_MAX_ROWS * ch->words * 4)))
+        return bail(rc);
+    ch->plen.assign(cfg->max_slots, 0);
+    ch->row_slot.assign(R, -1);
+    ch->row_len.assign(R, 0);
+    ch->lpos.assign(R, -1);
+    *out = ch;
+    return VR_OK;
+}
+
+extern "C" int vr_chat_destroy(vr_chat_t ch) {
+    if (!ch) return VR_OK;
+    (void)hipSetDevice(ch->model->device);
+    (void)hipDeviceSynchronize();
+    if (ch->work) vr_model_destroy(ch->work);
+    delete ch;
+    return VR_OK;
+}
+
+extern "C" int vr_chat_load_head(vr_chat_t ch, const void* data, const int64_t* shape, int32_t ndim, int32_t dtype, int32_t on_device) {
+    if (!ch || !data || !shape) return fail(VR_ERR_INVALID, "NULL argument");
+    if (dtype != VR_DTYPE_F32 && dtype != VR_DTYPE_BF16) return fail(VR_ERR_INVALID, "bad dtype %d", dtype);
+    if (!shape_is(shape, ndim, {ch->V, ch->E})) return fail(VR_ERR_INVALID, "lm_head must be [vocab_size][hidden_size]");
+    VRCHK(set_dev(ch->model->device));
+    const int bf = dtype == VR_DTYPE_BF16;
+    Staged st;
+    VRCHK(stage(data, (size_t)ch->V * ch->E * (bf ? 2 : 4), on_device, st));
+    return load_linear_part(ch->head, ch->V, ch->E, st.dev, bf, ch->V, ch->E, 0, ch->V, 0, 0);
+}
+
+// logits f32 of the step rows xn [n][E] (already normed and scaled) -> w_logits rows [lrow0, lrow0 + n)
+static int chat_head(vr_chat_s* ch, int n, int lrow0, hipStream_t s) {
+    GemmArgs a = gemm_args(ch->w_xn.p, ch->E, ch->head, n, ch->w_logits.as<float>() + (size_t)lrow0 * ch->Vpad, ch->Vpad);
+    HIPCHK(launch_gemm_skinny(a, s));
+    return VR_OK;
+}
+
+struct ChatPrefillCtx { vr_chat_s* ch; int slot; };
+static int chat_prefill_layer(void* ctx, int l, const void* qkv, int ldqkv, int T, hipStream_t s) {
+    const ChatPrefillCtx* p = (const ChatPrefillCtx*)ctx;
+    vr_chat_s* ch = p->ch;
+    HIPCHK(launch_chat_prompt_kv(qkv, ldqkv, T, ch->E, (char*)ch->prompt.p + chat_prompt_off(ch, l, 0, p->slot),
+                                 (char*)ch->prompt.p + chat_prompt_off(ch, l, 1, p->slot), s));
+    return VR_OK;
+}
+
+extern "C" int vr_chat_prefill(vr_chat_t ch, int32_t slot, int32_t row, const uint8_t* const* slices, const int32_t* slice_hw,
+                               int32_t n_slices, int32_t slices_on_device, const int32_t* input_ids, int32_t T,
+                               const int32_t* vision_rows, void* stream) {
+    if (!ch || !input_ids) return fail(VR_ERR_INVALID, "NULL argument");
+    if (!ch->head.has_w) return fail(VR_ERR_STATE, "vr_chat_load_head has not run");
+    if (slot < 0 || slot >= ch->c.max_slots || row < 0 || row >= ch->c.max_rows) return fail(VR_ERR_INVALID, "slot / row out of range");
+    if (T < 1) return fail(VR_ERR_INVALID, "empty prompt");
+    if (T > ch->c.max_len - 1) return fail(VR_ERR_CAPACITY, "prompt of %d tokens leaves no room below max_len=%d", T, ch->c.max_len);
+    if (T > ch->work->c.max_tokens) return fail(VR_ERR_CAPACITY, "prompt of %d tokens exceeds the model's max_tokens=%d", T, ch->work->c.max_tokens);
+    VRCHK(set_dev(ch->model->device));
+    hipStream_t s = (hipStream_t)stream;
+    vr_model_s* w = ch->work;
+    ch->plen[slot] = 0;                                  // the slot's cache is rewritten from here on
+    for (int r = 0; r < ch->c.max_rows; ++r)
+        if (ch->row_slot[r] == slot) { ch->row_slot[r] = -1; ch->row_len[r] = 0; ch->lpos[r] = -1; }
+    ChatPrefillCtx ctx{ch, slot};
+    EncodeHook hook;
+    hook.bf16_route = true;                              // the reference generator runs in bf16 (generate.py: torch_dtype=bfloat16)
+    hook.layer = chat_prefill_layer;
+    hook.ctx = &ctx;
+    const int32_t seq[2] = {0, T};
+    w->arena_open = false;
+    int rc = encode_impl(w, slices, slice_hw, n_slices, slices_on_device, input_ids, seq, 1, vision_rows, ch->w_reps.as<float>(), 1,
+                         stream, nullptr, 0, &hook);
+    arena_close(w, stream);
+    if (rc) return rc;
+    // last prompt token: final RMSNorm (scaled weight) -> head, modeling_minicpm.py:1411-1412
+    const vr_config_t& c = w->c;
+    HIPCHK(launch_rmsnorm(w->w_h.as<float>() + (size_t)(T - 1) * ch->E, 1, ch->E, ch->E, ch->norm_w.as<float>(), c.rms_norm_eps, ch->w_xn.p,
+                          ch->E, s));
+    const int lrow = ch->c.max_rows + row;               // prefill logits live in the upper half of w_logits
+    VRCHK(chat_head(ch, 1, lrow, s));
+    HIPCHK(hipMemsetAsync((unsigned*)ch->seen.p + (size_t)row * ch->words, 0, (size_t)ch->words * 4, s));
+    ch->plen[slot] = T;
+    ch->row_slot[row] = slot;
+    ch->row_len[row] = 0;
+    ch->lpos[row] = lrow;
+    return VR_OK;
+}
+
+extern "C" int vr_chat_step(vr_chat_t ch, int32_t n, const int32_t* slots, const int32_t* rows, const int32_t* tokens, void* stream) {
+    if (!ch || !slots || !rows || !tokens) return fail(VR_ERR_INVALID, "NULL argument");
+    if (!ch->head.has_w) return fail(VR_ERR_STATE, "vr_chat_load_head has not run");
+    const int R = ch->c.max_rows;
+    if (n < 1) return fail(VR_ERR_INVALID, "n must be positive");
+    if (n > R) return fail(VR_ERR_CAPACITY, "%d rows exceed max_rows=%d", n, R);
+    // ---- every check before any state changes
+    ChatStep st{};
+    st.n = n;
+    std::vector<char> used(R, 0), slot_done(ch->c.max_slots, 0);
+    for (int i = 0; i < n; ++i) {
+        const int sl = slots[i], r = rows[i], t = tokens[i];
+        if (sl < 0 || sl >= ch->c.max_slots || ch->plen[sl] <= 0) return fail(VR_ERR_INVALID, "step row %d: slot %d holds no prompt", i, sl);
+        if (r < 0 || r >= R || used[r]) return fail(VR_ERR_INVALID, "step row %d: row %d out of range or repeated", i, r);
+        if (t < 0 || t >= ch->V) return fail(VR_ERR_INVALID, "token id %d out of range", t);
+        used[r] = 1;
+        if (ch->row_slot[r] != sl && ch->row_len[r] > 0) return fail(VR_ERR_INVALID, "row %d continues slot %d, not %d", r, ch->row_slot[r], sl);
+        const int len = ch->row_slot[r] == sl ? ch->row_len[r] : 0;
+        if (ch->plen[sl] + len + 1 > ch->c.max_len || len + 1 > ch->c.max_new)
+            return fail(VR_ERR_CAPACITY, "row %d would exceed max_len=%d / max_new=%d", r, ch->c.max_len, ch->c.max_new);
+        if (i == 0 || slots[i - 1] != sl) {
+            if (slot_done[sl]) return fail(VR_ERR_INVALID, "the rows of slot %d must be adjacent", sl);
+            slot_done[sl] = 1;
+            st.g_lo[st.groups] = i;
+            st.plen[st.groups] = ch->plen[sl];
+            st.groups++;
+        }
+        st.row[i] = r; st.slot[i] = sl; st.tail[i] = len; st.pos[i] = ch->plen[sl] + len; st.token[i] = t;
+    }
+    st.g_lo[st.groups] = n;
+    int S = 1;                                           // prompt-key ranges of the attention: ~CHAT_KEYS keys each, per prompt
+    for (int g = 0; g < st.groups; ++g) {
+        st.gsplit[g] = std::min(CHAT_ATT_SPLITS, std::max(1, (st.plen[g] + CHAT_KEYS - 1) / CHAT_KEYS));
+        S = std::max(S, st.gsplit[g]);
+        for (int i = st.g_lo[g]; i < st.g_lo[g + 1]; ++i) st.rsplit[i] = st.gsplit[g];
+    }
+    VRCHK(set_dev(ch->model->device));
+    hipStream_t s = (hipStream_t)stream;
+    vr_model_s* m = ch->model;
+    const vr_config_t& c = m->c;
+    const int E = ch->E;
+    for (int i = 0; i < n; ++i)                          // a row that starts on a slot starts with an empty seen set
+        if (ch->row_slot[rows[i]] != slots[i])
+            HIPCHK(hipMemsetAsync((unsigned*)ch->seen.p + (size_t)rows[i] * ch->words, 0, (size_t)ch->words * 4, s));
+    float* h = ch->w_h.as<float>();
+    float* part = ch->w_part.as<float>();
+    HIPCHK(launch_chat_embed(st, m->embed.p, E, c.scale_emb, h, ch->seen.as<unsigned>(), ch->words, s));
+    const ChatCaps caps{ch->c.max_slots, ch->c.max_len, R, ch->c.max_new};
+    int pend_ks = 0;                                     // > 0: h still lacks residual_scale * (the last projection's planes)
+    auto norm = [&](const float* wn) -> int {
+        if (pend_ks) HIPCHK(launch_rmsnorm_accum(h, n, E, E, part, pend_ks, (size_t)n * E, E, c.residual_scale, wn, c.rms_norm_eps, ch->w_xn.p, E, s));
+        else HIPCHK(launch_rmsnorm(h, n, E, E, wn, c.rms_norm_eps, ch->w_xn.p, E, s));
+        pend_ks = 0;
+        return VR_OK;
+    };
+    for (int l = 0; l < ch->L; ++l) {
+        const DecLayer& Ly = m->layers[l];
+        VRCHK(norm(Ly.ln1.v.as<float>()));
+        {
+            GemmArgs a = gemm_args(ch->w_xn.p, E, Ly.qkv, n, part, Ly.qkv.n_pad);
+            a.ksplit = stream_ksplit(Ly.qkv.n_pad, Ly.qkv.k_pad); a.split_stride = (size_t)n * Ly.qkv.n_pad;
+            HIPCHK(launch_gemm_skinny(a, s));
+            HIPCHK(launch_chat_qkv(st, part, a.ksplit, a.split_stride, Ly.qkv.n_pad, ch->rope.as<float>(), E, ch->H, ch->w_q.p, ch->tails.p, l,
+                                   ch->c.max_rows, ch->c.max_new, s));
+        }
+        HIPCHK(launch_chat_attn(st, ch->w_q.p, ch->prompt.p, ch->tails.p, l, E, ch->H, caps, S, ch->w_po.as<float>(),
+                                ch->w_pml.as<float>(), ch->w_att.p, s));
+        {
+            GemmArgs a = gemm_args(ch->w_att.p, E, Ly.o, n, part, E);
+            a.ksplit = stream_ksplit(Ly.o.n_pad, Ly.o.k_pad); a.split_stride = (size_t)n * E;
+            HIPCHK(launch_gemm_skinny(a, s));
+            pend_ks = a.ksplit;
+        }
+        VRCHK(norm(Ly.ln2.v.as<float>()));
+        {
+            const int N2 = Ly.gu.n_pad;
+            GemmArgs g = gemm_args(ch->w_xn.p, E, Ly.gu, n, ch->w_act.p, ch->Ip);
+            g.ksplit = stream_ksplit(N2, Ly.gu.k_pad);
+            if (g.ksplit == 1) {
+                HIPCHK(launch_gemm_skinny(g, s, true));
+            } else {
+                g.out = part; g.ldo = N2; g.split_stride = (size_t)n * N2;
+                HIPCHK(launch_gemm_skinny(g, s));
+                HIPCHK(launch_swiglu_sum(part, g.ksplit, (size_t)n * N2, N2, n, m->I, ch->w_act.p, ch->Ip, s));
+            }
+        }
+        {
+            GemmArgs a = gemm_args(ch->w_act.p, ch->Ip, Ly.down, n, part, E);
+            a.ksplit = stream_ksplit(Ly.down.n_pad, Ly.down.k_pad); a.split_stride = (size_t)n * E;
+            HIPCHK(launch_gemm_skinny(a, s));
+            pend_ks = a.ksplit;
+        }
+    }
+    VRCHK(norm(ch->norm_w.as<float>()));
+    VRCHK(chat_head(ch, n, 0, s));
+    for (int r = 0; r < R; ++r)
+        if (ch->lpos[r] >= 0 && ch->lpos[r] < R) ch->lpos[r] = -1;        // step logits rows are overwritten
+    for (int i = 0; i < n; ++i) {
+        ch->row_slot[rows[i]] = slots[i];
+        ch->row_len[rows[i]] = st.tail[i] + 1;
+        ch->lpos[rows[i]] = i;
+    }
+    return VR_OK;
+}
+
+extern "C" int vr_chat_select(vr_chat_t ch, int32_t mode, int32_t n_groups, const int32_t* group_offsets, const int32_t* rows,
+                              const float* beam_scores, int32_t k, float repetition_penalty, float temperature, int32_t top_k,
+                              uint64_t seed, int32_t step, float* out_scores, int32_t* out_tokens, int32_t* out_parents, void* stream) {
+    if (!ch || !group_offsets || !rows || !out_scores || !out_tokens || !out_parents) return fail(VR_ERR_INVALID, "NULL argument");
+    if (mode < VR_CHAT_GREEDY || mode > VR_CHAT_SAMPLE) return fail(VR_ERR_INVALID, "mode %d", mode);
+    if (n_groups < 1 || group_offsets[0] != 0) return fail(VR_ERR_INVALID, "bad groups");
+    const int n = group_offsets[n_groups];
+    if (n > CHAT_MAX_ROWS || n > ch->c.max_rows) return fail(VR_ERR_CAPACITY, "%d rows exceed max_rows", n);
+    if (!(repetition_penalty > 0.f)) return fail(VR_ERR_INVALID, "repetition_penalty must be positive");
+    ChatSel sel{};
+    sel.n = n; sel.groups = n_groups;
+    for (int g = 0; g <= n_groups; ++g) sel.g_lo[g] = group_offsets[g];
+    for (int g = 0; g < n_groups; ++g) {
+        const int nb = group_offsets[g + 1] - group_offsets[g];
+        if (nb < 1) return fail(VR_ERR_INVALID, "empty group %d", g);
+        if (mode != VR_CHAT_BEAM && nb != 1) return fail(VR_ERR_INVALID, "greedy / sampling groups hold one row");
+    }
+    for (int i = 0; i < n; ++i) {
+        const int r = rows[i];
+        if (r < 0 || r >= ch->c.max_rows || ch->lpos[r] < 0) return fail(VR_ERR_STATE, "row %d has no logits", r);
+        sel.lrow[i] = ch->lpos[r]; sel.srow[i] = r;
+        sel.bscore[i] = mode == VR_CHAT_BEAM && beam_scores ? beam_scores[i] : 0.f;
+    }
+    int K = k;
+    if (mode == VR_CHAT_SAMPLE) {
+        if (k != 1 || !(temperature > 0.f)) return fail(VR_ERR_INVALID, "sampling: k must be 1 and temperature positive");
+        K = top_k;
+    }
+    if (K < 1 || K > CHAT_TOPK_MAX || k < 1 || k > CHAT_TOPK_MAX) return fail(VR_ERR_INVALID, "k / top_k must be 1..%d", CHAT_TOPK_MAX);
+    VRCHK(set_dev(ch->model->device));
+    hipStream_t s = (hipStream_t)stream;
+    float* o_score = ch->w_out.as<float>();
+    int* o_tok = (int*)(o_score + CHAT_MAX_ROWS * CHAT_TOPK_MAX);
+    int* o_par = o_tok + CHAT_MAX_ROWS * CHAT_TOPK_MAX;
+    const int cm = mode == VR_CHAT_BEAM ? CHAT_SEL_BEAM : mode == VR_CHAT_SAMPLE ? CHAT_SEL_SAMPLE : CHAT_SEL_GREEDY;
+    HIPCHK(launch_chat_select(sel, cm, ch->w_logits.as<float>(), ch->Vpad, ch->V, ch->seen.as<unsigned>(), ch->words, repetition_penalty,
+                              temperature, K, k, (unsigned long long)seed, (unsigned)step, ch->w_lse.as<float>(),
+                              ch->w_sel.as<unsigned long long>(), o_score, o_tok, o_par, s));
+    const size_t cnt = (size_t)n_groups * k;
+    HIPCHK(hipMemcpyAsync(out_scores, o_score, cnt * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out_tokens, o_tok, cnt * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out_parents, o_par, cnt * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
+}
+
+extern "C" int vr_chat_reorder(vr_chat_t ch, int32_t n, const int32_t* rows, const int32_t* parents, void* stream) {
+    if (!ch || !rows || !parents) return fail(VR_ERR_INVALID, "NULL argument");
+    const int R = ch->c.max_rows;
+    if (n < 1) return fail(VR_ERR_INVALID, "n must be positive");
+    if (n > R) return fail(VR_ERR_CAPACITY, "%d rows exceed max_rows=%d", n, R);
+    std::vector<char> used(R, 0);
+    ChatMove mv{};
+    int max_tail = 0;
+    for (int i = 0; i < n; ++i) {
+        const int r = rows[i], p = parents[i];
+        if (r < 0 || r >= R || used[r] || p < 0 || p >= R) return fail(VR_ERR_INVALID, "reorder %d: row %d / parent %d", i, r, p);
+        used[r] = 1;
+        if (p == r) continue;
+        mv.src[mv.n] = p; mv.dst[mv.n] = r; mv.len[mv.n] = ch->row_len[p];
+        max_tail = std::max(max_tail, ch->row_len[p]);
+        mv.n++;
+    }
+    if (!mv.n) return VR_OK;
+    VRCHK(set_dev(ch->model->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t need = (size_t)mv.n * 2 * ch->L * std::max(max_tail, 1) * ch->E * 2;
+    if (ch->w_move.bytes < need) {
+        HIPCHK(hipStreamSynchronize(s));                 // (the old scratch may still be read by an earlier reorder)
+        VRCHK(ch->w_move.reserve(need));
+    }
+    HIPCHK(launch_chat_move(mv, ch->tails.p, ch->w_move.p, ch->L, R, ch->c.max_new, ch->E, max_tail, ch->seen.as<unsigned>(),
+                            ch->w_move_seen.as<unsigned>(), ch->words, s));
+    const std::vector<int> old_slot = ch->row_slot, old_len = ch->row_len;
+    for (int i = 0; i < mv.n; ++i) {
+        ch->row_slot[mv.dst[i]] = old_slot[mv.src[i]];
+        ch->row_len[mv.dst[i]] = old_len[mv.src[i]];
+        ch->lpos[mv.dst[i]] = -1;
+    }
+    return VR_OK;
+}
+
+extern "C" int vr_chat_logits(vr_chat_t ch, int32_t row, float* out, void* stream) {
+    if (!ch || !out) return fail(VR_ERR_INVALID, "NULL argument");
+    if (row < 0 || row >= ch->c.max_rows || ch->lpos[row] < 0) return fail(VR_ERR_STATE, "row %d has no logits", row);
+    VRCHK(set_dev(ch->model->device));
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipMemcpyAsync(out, ch->w_logits.as<float>() + (size_t)ch->lpos[row] * ch->Vpad, (size_t)ch->V * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
+}
+
+extern "C" int vr_chat_row_len(vr_chat_t ch, int32_t row, int32_t* slot, int32_t* generated) {
+    if (!ch || !slot || !generated) return fail(VR_ERR_INVALID, "NULL argument");
+    if (row < 0 || row >= ch->c.max_rows) return fail(VR_ERR_INVALID, "row %d out of range", row);
+    *slot = ch->row_slot[row];
+    *generated = ch->row_len[row];
+    return VR_OK;
+}

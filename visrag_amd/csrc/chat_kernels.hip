@@ -1,4 +1,4 @@
-// Kernels of MiniCPM-V 2.0 answer generation on the VisRAG-Ret weights (vr_chat_*, engine.hip): the decode step's token
+// Kernels of MiniCPM-V 2.0 answer generation on the VisRAG-Ret weights (vr_chat_*, chat.hip): the decode step's token
 // embedding, q|k|v plane sum + RoPE + KV-tail append, decode attention for head_dim 64 (full multi-head), and the logits
 // processing of HF generate (repetition penalty, log_softmax + beam scores, top-k candidates, sampling).
 // The decode step's GEMMs are the weight streamer of gemm_skinny.hip; everything here is small and HBM / latency bound.

@@ -1,5 +1,5 @@
-// Host-side helpers shared by the engines of libvisrag_hip.so (engine.hip: the VisRAG-Ret encoder; gen.hip: the
-// EVisRAG generator's language model): error reporting, owning device buffers, packed weights and their loaders.
+// Host-side helpers shared by the engines of libvisrag_hip.so (model.hip / encode.hip / index.hip / ops.hip / chat.hip: the
+// VisRAG-Ret encoder, its index and its chat; gen.hip: the EVisRAG generator's language model): error reporting, owning device buffers, packed weights and their loaders.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -52,6 +52,8 @@ static inline int skinny_ksplit(int n, int k, int max_split) {
     }
     return best;
 }
+// ... of the encoder's weight-streaming passes (split-precision text route of short batches, chat decode step)
+static inline int stream_ksplit(int n, int k) { return skinny_ksplit(n, k, 32); }
 
 static inline int pad128(int x) { return (x + 127) / 128 * 128; }
 static inline int64_t pad128l(int64_t x) { return (x + 127) / 128 * 128; }

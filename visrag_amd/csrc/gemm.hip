@@ -151,11 +151,8 @@ hipError_t launch_gemm(const GemmArgs& a, int epi, int variant, hipStream_t s) {
     if (variant == GEMM_VARIANT_128W_256) return launch_gemm128w(a, epi, 256, s);
     if (variant == GEMM_VARIANT_AUTO) {
         // N = 1152 (SigLIP proj / fc2): 6 x 192 columns, big M -> the 256x192 kernel
-#ifndef VR_GEMM_AUTO_192W
-#define VR_GEMM_AUTO_192W 1
-#endif
         if (a.N % 192 == 0 && a.N % 256 != 0 && a.N <= 1536 && a.M >= 4096 && epi <= EPI_RESID) {
-            if (VR_GEMM_AUTO_192W && epi == EPI_RESID && !a.rowmap && gemm256w_fits(a, 192)) return launch_gemm192w(a, epi, s);
+            if (epi == EPI_RESID && !a.rowmap && gemm256w_fits(a, 192)) return launch_gemm192w(a, epi, s);
             return launch_gemm192(a, epi, s);
         }
         // 256x256 tiles when N is a multiple of 256 or wide enough that one partial tile column costs
@@ -169,16 +166,13 @@ hipError_t launch_gemm(const GemmArgs& a, int epi, int variant, hipStream_t s) {
         const long t128 = (long)(a.N / 128) * ((a.M + 127) / 128);
         const double e256 = 1.45 * (double)t256 / (double)(((t256 + 255) / 256) * 256);
         const double e128 = (double)t128 / (double)(((t128 + 511) / 512) * 512);
-#ifndef VR_GEMM_AUTO_W
-#define VR_GEMM_AUTO_W 0xFF
-#endif
         // Which 256x256 kernel: the one-wave-per-SIMD kernel (gemm256w.hip) is faster and leaner in isolation
         // everywhere (ViT qkv 230 vs 255 us, 302 vs 326 mJ), but its denser matrix-core stream pulls the shader
         // clock down (1.9 vs 2.1 GHz sustained, well below the 1400 W cap) and the clock recovers slowly, so in
         // the model the kernels that FOLLOW it lose part of what it gains: decide in-model, on one box
-        // (tools/ab_libs.sh; bit e of VR_GEMM_AUTO_W puts epilogue e on the new kernel).  Round 2: everything on
+        // (tools/ab_libs.sh).  Round 2: every epilogue on
         // it 48.1 ms/step, all but the ViT qkv GEMM 48.7, none (8-wave kernel, 128x128 gate/up) 50.5.
-        const bool w_ok = (((VR_GEMM_AUTO_W) >> epi) & 1) && gemm256w_fits(a, 256);     // (else: the 8-wave kernel, 64-bit addresses)
+        const bool w_ok = gemm256w_fits(a, 256);     // (else: the 8-wave kernel, 64-bit addresses)
         variant = (n_ok && e256 > e128) ? (w_ok ? GEMM_VARIANT_256W : GEMM_VARIANT_256IL) : GEMM_VARIANT_GLDS;
         if (variant == GEMM_VARIANT_256W) return launch_gemm256w(a, epi, s);
     }

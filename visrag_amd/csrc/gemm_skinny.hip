@@ -27,10 +27,7 @@ constexpr int sk_stage(int mb) { return SK_W_BYTES + mb * 16 * 128; }      // 32
 constexpr int sk_smem(int mb) { return SK_STAGES * sk_stage(mb); }
 constexpr unsigned SK_OOB = 0x80000000u;
 // cache policy of the weight loads: nt (aux bit 1) — every byte of W is read once, by one CU
-#ifndef VR_SKINNY_W_AUX
-#define VR_SKINNY_W_AUX 2
-#endif
-constexpr int SK_W_AUX = VR_SKINNY_W_AUX;
+constexpr int SK_W_AUX = 2;
 
 }  // namespace
 

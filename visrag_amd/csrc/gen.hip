@@ -33,13 +33,7 @@ static void drop_graph(vg_model_s* m) {
 // measured on the 7B layer (ms per token): gate/up 148 tiles as 148 x 56 K-steps 3.74, 296 x 28 (a second round of 40)
 // 3.94, 592 x 14 3.80; down 14 tiles as 252 x 17 3.74, 112 x 37 3.94, 518 x 8 4.08.  The splits need not divide the
 // K-steps (the last range is shorter); every range keeps >= 4 steps; more tiles than CUs: no split.
-#ifndef VR_KS_QKV
-#define VR_KS_QKV 0
-#define VR_KS_O 0
-#define VR_KS_GU 0
-#define VR_KS_DOWN 0
-#endif
-static int choose_ksplit(int n, int k, int forced = 0) { return forced > 0 ? forced : skinny_ksplit(n, k, GEN_KS_MAX); }
+static int choose_ksplit(int n, int k) { return skinny_ksplit(n, k, GEN_KS_MAX); }
 
 // The persistent layer kernel of the decode step (gen_persist.hip): decide whether this model / device takes it and build
 // its layer table for the CURRENT slot (the caches are per slot).  It is OPT-IN — VR_DECODE_PERSIST=1 in the environment
@@ -58,8 +52,8 @@ static int persist_setup(vg_model_s* m) {
     const int grid = prop.multiProcessorCount;
     const int E = m->E, QD = m->QD, QKV = m->QKV, G = m->H / m->KV;
     const GenLayer& L0 = m->layers[0];
-    const int ks_qkv = choose_ksplit(QKV, E, VR_KS_QKV), ks_o = choose_ksplit(E, QD, VR_KS_O);
-    const int ks_d = choose_ksplit(E, L0.down.k_pad, VR_KS_DOWN), ks_gu = choose_ksplit(L0.gu.n_pad, E, VR_KS_GU);
+    const int ks_qkv = choose_ksplit(QKV, E), ks_o = choose_ksplit(E, QD);
+    const int ks_d = choose_ksplit(E, L0.down.k_pad), ks_gu = choose_ksplit(L0.gu.n_pad, E);
     auto per64 = [](int k, int ks) { return ((k / 64 + ks - 1) / ks) * 64; };
     const bool fits =
         E <= 4096 && (E / 4 + 63) / 64 <= 16 && (E / 4 + 63) / 64 <= grid && G <= 16 && GEN_ATT_SPLITS * m->KV <= grid && ks_gu == 1 &&
@@ -94,8 +88,8 @@ static int persist_layers(vg_model_s* m, hipStream_t s) {
     a.layers = m->p_table.as<PersistLayer>(); a.n_layers = (int)m->layers.size();
     a.E = m->E; a.QKV = m->QKV; a.QD = m->QD; a.KVD = m->KVD; a.H = m->H; a.KV = m->KV; a.Ip = L0.down.k_pad; a.N2 = L0.gu.n_pad;
     a.ldw_qkv = L0.qkv.k_pad; a.ldw_o = L0.o.k_pad; a.ldw_gu = L0.gu.k_pad; a.ldw_d = L0.down.k_pad;
-    a.ks_qkv = choose_ksplit(m->QKV, m->E, VR_KS_QKV); a.ks_o = choose_ksplit(m->E, m->QD, VR_KS_O);
-    a.ks_d = choose_ksplit(m->E, L0.down.k_pad, VR_KS_DOWN);
+    a.ks_qkv = choose_ksplit(m->QKV, m->E); a.ks_o = choose_ksplit(m->E, m->QD);
+    a.ks_d = choose_ksplit(m->E, L0.down.k_pad);
     a.eps = m->c.rms_norm_eps; a.g_final = m->final_norm.v.as<float>();
     a.h = m->w_h.as<float>(); a.xn = m->w_xn.p; a.planes = m->w_part.as<float>(); a.act = m->w_act.p;
     a.attp = m->w_attp.p; a.lse = m->w_lse.as<float>(); a.ss = m->p_ss.as<float>();
@@ -281,7 +275,7 @@ static int gen_layer(vg_model_s* m, int l, int T, bool decode, const float* next
     if (decode) {
         GemmArgs a = gen_gemm_args(m->w_xn.p, E, L.qkv, T, part, QKV);
         a.bias = nullptr;
-        a.ksplit = choose_ksplit(QKV, E, VR_KS_QKV);
+        a.ksplit = choose_ksplit(QKV, E);
         a.split_stride = (size_t)QKV * T;
         HIPCHK(launch_gemm_skinny(a, s));
         GenState* st = m->w_state.as<GenState>();          // position and cache row of the step: on the device
@@ -324,7 +318,7 @@ static int gen_layer(vg_model_s* m, int l, int T, bool decode, const float* next
     // ---- o projection + residual, post-attention norm
     if (decode) {
         GemmArgs a = gen_gemm_args(m->w_att.p, QD, L.o, T, part, E);
-        a.ksplit = choose_ksplit(E, QD, VR_KS_O);
+        a.ksplit = choose_ksplit(E, QD);
         a.split_stride = (size_t)E * T;
         const int per = (QD / 64 + a.ksplit - 1) / a.ksplit;
         if (T == 1 && per <= 4) {
@@ -347,7 +341,7 @@ static int gen_layer(vg_model_s* m, int l, int T, bool decode, const float* next
     if (decode) {
         const int N2 = L.gu.n_pad;
         GemmArgs g = gen_gemm_args(m->w_xn.p, E, L.gu, T, part, N2);
-        g.ksplit = choose_ksplit(N2, E, VR_KS_GU);
+        g.ksplit = choose_ksplit(N2, E);
         if (g.ksplit == 1) {                        // the usual case (more tiles than a split would help): SwiGLU in the tile's epilogue
             g.out = m->w_act.p; g.ldo = Ip;
             HIPCHK(launch_gemm_skinny(g, s, true));
@@ -357,7 +351,7 @@ static int gen_layer(vg_model_s* m, int l, int T, bool decode, const float* next
             HIPCHK(launch_swiglu_sum(part, g.ksplit, (size_t)N2 * T, N2, T, m->I, m->w_act.p, Ip, s));
         }
         GemmArgs a = gen_gemm_args(m->w_act.p, Ip, L.down, T, part, E);
-        a.ksplit = choose_ksplit(E, L.down.k_pad, VR_KS_DOWN);
+        a.ksplit = choose_ksplit(E, L.down.k_pad);
         a.split_stride = (size_t)E * T;
         HIPCHK(launch_gemm_skinny(a, s));
         HIPCHK(launch_rmsnorm_accum(h, T, E, E, part, a.ksplit, (size_t)E * T, E, 1.0f, next_norm, c.rms_norm_eps, m->w_xn.p, E, s));
@@ -590,7 +584,7 @@ static int gen_layer_batch(vg_model_s* m, int l, int n, const float* next_norm, 
     {   // q | k | v: one pass over the weights for the n rows, then rotate + append to each sequence's cache
         GemmArgs a = gen_gemm_args(m->w_xn.p, E, L.qkv, n, part, QKV);
         a.bias = nullptr;
-        a.ksplit = choose_ksplit(QKV, E, VR_KS_QKV);
+        a.ksplit = choose_ksplit(QKV, E);
         a.split_stride = (size_t)QKV * n;
         HIPCHK(launch_gemm_skinny(a, s));
         HIPCHK(launch_mrope_cache(nullptr, part, a.ksplit, (size_t)QKV * n, L.qkv.b.as<float>(), QKV, n, m->H, m->KV, &bt->pos[0][0], 16,
@@ -610,7 +604,7 @@ static int gen_layer_batch(vg_model_s* m, int l, int n, const float* next_norm, 
     }
     {
         GemmArgs a = gen_gemm_args(m->w_att.p, QD, L.o, n, part, E);
-        a.ksplit = choose_ksplit(E, QD, VR_KS_O);
+        a.ksplit = choose_ksplit(E, QD);
         a.split_stride = (size_t)E * n;
         HIPCHK(launch_gemm_skinny(a, s));
         HIPCHK(launch_rmsnorm_accum(h, n, E, E, part, a.ksplit, (size_t)E * n, E, 1.0f, L.ln2.v.as<float>(), c.rms_norm_eps, m->w_xn.p, E, s));
@@ -618,7 +612,7 @@ static int gen_layer_batch(vg_model_s* m, int l, int n, const float* next_norm, 
     {
         const int N2 = L.gu.n_pad;
         GemmArgs g = gen_gemm_args(m->w_xn.p, E, L.gu, n, part, N2);
-        g.ksplit = choose_ksplit(N2, E, VR_KS_GU);
+        g.ksplit = choose_ksplit(N2, E);
         if (g.ksplit == 1) {
             g.out = m->w_act.p; g.ldo = Ip;
             HIPCHK(launch_gemm_skinny(g, s, true));
@@ -628,7 +622,7 @@ static int gen_layer_batch(vg_model_s* m, int l, int n, const float* next_norm, 
             HIPCHK(launch_swiglu_sum(part, g.ksplit, (size_t)N2 * n, N2, n, m->I, m->w_act.p, Ip, s));
         }
         GemmArgs a = gen_gemm_args(m->w_act.p, Ip, L.down, n, part, E);
-        a.ksplit = choose_ksplit(E, L.down.k_pad, VR_KS_DOWN);
+        a.ksplit = choose_ksplit(E, L.down.k_pad);
         a.split_stride = (size_t)E * n;
         HIPCHK(launch_gemm_skinny(a, s));
         HIPCHK(launch_rmsnorm_accum(h, n, E, E, part, a.ksplit, (size_t)E * n, E, 1.0f, next_norm, c.rms_norm_eps, m->w_xn.p, E, s));
@@ -646,8 +640,8 @@ extern "C" int vg_decode_batch(vg_model_t m, int32_t n, const int32_t* slots, co
     const int G = m->H / m->KV;
     {   // the widest split-K plane set of the step must fit the partial buffer
         const size_t cap = m->w_part.bytes / 4;
-        const size_t need = (size_t)n * std::max({(size_t)choose_ksplit(m->QKV, m->E, VR_KS_QKV) * m->QKV, (size_t)choose_ksplit(m->E, m->QD, VR_KS_O) * m->E,
-                                                  (size_t)choose_ksplit(m->E, pad128(m->I), VR_KS_DOWN) * m->E});
+        const size_t need = (size_t)n * std::max({(size_t)choose_ksplit(m->QKV, m->E) * m->QKV, (size_t)choose_ksplit(m->E, m->QD) * m->E,
+                                                  (size_t)choose_ksplit(m->E, pad128(m->I)) * m->E});
         if (need > cap) return fail(VR_ERR_CAPACITY, "%d rows need %zu partial-sum floats (%zu available)", n, need, cap);
     }
     GenBatch b{};

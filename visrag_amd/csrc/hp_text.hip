@@ -6,7 +6,7 @@
 // the path's work, so their decoder pass runs at fp32-class precision instead:
 //   * every GEMM operand is split into hi + lo bf16 parts (x = hi + lo to ~16 mantissa bits) and the
 //     product is accumulated from A_hi W_hi + A_lo W_hi + A_hi W_lo on the SAME MFMA kernels
-//     (engine.hip issues them as an EPI_F32 launch followed by in-place EPI_RESID launches);
+//     (encode.hip issues them as an EPI_F32 launch followed by in-place EPI_RESID launches);
 //   * everything between the GEMMs stays fp32: the kernels below (RMSNorm -> split, RoPE, causal
 //     attention, SwiGLU -> split, embedding gather from a hi + lo table).
 // Reference arithmetic: modeling_minicpm.py:119-136 (RMSNorm), :259-290 (rotary), :816-910 (SDPA,

@@ -97,7 +97,7 @@ struct AttnArgs {
 };
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
 
-// ---- MiniCPM-V 2.0 answer generation (chat_kernels.hip; host side vr_chat_* in engine.hip) ------
+// ---- MiniCPM-V 2.0 answer generation (chat_kernels.hip; host side vr_chat_* in chat.hip) ------
 constexpr int CHAT_MAX_ROWS = 16;   // rows (prompts x beams) of one decode step
 constexpr int CHAT_ATT_SPLITS = 8;  // most prompt-key ranges of one (prompt, head) in the decode attention
 constexpr int CHAT_KEYS = 256;      // keys per chunk of the decode attention (one per thread)

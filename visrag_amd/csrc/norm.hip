@@ -92,10 +92,7 @@ hipError_t launch_layernorm(const float* x, int rows, int dim, int ldx, const fl
                             float eps, void* out, int ldo, hipStream_t s) {
     if (rows <= 0) return hipSuccess;
     if (dim % 4 || ldo % 4 || ldx % 4 || ldo > 64 * 4 * NORM_MAXV || dim > ldo || dim > ldx) return hipErrorInvalidValue;
-#ifndef VR_NORM_VITV
-#define VR_NORM_VITV 1
-#endif
-    if (VR_NORM_VITV && ldo <= 64 * 4 * NORM_VITV)
+    if (ldo <= 64 * 4 * NORM_VITV)
         hipLaunchKernelGGL((norm_kernel<false, NORM_VITV, 2>), dim3((rows + 7) / 8), dim3(256), 0, s, x, rows, dim, ldx, w, b, eps, (bf16_t*)out, ldo);
     else if (ldo <= 64 * 4 * NORM_STDV)
         hipLaunchKernelGGL((norm_kernel<false, NORM_STDV>), dim3((rows + 3) / 4), dim3(256), 0, s, x, rows, dim, ldx, w, b, eps, (bf16_t*)out, ldo);

@@ -466,13 +466,10 @@ int search_num_chunks(int64_t n_docs, int nq) {
 
 constexpr int SMALL_NQ = 16;        // up to here: no pre-pass, workgroup-per-query merge
 
-#ifndef VR_PREPASS_OWN
-#define VR_PREPASS_OWN 1
-#endif
 int search_prepass_owned(int64_t n_docs, int nq, int dim) {
     const int64_t tiles = (n_docs + 255) / 256;
     // (one tile in eight at most — as for the plain pre-pass — and the one-wave sweep's conditions: search256w.hip)
-    if (!VR_PREPASS_OWN || !search_uses_256(nq) || nq <= SMALL_NQ || dim % 128 || tiles < 8 * SEARCH_PRE_SPOTS) return 0;
+    if (!search_uses_256(nq) || nq <= SMALL_NQ || dim % 128 || tiles < 8 * SEARCH_PRE_SPOTS) return 0;
     // only where it shortens the sweep: the lists of its own cost the threshold kernel and the merge ~15 us (1k x 100k: 7 -> 6
     // tiles per workgroup, -36 us of sweep; 256 queries x 100k: 2 tiles per workgroup either way)
     const int c_all = search_num_chunks(n_docs, nq), c_own = search_num_chunks(n_docs - (int64_t)SEARCH_PRE_SPOTS * 256, nq);

@@ -367,12 +367,9 @@ static hipError_t launch_t(const SearchArgs& a, const float* thr, hipStream_t s)
     const int q_tiles = (a.nq + 255) / 256;
     const int n_tiles = (int)((a.n_docs + 255) / 256);
     const int tpc = (n_tiles + a.n_chunks - 1) / a.n_chunks;
-#ifndef VR_SWEEP_W
-#define VR_SWEEP_W 1
-#endif
     hipError_t e;
-    if (a.pre_own_chunks && !(VR_SWEEP_W && sweep256w_ok(a))) return hipErrorInvalidValue;   // (only that sweep skips tiles)
-    if (VR_SWEEP_W && sweep256w_ok(a)) {     // the one-wave-per-SIMD form of the sweep (search256w.hip)
+    if (a.pre_own_chunks && !sweep256w_ok(a)) return hipErrorInvalidValue;   // (only that sweep skips tiles)
+    if (sweep256w_ok(a)) {     // the one-wave-per-SIMD form of the sweep (search256w.hip)
         e = launch_sweep256w(a, KP, thr, s);
     } else {
         auto k = search_sweep256_kernel<KP>;

@@ -48,12 +48,9 @@ __device__ __forceinline__ uint64_t wave_merge_top64(uint64_t cur, uint64_t fres
 
 constexpr int MERGE_MAXV = 10;     // dim <= 64 * 4 * MERGE_MAXV
 constexpr int MERGE_CAP = 1024;    // survivor buffer per query (merge kernels): what the certification can re-score in place
-#ifndef VR_MERGE_GD
-#define VR_MERGE_GD 16
-#endif
 // gather depth of the merge kernels beyond KP: the first gather keeps every list entry above (a lower bound of) the
 // (KP + MERGE_GD_EXTRA)-th best key — deep enough that the certification rarely has to gather again
-constexpr int MERGE_GD_EXTRA = VR_MERGE_GD;
+constexpr int MERGE_GD_EXTRA = 16;
 
 // ---- exact fp32 scores ------------------------------------------------------------------------
 // ONE definition of the fp32 dot product behind every score the library returns: lane l owns the
@@ -202,15 +199,12 @@ __device__ __forceinline__ bool certify_tail(const SearchArgs& p, int q, const u
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
     const int nv = p.dim >> 2;
     const float* qrow = p.q_f32 + (size_t)q * p.dim;
-#ifndef VR_RESCORE_PAIRS
-#define VR_RESCORE_PAIRS 1
-#endif
     // q_s (LDS, MERGE_MAXV * 64 float4, the 256-thread merge of the big sweeps): the bf16 top-KP is re-scored with TWO candidate
     // rows per wave in flight — a wave has KP / 4 of these 9 KB rows to fetch, each a memory round trip — and the query read
     // from LDS meanwhile, so that the two rows' 80 registers do not push the kernel past 128 (four workgroups per CU; with the
     // query in registers too: 207).  Up to 512 queries only: 256 queries 55.5 -> 45.5 us per merge, but with 1 000 workgroups
-    // resident the memory system is what the merge waits for — twice the requests in flight: 69.5 -> 83 us (tools/r6/merge_pairs.sh)
-    const bool pairs = VR_RESCORE_PAIRS && q_s != nullptr && nw * 2 <= KP && gridDim.x <= 512;
+    // resident the memory system is what the merge waits for — twice the requests in flight: 69.5 -> 83 us
+    const bool pairs = q_s != nullptr && nw * 2 <= KP && gridDim.x <= 512;
     if (pairs) {
         if (tid < 64) exact_s[tid] = KEY_NONE;
         for (int c = tid; c < MERGE_MAXV * 64; c += blockDim.x)
