@@ -219,7 +219,7 @@ int vr_chat_prefill(vr_chat_t ch, int32_t slot, int32_t row, const uint8_t* cons
 int vr_chat_step(vr_chat_t ch, int32_t n, const int32_t* slots, const int32_t* rows, const int32_t* tokens, void* stream);
 /* Next-token candidates from the current logits of rows[] grouped by group_offsets [n_groups + 1] (beam search: one group
  * per prompt; greedy / sampling: one row per group).  Host outputs [n_groups][k]: score, token, parent (row index within the
- * group), best first; missing candidates are (-inf, -1, -1).
+ * group), best first; missing candidates are (-inf, -1, -1); a token whose score is -inf (a masked logit) is no candidate.
  *   VR_CHAT_GREEDY: score = penalised logit;  VR_CHAT_BEAM: score = penalised log-prob + beam_scores[i];
  *   VR_CHAT_SAMPLE: k = 1, top_k candidates (1..64), temperature > 0, noise selected by (seed, step, token). */
 int vr_chat_select(vr_chat_t ch, int32_t mode, int32_t n_groups, const int32_t* group_offsets, const int32_t* rows,
@@ -352,6 +352,42 @@ int vr_op_attention(int device_id, const void* q, int32_t ldq, const void* k, in
                     const int32_t* cu_q, const int32_t* cu_kv, int32_t B, int32_t heads,
                     int32_t head_dim, int32_t max_q, int32_t causal, int32_t q_shared,
                     float scale, void* stream);
+/* The decode step's weight streamer (gemm_skinny.hip): A bf16 [M <= 32][lda], W bf16 [N][ldw] (nn.Linear layout), K % 64 == 0,
+ * N % 4 == 0.  The CALLER pads: A readable up to 16 rows (32 when M > 16), W up to the next multiple of 256 rows.
+ *   swiglu 0: fp32 planes out[ksplit][M][ldo] (plane s at out + s * split_stride floats); split s covers the K-steps
+ *             [s * ceil(steps / ksplit), ...), a split past the end writes zeros; bias (f32 [N] or NULL) rides with split 0.
+ *   swiglu 1: ksplit 1, M <= 16, N % 32 == 0, W rows (and bias) interleaved [16 gate | 16 up]: out = bf16 act [M][ldo],
+ *             act[m][i] = silu(gate) * up, N / 2 columns.
+ * Rows >= M and columns >= N of out are not written. */
+int vr_op_gemm_skinny(int device_id, const void* A, int32_t lda, const void* W, int32_t ldw, int32_t M, int32_t N,
+                      int32_t K, int32_t ksplit, const float* bias, int32_t swiglu, void* out, int32_t ldo,
+                      int64_t split_stride, void* stream);
+/* The consumers of those planes (parts f32 [nsplit][rows][ldp], plane s at parts + s * split_stride), summed in plane order.
+ *   kind 0: x[rows][ldx] += alpha * sum_s parts[s] in place (dim columns), then out = bf16 RMSNorm(x) * weight [rows][ldo],
+ *           columns [dim, ldo) zero; out NULL: the update only.  dim <= 3584.
+ *   kind 1: out = bf16 [rows][ldo], out[m][i] = silu(gate) * up of the summed planes, i < dim, gate of column i at
+ *           (i / 16) * 32 + i % 16 and up 16 further (x, alpha, weight, eps unused). */
+int vr_op_plane_sum(int device_id, int32_t kind, const float* parts, int32_t nsplit, int64_t split_stride, int32_t ldp,
+                    int32_t rows, int32_t dim, float* x, int32_t ldx, float alpha, const float* weight, float eps,
+                    void* out, int32_t ldo, void* stream);
+/* Decode attention of one step (chat_kernels.hip), head_dim 64, E / 64 heads, scale 64^-0.5: q bf16 [n][E]; prompt cache bf16
+ * [layers][K|V][slots][max_len][E]; tail cache bf16 [layers][K|V][rows][max_new][E]; layer l.  Step row i attends to the
+ * slot_plen[step_slot[i]] prompt keys of its slot and to the tail keys 0..step_tail[i] of cache row step_row[i]; the rows of a
+ * slot are adjacent and form one group.  The key ranges come from the policy vr_chat_step uses; force_splits 1..8 sets the
+ * number of ranges of every group instead (0: the policy).  step_* and slot_plen are host arrays; att bf16 [n][E].
+ * Synchronises the stream. */
+int vr_op_chat_attention(int device_id, const void* q, const void* prompt, const void* tails, int32_t layers, int32_t l,
+                         int32_t E, int32_t slots, int32_t max_len, int32_t rows, int32_t max_new, int32_t n,
+                         const int32_t* step_row, const int32_t* step_slot, const int32_t* step_tail,
+                         const int32_t* slot_plen, int32_t force_splits, void* att, void* stream);
+/* vr_chat_select's kernels on the caller's logits: logits f32 [n][ld] and seen bit sets u32 [n][words] on the device (row i of
+ * both belongs to selected row i), group_offsets [n_groups + 1] and beam_scores [n] (or NULL) on the host.  mode VR_CHAT_*;
+ * K candidates are ranked (the sampler draws among them), kout are returned per group: out_* [n_groups][kout] on the host,
+ * outputs past the candidates are (-inf, -1, -1).  Ties: the lower flat index parent * V + token first. */
+int vr_op_chat_select(int device_id, int32_t mode, const float* logits, int32_t ld, int32_t V, const uint32_t* seen,
+                      int32_t words, int32_t n_groups, const int32_t* group_offsets, const float* beam_scores, int32_t K,
+                      int32_t kout, float repetition_penalty, float temperature, uint64_t seed, int32_t step,
+                      float* out_scores, int32_t* out_tokens, int32_t* out_parents, void* stream);
 
 #ifdef __cplusplus
 }

@@ -57,3 +57,69 @@ def op_attention(q, k, v, cu_q, cu_kv, heads, hd, max_q, causal, q_shared, scale
                                    int(q_shared), float(scale), None), "vr_op_attention")
     torch.cuda.synchronize()
     return out
+
+
+def from_bf16_bits(bits, device="cuda:0"):
+    """uint16 bf16 bit patterns (numpy) -> torch.bfloat16 on the device"""
+    import numpy as np
+    return torch.from_numpy(np.ascontiguousarray(bits).view(np.int16)).to(device).view(torch.bfloat16)
+
+
+def _i32(v):
+    return (C.c_int32 * len(v))(*[int(x) for x in v])
+
+
+def op_gemm_skinny(A, W, M, N, K, ksplit=1, bias=None, swiglu=False, out=None, ldo=None, split_stride=None):
+    """A bf16 [>= 16 / 32 rows][K], W bf16 [multiple of 256 rows][K] (the caller pads) -> `out`, written in place: fp32
+    planes [ksplit][rows][ldo], or bf16 act [rows][ldo] with swiglu."""
+    lib = _lib.load()
+    ldo = ldo or out.shape[-1]
+    split_stride = split_stride if split_stride is not None else (out.shape[-2] * out.shape[-1] if out.dim() == 3 else 0)
+    _lib.check(lib.vr_op_gemm_skinny(A.device.index or 0, P(A), A.stride(0), P(W), W.stride(0), M, N, K, ksplit, P(bias), int(swiglu),
+                                     P(out), ldo, split_stride, None), "vr_op_gemm_skinny")
+    torch.cuda.synchronize()
+    return out
+
+
+def op_plane_sum(kind, parts, rows, dim, x=None, alpha=1.0, weight=None, eps=1e-5, out=None):
+    """parts fp32 [nsplit][rows_alloc][ldp]; kind 0: x fp32 [rows][ldx] updated in place, out bf16 [rows][ldo] or None;
+    kind 1: out bf16 [rows][ldo] = SwiGLU of the summed planes."""
+    lib = _lib.load()
+    nsplit, ldp = parts.shape[0], parts.shape[2]
+    _lib.check(lib.vr_op_plane_sum(parts.device.index or 0, kind, P(parts), nsplit, parts.stride(0), ldp, rows, dim, P(x),
+                                   x.stride(0) if x is not None else 0, float(alpha), P(weight), float(eps), P(out),
+                                   out.stride(0) if out is not None else 0, None), "vr_op_plane_sum")
+    torch.cuda.synchronize()
+    return out
+
+
+def op_chat_attention(q, prompt, tails, l, step_row, step_slot, step_tail, slot_plen, force_splits=0):
+    """q bf16 [n][E]; prompt bf16 [L][2][slots][max_len][E]; tails bf16 [L][2][rows][max_new][E] -> att bf16 [n][E]"""
+    lib = _lib.load()
+    n, E = q.shape
+    L, _, slots, max_len, _ = prompt.shape
+    rows, max_new = tails.shape[2], tails.shape[3]
+    att = torch.full((n, E), 7.0, dtype=torch.bfloat16, device=q.device)
+    _lib.check(lib.vr_op_chat_attention(q.device.index or 0, P(q), P(prompt), P(tails), L, l, E, slots, max_len, rows, max_new, n,
+                                        _i32(step_row), _i32(step_slot), _i32(step_tail), _i32(slot_plen), force_splits, P(att),
+                                        None), "vr_op_chat_attention")
+    torch.cuda.synchronize()
+    return att
+
+
+def op_chat_select(mode, logits, seen, V, group_offsets, K, kout, beam_scores=None, penalty=1.0, temperature=1.0, seed=0, step=0):
+    """logits fp32 [n][ld], seen int32 words [n][words] (cuda) -> (scores, tokens, parents), numpy [groups][kout]"""
+    import numpy as np
+    lib = _lib.load()
+    G = len(group_offsets) - 1
+    n = group_offsets[-1]
+    sc = np.zeros((G, kout), dtype=np.float32)
+    tk = np.zeros((G, kout), dtype=np.int32)
+    pa = np.zeros((G, kout), dtype=np.int32)
+    bs = (C.c_float * n)(*[float(x) for x in beam_scores]) if beam_scores is not None else None
+    p32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
+    _lib.check(lib.vr_op_chat_select(logits.device.index or 0, int(mode), P(logits), logits.stride(0), V, P(seen), seen.stride(0), G,
+                                     _i32(group_offsets), bs, K, kout, float(penalty), float(temperature),
+                                     C.c_uint64(int(seed) & (2 ** 64 - 1)), int(step), sc.ctypes.data_as(C.POINTER(C.c_float)), p32(tk),
+                                     p32(pa), None), "vr_op_chat_select")
+    return sc, tk, pa

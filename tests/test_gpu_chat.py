@@ -144,6 +144,108 @@ def test_sampling_seeded_and_inside_top50(tiny):
         seen.add(tok)
 
 
+def _three_rows(chat, item):
+    """rows 0, 1, 2 on slot 0 with tails of 2, 5 and 9 tokens and different seen sets"""
+    chat.prefill(0, 0, item)
+    chat.reorder([1, 2], [0, 0])
+    for t in range(9):
+        rows = [r for r, n in ((0, 2), (1, 5), (2, 9)) if t < n]
+        chat.step([0] * len(rows), rows, [20 + 37 * r + 3 * t for r in rows])
+    assert [chat.row_state(r) for r in range(3)] == [(0, 2), (0, 5), (0, 9)]
+
+
+def _next_step(chat, rows, tokens, beam_order):
+    """step `rows` with `tokens`; -> per row (logits, greedy top-8 at penalty 1.2), and the beam candidates of the group"""
+    chat.step([0] * len(rows), rows, tokens)
+    per_row = [(chat.logits(r), chat.select(GREEDY, [[r]], 8, repetition_penalty=1.2)) for r in rows]
+    beam = chat.select(BEAM, [beam_order], 6, [-0.5, -0.7, -1.1], repetition_penalty=1.2)
+    return per_row, beam
+
+
+WIDE_SCORES = [-0.5, -0.52, -0.55]       # close together: every row of the group has candidates among the 64 best
+
+
+def _beam_by_parent(chat, scores):
+    """the 64 best beam candidates of the group [0, 1, 2] at penalty 1.2 -> per parent row its (score, token) list, best first"""
+    sc, tk, pa = chat.select(BEAM, [[0, 1, 2]], 64, scores, repetition_penalty=1.2)
+    return [[(sc[0, i], tk[0, i]) for i in range(64) if pa[0, i] == r] for r in range(3)]
+
+
+@pytest.mark.parametrize("parents", [[1, 2, 0], [2, 2, 0]])
+def test_reorder_is_a_permutation(tiny, parents):
+    """vr_chat_reorder with rows that are source AND destination (the two-pass copy of chat_tail_move / chat_seen_move):
+    after reorder([0, 1, 2], parents) row r IS row parents[r] of an untouched twin run — next-step logits bit for bit, and
+    the same greedy / beam candidates at penalty 1.2 (the seen sets moved with the tails)."""
+    cfg, enc, W, head, chat = tiny
+    item = _text_item(cfg, "<用户>three beams with tails of their own")
+    tok = [301, 302, 303]
+    _three_rows(chat, item)
+    twin, twin_beam = _next_step(chat, [0, 1, 2], tok, [0, 1, 2])
+    twin_wide = _beam_by_parent(chat, WIDE_SCORES)
+    assert not np.array_equal(twin[0][0], twin[1][0]) and not np.array_equal(twin[1][0], twin[2][0])
+    _three_rows(chat, item)
+    chat.reorder([0, 1, 2], parents)
+    assert [chat.row_state(r) for r in range(3)] == [(0, (2, 5, 9)[p]) for p in parents]
+    got, _ = _next_step(chat, [0, 1, 2], [tok[p] for p in parents], [0, 1, 2])
+    for r, p in enumerate(parents):
+        assert np.array_equal(got[r][0], twin[p][0]), (r, p)
+        for a, b in zip(got[r][1], twin[p][1]):
+            assert np.array_equal(a, b), (r, p)
+    # the beam select of the whole group, rows duplicated or not: row r carrying the twin's beam score of row parents[r]
+    # contributes the twin row's candidates, bit for bit, as far as both lists reach into the 64 best
+    wide = _beam_by_parent(chat, [WIDE_SCORES[p] for p in parents])
+    for r, p in enumerate(parents):
+        m = min(len(wide[r]), len(twin_wide[p]))
+        assert m >= 1, (r, p)
+        assert wide[r][:m] == twin_wide[p][:m], (r, p)
+    if sorted(parents) == [0, 1, 2]:         # the group with its old rows in the old order: the same candidates, parents included
+        where = [parents.index(p) for p in range(3)]
+        beam = chat.select(BEAM, [where], 6, [-0.5, -0.7, -1.1], repetition_penalty=1.2)
+        for a, b in zip(beam, twin_beam):
+            assert np.array_equal(a, b)
+
+
+def test_batch_mates_do_not_change_a_row(tiny):
+    """A row's sums do not depend on its batch mates (the design rule stated at chat_attn_kernel's gsplit): the logits of a row
+    stepped alone equal, bit for bit, those of the same row inside a 9-row step over 3 slots."""
+    cfg, enc, W, head, chat = tiny
+    items = [_text_item(cfg, "<用户>first prompt with several words in it"), _page_item(cfg, seed=3), _text_item(cfg, "<用户>second")]
+
+    def setup():
+        for s, it in enumerate(items):
+            chat.prefill(s, 3 * s, it)
+            chat.reorder([3 * s + 1, 3 * s + 2], [3 * s, 3 * s])
+        chat.step([r // 3 for r in range(9)], list(range(9)), [40 + 11 * r for r in range(9)])
+
+    setup()
+    chat.step([r // 3 for r in range(9)], list(range(9)), [500 + r for r in range(9)])
+    together = {r: chat.logits(r) for r in (0, 4, 8)}
+    for r in (0, 4, 8):
+        setup()
+        chat.step([r // 3], [r], [500 + r])
+        assert np.array_equal(chat.logits(r), together[r]), r
+
+
+def test_tail_across_the_chunk_edge(tiny):
+    """260 teacher-forced tokens with max_new = 300: the decode attention's tail loop crosses CHAT_KEYS = 256 keys.  Logits at
+    255, 256, 257 and 260 generated tokens against the oracle's encode of the extended prompt (first MI355X run: 6.2e-3,
+    5.5e-3, 8.0e-3, 7.8e-3)."""
+    cfg, enc, W, head, _ = tiny
+    chat = HipChat(enc, max_len=330, max_rows=1, dim_model_base=DMB, max_slots=1, max_new=300)
+    chat.load_head(head.cuda())
+    item = _text_item(cfg, "<用户>a long answer follows")
+    toks = np.random.default_rng(7).integers(16, cfg.vocab_size, 260).tolist()
+    chat.prefill(0, 0, item)
+    errs = {}
+    for n, t in enumerate(toks, start=1):
+        chat.step([0], [0], [t])
+        if n in (255, 256, 257, 260):
+            errs[n] = _rel(chat.logits(0), _oracle_logits(cfg, W, head, item, toks[:n]))
+    chat.close()
+    print("tail across the chunk edge: rel err per generated length", errs)
+    assert chat.max_new == 300 and all(e < LOGIT_BAR for e in errs.values()), errs
+
+
 def test_capacity_errors_leave_state(tiny):
     cfg, enc, W, head, chat = tiny
     item = _text_item(cfg, "<用户>capacity")

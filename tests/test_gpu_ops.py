@@ -1,5 +1,6 @@
 """-m gpu: every HIP kernel, called through the C ABI, against an fp32 restatement of the same
-op on the same (bf16-rounded) inputs.  Tolerances are stated per test."""
+op on the same (bf16-rounded) inputs.  Tolerances are stated per test.
+The decode step's kernels (chat_kernels.hip, gemm_skinny.hip, swiglu_sum, rmsnorm_accum): tests/test_gpu_decode_ops.py."""
 import math
 
 import numpy as np

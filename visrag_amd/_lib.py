@@ -99,6 +99,12 @@ SIGNATURES = {
     "vr_op_norm": (C.c_int, [C.c_int, _i32, _vp, _i32, _i32, _vp, _vp, _f32, _vp, _i32, _vp]),
     "vr_op_attention": (C.c_int, [C.c_int, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32,
                                   _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
+    "vr_op_gemm_skinny": (C.c_int, [C.c_int, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i64, _vp]),
+    "vr_op_plane_sum": (C.c_int, [C.c_int, _i32, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _i32, _f32, _vp, _f32, _vp, _i32, _vp]),
+    "vr_op_chat_attention": (C.c_int, [C.c_int, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32),
+                                       C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _i32, _vp, _vp]),
+    "vr_op_chat_select": (C.c_int, [C.c_int, _i32, _vp, _i32, _i32, _vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_f32), _i32, _i32,
+                                    _f32, _f32, C.c_uint64, _i32, C.POINTER(_f32), C.POINTER(_i32), C.POINTER(_i32), _vp]),
     "vr_chat_create": (C.c_int, [_vp, C.POINTER(VRChatConfig), C.POINTER(_vp)]),
     "vr_chat_destroy": (C.c_int, [_vp]),
     "vr_chat_load_head": (C.c_int, [_vp, _vp, C.POINTER(_i64), _i32, _i32, _i32]),

@@ -170,7 +170,7 @@ extern "C" int vr_chat_step(vr_chat_t ch, int32_t n, const int32_t* slots, const
     // ---- every check before any state changes
     ChatStep st{};
     st.n = n;
-    std::vector<char> used(R, 0), slot_done(ch->c.max_slots, 0);
+    std::vector<char> used(R, 0);
     for (int i = 0; i < n; ++i) {
         const int sl = slots[i], r = rows[i], t = tokens[i];
         if (sl < 0 || sl >= ch->c.max_slots || ch->plen[sl] <= 0) return fail(VR_ERR_INVALID, "step row %d: slot %d holds no prompt", i, sl);
@@ -181,22 +181,10 @@ extern "C" int vr_chat_step(vr_chat_t ch, int32_t n, const int32_t* slots, const
         const int len = ch->row_slot[r] == sl ? ch->row_len[r] : 0;
         if (ch->plen[sl] + len + 1 > ch->c.max_len || len + 1 > ch->c.max_new)
             return fail(VR_ERR_CAPACITY, "row %d would exceed max_len=%d / max_new=%d", r, ch->c.max_len, ch->c.max_new);
-        if (i == 0 || slots[i - 1] != sl) {
-            if (slot_done[sl]) return fail(VR_ERR_INVALID, "the rows of slot %d must be adjacent", sl);
-            slot_done[sl] = 1;
-            st.g_lo[st.groups] = i;
-            st.plen[st.groups] = ch->plen[sl];
-            st.groups++;
-        }
         st.row[i] = r; st.slot[i] = sl; st.tail[i] = len; st.pos[i] = ch->plen[sl] + len; st.token[i] = t;
     }
-    st.g_lo[st.groups] = n;
-    int S = 1;                                           // prompt-key ranges of the attention: ~CHAT_KEYS keys each, per prompt
-    for (int g = 0; g < st.groups; ++g) {
-        st.gsplit[g] = std::min(CHAT_ATT_SPLITS, std::max(1, (st.plen[g] + CHAT_KEYS - 1) / CHAT_KEYS));
-        S = std::max(S, st.gsplit[g]);
-        for (int i = st.g_lo[g]; i < st.g_lo[g + 1]; ++i) st.rsplit[i] = st.gsplit[g];
-    }
+    const int S = chat_step_groups(st, ch->plen.data(), ch->c.max_slots);      // groups and their prompt-key ranges
+    if (!S) return fail(VR_ERR_INVALID, "the rows of a slot must be adjacent");
     VRCHK(set_dev(ch->model->device));
     hipStream_t s = (hipStream_t)stream;
     vr_model_s* m = ch->model;

@@ -2,6 +2,9 @@
 // embedding, q|k|v plane sum + RoPE + KV-tail append, decode attention for head_dim 64 (full multi-head), and the logits
 // processing of HF generate (repetition penalty, log_softmax + beam scores, top-k candidates, sampling).
 // The decode step's GEMMs are the weight streamer of gemm_skinny.hip; everything here is small and HBM / latency bound.
+#include <algorithm>
+#include <vector>
+
 #include "common.h"
 #include "gen_math.h"
 #include "kernels.h"
@@ -259,7 +262,7 @@ __device__ __forceinline__ float chat_score(int mode, float x, bool seen, float 
 
 // Top-K keys (score, -flat index) of group g's candidates: flat index f = r * V + tok over the group's rows.  Grid
 // (CHAT_SEL_WGS, groups): workgroup w takes a slice of the flat range and finds its K best by K rounds of a max below the
-// previous round's key (keys are distinct: the index is part of them).  Key 0 = no candidate.
+// previous round's key (keys are distinct: the index is part of them).  Key 0 = no candidate; a score of -inf is none either.
 __global__ __launch_bounds__(256) void chat_topk_partial_kernel(ChatSel sel, int mode, const float* __restrict__ logits, int ld, int V,
                                                                 const unsigned* __restrict__ seen, int words, const float* __restrict__ lse,
                                                                 float pen, int K, unsigned long long* __restrict__ part) {
@@ -277,7 +280,8 @@ __global__ __launch_bounds__(256) void chat_topk_partial_kernel(ChatSel sel, int
             const float x = logits[(size_t)sel.lrow[i] * ld + tok];
             const bool sn = (seen[(size_t)sel.srow[i] * words + (tok >> 5)] >> (tok & 31)) & 1u;
             const float s = chat_score(mode, x, sn, pen, mode == CHAT_SEL_BEAM ? lse[i] : 0.f, sel.bscore[i]);
-            const unsigned long long key = ((unsigned long long)f2ord(s) << 32) | (unsigned)(~f);
+            // (a score of -inf — a masked logit — is no candidate: key 0, like the end of the range)
+            const unsigned long long key = s > -INFINITY ? ((unsigned long long)f2ord(s) << 32) | (unsigned)(~f) : 0ull;
             if (key < prev && key > best) best = key;
         }
         best = block_key_max(best, red);
@@ -334,7 +338,8 @@ __global__ __launch_bounds__(256) void chat_topk_final_kernel(const unsigned lon
     unsigned long long key = tok >= 0 ? ((unsigned long long)f2ord(v) << 32) | (unsigned)(~(unsigned)tid) : 0ull;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) key = key_max(key, __shfl_xor(key, off, 64));
-    const int win = key ? (int)(~(unsigned)(key & 0xFFFFFFFFull)) : -1;
+    // (no candidate at all — every score of the row -inf or NaN: lane 0 reports "none", its s / tok / par are then -inf, -1, -1)
+    const int win = key ? (int)(~(unsigned)(key & 0xFFFFFFFFull)) : 0;
     if (tid == win) {
         for (int j = 0; j < kout; ++j) {
             o_score[(size_t)g * kout + j] = j == 0 ? s : -INFINITY;
@@ -354,6 +359,29 @@ hipError_t launch_chat_qkv(const ChatStep& st, const float* parts, int n_parts, 
     hipLaunchKernelGGL(chat_qkv_kernel, dim3(st.n, heads), dim3(96), 0, s, st, parts, n_parts, plane, ldp, rope, E, (bf16_t*)q_out,
                        (bf16_t*)tails, l, max_rows, max_new);
     return hipGetLastError();
+}
+int chat_step_groups(ChatStep& st, const int* slot_plen, int max_slots, int force_splits) {
+    std::vector<char> slot_done(max_slots, 0);
+    st.groups = 0;
+    for (int i = 0; i < st.n; ++i) {
+        const int sl = st.slot[i];
+        if (i == 0 || st.slot[i - 1] != sl) {
+            if (slot_done[sl]) return 0;
+            slot_done[sl] = 1;
+            st.g_lo[st.groups] = i;
+            st.plen[st.groups] = slot_plen[sl];
+            st.groups++;
+        }
+    }
+    st.g_lo[st.groups] = st.n;
+    int S = 1;                                           // prompt-key ranges of the attention: ~CHAT_KEYS keys each, per prompt
+    for (int g = 0; g < st.groups; ++g) {
+        st.gsplit[g] = force_splits > 0 ? std::min(CHAT_ATT_SPLITS, force_splits)
+                                        : std::min(CHAT_ATT_SPLITS, std::max(1, (st.plen[g] + CHAT_KEYS - 1) / CHAT_KEYS));
+        S = std::max(S, st.gsplit[g]);
+        for (int i = st.g_lo[g]; i < st.g_lo[g + 1]; ++i) st.rsplit[i] = st.gsplit[g];
+    }
+    return S;
 }
 hipError_t launch_chat_attn(const ChatStep& st, const void* q, const void* prompt, const void* tails, int l, int E, int heads,
                             const ChatCaps& cap, int S_max, float* po, float* pml, void* att, hipStream_t s) {

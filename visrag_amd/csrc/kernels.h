@@ -122,6 +122,11 @@ struct ChatSel {
     int lrow[CHAT_MAX_ROWS], srow[CHAT_MAX_ROWS], g_lo[CHAT_MAX_ROWS + 1];
     float bscore[CHAT_MAX_ROWS];
 };
+// The attention's view of a step whose n, slot[] are set: groups of adjacent rows with one slot (g_lo, groups, plen[g] =
+// slot_plen[slot]) and their prompt-key ranges (gsplit / rsplit: ~CHAT_KEYS keys each, at most CHAT_ATT_SPLITS).  Returns the
+// largest gsplit (launch_chat_attn's S_max), or 0 when the rows of a slot are not adjacent.  force_splits in
+// 1..CHAT_ATT_SPLITS overrides the policy for every group (op-level tests: ranges that hold no key).
+int chat_step_groups(ChatStep& st, const int* slot_plen, int max_slots, int force_splits = 0);
 hipError_t launch_chat_embed(const ChatStep& st, const void* table, int E, float scale, float* h, unsigned* seen, int words, hipStream_t s);
 hipError_t launch_chat_qkv(const ChatStep& st, const float* parts, int n_parts, size_t plane, int ldp, const float* rope, int E, int heads,
                            void* q_out, void* tails, int l, int max_rows, int max_new, hipStream_t s);

@@ -154,3 +154,140 @@ extern "C" int vr_op_attention(int device_id, const void* q, int32_t ldq, const 
     HIPCHK(launch_attention(a, (hipStream_t)stream));
     return VR_OK;
 }
+
+// ---- the decode step's kernels (gemm_skinny.hip, norm.hip, chat_kernels.hip) ---
+extern "C" int vr_op_gemm_skinny(int device_id, const void* A, int32_t lda, const void* W, int32_t ldw, int32_t M, int32_t N,
+                                 int32_t K, int32_t ksplit, const float* bias, int32_t swiglu, void* out, int32_t ldo,
+                                 int64_t split_stride, void* stream) {
+    if (!A || !W || !out) return fail(VR_ERR_INVALID, "NULL argument");
+    if (M < 1 || N < 1 || K < 64 || K % 64 || N % 4) return fail(VR_ERR_INVALID, "need M >= 1, N %% 4 == 0, K %% 64 == 0");
+    if (M > 32 || (swiglu && M > 16)) return fail(VR_ERR_CAPACITY, "%d rows: at most 32 (16 with swiglu)", M);
+    if (ksplit < 1 || ksplit > 64) return fail(VR_ERR_INVALID, "ksplit must be 1..64");
+    if (lda < K || ldw < K || lda % 8 || ldw % 8) return fail(VR_ERR_INVALID, "lda / ldw must cover K and be multiples of 8");
+    if (((uintptr_t)A | (uintptr_t)W | (uintptr_t)out | (uintptr_t)bias) & 15) return fail(VR_ERR_INVALID, "pointers must be 16-byte aligned");
+    if (swiglu) {
+        if (ksplit != 1 || N % 32) return fail(VR_ERR_INVALID, "swiglu needs ksplit 1 and N %% 32 == 0");
+        if (ldo < N / 2 || ldo % 8) return fail(VR_ERR_INVALID, "swiglu: ldo must cover N / 2 and be a multiple of 8");
+    } else {
+        if (ldo < N || ldo % 4) return fail(VR_ERR_INVALID, "ldo must cover N and be a multiple of 4");
+        if (ksplit > 1 && (split_stride < (int64_t)M * ldo || split_stride % 4)) return fail(VR_ERR_INVALID, "split_stride must cover a plane of M x ldo and be a multiple of 4");
+    }
+    VRCHK(set_dev(device_id));
+    GemmArgs a{};
+    a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.M = M; a.N = N; a.K = K; a.bias = bias; a.out = out; a.ldo = ldo;
+    a.ksplit = ksplit; a.split_stride = (size_t)split_stride;
+    HIPCHK(launch_gemm_skinny(a, (hipStream_t)stream, swiglu != 0));
+    return VR_OK;
+}
+
+extern "C" int vr_op_plane_sum(int device_id, int32_t kind, const float* parts, int32_t nsplit, int64_t split_stride, int32_t ldp,
+                               int32_t rows, int32_t dim, float* x, int32_t ldx, float alpha, const float* weight, float eps,
+                               void* out, int32_t ldo, void* stream) {
+    if (!parts) return fail(VR_ERR_INVALID, "NULL argument");
+    if (kind != 0 && kind != 1) return fail(VR_ERR_INVALID, "kind %d: 0 (residual + RMSNorm), 1 (SwiGLU)", kind);
+    if (rows < 1 || dim < 1 || nsplit < 1 || nsplit > 64) return fail(VR_ERR_INVALID, "need rows, dim >= 1 and nsplit 1..64");
+    if (split_stride % 4 || (nsplit > 1 && split_stride < (int64_t)rows * ldp)) return fail(VR_ERR_INVALID, "split_stride must cover a plane of rows x ldp and be a multiple of 4");
+    VRCHK(set_dev(device_id));
+    if (kind == 0) {
+        if (!x || (out && !weight)) return fail(VR_ERR_INVALID, "NULL argument");
+        if (dim > 3584 || (out && ldo > 3584)) return fail(VR_ERR_CAPACITY, "rows of at most 3584 columns");
+        if (dim % 4 || ldx % 4 || ldp % 4 || ldx < dim || ldp < dim || (out && (ldo % 4 || ldo < dim)))
+            return fail(VR_ERR_INVALID, "dim, ldx, ldp, ldo must be multiples of 4 and the strides cover dim");
+        if (((uintptr_t)parts | (uintptr_t)x | (uintptr_t)weight) & 15 || (uintptr_t)out & 7) return fail(VR_ERR_INVALID, "misaligned pointer");
+        HIPCHK(launch_rmsnorm_accum(x, rows, dim, ldx, parts, nsplit, (size_t)split_stride, ldp, alpha, weight, eps, out, ldo, (hipStream_t)stream));
+    } else {
+        if (!out) return fail(VR_ERR_INVALID, "NULL argument");
+        if (dim % 16 || ldp < 2 * dim || ldo < dim) return fail(VR_ERR_INVALID, "swiglu: dim %% 16 == 0, ldp >= 2 dim, ldo >= dim");
+        HIPCHK(launch_swiglu_sum(parts, nsplit, (size_t)split_stride, ldp, rows, dim, out, ldo, (hipStream_t)stream));
+    }
+    return VR_OK;
+}
+
+// grow-only scratch of the two entries below, per device (the sampler test calls vr_op_chat_select thousands of times)
+static std::map<int, DevBuf> g_chat_op_scratch;
+
+extern "C" int vr_op_chat_attention(int device_id, const void* q, const void* prompt, const void* tails, int32_t layers, int32_t l,
+                                    int32_t E, int32_t slots, int32_t max_len, int32_t rows, int32_t max_new, int32_t n,
+                                    const int32_t* step_row, const int32_t* step_slot, const int32_t* step_tail,
+                                    const int32_t* slot_plen, int32_t force_splits, void* att, void* stream) {
+    if (!q || !prompt || !tails || !step_row || !step_slot || !step_tail || !slot_plen || !att) return fail(VR_ERR_INVALID, "NULL argument");
+    if (E < 64 || E % 64) return fail(VR_ERR_INVALID, "E must be a multiple of the head dim 64");
+    if (layers < 1 || l < 0 || l >= layers) return fail(VR_ERR_INVALID, "layer %d of %d", l, layers);
+    if (slots < 1 || max_len < 1 || rows < 1 || max_new < 1) return fail(VR_ERR_INVALID, "bad cache geometry");
+    if (force_splits < 0 || force_splits > CHAT_ATT_SPLITS) return fail(VR_ERR_INVALID, "force_splits must be 0..%d", CHAT_ATT_SPLITS);
+    if (n < 1) return fail(VR_ERR_INVALID, "n must be positive");
+    if (n > CHAT_MAX_ROWS) return fail(VR_ERR_CAPACITY, "%d rows exceed %d", n, CHAT_MAX_ROWS);
+    if (((uintptr_t)q | (uintptr_t)prompt | (uintptr_t)tails | (uintptr_t)att) & 15) return fail(VR_ERR_INVALID, "pointers must be 16-byte aligned");
+    ChatStep st{};
+    st.n = n;
+    std::vector<char> used(rows, 0);
+    for (int i = 0; i < n; ++i) {
+        const int r = step_row[i], sl = step_slot[i], t = step_tail[i];
+        if (sl < 0 || sl >= slots || slot_plen[sl] < 1) return fail(VR_ERR_INVALID, "step row %d: slot %d holds no prompt", i, sl);
+        if (slot_plen[sl] > max_len) return fail(VR_ERR_CAPACITY, "slot %d: %d prompt keys exceed max_len=%d", sl, slot_plen[sl], max_len);
+        if (r < 0 || r >= rows || used[r]) return fail(VR_ERR_INVALID, "step row %d: row %d out of range or repeated", i, r);
+        if (t < 0) return fail(VR_ERR_INVALID, "step row %d: negative tail index", i);
+        if (t >= max_new) return fail(VR_ERR_CAPACITY, "step row %d: tail index %d exceeds max_new=%d", i, t, max_new);
+        used[r] = 1;
+        st.row[i] = r; st.slot[i] = sl; st.tail[i] = t; st.pos[i] = slot_plen[sl] + t;
+    }
+    const int S = chat_step_groups(st, slot_plen, slots, force_splits);
+    if (!S) return fail(VR_ERR_INVALID, "the rows of a slot must be adjacent");
+    VRCHK(set_dev(device_id));
+    hipStream_t s = (hipStream_t)stream;
+    const int H = E / 64;
+    const size_t po = (size_t)CHAT_MAX_ROWS * H * CHAT_ATT_SPLITS * 64 * 4, pml = (size_t)CHAT_MAX_ROWS * H * CHAT_ATT_SPLITS * 2 * 4;
+    DevBuf& sc = g_chat_op_scratch[device_id];
+    if (sc.bytes < po + pml) { HIPCHK(hipStreamSynchronize(s)); VRCHK(sc.reserve(po + pml)); }
+    const ChatCaps caps{slots, max_len, rows, max_new};
+    HIPCHK(launch_chat_attn(st, q, prompt, tails, l, E, H, caps, S, sc.as<float>(), (float*)((char*)sc.p + po), att, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
+}
+
+extern "C" int vr_op_chat_select(int device_id, int32_t mode, const float* logits, int32_t ld, int32_t V, const uint32_t* seen,
+                                 int32_t words, int32_t n_groups, const int32_t* group_offsets, const float* beam_scores, int32_t K,
+                                 int32_t kout, float repetition_penalty, float temperature, uint64_t seed, int32_t step,
+                                 float* out_scores, int32_t* out_tokens, int32_t* out_parents, void* stream) {
+    if (!logits || !seen || !group_offsets || !out_scores || !out_tokens || !out_parents) return fail(VR_ERR_INVALID, "NULL argument");
+    if (mode < VR_CHAT_GREEDY || mode > VR_CHAT_SAMPLE) return fail(VR_ERR_INVALID, "mode %d", mode);
+    if (V < 1 || ld < V || words < (V + 31) / 32) return fail(VR_ERR_INVALID, "need V >= 1, ld >= V, words >= ceil(V / 32)");
+    if (n_groups < 1 || n_groups > CHAT_MAX_ROWS || group_offsets[0] != 0) return fail(VR_ERR_INVALID, "bad groups");
+    const int n = group_offsets[n_groups];
+    if (n > CHAT_MAX_ROWS) return fail(VR_ERR_CAPACITY, "%d rows exceed %d", n, CHAT_MAX_ROWS);
+    if (K < 1 || kout < 1) return fail(VR_ERR_INVALID, "K / kout must be positive");
+    if (K > CHAT_TOPK_MAX || kout > CHAT_TOPK_MAX) return fail(VR_ERR_CAPACITY, "K / kout exceed %d", CHAT_TOPK_MAX);
+    if (!(repetition_penalty > 0.f)) return fail(VR_ERR_INVALID, "repetition_penalty must be positive");
+    if (mode == VR_CHAT_SAMPLE && !(temperature > 0.f)) return fail(VR_ERR_INVALID, "sampling: temperature must be positive");
+    ChatSel sel{};
+    sel.n = n; sel.groups = n_groups;
+    for (int g = 0; g <= n_groups; ++g) sel.g_lo[g] = group_offsets[g];
+    for (int g = 0; g < n_groups; ++g) {
+        const int nb = group_offsets[g + 1] - group_offsets[g];
+        if (nb < 1) return fail(VR_ERR_INVALID, "empty group %d", g);
+        if (mode != VR_CHAT_BEAM && nb != 1) return fail(VR_ERR_INVALID, "greedy / sampling groups hold one row");
+    }
+    for (int i = 0; i < n; ++i) {
+        sel.lrow[i] = i; sel.srow[i] = i;
+        sel.bscore[i] = mode == VR_CHAT_BEAM && beam_scores ? beam_scores[i] : 0.f;
+    }
+    VRCHK(set_dev(device_id));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t b_lse = CHAT_MAX_ROWS * 4, b_part = (size_t)CHAT_MAX_ROWS * CHAT_SEL_WGS * CHAT_TOPK_MAX * 8, b_out = (size_t)CHAT_MAX_ROWS * CHAT_TOPK_MAX * 4;
+    DevBuf& sc = g_chat_op_scratch[device_id];
+    if (sc.bytes < b_part + b_lse + 3 * b_out) { HIPCHK(hipStreamSynchronize(s)); VRCHK(sc.reserve(b_part + b_lse + 3 * b_out)); }
+    unsigned long long* part = sc.as<unsigned long long>();
+    float* lse = (float*)((char*)sc.p + b_part);
+    float* o_score = (float*)((char*)lse + b_lse);
+    int* o_tok = (int*)((char*)o_score + b_out);
+    int* o_par = (int*)((char*)o_tok + b_out);
+    const int cm = mode == VR_CHAT_BEAM ? CHAT_SEL_BEAM : mode == VR_CHAT_SAMPLE ? CHAT_SEL_SAMPLE : CHAT_SEL_GREEDY;
+    HIPCHK(launch_chat_select(sel, cm, logits, ld, V, (const unsigned*)seen, words, repetition_penalty, temperature, K, kout,
+                              (unsigned long long)seed, (unsigned)step, lse, part, o_score, o_tok, o_par, s));
+    const size_t cnt = (size_t)n_groups * kout;
+    HIPCHK(hipMemcpyAsync(out_scores, o_score, cnt * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out_tokens, o_tok, cnt * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out_parents, o_par, cnt * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
+}
