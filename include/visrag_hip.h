@@ -213,6 +213,17 @@ int vr_chat_load_head(vr_chat_t ch, const void* data, const int64_t* shape, int3
 int vr_chat_prefill(vr_chat_t ch, int32_t slot, int32_t row, const uint8_t* const* slices, const int32_t* slice_hw,
                     int32_t n_slices, int32_t slices_on_device, const int32_t* input_ids, int32_t T,
                     const int32_t* vision_rows, void* stream);
+/* The same for B prompts in ONE packed pass (the arguments of vr_encode for B items: seq_offsets [B + 1], vision_rows index the
+ * packed rows): every layer's K / V rows of prompt b go to slot slots[b], its last token's logits to row rows[b], which is
+ * bound to the slot as vr_chat_prefill binds it; rows that continued one of the slots lose their tails; the logits of rows
+ * the call does not name stay readable.  The head streams its weights once per run of adjacent rows[] values.  The tile
+ * and split-K choices of the decoder pass follow the packed token count, so a prompt's logits equal those of a lone
+ * vr_chat_prefill to bf16 accuracy, not bit for bit.  Checked before anything changes: slots distinct and in range, rows
+ * distinct and in range (VR_ERR_INVALID); a prompt of max_len tokens or more, more than the model's max_tokens tokens or
+ * max_seqs prompts in all (VR_ERR_CAPACITY). */
+int vr_chat_prefill_batch(vr_chat_t ch, int32_t B, const int32_t* slots, const int32_t* rows, const uint8_t* const* slices,
+                          const int32_t* slice_hw, int32_t n_slices, int32_t slices_on_device, const int32_t* input_ids,
+                          const int32_t* seq_offsets, const int32_t* vision_rows, void* stream);
 /* Append tokens[i] to row rows[i] of prompt slot slots[i] (the rows of one slot adjacent) and compute each row's logits:
  * one pass over the weights for all n rows.  The token joins the row's seen set.  A row with an empty tail may start on any
  * slot.  n > max_rows, or a row past max_len or max_new: VR_ERR_CAPACITY, nothing changed. */
@@ -388,6 +399,13 @@ int vr_op_chat_select(int device_id, int32_t mode, const float* logits, int32_t 
                       int32_t words, int32_t n_groups, const int32_t* group_offsets, const float* beam_scores, int32_t K,
                       int32_t kout, float repetition_penalty, float temperature, uint64_t seed, int32_t step,
                       float* out_scores, int32_t* out_tokens, int32_t* out_parents, void* stream);
+/* The batched prefill's per-layer K / V scatter (chat_kernels.hip) on the caller's buffers, ONE layer's planes: qkv bf16
+ * [seq_offsets[B]][ld], row t = q | k | v of a packed token (k at column E, v at 2 E; ld >= 3 E; E, ld multiples of 8);
+ * kplane / vplane bf16 [n_slots][max_len][E].  Token t of prompt b (seq_offsets[b] <= t < seq_offsets[b + 1]) goes to
+ * row t - seq_offsets[b] of slot slots[b]; nothing else of the planes is written.  slots are distinct, every prompt holds
+ * 1..max_len rows, B <= 16; seq_offsets and slots are host arrays, all pointers 16-byte aligned.  Synchronises the stream. */
+int vr_op_chat_prompt_scatter(int device_id, const void* qkv, int32_t ld, int32_t E, int32_t B, const int32_t* seq_offsets,
+                              const int32_t* slots, int32_t n_slots, int32_t max_len, void* kplane, void* vplane, void* stream);
 
 #ifdef __cplusplus
 }

@@ -112,15 +112,18 @@ class Hyps:
         return self.worst_score >= best_sum_logprobs / cur_len
 
 
-def beam(lm):
-    """_beam_search + BeamSearchScorer (4.40.2) for one item with inputs_embeds (input_ids start empty: decoder_prompt_len 0)."""
+def beam(lm, max_new=None, nbest=False):
+    """_beam_search + BeamSearchScorer (4.40.2) for one item with inputs_embeds (input_ids start empty: decoder_prompt_len 0).
+    nbest: also return every finished hypothesis as (score, output ids), best first — finalize's repeated
+    `sorted(...).pop()`, what num_return_sequences > 1 and output_scores hand out as sequences / sequences_scores."""
+    max_new = MAX_NEW if max_new is None else max_new
     V = lm.model.llm.config.vocab_size
     input_ids = [[] for _ in range(NUM_BEAMS)]
     beam_scores = torch.zeros(NUM_BEAMS)
     beam_scores[1:] = -1e9
     hyps = Hyps(NUM_BEAMS)
     queries, steps, done = {}, [], False
-    for step in range(MAX_NEW):
+    for step in range(max_new):
         rows = []
         for b in range(NUM_BEAMS):
             key = tuple(input_ids[b])
@@ -159,7 +162,10 @@ def beam(lm):
         for b in range(NUM_BEAMS):
             hyps.add(list(input_ids[b]), float(beam_scores[b]), len(input_ids[b]))
     best_score, best = sorted(hyps.beams, key=lambda x: x[0]).pop()
-    out = best + ([EOS] if len(best) < MAX_NEW else [])
+    out = best + ([EOS] if len(best) < max_new else [])
+    if nbest:
+        ranked = [(sc, h + ([EOS] if len(h) < max_new else [])) for sc, h in sorted(hyps.beams, key=lambda x: x[0])[::-1]]
+        return out, best_score, queries, steps, ranked
     return out, best_score, queries, steps
 
 

@@ -105,11 +105,14 @@ SIGNATURES = {
                                        C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _i32, _vp, _vp]),
     "vr_op_chat_select": (C.c_int, [C.c_int, _i32, _vp, _i32, _i32, _vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_f32), _i32, _i32,
                                     _f32, _f32, C.c_uint64, _i32, C.POINTER(_f32), C.POINTER(_i32), C.POINTER(_i32), _vp]),
+    "vr_op_chat_prompt_scatter": (C.c_int, [C.c_int, _vp, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _vp, _vp, _vp]),
     "vr_chat_create": (C.c_int, [_vp, C.POINTER(VRChatConfig), C.POINTER(_vp)]),
     "vr_chat_destroy": (C.c_int, [_vp]),
     "vr_chat_load_head": (C.c_int, [_vp, _vp, C.POINTER(_i64), _i32, _i32, _i32]),
     "vr_chat_prefill": (C.c_int, [_vp, _i32, _i32, C.POINTER(_vp), C.POINTER(_i32), _i32, _i32, C.POINTER(_i32), _i32,
                                   C.POINTER(_i32), _vp]),
+    "vr_chat_prefill_batch": (C.c_int, [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_vp), C.POINTER(_i32), _i32, _i32,
+                                        C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp]),
     "vr_chat_step": (C.c_int, [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp]),
     "vr_chat_select": (C.c_int, [_vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_f32), _i32, _f32, _f32, _i32,
                                  C.c_uint64, _i32, C.POINTER(_f32), C.POINTER(_i32), C.POINTER(_i32), _vp]),

@@ -20,6 +20,7 @@ struct vr_chat_s {
     DevBuf rope;                          // f32 [max_len][64], the table of vr_model_finalize extended to max_len
     DevBuf prompt, tails, seen;           // caches; seen-id bit sets [max_rows][words]
     DevBuf w_h, w_xn, w_q, w_att, w_act, w_part, w_po, w_pml, w_logits, w_lse, w_sel, w_out, w_reps, w_move, w_move_seen;
+    DevBuf w_pxn;                         // bf16 [2 * CHAT_MAX_ROWS][E]: the normed last rows of a batched prefill (the head reads 16 rows from any of the first 16)
     std::vector<int> plen;                // per slot: prompt tokens (0 = none)
     std::vector<int> row_slot, row_len;   // per row: its prompt slot (-1 = unbound), generated tokens in its tail
     std::vector<int> lpos;                // per row: its logits row in w_logits (-1 = none)
@@ -74,7 +75,8 @@ extern "C" int vr_chat_create(vr_model_t m, const vr_chat_config_t* cfg, vr_chat
         (rc = ch->w_pml.alloc((size_t)CHAT_MAX_ROWS * H * CHAT_ATT_SPLITS * 2 * 4)) ||
         (rc = ch->w_logits.alloc((size_t)2 * R * ch->Vpad * 4)) || (rc = ch->w_lse.alloc(CHAT_MAX_ROWS * 4)) ||
         (rc = ch->w_sel.alloc((size_t)CHAT_MAX_ROWS * CHAT_SEL_WGS * CHAT_TOPK_MAX * 8)) ||
-        (rc = ch->w_out.alloc((size_t)CHAT_MAX_ROWS * CHAT_TOPK_MAX * 12)) || (rc = ch->w_reps.alloc((size_t)E * 4)) ||
+        (rc = ch->w_out.alloc((size_t)CHAT_MAX_ROWS * CHAT_TOPK_MAX * 12)) || (rc = ch->w_reps.alloc((size_t)CHAT_MAX_ROWS * E * 4)) ||
+        (rc = ch->w_pxn.alloc((size_t)2 * CHAT_MAX_ROWS * E * 2)) ||
         (rc = ch->w_move_seen.alloc((size_t)CHAT_MAX_ROWS * ch->words * 4)))
         return bail(rc);
     ch->plen.assign(cfg->max_slots, 0);
@@ -158,6 +160,91 @@ extern "C" int vr_chat_prefill(vr_chat_t ch, int32_t slot, int32_t row, const ui
     ch->row_slot[row] = slot;
     ch->row_len[row] = 0;
     ch->lpos[row] = lrow;
+    return VR_OK;
+}
+
+// ---- batched prefill: B prompts in ONE packed encode pass (the pass is ragged already; this is the cache and logits side)
+struct ChatPrefillBatchCtx { vr_chat_s* ch; ChatBatch bt; };
+static int chat_prefill_batch_layer(void* ctx, int l, const void* qkv, int ldqkv, int T, hipStream_t s) {
+    const ChatPrefillBatchCtx* p = (const ChatPrefillBatchCtx*)ctx;
+    vr_chat_s* ch = p->ch;
+    if (T != p->bt.off[p->bt.n]) return fail(VR_ERR_STATE, "prefill hook: %d rows, expected %d", T, p->bt.off[p->bt.n]);
+    HIPCHK(launch_chat_prompt_scatter(p->bt, qkv, ldqkv, ch->E, ch->c.max_len, (char*)ch->prompt.p + chat_prompt_off(ch, l, 0, 0),
+                                      (char*)ch->prompt.p + chat_prompt_off(ch, l, 1, 0), s));
+    return VR_OK;
+}
+
+extern "C" int vr_chat_prefill_batch(vr_chat_t ch, int32_t B, const int32_t* slots, const int32_t* rows, const uint8_t* const* slices,
+                                     const int32_t* slice_hw, int32_t n_slices, int32_t slices_on_device, const int32_t* input_ids,
+                                     const int32_t* seq_offsets, const int32_t* vision_rows, void* stream) {
+    if (!ch || !slots || !rows || !input_ids || !seq_offsets) return fail(VR_ERR_INVALID, "NULL argument");
+    if (!ch->head.has_w) return fail(VR_ERR_STATE, "vr_chat_load_head has not run");
+    if (B < 1) return fail(VR_ERR_INVALID, "B must be positive");
+    const int R = ch->c.max_rows;
+    vr_model_s* w = ch->work;
+    // ---- every check before any state changes
+    if (B > ch->c.max_slots || B > R) return fail(VR_ERR_INVALID, "%d prompts exceed max_slots=%d / max_rows=%d", B, ch->c.max_slots, R);
+    if (seq_offsets[0] != 0) return fail(VR_ERR_INVALID, "seq_offsets[0] must be 0");
+    std::vector<char> slot_used(ch->c.max_slots, 0), row_used(R, 0);
+    for (int b = 0; b < B; ++b) {
+        const int sl = slots[b], r = rows[b], T = seq_offsets[b + 1] - seq_offsets[b];
+        if (sl < 0 || sl >= ch->c.max_slots || slot_used[sl]) return fail(VR_ERR_INVALID, "prompt %d: slot %d out of range or repeated", b, sl);
+        if (r < 0 || r >= R || row_used[r]) return fail(VR_ERR_INVALID, "prompt %d: row %d out of range or repeated", b, r);
+        slot_used[sl] = 1; row_used[r] = 1;
+        if (T < 1) return fail(VR_ERR_INVALID, "empty prompt %d", b);
+        if (T > ch->c.max_len - 1) return fail(VR_ERR_CAPACITY, "prompt %d of %d tokens leaves no room below max_len=%d", b, T, ch->c.max_len);
+    }
+    const int Ttot = seq_offsets[B];
+    if (Ttot > w->c.max_tokens) return fail(VR_ERR_CAPACITY, "%d prompt tokens exceed the model's max_tokens=%d", Ttot, w->c.max_tokens);
+    if (B > w->c.max_seqs) return fail(VR_ERR_CAPACITY, "%d prompts exceed the model's max_seqs=%d", B, w->c.max_seqs);
+    for (int t = 0; t < Ttot; ++t)
+        if (input_ids[t] < 0 || input_ids[t] >= ch->V) return fail(VR_ERR_INVALID, "token id %d out of range at %d", input_ids[t], t);
+    VRCHK(set_dev(ch->model->device));
+    hipStream_t s = (hipStream_t)stream;
+    // the slots' caches are rewritten from here on: rows that continued them lose their tails
+    auto unbind = [&]() {
+        for (int b = 0; b < B; ++b) ch->plen[slots[b]] = 0;
+        for (int r = 0; r < R; ++r)
+            if (ch->row_slot[r] >= 0 && slot_used[ch->row_slot[r]]) { ch->row_slot[r] = -1; ch->row_len[r] = 0; ch->lpos[r] = -1; }
+    };
+    unbind();
+    ChatPrefillBatchCtx ctx{ch, {}};
+    ctx.bt.n = B;
+    for (int b = 0; b < B; ++b) { ctx.bt.off[b] = seq_offsets[b]; ctx.bt.idx[b] = slots[b]; }
+    ctx.bt.off[B] = Ttot;
+    EncodeHook hook;
+    hook.bf16_route = true;
+    hook.layer = chat_prefill_batch_layer;
+    hook.ctx = &ctx;
+    w->arena_open = false;
+    int rc = encode_impl(w, slices, slice_hw, n_slices, slices_on_device, input_ids, seq_offsets, B, vision_rows, ch->w_reps.as<float>(), 1,
+                         stream, nullptr, 0, &hook);
+    arena_close(w, stream);
+    if (rc) return rc;
+    // last prompt tokens -> final RMSNorm (scaled weight), the rows in the order of their logits rows: a run of adjacent logits
+    // rows is one pass of the head over its weights
+    std::vector<int> order(B);
+    for (int b = 0; b < B; ++b) order[b] = b;
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return rows[a] < rows[b]; });
+    ChatBatch lr = ctx.bt;
+    for (int j = 0; j < B; ++j) lr.idx[order[j]] = j;
+    HIPCHK(launch_chat_last_rows(lr, w->w_h.as<float>(), ch->E, ch->norm_w.as<float>(), w->c.rms_norm_eps, ch->w_pxn.p, s));
+    for (int j = 0; j < B;) {
+        int n = 1;
+        while (j + n < B && rows[order[j + n]] == rows[order[j]] + n) ++n;
+        GemmArgs a = gemm_args((const char*)ch->w_pxn.p + (size_t)j * ch->E * 2, ch->E, ch->head, n,
+                               ch->w_logits.as<float>() + (size_t)(R + rows[order[j]]) * ch->Vpad, ch->Vpad);
+        HIPCHK(launch_gemm_skinny(a, s));
+        j += n;
+    }
+    for (int b = 0; b < B; ++b) {
+        const int r = rows[b];
+        HIPCHK(hipMemsetAsync((unsigned*)ch->seen.p + (size_t)r * ch->words, 0, (size_t)ch->words * 4, s));
+        ch->plen[slots[b]] = seq_offsets[b + 1] - seq_offsets[b];
+        ch->row_slot[r] = slots[b];
+        ch->row_len[r] = 0;
+        ch->lpos[r] = R + r;
+    }
     return VR_OK;
 }
 

@@ -207,6 +207,48 @@ __global__ __launch_bounds__(256) void chat_prompt_kv_kernel(const bf16_t* __res
     }
 }
 
+// The batched prefill's form of the copy above: the packed rows hold several prompts, token t of prompt b (bt.off[b] <= t <
+// bt.off[b + 1]) is position t - off[b] of prompt slot bt.idx[b].  kplane / vplane: the layer's [slots][max_len][E] planes.
+// One workgroup per token, 16 bytes per thread and copy.
+__global__ __launch_bounds__(256) void chat_prompt_scatter_kernel(ChatBatch bt, const bf16_t* __restrict__ qkv, int ld, int E, int max_len,
+                                                                  bf16_t* __restrict__ kplane, bf16_t* __restrict__ vplane) {
+    const int t = blockIdx.x;
+    int b = 0;
+    while (b + 1 < bt.n && t >= bt.off[b + 1]) ++b;
+    const bf16_t* src = qkv + (size_t)t * ld;
+    const size_t dst = ((size_t)bt.idx[b] * max_len + (t - bt.off[b])) * E;
+    for (int c = threadIdx.x * 8; c < E; c += 256 * 8) {
+        *reinterpret_cast<bf16x8*>(kplane + dst + c) = *reinterpret_cast<const bf16x8*>(src + E + c);
+        *reinterpret_cast<bf16x8*>(vplane + dst + c) = *reinterpret_cast<const bf16x8*>(src + 2 * E + c);
+    }
+}
+
+// The last token of every packed prompt: out[bt.idx[b]] = bf16(h[off[b + 1] - 1] * rsqrt(mean(h^2) + eps) * w), w = the final
+// norm's weight with the head's input scale folded in.  One workgroup per prompt.
+__global__ __launch_bounds__(256) void chat_last_rows_kernel(ChatBatch bt, const float* __restrict__ h, int E, const float* __restrict__ w,
+                                                             float eps, bf16_t* __restrict__ out) {
+    __shared__ float red[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* x = h + (size_t)(bt.off[b + 1] - 1) * E;
+    float q = 0.f;
+    for (int c = tid * 4; c < E; c += 256 * 4) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(x + c);
+        q += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+    }
+    q = wave_sum(q);
+    if ((tid & 63) == 0) red[tid >> 6] = q;
+    __syncthreads();
+    const float rstd = 1.0f / sqrtf(((red[0] + red[1]) + (red[2] + red[3])) / E + eps);
+    bf16_t* dst = out + (size_t)bt.idx[b] * E;
+    for (int c = tid * 4; c < E; c += 256 * 4) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(x + c), ww = *reinterpret_cast<const f32x4*>(w + c);
+        bf16x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = f2bf(v[e] * rstd * ww[e]);
+        *reinterpret_cast<bf16x4*>(dst + c) = o;
+    }
+}
+
 // beam reordering: dir 0 copies the first len_i rows of every (layer, K|V) tail plane of row src_i to scratch slot i, dir 1
 // copies scratch slot i to row dst_i (two passes: a row may be both a source and a destination).  Grid (2 * layers, n).
 __global__ __launch_bounds__(256) void chat_tail_move_kernel(ChatMove mv, bf16_t* __restrict__ tails, bf16_t* __restrict__ scratch,
@@ -395,6 +437,20 @@ hipError_t launch_chat_prompt_kv(const void* qkv, int ld, int T, int E, void* kd
     if (T <= 0) return hipSuccess;
     if (E % 8 || ld % 8) return hipErrorInvalidValue;
     hipLaunchKernelGGL(chat_prompt_kv_kernel, dim3(T), dim3(256), 0, s, (const bf16_t*)qkv, ld, E, (bf16_t*)kdst, (bf16_t*)vdst);
+    return hipGetLastError();
+}
+hipError_t launch_chat_prompt_scatter(const ChatBatch& bt, const void* qkv, int ld, int E, int max_len, void* kplane, void* vplane,
+                                      hipStream_t s) {
+    if (bt.n < 1 || bt.n > CHAT_MAX_ROWS || bt.off[0] != 0 || E % 8 || ld % 8 || ld < 3 * E) return hipErrorInvalidValue;
+    for (int b = 0; b < bt.n; ++b)
+        if (bt.off[b + 1] <= bt.off[b] || bt.off[b + 1] - bt.off[b] > max_len || bt.idx[b] < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(chat_prompt_scatter_kernel, dim3(bt.off[bt.n]), dim3(256), 0, s, bt, (const bf16_t*)qkv, ld, E, max_len,
+                       (bf16_t*)kplane, (bf16_t*)vplane);
+    return hipGetLastError();
+}
+hipError_t launch_chat_last_rows(const ChatBatch& bt, const float* h, int E, const float* w, float eps, void* out, hipStream_t s) {
+    if (bt.n < 1 || bt.n > CHAT_MAX_ROWS || E % 4) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(chat_last_rows_kernel, dim3(bt.n), dim3(256), 0, s, bt, h, E, w, eps, (bf16_t*)out);
     return hipGetLastError();
 }
 hipError_t launch_chat_move(const ChatMove& mv, void* tails, void* scratch, int layers, int max_rows, int max_new, int E, int max_tail,

@@ -133,6 +133,15 @@ hipError_t launch_chat_qkv(const ChatStep& st, const float* parts, int n_parts, 
 hipError_t launch_chat_attn(const ChatStep& st, const void* q, const void* prompt, const void* tails, int l, int E, int heads,
                             const ChatCaps& cap, int S_max, float* po, float* pml, void* att, hipStream_t s);
 hipError_t launch_chat_prompt_kv(const void* qkv, int ld, int T, int E, void* kdst, void* vdst, hipStream_t s);
+// a batched prefill, passed by value: prompt b owns the packed rows [off[b], off[b + 1]); idx[b] = its prompt slot (the
+// scatter) or its output row (the last-rows norm)
+struct ChatBatch { int n; int off[CHAT_MAX_ROWS + 1], idx[CHAT_MAX_ROWS]; };
+// one layer's rope'd K / V rows of the packed q | k | v rows [off[n]][ld] -> position t - off[b] of slot idx[b] in the layer's
+// K / V planes [slots][max_len][E]; the caller has checked idx[b] < slots and off[b + 1] - off[b] <= max_len
+hipError_t launch_chat_prompt_scatter(const ChatBatch& bt, const void* qkv, int ld, int E, int max_len, void* kplane, void* vplane,
+                                      hipStream_t s);
+// out[idx[b]][E] = bf16 RMSNorm(h[off[b + 1] - 1]) * w: the last token of every packed prompt, ready for the head
+hipError_t launch_chat_last_rows(const ChatBatch& bt, const float* h, int E, const float* w, float eps, void* out, hipStream_t s);
 hipError_t launch_chat_move(const ChatMove& mv, void* tails, void* scratch, int layers, int max_rows, int max_new, int E, int max_tail,
                             unsigned* seen, unsigned* seen_scratch, int words, hipStream_t s);
 hipError_t launch_chat_select(const ChatSel& sel, int mode, const float* logits, int ld, int V, const unsigned* seen, int words, float pen,

@@ -291,3 +291,31 @@ extern "C" int vr_op_chat_select(int device_id, int32_t mode, const float* logit
     HIPCHK(hipStreamSynchronize(s));
     return VR_OK;
 }
+
+extern "C" int vr_op_chat_prompt_scatter(int device_id, const void* qkv, int32_t ld, int32_t E, int32_t B, const int32_t* seq_offsets,
+                                         const int32_t* slots, int32_t n_slots, int32_t max_len, void* kplane, void* vplane, void* stream) {
+    if (!qkv || !seq_offsets || !slots || !kplane || !vplane) return fail(VR_ERR_INVALID, "NULL argument");
+    if (E < 8 || E % 8 || ld % 8 || ld < 3 * E) return fail(VR_ERR_INVALID, "E and ld must be multiples of 8 and ld >= 3 E");
+    if (n_slots < 1 || max_len < 1) return fail(VR_ERR_INVALID, "bad cache geometry");
+    if (B < 1) return fail(VR_ERR_INVALID, "B must be positive");
+    if (B > CHAT_MAX_ROWS || B > n_slots) return fail(VR_ERR_CAPACITY, "%d prompts exceed %d / the %d slots", B, CHAT_MAX_ROWS, n_slots);
+    if (((uintptr_t)qkv | (uintptr_t)kplane | (uintptr_t)vplane) & 15) return fail(VR_ERR_INVALID, "pointers must be 16-byte aligned");
+    if (seq_offsets[0] != 0) return fail(VR_ERR_INVALID, "seq_offsets[0] must be 0");
+    ChatBatch bt{};
+    bt.n = B;
+    std::vector<char> used(n_slots, 0);
+    for (int b = 0; b < B; ++b) {
+        const int T = seq_offsets[b + 1] - seq_offsets[b], sl = slots[b];
+        if (T < 1) return fail(VR_ERR_INVALID, "empty prompt %d", b);
+        if (T > max_len) return fail(VR_ERR_CAPACITY, "prompt %d: %d rows exceed max_len=%d", b, T, max_len);
+        if (sl < 0 || sl >= n_slots || used[sl]) return fail(VR_ERR_INVALID, "prompt %d: slot %d out of range or repeated", b, sl);
+        used[sl] = 1;
+        bt.off[b] = seq_offsets[b]; bt.idx[b] = sl;
+    }
+    bt.off[B] = seq_offsets[B];
+    VRCHK(set_dev(device_id));
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(launch_chat_prompt_scatter(bt, qkv, ld, E, max_len, kplane, vplane, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
+}

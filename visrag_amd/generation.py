@@ -116,12 +116,19 @@ class _Hyps:
     def best(self) -> Tuple[float, List[int]]:
         return sorted(self.beams, key=lambda x: x[0]).pop()
 
+    def ranked(self) -> List[Tuple[float, List[int]]]:
+        """Best first, in the order repeated `sorted(...).pop()` (HF's finalize) hands them out: among equal scores the one
+        added last comes first."""
+        return sorted(self.beams, key=lambda x: x[0])[::-1]
+
 
 def beam_rule(num_beams: int, max_new_tokens: int, eos: int = EOS_ID, length_penalty: float = 1.0):
     """One item's beam search as a generator of requests: yields ("select", n_rows, beam_scores, k) and receives the
     candidates [(score, token, parent)] best first over the first n_rows beams; yields ("advance", parents, tokens) (beam i
     continues beam parents[i] with tokens[i]) and receives None.  Returns {"tokens": output ids (one eos appended when
-    shorter than max_new_tokens), "score": the best hypothesis score, "steps": [(candidates, next beams)] per step}."""
+    shorter than max_new_tokens), "score": the best hypothesis score, "steps": [(candidates, next beams)] per step,
+    "hyps": every finished hypothesis as (score, output ids), best first — HF's sequences_scores / sequences for
+    num_return_sequences up to num_beams; hyps[0] is (score, tokens)}."""
     hyps = _Hyps(num_beams, length_penalty)
     seqs: List[List[int]] = [[]]
     scores = [0.0]
@@ -152,9 +159,9 @@ def beam_rule(num_beams: int, max_new_tokens: int, eos: int = EOS_ID, length_pen
     if not done:
         for s, q in zip(scores, seqs):
             hyps.add(q, s, len(q))
-    score, best = hyps.best()
-    tokens = best + ([eos] if len(best) < max_new_tokens else [])
-    return {"tokens": tokens, "score": score, "steps": steps}
+    ranked = [(sc, q + ([eos] if len(q) < max_new_tokens else [])) for sc, q in hyps.ranked()]
+    score, tokens = ranked[0]
+    return {"tokens": tokens, "score": score, "steps": steps, "hyps": ranked}
 
 
 def greedy_rule(max_new_tokens: int, eos: int = EOS_ID):
@@ -251,6 +258,37 @@ class HipChat:
         _lib.check(self.lib.vr_chat_prefill(self._h, int(slot), int(row), ptrs, hw, n, 0, ids.ctypes.data_as(C.POINTER(C.c_int32)),
                                             len(ids), rp, self._stream()), "vr_chat_prefill")
 
+    def prefill_batch(self, slots: Sequence[int], rows: Sequence[int], items: Sequence) -> None:
+        """PreparedItems in ONE packed pass: item b into prompt slot slots[b], its logits on row rows[b] (vr_chat_prefill_batch).
+        The caller keeps the batch inside the encoder workspace (max_tokens, max_seqs)."""
+        B, Q = len(items), self.enc.cfg.query_num
+        if not (B == len(slots) == len(rows)) or B < 1:
+            raise ValueError("prefill_batch needs one slot and one row per item, and at least one item")
+        ids = np.ascontiguousarray(np.concatenate([np.asarray(it.input_ids, dtype=np.int32) for it in items]))
+        off = np.zeros(B + 1, dtype=np.int32)
+        off[1:] = np.cumsum([len(it.input_ids) for it in items])
+        keep, vrows = [], []
+        for b, it in enumerate(items):
+            n = len(it.slices)
+            keep += [np.ascontiguousarray(s, dtype=np.uint8) for s in it.slices]
+            r = np.full((n, Q), -1, dtype=np.int32)
+            for k, (b0, b1) in enumerate(it.image_bound[:n]):
+                m = max(0, min(Q, b1 - b0))
+                r[k, :m] = int(off[b]) + b0 + np.arange(m, dtype=np.int32)
+            vrows.append(r.reshape(-1))
+        n = len(keep)
+        if n:
+            ptrs = (C.c_void_p * n)(*[C.c_void_p(a.ctypes.data) for a in keep])
+            hw = (C.c_int32 * (2 * n))(*[v for a in keep for v in (a.shape[0], a.shape[1])])
+            vr = np.ascontiguousarray(np.concatenate(vrows))
+            rp = vr.ctypes.data_as(C.POINTER(C.c_int32))
+        else:
+            ptrs, hw, rp = None, None, None
+        a = lambda v: (C.c_int32 * B)(*[int(x) for x in v])
+        p32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_int32))
+        _lib.check(self.lib.vr_chat_prefill_batch(self._h, B, a(slots), a(rows), ptrs, hw, n, 0, p32(ids), p32(off), rp, self._stream()),
+                   "vr_chat_prefill_batch")
+
     def step(self, slots: Sequence[int], rows: Sequence[int], tokens: Sequence[int]) -> None:
         n = len(rows)
         a = lambda v: (C.c_int32 * n)(*[int(x) for x in v])
@@ -289,16 +327,24 @@ class HipChat:
 
 
 # what HF generate would accept but this generator does not implement: refused rather than silently dropped
-_NEUTRAL = {"top_p": 1.0, "length_penalty": 1.0, "min_new_tokens": 0, "no_repeat_ngram_size": 0, "num_return_sequences": 1,
+_NEUTRAL = {"top_p": 1.0, "length_penalty": 1.0, "min_new_tokens": 0, "no_repeat_ngram_size": 0,
             "early_stopping": False, "typical_p": 1.0, "num_beam_groups": 1, "diversity_penalty": 0.0}
 
 
 def generate_items(chat: HipChat, items: Sequence, max_new_tokens: int = 20, num_beams: int = 1, do_sample: bool = False,
                    repetition_penalty: float = 1.0, temperature: float = 1.0, top_k: int = 50, seed: int = 0,
-                   eos: int = EOS_ID, details: bool = False, **kwargs) -> List:
+                   eos: int = EOS_ID, details: bool = False, prefill: str = "single", num_return_sequences: int = 1,
+                   **kwargs) -> List:
     """Generate every PreparedItem independently, the items of a batch in lockstep (one decode step streams the weights once
     for all their rows).  Returns the output ids per item (HF's sequences without the empty prompt part), or with
-    details=True the rule's result per item (tokens, score, per-step candidates)."""
+    details=True the rule's result per item (tokens, score, per-step candidates; beam search: "hyps", the
+    num_return_sequences best finished hypotheses as (score, tokens), best first).  num_return_sequences > 1 (beam search
+    only, up to num_beams) without details returns per item the list of that many output id lists.
+
+    prefill: "single" runs one prefill pass per item — an item's output is then a function of the item alone, bit for
+    bit, whatever else is in flight.  "batched" packs the prompts of a chunk into as few passes as the encoder workspace
+    (max_tokens, max_seqs) allows: the decoder's tile and split-K choices follow the packed token count, so an item's logits
+    then agree with its lone run to bf16 accuracy only — for callers whose unit of work is the group (weighted selection)."""
     for k, v in kwargs.items():
         if k not in _NEUTRAL or v != _NEUTRAL[k]:
             raise NotImplementedError(f"generation option {k}={v!r} is not supported")
@@ -313,23 +359,56 @@ def generate_items(chat: HipChat, items: Sequence, max_new_tokens: int = 20, num
         raise ValueError("temperature must be positive when sampling")
     if nb > chat.max_rows:
         raise ValueError(f"num_beams={nb} exceeds the chat handle's max_rows={chat.max_rows}")
+    if prefill not in ("single", "batched"):
+        raise ValueError(f"prefill={prefill!r}: 'single' or 'batched'")
+    nret = int(num_return_sequences)
+    if nret < 1 or nret > (nb if nb > 1 and not do_sample else 1):
+        raise ValueError(f"num_return_sequences={nret}: 1..num_beams for beam search, 1 for greedy search and sampling")
     if max_new_tokens > chat.max_new:
         raise ValueError(f"max_new_tokens={max_new_tokens} exceeds the chat handle's max_new={chat.max_new}")
     per = max(1, min(chat.max_rows // nb, chat.max_slots))
     out: List[List[int]] = []
     for lo in range(0, len(items), per):
-        res = _generate_chunk(chat, items[lo:lo + per], max_new_tokens, nb, do_sample, repetition_penalty, temperature, top_k, seed, eos)
-        out += res if details else [r["tokens"] for r in res]
+        res = _generate_chunk(chat, items[lo:lo + per], max_new_tokens, nb, do_sample, repetition_penalty, temperature, top_k, seed, eos,
+                              prefill)
+        for r in res:
+            if "hyps" in r:
+                r["hyps"] = r["hyps"][:nret]
+        if details:
+            out += res
+        elif nret > 1:
+            out += [[t for _, t in r["hyps"]] for r in res]
+        else:
+            out += [r["tokens"] for r in res]
     return out
 
 
-def _generate_chunk(chat, items, max_new, nb, do_sample, pen, temp, top_k, seed, eos):
+def prefill_groups(lengths: Sequence[int], max_tokens: int, max_seqs: int) -> List[List[int]]:
+    """Consecutive runs of the items that fit one packed pass each: at most max_tokens tokens and max_seqs items (an item
+    longer than max_tokens stands alone and fails as it would on its own)."""
+    groups, cur, tok = [], [], 0
+    for i, n in enumerate(lengths):
+        if cur and (tok + n > max_tokens or len(cur) >= max_seqs):
+            groups.append(cur)
+            cur, tok = [], 0
+        cur.append(i)
+        tok += n
+    if cur:
+        groups.append(cur)
+    return groups
+
+
+def _generate_chunk(chat, items, max_new, nb, do_sample, pen, temp, top_k, seed, eos, prefill="single"):
     """Every item's rule is a generator of select / advance requests; each round serves all pending requests of one kind in
     ONE device call (advances first: a select must see the appended token), so the items advance in lockstep."""
     rules, rows, reqs, results = [], [], [], [None] * len(items)
+    if prefill == "batched":
+        for g in prefill_groups([len(it.input_ids) for it in items], chat.enc.max_tokens, chat.enc.max_seqs):
+            chat.prefill_batch(g, [i * nb for i in g], [items[i] for i in g])
     for i, it in enumerate(items):
         r = list(range(i * nb, (i + 1) * nb))
-        chat.prefill(i, r[0], it)
+        if prefill == "single":
+            chat.prefill(i, r[0], it)
         rule = greedy_rule(max_new, eos) if (do_sample or nb == 1) else beam_rule(nb, max_new, eos)
         rules.append(rule); rows.append(r); reqs.append(next(rule))
     mode = SAMPLE if do_sample else (BEAM if nb > 1 else GREEDY)

@@ -312,18 +312,77 @@ class VisRAGRet:
         return decode_text(ids, tokenizer)
 
     def chat(self, image_list, msgs_list, tokenizer, vision_hidden_states=None, max_new_tokens: int = 1024, sampling: bool = True,
-             max_inp_length: int = 2048, seed: int = 0, **kwargs):
+             max_inp_length: int = 2048, seed: int = 0, assistant_turn: bool = False, return_scores: bool = False, **kwargs):
         """The reference's chat (modeling_minicpmv.py:321-398).  `seed` (not in the reference, whose draws come from torch's
-        global generator) selects the sampling noise: chat(sampling=True) with one seed returns the same answer each call."""
-        from .generation import chat_generation_config
+        global generator) selects the sampling noise: chat(sampling=True) with one seed returns the same answer each call.
+        assistant_turn=True ends the prompt with "<AI>", as the chat of the reference's answer-generation package does;
+        return_scores=True (beam search only) returns (answers, scores): per item the sequence scores of its finished
+        hypotheses, best first — that package's `sequences_scores` (it asks for num_return_sequences=2)."""
+        from .generation import chat_generation_config, decode_text, generate_items
+        if return_scores and sampling:
+            raise NotImplementedError("return_scores needs beam search (sampling=False): sampling yields no sequence scores")
         prompts, images = [], []
         for msgs, image in zip(msgs_list, image_list):
             p, imgs = chat_prompt(msgs, image, tokenizer, self.config)
-            prompts.append(p)
+            prompts.append(p + ("<AI>" if assistant_turn else ""))
             images.append(imgs)
         gen = chat_generation_config(sampling, kwargs)
-        return self.generate(data_list=prompts, img_list=images, tokenizer=tokenizer, max_inp_length=max_inp_length,
-                             vision_hidden_states=vision_hidden_states, max_new_tokens=max_new_tokens, seed=seed, **gen)
+        if not return_scores:
+            return self.generate(data_list=prompts, img_list=images, tokenizer=tokenizer, max_inp_length=max_inp_length,
+                                 vision_hidden_states=vision_hidden_states, max_new_tokens=max_new_tokens, seed=seed, **gen)
+        if vision_hidden_states is not None:
+            raise NotImplementedError("vision_hidden_states are not supported")
+        if getattr(self, "_chat", None) is None:
+            raise RuntimeError("chat() needs an LM head: call attach_generator() first (or load_generator())")
+        items = [_prompt_item(t, imgs, tokenizer, max_inp_length) for t, imgs in zip(prompts, images)]
+        res = generate_items(self._chat, items, eos=tokenizer.eos_id, max_new_tokens=max_new_tokens, details=True,
+                             num_return_sequences=min(2, gen["num_beams"]), **gen)
+        return decode_text([r["tokens"] for r in res], tokenizer), [[sc for sc, _ in r["hyps"]] for r in res]
+
+    def weighted_selection(self, image_list, msgs, doc_scores, tokenizer, max_new_tokens: int = 1024, sampling: bool = False,
+                           max_inp_length: int = 2048, details: bool = False, prefill: str = "single", **kwargs):
+        """The reference's weighted selection (weighted_selection/MiniCPMV20/modeling_minicpmv.py:394-425): one beam-search
+        answer per retrieved page, the answer of the page with the largest softmax(doc_scores)_i * exp(sequence score_i)
+        wins (the first page among equals).  The pages of a request are decoded in lockstep; prefill="batched" also
+        prefills them in one packed pass (vr_chat_prefill_batch; the default stays "single" until the batched pass has been
+        timed on an MI355X: DESIGN.md ledger 70).  Either way the request is the unit: its result depends on (question,
+        pages, scores) and on nothing else in flight.
+        details=True -> (answer, {"answers": per page, "scores": per page its sequence scores best first, "weights",
+        "doc_probs", "index": the chosen page, "tokens": per page, "results": generate_items' details per page})."""
+        from .generation import chat_generation_config, decode_text, generate_items
+        if sampling:
+            raise NotImplementedError("weighted selection needs sequence scores: beam search only (sampling=False)")
+        image_list, doc_scores = list(image_list), [float(x) for x in doc_scores]
+        if not image_list:
+            raise ValueError("weighted_selection needs at least one page")
+        if len(image_list) != len(doc_scores):
+            raise ValueError(f"{len(image_list)} pages but {len(doc_scores)} doc_scores")
+        if getattr(self, "_chat", None) is None:
+            raise RuntimeError("weighted_selection() needs an LM head: call attach_generator() first (or load_generator())")
+        items = []
+        for image in image_list:
+            p, imgs = chat_prompt(msgs, image, tokenizer, self.config)
+            items.append(_prompt_item(p + "<AI>", imgs, tokenizer, max_inp_length))
+        gen = chat_generation_config(False, kwargs)
+        # generate_items cuts the pages into chunks of max_rows // num_beams
+        res = generate_items(self._chat, items, eos=tokenizer.eos_id, max_new_tokens=max_new_tokens, details=True, prefill=prefill,
+                             num_return_sequences=min(2, gen["num_beams"]), **gen)
+        answers = decode_text([r["tokens"] for r in res], tokenizer)
+        index, weights, p = select_weighted([r["score"] for r in res], doc_scores)
+        if not details:
+            return answers[index]
+        return answers[index], {"answers": answers, "scores": [[sc for sc, _ in r["hyps"]] for r in res], "weights": weights,
+                                "doc_probs": p, "index": index, "tokens": [r["tokens"] for r in res], "results": res}
+
+
+def select_weighted(seq_scores, doc_scores):
+    """-> (index, weights, p): p = softmax(doc_scores) in fp64, weights[i] = p[i] * exp(seq_scores[i]), index = the first
+    largest weight (`list.index(max(..))` of the reference)."""
+    d = np.asarray(doc_scores, dtype=np.float64)
+    e = np.exp(d - d.max())
+    p = (e / e.sum()).tolist()
+    weights = [pi * float(np.exp(np.float64(s))) for pi, s in zip(p, seq_scores)]
+    return weights.index(max(weights)), weights, p
 
 
 def chat_prompt(msgs, image, tokenizer, cfg):
