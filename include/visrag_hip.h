@@ -351,18 +351,88 @@ int vr_op_gemm(int device_id, const void* A, int32_t lda, const void* W, int32_t
                const float* resid, float alpha, void* out, int32_t ldo,
                const int32_t* rope_pos, const float* rope_table, int32_t rope_cols,
                int32_t variant, void* stream);
+/* vr_op_gemm with the rest of the launch arguments (GemmArgs, csrc/kernels.h); extras NULL: all zero, i.e. vr_op_gemm.
+ * Nothing is checked here beyond what vr_op_gemm checks: every field is either HONOURED by the variant it reaches or the
+ * launchers REFUSE the call (VR_ERR_HIP, hipErrorInvalidValue) before anything is launched — for every variant and for 3
+ * (the rule applies to the variant the engine's choice lands on):
+ *   rowmap (i32 [M], device: output row of input row m, -1 = drop; EPI_RESID reads the residual at the mapped row)
+ *                   honoured by 0, 7, 9, 12, 13 for each epilogue the variant has; refused by 14 / 15
+ *   rowbias (f32 [rowbias_period][rowbias_ld], device: row m % rowbias_period is added to the columns n < rowbias_cols)
+ *                   honoured with epilogues 0, 1, 2 on 0, 7, 9, 12 and with epilogue 2 on 13; refused with epilogues 3, 4, 5,
+ *                   with rowbias_period < 1, and by 14 / 15
+ *   ksplit > 1      (split s covers the K columns [s, s + 1) * K / ksplit and writes its fp32 plane to out + s * split_stride
+ *                   floats; the bias rides with plane 0) honoured by 9, 12, 13 with epilogue 2 and K % (ksplit * 64) == 0;
+ *                   refused everywhere else (0, 7, 14, 15, any other epilogue) and together with rowmap / rowbias
+ *   m_dev, m_sub    (i32 on the device: only the rows m < *m_dev - m_sub exist; 256-row tiles at or past that count are not
+ *                   computed, rows between the count and the next multiple of 256 are unspecified) honoured by 9; refused
+ *                   everywhere else
+ *   col_scale, col_scale_n   (columns n < col_scale_n leave as bf16((acc + bias + rowbias) * col_scale)) honoured with epilogue 0
+ *                   and col_scale_n a non-negative multiple of 64 on 0, 7, 9, 12; refused otherwise (any other epilogue, any
+ *                   other col_scale_n) and, whatever the epilogue, by 14 / 15
+ *   raster_gm       (m-tiles per rasterisation group, 0 = the launcher's choice) honoured everywhere: the order of the tiles
+ *                   never changes a result bit */
+typedef struct vr_gemm_extras {
+    const int32_t* rowmap;
+    const float* rowbias;
+    int32_t rowbias_period, rowbias_ld, rowbias_cols;
+    float col_scale;
+    int32_t col_scale_n;
+    int32_t ksplit;
+    int64_t split_stride;
+    const int32_t* m_dev;
+    int32_t m_sub;
+    int32_t raster_gm;
+} vr_gemm_extras_t;
+int vr_op_gemm_ex(int device_id, const void* A, int32_t lda, const void* W, int32_t ldw,
+                  int32_t M, int32_t N, int32_t K, int32_t epilogue, const float* bias,
+                  const float* resid, float alpha, void* out, int32_t ldo,
+                  const int32_t* rope_pos, const float* rope_table, int32_t rope_cols,
+                  int32_t variant, const vr_gemm_extras_t* extras, void* stream);
 /* y = LN(x) (kind 0, affine, eps) or RMSNorm(x) (kind 1): x f32 [rows][dim] -> bf16 [rows][ldo]. */
 int vr_op_norm(int device_id, int32_t kind, const float* x, int32_t rows, int32_t dim,
                const float* weight, const float* bias, float eps, void* out, int32_t ldo,
                void* stream);
 /* Flash attention over bf16 q/k/v with row strides ld*, per-batch row ranges cu_q/cu_kv
- * ([B+1], device), head_dim in {64,72,128}; causal uses absolute positions within the
+ * ([B+1], device), head_dim in {64,72,80,128}; causal uses absolute positions within the
  * sequence.  q_batch_stride==0 shares q across the batch (resampler). out bf16 [rows_q][ldo]. */
 int vr_op_attention(int device_id, const void* q, int32_t ldq, const void* k, int32_t ldk,
                     const void* v, int32_t ldv, void* out, int32_t ldo,
                     const int32_t* cu_q, const int32_t* cu_kv, int32_t B, int32_t heads,
                     int32_t head_dim, int32_t max_q, int32_t causal, int32_t q_shared,
                     float scale, void* stream);
+/* vr_op_attention with the rest of the launch arguments (AttnArgs, csrc/kernels.h); extras NULL: all zero.
+ *   kv_group       grouped-query attention: query head h reads K / V head h / kv_group (0 or 1: one each)
+ *   kv_end         i32 [B] (device) or NULL: item b's K / V rows are [cu_kv[b], kv_end[b]) — ranges of different caches
+ *   q_in_rows      i32 [B] (device) or NULL: first q row of item b (reading q only; the out rows stay cu_q)
+ *   q_head_stride  elements between the heads of a q row (0: head_dim): the query heads of a group as the ROWS of a tile
+ *   q_prescaled    the q rows already carry scale * log2(e) (vr_gemm_extras_t::col_scale): no kernel scales again
+ *   lse            f32 [rows_q][heads] (device) or NULL: log2(sum_k exp(scale * s_k)) of every row that has keys
+ * An item without keys writes neither its out rows nor its lse. */
+typedef struct vr_attn_extras {
+    int32_t kv_group;
+    const int32_t* kv_end;
+    const int32_t* q_in_rows;
+    int32_t q_head_stride;
+    int32_t q_prescaled;
+    float* lse;
+} vr_attn_extras_t;
+int vr_op_attention_ex(int device_id, const void* q, int32_t ldq, const void* k, int32_t ldk,
+                       const void* v, int32_t ldv, void* out, int32_t ldo,
+                       const int32_t* cu_q, const int32_t* cu_kv, int32_t B, int32_t heads,
+                       int32_t head_dim, int32_t max_q, int32_t causal, int32_t q_shared,
+                       float scale, const vr_attn_extras_t* extras, void* stream);
+/* Merge of the KV ranges of a decode step's attention (head_dim 128): part bf16 / lse f32 are the out / lse of
+ * vr_op_attention_ex run with the `group` query heads of a KV head as rows — the layout is SkinnyCombine's in
+ * csrc/kernels.h; row r of n_rows owns the 16 ranges from 16 r on, the first S (or S_dev[r], i32 on the device, when S_dev is
+ * not NULL) of which are merged.
+ *   W NULL: out bf16, row r at out + r * ld_out elements, out[h * 128 + d] for the `heads` query heads.
+ *   W bf16 [N][ldw] (rows readable up to the next multiple of 256): the merged row (rounded to bf16) times W^T as fp32
+ *           planes out[ksplit][M][ldo], plane s at out + s * split_stride floats, `planes` of them allocated (ksplit <= planes)
+ *           — the decode step's o projection, merged inside gemm_skinny.hip.  M = 1, K = heads * 128 and at most four
+ *           K-steps per split are the LAUNCHER's limits: anything else is refused there (VR_ERR_HIP) before a launch. */
+int vr_op_attn_combine(int device_id, const void* part, const float* lse, int32_t S, const int32_t* S_dev, int32_t heads,
+                       int32_t group, int32_t n_rows, void* out, int32_t ld_out, const void* W, int32_t ldw, int32_t M,
+                       int32_t N, int32_t K, int32_t ksplit, int32_t planes, int32_t ldo, int64_t split_stride, void* stream);
 /* The decode step's weight streamer (gemm_skinny.hip): A bf16 [M <= 32][lda], W bf16 [N][ldw] (nn.Linear layout), K % 64 == 0,
  * N % 4 == 0.  The CALLER pads: A readable up to 16 rows (32 when M > 16), W up to the next multiple of 256 rows.
  *   swiglu 0: fp32 planes out[ksplit][M][ldo] (plane s at out + s * split_stride floats); split s covers the K-steps

@@ -123,3 +123,53 @@ def op_chat_select(mode, logits, seen, V, group_offsets, K, kout, beam_scores=No
                                      C.c_uint64(int(seed) & (2 ** 64 - 1)), int(step), sc.ctypes.data_as(C.POINTER(C.c_float)), p32(tk),
                                      p32(pa), None), "vr_op_chat_select")
     return sc, tk, pa
+
+
+# ---- every launch argument (tests/test_gpu_launch_args.py).  The caller owns the output tensor and prefills it with a sentinel:
+#      a zero fill here would hide a row that was never written.
+def op_gemm_ex(A, W, M, N, epi, out, bias=None, resid=None, alpha=1.0, rope_pos=None, rope_table=None, rope_cols=0, variant=0,
+               ldo=None, rowmap=None, rowbias=None, rowbias_period=0, rowbias_ld=None, rowbias_cols=0, col_scale=0.0,
+               col_scale_n=0, ksplit=0, split_stride=0, m_dev=None, m_sub=0, raster_gm=0):
+    """A bf16 [M padded by the caller][K], W bf16 [N padded by the caller][K] -> `out`, written in place (row pitch ldo);
+    resid f32 with out's row pitch; rowmap / m_dev int32 and rowbias f32 on the device."""
+    lib = _lib.load()
+    K = W.shape[1]
+    ex = _lib.VRGemmExtras(rowmap=rowmap.data_ptr() if rowmap is not None else None,
+                           rowbias=rowbias.data_ptr() if rowbias is not None else None, rowbias_period=rowbias_period,
+                           rowbias_ld=(rowbias_ld if rowbias_ld is not None else (rowbias.stride(0) if rowbias is not None else 0)),
+                           rowbias_cols=rowbias_cols, col_scale=float(col_scale), col_scale_n=col_scale_n, ksplit=ksplit,
+                           split_stride=split_stride, m_dev=m_dev.data_ptr() if m_dev is not None else None, m_sub=m_sub,
+                           raster_gm=raster_gm)
+    ldo = ldo if ldo is not None else out.stride(-2)
+    _lib.check(lib.vr_op_gemm_ex(A.device.index or 0, P(A), A.stride(0), P(W), W.stride(0), M, N, K, epi, P(bias), P(resid),
+                                 float(alpha), P(out), ldo, P(rope_pos), P(rope_table), rope_cols, variant, C.byref(ex), None),
+               "vr_op_gemm_ex")
+    torch.cuda.synchronize()
+    return out
+
+
+def op_attention_ex(q, k, v, out, cu_q, cu_kv, heads, hd, max_q, causal, q_shared, scale, B=None, ldq=None, kv_group=0,
+                    kv_end=None, q_in_rows=None, q_head_stride=0, q_prescaled=0, lse=None):
+    """`out` bf16 (and `lse` f32 [rows_q][heads]) are the caller's, prefilled with a sentinel"""
+    lib = _lib.load()
+    ex = _lib.VRAttnExtras(kv_group=kv_group, kv_end=kv_end.data_ptr() if kv_end is not None else None,
+                           q_in_rows=q_in_rows.data_ptr() if q_in_rows is not None else None, q_head_stride=q_head_stride,
+                           q_prescaled=int(q_prescaled), lse=lse.data_ptr() if lse is not None else None)
+    B = B if B is not None else cu_kv.numel() - 1
+    _lib.check(lib.vr_op_attention_ex(q.device.index or 0, P(q), ldq if ldq is not None else q.stride(0), P(k), k.stride(0), P(v),
+                                      v.stride(0), P(out), out.stride(0), P(cu_q), P(cu_kv), B, heads, hd, max_q, int(causal),
+                                      int(q_shared), float(scale), C.byref(ex), None), "vr_op_attention_ex")
+    torch.cuda.synchronize()
+    return out
+
+
+def op_attn_combine(part, lse, heads, group, out, S=0, S_dev=None, n_rows=1, ld_out=0, W=None, M=1, N=0, K=0, ksplit=1,
+                    planes=1, ldo=0, split_stride=0):
+    """part bf16 / lse f32: a decode attention's partial rows (layout: SkinnyCombine, csrc/kernels.h).  W None: `out` bf16
+    [n_rows][ld_out] merged rows; W bf16 [N padded to 256][K]: `out` fp32 planes [planes][M][ldo] of merged @ W^T."""
+    lib = _lib.load()
+    _lib.check(lib.vr_op_attn_combine(part.device.index or 0, P(part), P(lse), S, P(S_dev), heads, group, n_rows, P(out), ld_out,
+                                      P(W), W.stride(0) if W is not None else 0, M, N, K, ksplit, planes, ldo, split_stride, None),
+               "vr_op_attn_combine")
+    torch.cuda.synchronize()
+    return out

@@ -1,6 +1,8 @@
 """-m gpu: every HIP kernel, called through the C ABI, against an fp32 restatement of the same
 op on the same (bf16-rounded) inputs.  Tolerances are stated per test.
-The decode step's kernels (chat_kernels.hip, gemm_skinny.hip, swiglu_sum, rmsnorm_accum): tests/test_gpu_decode_ops.py."""
+The decode step's kernels (chat_kernels.hip, gemm_skinny.hip, swiglu_sum, rmsnorm_accum): tests/test_gpu_decode_ops.py.
+The optional launch arguments of the GEMM and attention kernels (row map, row bias, column scale, split K, device-side row
+count, rasterisation; grouped-query ranges, lse and their merge): tests/test_gpu_launch_args.py."""
 import math
 
 import numpy as np

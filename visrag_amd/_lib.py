@@ -50,6 +50,17 @@ class VGVisionConfig(C.Structure):     # vg_vision_config_t (include/visrag_gen.
     ]
 
 
+class VRGemmExtras(C.Structure):       # vr_gemm_extras_t (include/visrag_hip.h)
+    _fields_ = [("rowmap", C.c_void_p), ("rowbias", C.c_void_p), ("rowbias_period", C.c_int32), ("rowbias_ld", C.c_int32),
+                ("rowbias_cols", C.c_int32), ("col_scale", C.c_float), ("col_scale_n", C.c_int32), ("ksplit", C.c_int32),
+                ("split_stride", C.c_int64), ("m_dev", C.c_void_p), ("m_sub", C.c_int32), ("raster_gm", C.c_int32)]
+
+
+class VRAttnExtras(C.Structure):       # vr_attn_extras_t (include/visrag_hip.h)
+    _fields_ = [("kv_group", C.c_int32), ("kv_end", C.c_void_p), ("q_in_rows", C.c_void_p), ("q_head_stride", C.c_int32),
+                ("q_prescaled", C.c_int32), ("lse", C.c_void_p)]
+
+
 class VisragHipError(RuntimeError):
     pass
 
@@ -96,9 +107,15 @@ SIGNATURES = {
     "vr_resize_bicubic": (C.c_int, [C.c_int, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
     "vr_op_gemm": (C.c_int, [C.c_int, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _f32,
                              _vp, _i32, _vp, _vp, _i32, _i32, _vp]),
+    "vr_op_gemm_ex": (C.c_int, [C.c_int, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _f32,
+                                _vp, _i32, _vp, _vp, _i32, _i32, C.POINTER(VRGemmExtras), _vp]),
     "vr_op_norm": (C.c_int, [C.c_int, _i32, _vp, _i32, _i32, _vp, _vp, _f32, _vp, _i32, _vp]),
     "vr_op_attention": (C.c_int, [C.c_int, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32,
                                   _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
+    "vr_op_attention_ex": (C.c_int, [C.c_int, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32,
+                                     _i32, _i32, _i32, _i32, _i32, _f32, C.POINTER(VRAttnExtras), _vp]),
+    "vr_op_attn_combine": (C.c_int, [C.c_int, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32,
+                                     _i32, _i32, _i64, _vp]),
     "vr_op_gemm_skinny": (C.c_int, [C.c_int, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i64, _vp]),
     "vr_op_plane_sum": (C.c_int, [C.c_int, _i32, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _i32, _f32, _vp, _f32, _vp, _i32, _vp]),
     "vr_op_chat_attention": (C.c_int, [C.c_int, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32),

@@ -119,15 +119,11 @@ static hipError_t launch_epi(const GemmArgs& a_in, int variant, hipStream_t s) {
         static unsigned long long attr = 0;     // bit d: set on device d
         set_max_dynamic_lds((const void*)k, G256_SMEM_BYTES, attr);
         int grid = tn * tm;
-        if (a.ksplit > 1) {
-            if (EPI != EPI_F32 || a.K % (a.ksplit * GEMM_BK) || a.rowmap || a.rowbias) return hipErrorInvalidValue;
-            grid *= a.ksplit;
-        }
+        if (a.ksplit > 1) grid *= a.ksplit;             // (legal: gemm_args_refused, asked by launch_gemm)
         hipLaunchKernelGGL(k, dim3(grid), dim3(512), G256_SMEM_BYTES, s, a);
         return hipGetLastError();
     }
     if (variant != GEMM_VARIANT_GLDS) return hipErrorInvalidValue;
-    if (a.ksplit > 1) return hipErrorInvalidValue;          // split-K exists on the 256-tile kernel only
     const int tiles = (a.N / GEMM_BN) * ((a.M + GEMM_BM - 1) / GEMM_BM);
     if (a.raster_gm <= 0) {
         const int tm = (a.M + GEMM_BM - 1) / GEMM_BM;
@@ -140,10 +136,27 @@ static hipError_t launch_epi(const GemmArgs& a_in, int variant, hipStream_t s) {
     return hipGetLastError();
 }
 
+// An optional field is honoured by the kernel the launch reaches, or the launch is refused: which of the two, per field
+// (kernels.h; the table is in include/visrag_hip.h at vr_op_gemm_ex).  Host-side integer tests only.
+bool gemm_args_refused(const GemmArgs& a, int epi, int variant) {
+    // column scaling exists in the bf16-output epilogues only, on whole 64-column blocks (the tile forms test the block start)
+    if (a.col_scale_n != 0 && (epi != EPI_BF16 || a.col_scale_n < 0 || a.col_scale_n % 64 != 0)) return true;
+    const bool half_tile = variant == GEMM_VARIANT_128W_192 || variant == GEMM_VARIANT_128W_256;
+    const bool split_tile = variant == GEMM_VARIANT_256IL || variant == GEMM_VARIANT_256W || variant == GEMM_VARIANT_192W;
+    // the half-height tiles carry no per-row lookups at all
+    if (half_tile && (a.rowmap || a.rowbias)) return true;
+    // a row bias is added by the bf16 / GELU / fp32 epilogues; the residual, SwiGLU and RoPE epilogues have no such term
+    if (a.rowbias && ((epi != EPI_BF16 && epi != EPI_GELU && epi != EPI_F32) || a.rowbias_period < 1)) return true;
+    // split K: fp32 planes of the 256-row tiles, K a whole number of steps per split, no per-row lookups in the plane epilogue
+    if (a.ksplit > 1 && (!split_tile || epi != EPI_F32 || a.K % (a.ksplit * GEMM_BK) || a.rowmap || a.rowbias)) return true;
+    // a device-side row count is read by the 8-wave 256-tile kernel only
+    if (a.m_dev && variant != GEMM_VARIANT_256IL) return true;
+    return false;
+}
+
 hipError_t launch_gemm(const GemmArgs& a, int epi, int variant, hipStream_t s) {
     if (a.M <= 0) return hipSuccess;
-    // column scaling exists in the bf16-output epilogues only, on whole 64-column blocks (the tile forms test the block start)
-    if (a.col_scale_n != 0 && (epi != EPI_BF16 || a.col_scale_n < 0 || a.col_scale_n % 64 != 0)) return hipErrorInvalidValue;
+    // (each variant launcher applies gemm_args_refused to itself; AUTO is judged as the variant it picks)
     if (variant == GEMM_VARIANT_192) return launch_gemm192(a, epi, s);
     if (variant == GEMM_VARIANT_256W) return launch_gemm256w(a, epi, s);
     if (variant == GEMM_VARIANT_192W) return launch_gemm192w(a, epi, s);
@@ -176,6 +189,7 @@ hipError_t launch_gemm(const GemmArgs& a, int epi, int variant, hipStream_t s) {
         variant = (n_ok && e256 > e128) ? (w_ok ? GEMM_VARIANT_256W : GEMM_VARIANT_256IL) : GEMM_VARIANT_GLDS;
         if (variant == GEMM_VARIANT_256W) return launch_gemm256w(a, epi, s);
     }
+    if (gemm_args_refused(a, epi, variant)) return hipErrorInvalidValue;
     switch (epi) {
         case EPI_BF16: return launch_epi<EPI_BF16>(a, variant, s);
         case EPI_GELU: return launch_epi<EPI_GELU>(a, variant, s);

@@ -323,7 +323,7 @@ bool gemm128w_fits(const GemmArgs& a, int bn) {
 template <int EPI, int NJ>
 static hipError_t launch_h(GemmArgs a, hipStream_t s) {
     constexpr int BN = 32 * NJ;
-    if (!gemm128w_fits(a, BN)) return hipErrorInvalidValue;
+    if (!gemm128w_fits(a, BN) || gemm_args_refused(a, EPI, NJ == 6 ? GEMM_VARIANT_128W_192 : GEMM_VARIANT_128W_256)) return hipErrorInvalidValue;
     if (EPI != EPI_RESID && ((a.ldo & 7) != 0 || a.col_scale_n != 0)) return hipErrorInvalidValue;
     const int tn = a.N / BN, tm = (a.M + H_BM - 1) / H_BM;
     // m-tiles per raster group: an XCD's share of the grid (total / 8 consecutive tiles) should be a squarish block — with

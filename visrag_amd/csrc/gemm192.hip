@@ -98,8 +98,10 @@ __global__ __launch_bounds__(512, 2) void gemm192_bf16_kernel(GemmArgs p) {
         }
     }
     if constexpr (EPI == EPI_RESID) {
-        gemm_epilogue_resid_tile<4, 6, 4>(acc, p, m0 + wm * 64 + fr, n0 + wn * 96, fq);
-    } else {
+        // (wave-uniform, as in gemm.hip: the whole-tile form knows no row map — mapped rows take the per-row epilogue)
+        if (!p.rowmap) { gemm_epilogue_resid_tile<4, 6, 4>(acc, p, m0 + wm * 64 + fr, n0 + wn * 96, fq); return; }
+    }
+    {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             gemm_epilogue_row<EPI, 6>(acc[i], p, m0 + wm * 64 + i * 16 + fr, n0 + wn * 96, fq);
@@ -118,7 +120,7 @@ static hipError_t launch192_t(GemmArgs a, hipStream_t s) {
 }
 
 hipError_t launch_gemm192(const GemmArgs& a, int epi, hipStream_t s) {
-    if (a.N % G192_BN || a.K % GEMM_BK) return hipErrorInvalidValue;
+    if (a.N % G192_BN || a.K % GEMM_BK || gemm_args_refused(a, epi, GEMM_VARIANT_192)) return hipErrorInvalidValue;
     switch (epi) {
         case EPI_BF16: return launch192_t<EPI_BF16>(a, s);
         case EPI_GELU: return launch192_t<EPI_GELU>(a, s);

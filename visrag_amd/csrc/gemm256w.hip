@@ -81,11 +81,9 @@ static hipError_t launch_wp(GemmArgs a, hipStream_t s) {
     const int tn = (a.N + BN - 1) / BN, tm = (a.M + G256_BM - 1) / G256_BM;
     if (a.raster_gm <= 0) a.raster_gm = tm <= 16 ? tm : 4;
     if (!gemm256w_fits(a, BN)) return hipErrorInvalidValue;
+    if (gemm_args_refused(a, EPI, NJ == 6 ? GEMM_VARIANT_192W : GEMM_VARIANT_256W)) return hipErrorInvalidValue;
     int total = tn * tm;
-    if (a.ksplit > 1) {
-        if (EPI != EPI_F32 || a.K % (a.ksplit * GEMM_BK) || a.rowmap || a.rowbias) return hipErrorInvalidValue;
-        total *= a.ksplit;
-    }
+    if (a.ksplit > 1) total *= a.ksplit;
     auto k = gemm256w_bf16_kernel<EPI, PLAIN, NJ>;
     static unsigned long long attr = 0;     // bit d: set on device d
     set_max_dynamic_lds((const void*)k, W_SMEM_BYTES, attr);

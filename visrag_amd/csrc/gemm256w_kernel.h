@@ -390,8 +390,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                         done = true;
                     }
                 }
-                if constexpr (EPI == EPI_RESID) {       // (row-mapped residual outputs)
-                    gemm_epilogue_resid_tile<MI, NF, 2>(acc, p, mr + fr, nb, fq);
+                if constexpr (EPI == EPI_RESID) {       // (row-mapped residual outputs: the per-row form reads the map, the whole-tile form does not)
+#pragma unroll
+                    for (int i = 0; i < MI; ++i) gemm_epilogue_row<EPI_RESID, NF>(acc[i], p, mr + i * 16 + fr, nb, fq);
                     done = true;
                 }
                 if constexpr (NF == 4 && (EPI == EPI_BF16 || EPI == EPI_GELU || EPI == EPI_SWIGLU || EPI == EPI_ROPE)) {

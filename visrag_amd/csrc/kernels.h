@@ -23,7 +23,7 @@ struct GemmArgs {
     float alpha;                     // EPI_RESID scale
     void* out; int ldo;
     const int* rowmap;               // optional: output row of input row m (-1 = drop)
-    const float* rowbias;            // optional: f32 [period][rowbias_ld], added for n < rowbias_cols
+    const float* rowbias;            // optional: f32 [period][rowbias_ld], added for n < rowbias_cols (EPI_BF16 / GELU / F32; refused with the others)
     int rowbias_period, rowbias_ld, rowbias_cols;
     const int* rope_pos;             // EPI_ROPE: position of row m
     const float* rope_table;         // f32 [max_pos][64] = cos[32] | sin[32]
@@ -31,13 +31,18 @@ struct GemmArgs {
     int raster_gm;                   // 256-tile kernels: m-tiles per raster group (0 = choose by W size)
     int ksplit;                      // 256-tile kernels, EPI_F32 only: split K over ksplit workgroups per tile;
     size_t split_stride;             //   split s writes its partial product to out + s * split_stride (elements)
-    float col_scale; int col_scale_n;   // optional, bf16-output plain epilogue (EPI_BF16, no row map / row bias): columns n < col_scale_n
+    float col_scale; int col_scale_n;   // optional, EPI_BF16 only (the general forms scale per column under a row map / row bias): columns n < col_scale_n
                                      // (a multiple of 64) leave as bf16((acc + bias) * col_scale) — the ViT's q columns carry
                                      // head_dim^-0.5 * log2(e) into the attention kernel with ONE rounding (attention_w.hip)
-    const int* m_dev; int m_sub;     // optional, GEMM_VARIANT_256IL only: rows < *m_dev - m_sub exist (a row count known on the
+    const int* m_dev; int m_sub;     // optional, GEMM_VARIANT_256IL only (refused elsewhere): rows < *m_dev - m_sub exist (a row count known on the
                                      // device only: tiles at or past it leave at once — the search's band pass)
 };
 hipError_t launch_gemm(const GemmArgs& a, int epilogue, int variant, hipStream_t s);
+// The rule of the optional fields: each is HONOURED by the kernel a launch reaches or the launch is REFUSED (hipErrorInvalidValue)
+// before anything runs — never silently ignored.  `variant` is a concrete one (AUTO resolved); true = refuse.  Every variant
+// launcher below asks this itself, so a direct caller gets the same answer as launch_gemm's.  (include/visrag_hip.h,
+// vr_op_gemm_ex, has the table.)
+bool gemm_args_refused(const GemmArgs& a, int epilogue, int variant);
 // 256x192 tile (gemm192.hip): N % 192 == 0, epilogues BF16 / GELU / F32 / RESID only
 hipError_t launch_gemm192(const GemmArgs& a, int epilogue, hipStream_t s);
 // 256x256 tile, one wave per SIMD (gemm256w.hip): same contract as the 256-tile path of launch_gemm

@@ -113,10 +113,11 @@ extern "C" int vr_streams_overlap(int device_id, void* stream_a, void* stream_b,
 }
 
 // ------------------------------------------------------------------------------ op-level ---
-extern "C" int vr_op_gemm(int device_id, const void* A, int32_t lda, const void* W, int32_t ldw, int32_t M, int32_t N,
-                          int32_t K, int32_t epilogue, const float* bias, const float* resid, float alpha, void* out,
-                          int32_t ldo, const int32_t* rope_pos, const float* rope_table, int32_t rope_cols,
-                          int32_t variant, void* stream) {
+// (extras: the fields of GemmArgs beyond vr_op_gemm's arguments, copied as they are — what is legal is the launchers' decision)
+extern "C" int vr_op_gemm_ex(int device_id, const void* A, int32_t lda, const void* W, int32_t ldw, int32_t M, int32_t N,
+                             int32_t K, int32_t epilogue, const float* bias, const float* resid, float alpha, void* out,
+                             int32_t ldo, const int32_t* rope_pos, const float* rope_table, int32_t rope_cols,
+                             int32_t variant, const vr_gemm_extras_t* extras, void* stream) {
     if (!A || !W || !out) return fail(VR_ERR_INVALID, "NULL argument");
     if (variant != GEMM_VARIANT_GLDS && variant != GEMM_VARIANT_AUTO && variant != GEMM_VARIANT_192 && variant != GEMM_VARIANT_256IL && variant != GEMM_VARIANT_256W && variant != GEMM_VARIANT_192W &&
         variant != GEMM_VARIANT_128W_192 && variant != GEMM_VARIANT_128W_256)
@@ -128,8 +129,24 @@ extern "C" int vr_op_gemm(int device_id, const void* A, int32_t lda, const void*
     GemmArgs a{};
     a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.M = M; a.N = N; a.K = K; a.bias = bias; a.resid = resid;
     a.alpha = alpha; a.out = out; a.ldo = ldo; a.rope_pos = rope_pos; a.rope_table = rope_table; a.rope_cols = rope_cols;
+    if (extras) {
+        a.rowmap = extras->rowmap;
+        a.rowbias = extras->rowbias; a.rowbias_period = extras->rowbias_period; a.rowbias_ld = extras->rowbias_ld; a.rowbias_cols = extras->rowbias_cols;
+        a.col_scale = extras->col_scale; a.col_scale_n = extras->col_scale_n;
+        a.ksplit = extras->ksplit; a.split_stride = (size_t)extras->split_stride;
+        a.m_dev = extras->m_dev; a.m_sub = extras->m_sub;
+        a.raster_gm = extras->raster_gm;
+    }
     HIPCHK(launch_gemm(a, epilogue, variant, (hipStream_t)stream));
     return VR_OK;
+}
+
+extern "C" int vr_op_gemm(int device_id, const void* A, int32_t lda, const void* W, int32_t ldw, int32_t M, int32_t N,
+                          int32_t K, int32_t epilogue, const float* bias, const float* resid, float alpha, void* out,
+                          int32_t ldo, const int32_t* rope_pos, const float* rope_table, int32_t rope_cols,
+                          int32_t variant, void* stream) {
+    return vr_op_gemm_ex(device_id, A, lda, W, ldw, M, N, K, epilogue, bias, resid, alpha, out, ldo, rope_pos, rope_table, rope_cols,
+                         variant, nullptr, stream);
 }
 
 extern "C" int vr_op_norm(int device_id, int32_t kind, const float* x, int32_t rows, int32_t dim, const float* weight,
@@ -141,17 +158,57 @@ extern "C" int vr_op_norm(int device_id, int32_t kind, const float* x, int32_t r
     return VR_OK;
 }
 
-extern "C" int vr_op_attention(int device_id, const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v,
-                               int32_t ldv, void* out, int32_t ldo, const int32_t* cu_q, const int32_t* cu_kv, int32_t B,
-                               int32_t heads, int32_t head_dim, int32_t max_q, int32_t causal, int32_t q_shared,
-                               float scale, void* stream) {
+extern "C" int vr_op_attention_ex(int device_id, const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v,
+                                  int32_t ldv, void* out, int32_t ldo, const int32_t* cu_q, const int32_t* cu_kv, int32_t B,
+                                  int32_t heads, int32_t head_dim, int32_t max_q, int32_t causal, int32_t q_shared,
+                                  float scale, const vr_attn_extras_t* extras, void* stream) {
     if (!q || !k || !v || !out || !cu_q || !cu_kv) return fail(VR_ERR_INVALID, "NULL argument");
     VRCHK(set_dev(device_id));
     AttnArgs a{};
     a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldk; a.v = v; a.ldv = ldv; a.out = out; a.ldo = ldo; a.cu_q = cu_q;
     a.cu_kv = cu_kv; a.B = B; a.heads = heads; a.head_dim = head_dim; a.max_q = max_q; a.causal = causal;
     a.q_shared = q_shared; a.scale = scale;
+    if (extras) {
+        a.kv_group = extras->kv_group; a.kv_end = extras->kv_end; a.q_in_rows = extras->q_in_rows;
+        a.q_head_stride = extras->q_head_stride; a.q_prescaled = extras->q_prescaled; a.lse = extras->lse;
+    }
     HIPCHK(launch_attention(a, (hipStream_t)stream));
+    return VR_OK;
+}
+
+extern "C" int vr_op_attention(int device_id, const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v,
+                               int32_t ldv, void* out, int32_t ldo, const int32_t* cu_q, const int32_t* cu_kv, int32_t B,
+                               int32_t heads, int32_t head_dim, int32_t max_q, int32_t causal, int32_t q_shared,
+                               float scale, void* stream) {
+    return vr_op_attention_ex(device_id, q, ldq, k, ldk, v, ldv, out, ldo, cu_q, cu_kv, B, heads, head_dim, max_q, causal, q_shared,
+                              scale, nullptr, stream);
+}
+
+// the merge of a decode step's KV ranges: on its own (gen_kernels.hip) or inside the o projection (gemm_skinny.hip, COMBINE)
+extern "C" int vr_op_attn_combine(int device_id, const void* part, const float* lse, int32_t S, const int32_t* S_dev, int32_t heads,
+                                  int32_t group, int32_t n_rows, void* out, int32_t ld_out, const void* W, int32_t ldw, int32_t M,
+                                  int32_t N, int32_t K, int32_t ksplit, int32_t planes, int32_t ldo, int64_t split_stride, void* stream) {
+    if (!part || !lse || !out) return fail(VR_ERR_INVALID, "NULL argument");
+    if (heads < 1 || n_rows < 1 || n_rows > 16) return fail(VR_ERR_INVALID, "need heads >= 1 and 1..16 rows");
+    if (!S_dev && (S < 1 || S > GEN_ATT_SPLITS)) return fail(VR_ERR_INVALID, "S must be 1..%d", GEN_ATT_SPLITS);
+    VRCHK(set_dev(device_id));
+    if (!W) {
+        if (ld_out < heads * 128 && n_rows > 1) return fail(VR_ERR_INVALID, "ld_out must cover heads * 128");
+        HIPCHK(launch_attn_combine(part, lse, S, heads, group, out, (hipStream_t)stream, S_dev, n_rows, ld_out));
+        return VR_OK;
+    }
+    // (what keeps the launch inside the caller's buffers is checked here; what the kernel can do is the launcher's to refuse)
+    if (n_rows != 1) return fail(VR_ERR_INVALID, "the fused form merges one row");
+    if (N < 1 || N % 4 || K < 64 || K % 64 || ldw < K || ldw % 8) return fail(VR_ERR_INVALID, "need N %% 4 == 0, K %% 64 == 0, ldw >= K, ldw %% 8 == 0");
+    if (ksplit < 1 || ksplit > planes) return fail(VR_ERR_INVALID, "ksplit must be 1..planes");
+    if (ldo < N || ldo % 4 || (ksplit > 1 && (split_stride < (int64_t)(M > 0 ? M : 1) * ldo || split_stride % 4)))
+        return fail(VR_ERR_INVALID, "ldo must cover N, split_stride a plane of M x ldo; both multiples of 4");
+    if (((uintptr_t)W | (uintptr_t)out) & 15) return fail(VR_ERR_INVALID, "pointers must be 16-byte aligned");
+    GemmArgs a{};
+    a.A = nullptr; a.lda = K; a.W = W; a.ldw = ldw; a.M = M; a.N = N; a.K = K; a.out = out; a.ldo = ldo;
+    a.ksplit = ksplit; a.split_stride = (size_t)split_stride;
+    const SkinnyCombine cb{part, lse, S, heads, group, S_dev};
+    HIPCHK(launch_gemm_skinny(a, (hipStream_t)stream, false, &cb));
     return VR_OK;
 }
 
