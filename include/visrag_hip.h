@@ -392,6 +392,75 @@ int vr_op_gemm_ex(int device_id, const void* A, int32_t lda, const void* W, int3
 int vr_op_norm(int device_id, int32_t kind, const float* x, int32_t rows, int32_t dim,
                const float* weight, const float* bias, float eps, void* out, int32_t ldo,
                void* stream);
+/* vr_op_norm with the row pitch of x (ldx >= dim floats; the pitch columns are not read): the ViT's LayerNorms read rows of
+ * the padded width. */
+int vr_op_norm_ex(int device_id, int32_t kind, const float* x, int32_t rows, int32_t dim, int32_t ldx, const float* weight,
+                  const float* bias, float eps, void* out, int32_t ldo, void* stream);
+
+/* ---- the fp32 text path (csrc/hp_text.hip) and the encode glue kernels (csrc/misc.hip, csrc/patch_embed.hip) ----
+ * Thin forwards to the launchers the encode path calls.  The entries check NULL pointers only (VR_ERR_INVALID); a shape a
+ * launcher cannot run is refused THERE, before anything is launched, and comes back as VR_ERR_HIP.  All buffers are the
+ * caller's, on the device, 16-byte aligned unless stated otherwise.
+ *
+ *   entry                      launcher(s)                                  kernel file
+ *   vr_op_text_rmsnorm_split   launch_rmsnorm_split                         hp_text.hip
+ *   vr_op_text_rope            launch_rope_f32                              hp_text.hip
+ *   vr_op_text_attention       launch_seq_of + launch_attn_f32              hp_text.hip
+ *   vr_op_text_swiglu_split    launch_swiglu_split                          hp_text.hip
+ *   vr_op_embed_gather         launch_embed_gather / launch_embed_gather_hp misc.hip / hp_text.hip
+ *   vr_op_pool                 launch_pool                                  misc.hip
+ *   vr_op_convert              launch_f32_to_bf16 / _pad / launch_split_bf16 / launch_any_nonzero16 / launch_iota_pos /
+ *                              launch_seq_of                                misc.hip / hp_text.hip
+ *   vr_op_planes_sum           launch_planes_sum                            hp_text.hip
+ *   vr_op_patch_embed          launch_pack_patch_weight + launch_patch_embed  pack.hip / patch_embed.hip
+ *   vr_op_norm_ex              launch_layernorm / launch_rmsnorm            norm.hip */
+/* y = x * rsqrt(mean(x^2) + eps) * weight of f32 rows [rows][dim], written as hi + lo bf16 rows [rows][dim] each (y ~= hi + lo
+ * to 16 mantissa bits).  hi and lo are separate pointers: the encode path puts lo right behind the `rows` hi rows.
+ * dim % 4 == 0, dim <= 2560. */
+int vr_op_text_rmsnorm_split(int device_id, const float* x, int32_t rows, int32_t dim, const float* weight, float eps, void* hi,
+                             void* lo, void* stream);
+/* Rotates, in place, the heads (64 columns, pairs (c, c + 32)) of the first rope_cols columns of the f32 rows qkv [T][ld] by
+ * table [pos[t]][32 cos | 32 sin]; pos i32 [T].  rope_cols % 64 == 0. */
+int vr_op_text_rope(int device_id, float* qkv, int32_t T, int32_t ld, int32_t rope_cols, const int32_t* pos, const float* table,
+                    void* stream);
+/* Causal fp32 attention over packed ragged sequences, head_dim 64: qkv f32 [T][ld] holds q | k | v at columns 0, E, 2 E;
+ * seq_offsets i32 [B + 1] on the device (seq_offsets[B] == T); out f32 [T][E].  E == 64 heads.  Synchronises the stream. */
+int vr_op_text_attention(int device_id, const float* qkv, int32_t ld, int32_t E, const int32_t* seq_offsets, int32_t B, int32_t T,
+                         int32_t heads, float scale, float* out, void* stream);
+/* act = silu(gate) * up of gu f32 [T][ld_gu] (gate of column i at (i / 16) * 32 + i % 16, up 16 further), written as hi + lo
+ * bf16 rows [T][ld_act], columns [I, ld_act) zero.  I % 16 == 0, ld_act % 4 == 0, ld_act >= I. */
+int vr_op_text_swiglu_split(int device_id, const float* gu, int32_t T, int32_t ld_gu, int32_t I, int32_t ld_act, void* hi, void* lo,
+                            void* stream);
+/* out f32 [T][dim] = table[ids[t]] * scale (table_lo NULL) or (table[ids[t]] + table_lo[ids[t]]) * scale; tables bf16
+ * [rows][dim], ids i32 [T] on the device.  dim % 4 == 0. */
+int vr_op_embed_gather(int device_id, const int32_t* ids, int32_t T, const void* table, const void* table_lo, int32_t dim,
+                       float scale, float* out, void* stream);
+/* Final RMSNorm, pooling (mode 0 wmean, 1 mean, 2 last token, 3 first token) and L2 normalisation of the packed f32 rows
+ * h [seq_offsets[B]][dim]: out f32 [B][dim]; tap (or NULL) f32 [seq_offsets[B]][dim] receives the normed rows.  Every
+ * sequence holds at least one row.  dim % 4 == 0, dim <= 2560. */
+int vr_op_pool(int device_id, const float* h, const int32_t* seq_offsets, int32_t B, int32_t dim, const float* norm_w, float eps,
+               float* out, float* tap, int32_t mode, void* stream);
+/* The conversions and index fills:
+ *   kind 0: out bf16 [n] = round-to-nearest-even of in f32 [n]
+ *   kind 1: the same for the first n elements, zeros up to n_total (n, n_total % 4 == 0); aux (or NULL): two i32 cleared
+ *   kind 2: out / out2 bf16 [n] = hi / lo parts of in f32 [n], hi = bf16(v), lo = bf16(v - hi)
+ *   kind 3: *aux |= 1 if any of the n 16-bit words of `in` is neither +0 nor -0
+ *   kind 4: in = seq_offsets i32 [n + 1]: out i32 [t] = t - seq_offsets[b] for every token t of sequence b
+ *   kind 5: in = seq_offsets i32 [n + 1]: out i32 [t] = b */
+int vr_op_convert(int device_id, int32_t kind, const void* in, void* out, void* out2, int64_t n, int64_t n_total, int32_t* aux,
+                  void* stream);
+/* out[t][c] = (accumulate ? out[t][c] : 0) + alpha * (parts[0][t][c] + parts[1][t][c] + ...), c < N: n_parts f32 planes
+ * [T][ldp], plane p at parts + p * stride floats, summed in plane order; out f32 [T][ldo], columns >= N not written.
+ * N, ldp, ldo % 4 == 0. */
+int vr_op_planes_sum(int device_id, const float* parts, int32_t n_parts, int64_t stride, int32_t ldp, int32_t T, int32_t N,
+                     float* out, int32_t ldo, float alpha, int32_t accumulate, void* stream);
+/* ToTensor + Normalize(0.5, 0.5) + Conv2d(3, D, kernel = stride = P) + bias + position embedding of n HWC u8 images of H x W:
+ * imgs is a HOST array of n device pointers; weight f32 [D][3][P][P] (packed into a temporary as vr_model_load_weight packs
+ * it, K columns per row, K % 64 == 0, K >= 3 P^2); bias f32 [D]; pos f32 [(H / P)(W / P)][ld_pos]; out f32
+ * [n (H / P)(W / P)][ldo], row (img, py, px).  D % 128 == 0, H % P == 0, W % P == 0.  Synchronises the stream. */
+int vr_op_patch_embed(int device_id, const void* const* imgs, int32_t n, int32_t H, int32_t W, int32_t P, const float* weight,
+                      int32_t D, int32_t K, const float* bias, const float* pos, int32_t ld_pos, float* out, int32_t ldo,
+                      void* stream);
 /* Flash attention over bf16 q/k/v with row strides ld*, per-batch row ranges cu_q/cu_kv
  * ([B+1], device), head_dim in {64,72,80,128}; causal uses absolute positions within the
  * sequence.  q_batch_stride==0 shares q across the batch (resampler). out bf16 [rows_q][ldo]. */

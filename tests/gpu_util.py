@@ -173,3 +173,79 @@ def op_attn_combine(part, lse, heads, group, out, S=0, S_dev=None, n_rows=1, ld_
                "vr_op_attn_combine")
     torch.cuda.synchronize()
     return out
+
+
+# ---- the fp32 text path and the encode glue kernels (tests/test_gpu_text_ops.py).  As above the outputs are the caller's,
+#      prefilled with a sentinel; pointers are passed as they are, so a view into a larger guarded buffer can be handed in.
+def op_norm_ex(kind, x, rows, dim, ldx, w, b, eps, out, ldo):
+    lib = _lib.load()
+    _lib.check(lib.vr_op_norm_ex(x.device.index or 0, kind, P(x), rows, dim, ldx, P(w), P(b), float(eps), P(out), ldo, None), "vr_op_norm_ex")
+    torch.cuda.synchronize()
+    return out
+
+
+def op_text_rmsnorm_split(x, rows, dim, w, eps, hi, lo):
+    lib = _lib.load()
+    _lib.check(lib.vr_op_text_rmsnorm_split(x.device.index or 0, P(x), rows, dim, P(w), float(eps), P(hi), P(lo), None), "vr_op_text_rmsnorm_split")
+    torch.cuda.synchronize()
+
+
+def op_text_rope(qkv, T, ld, rope_cols, pos, table):
+    lib = _lib.load()
+    _lib.check(lib.vr_op_text_rope(qkv.device.index or 0, P(qkv), T, ld, rope_cols, P(pos), P(table), None), "vr_op_text_rope")
+    torch.cuda.synchronize()
+    return qkv
+
+
+def op_text_attention(qkv, ld, E, seq_offsets, B, T, heads, scale, out):
+    lib = _lib.load()
+    _lib.check(lib.vr_op_text_attention(qkv.device.index or 0, P(qkv), ld, E, P(seq_offsets), B, T, heads, float(scale), P(out), None),
+               "vr_op_text_attention")
+    torch.cuda.synchronize()
+    return out
+
+
+def op_text_swiglu_split(gu, T, ld_gu, I, ld_act, hi, lo):
+    lib = _lib.load()
+    _lib.check(lib.vr_op_text_swiglu_split(gu.device.index or 0, P(gu), T, ld_gu, I, ld_act, P(hi), P(lo), None), "vr_op_text_swiglu_split")
+    torch.cuda.synchronize()
+
+
+def op_embed_gather(ids, T, table, table_lo, dim, scale, out):
+    lib = _lib.load()
+    _lib.check(lib.vr_op_embed_gather(ids.device.index or 0, P(ids), T, P(table), P(table_lo), dim, float(scale), P(out), None), "vr_op_embed_gather")
+    torch.cuda.synchronize()
+    return out
+
+
+def op_pool(h, seq_offsets, B, dim, w, eps, out, tap, mode):
+    lib = _lib.load()
+    _lib.check(lib.vr_op_pool(h.device.index or 0, P(h), P(seq_offsets), B, dim, P(w), float(eps), P(out), P(tap), mode, None), "vr_op_pool")
+    torch.cuda.synchronize()
+    return out
+
+
+def op_convert(kind, src, out=None, out2=None, n=0, n_total=0, aux=None):
+    """kind 0 f32 -> bf16, 1 the same + zeros up to n_total (aux: two i32 cleared), 2 hi / lo split, 3 *aux |= any non-zero 16-bit
+    word, 4 / 5 positions / sequence index of the tokens of src = seq_offsets [n + 1]"""
+    lib = _lib.load()
+    _lib.check(lib.vr_op_convert(src.device.index or 0, kind, P(src), P(out), P(out2), int(n), int(n_total), P(aux), None), "vr_op_convert")
+    torch.cuda.synchronize()
+
+
+def op_planes_sum(parts, n_parts, stride, ldp, T, N, out, ldo, alpha, accumulate):
+    lib = _lib.load()
+    _lib.check(lib.vr_op_planes_sum(parts.device.index or 0, P(parts), n_parts, int(stride), ldp, T, N, P(out), ldo, float(alpha), int(accumulate),
+                                    None), "vr_op_planes_sum")
+    torch.cuda.synchronize()
+    return out
+
+
+def op_patch_embed(imgs, H, W, patch, weight, D, K, bias, pos, ld_pos, out, ldo):
+    """imgs: a list of u8 HWC device tensors; weight f32 [D][3][patch][patch]; out f32 [>= n (H / patch)(W / patch)][ldo]"""
+    lib = _lib.load()
+    ptrs = (C.c_void_p * len(imgs))(*[t.data_ptr() for t in imgs])
+    _lib.check(lib.vr_op_patch_embed(weight.device.index or 0, ptrs, len(imgs), H, W, patch, P(weight), D, K, P(bias), P(pos), ld_pos, P(out), ldo,
+                                     None), "vr_op_patch_embed")
+    torch.cuda.synchronize()
+    return out

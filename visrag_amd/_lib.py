@@ -110,6 +110,16 @@ SIGNATURES = {
     "vr_op_gemm_ex": (C.c_int, [C.c_int, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _f32,
                                 _vp, _i32, _vp, _vp, _i32, _i32, C.POINTER(VRGemmExtras), _vp]),
     "vr_op_norm": (C.c_int, [C.c_int, _i32, _vp, _i32, _i32, _vp, _vp, _f32, _vp, _i32, _vp]),
+    "vr_op_norm_ex": (C.c_int, [C.c_int, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _f32, _vp, _i32, _vp]),
+    "vr_op_text_rmsnorm_split": (C.c_int, [C.c_int, _vp, _i32, _i32, _vp, _f32, _vp, _vp, _vp]),
+    "vr_op_text_rope": (C.c_int, [C.c_int, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "vr_op_text_attention": (C.c_int, [C.c_int, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _f32, _vp, _vp]),
+    "vr_op_text_swiglu_split": (C.c_int, [C.c_int, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "vr_op_embed_gather": (C.c_int, [C.c_int, _vp, _i32, _vp, _vp, _i32, _f32, _vp, _vp]),
+    "vr_op_pool": (C.c_int, [C.c_int, _vp, _vp, _i32, _i32, _vp, _f32, _vp, _vp, _i32, _vp]),
+    "vr_op_convert": (C.c_int, [C.c_int, _i32, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "vr_op_planes_sum": (C.c_int, [C.c_int, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _i32, _f32, _i32, _vp]),
+    "vr_op_patch_embed": (C.c_int, [C.c_int, C.POINTER(_vp), _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp]),
     "vr_op_attention": (C.c_int, [C.c_int, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32,
                                   _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
     "vr_op_attention_ex": (C.c_int, [C.c_int, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32,

@@ -2,6 +2,7 @@
 // calls (vr_op_*) the kernel tests drive.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <map>
 #include <tuple>
@@ -374,5 +375,120 @@ extern "C" int vr_op_chat_prompt_scatter(int device_id, const void* qkv, int32_t
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(launch_chat_prompt_scatter(bt, qkv, ld, E, max_len, kplane, vplane, s));
     HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
+}
+
+// ---- the fp32 text path (hp_text.hip) and the encode glue kernels (misc.hip, patch_embed.hip, norm.hip) ---
+// Thin forwards: only NULL pointers are checked here; what a kernel cannot do is the launcher's to refuse (VR_ERR_HIP).
+extern "C" int vr_op_norm_ex(int device_id, int32_t kind, const float* x, int32_t rows, int32_t dim, int32_t ldx, const float* weight,
+                             const float* bias, float eps, void* out, int32_t ldo, void* stream) {
+    if (!x || !weight || !out || (kind == 0 && !bias)) return fail(VR_ERR_INVALID, "NULL argument");
+    VRCHK(set_dev(device_id));
+    if (kind == 0) HIPCHK(launch_layernorm(x, rows, dim, ldx, weight, bias, eps, out, ldo, (hipStream_t)stream));
+    else HIPCHK(launch_rmsnorm(x, rows, dim, ldx, weight, eps, out, ldo, (hipStream_t)stream));
+    return VR_OK;
+}
+
+extern "C" int vr_op_text_rmsnorm_split(int device_id, const float* x, int32_t rows, int32_t dim, const float* weight, float eps,
+                                        void* hi, void* lo, void* stream) {
+    if (!x || !weight || !hi || !lo) return fail(VR_ERR_INVALID, "NULL argument");
+    VRCHK(set_dev(device_id));
+    HIPCHK(launch_rmsnorm_split(x, rows, dim, weight, eps, hi, lo, (hipStream_t)stream));
+    return VR_OK;
+}
+
+extern "C" int vr_op_text_rope(int device_id, float* qkv, int32_t T, int32_t ld, int32_t rope_cols, const int32_t* pos,
+                               const float* table, void* stream) {
+    if (!qkv || !pos || !table) return fail(VR_ERR_INVALID, "NULL argument");
+    VRCHK(set_dev(device_id));
+    HIPCHK(launch_rope_f32(qkv, T, ld, rope_cols, pos, table, (hipStream_t)stream));
+    return VR_OK;
+}
+
+extern "C" int vr_op_text_attention(int device_id, const float* qkv, int32_t ld, int32_t E, const int32_t* seq_offsets, int32_t B,
+                                    int32_t T, int32_t heads, float scale, float* out, void* stream) {
+    if (!qkv || !seq_offsets || !out) return fail(VR_ERR_INVALID, "NULL argument");
+    VRCHK(set_dev(device_id));
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf seq_of;                                          // (freed on return: the stream is drained first)
+    VRCHK(seq_of.alloc((size_t)(T > 0 ? T : 1) * 4));
+    HIPCHK(launch_seq_of(seq_offsets, B, seq_of.as<int>(), s));
+    HIPCHK(launch_attn_f32(qkv, ld, E, seq_of.as<int>(), seq_offsets, T, heads, scale, out, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
+}
+
+extern "C" int vr_op_text_swiglu_split(int device_id, const float* gu, int32_t T, int32_t ld_gu, int32_t I, int32_t ld_act, void* hi,
+                                       void* lo, void* stream) {
+    if (!gu || !hi || !lo) return fail(VR_ERR_INVALID, "NULL argument");
+    VRCHK(set_dev(device_id));
+    HIPCHK(launch_swiglu_split(gu, T, ld_gu, I, ld_act, hi, lo, (hipStream_t)stream));
+    return VR_OK;
+}
+
+extern "C" int vr_op_embed_gather(int device_id, const int32_t* ids, int32_t T, const void* table, const void* table_lo, int32_t dim,
+                                  float scale, float* out, void* stream) {
+    if (!ids || !table || !out) return fail(VR_ERR_INVALID, "NULL argument");
+    VRCHK(set_dev(device_id));
+    if (!table_lo) HIPCHK(launch_embed_gather(ids, T, table, dim, scale, out, (hipStream_t)stream));
+    else HIPCHK(launch_embed_gather_hp(ids, T, table, table_lo, dim, scale, out, (hipStream_t)stream));
+    return VR_OK;
+}
+
+extern "C" int vr_op_pool(int device_id, const float* h, const int32_t* seq_offsets, int32_t B, int32_t dim, const float* norm_w,
+                          float eps, float* out, float* tap, int32_t mode, void* stream) {
+    if (!h || !seq_offsets || !norm_w || !out) return fail(VR_ERR_INVALID, "NULL argument");
+    VRCHK(set_dev(device_id));
+    HIPCHK(launch_pool(h, seq_offsets, B, dim, norm_w, eps, out, tap, (hipStream_t)stream, mode));
+    return VR_OK;
+}
+
+extern "C" int vr_op_convert(int device_id, int32_t kind, const void* in, void* out, void* out2, int64_t n, int64_t n_total,
+                             int32_t* aux, void* stream) {
+    if (kind < 0 || kind > 5) return fail(VR_ERR_INVALID, "kind %d: 0 f32->bf16, 1 f32->bf16 + zero pad, 2 hi/lo split, 3 any non-zero, 4 positions, 5 sequence of a token", kind);
+    if (!in || (kind != 3 && !out) || (kind == 2 && !out2) || (kind == 3 && !aux)) return fail(VR_ERR_INVALID, "NULL argument");
+    VRCHK(set_dev(device_id));
+    hipStream_t s = (hipStream_t)stream;
+    switch (kind) {
+        case 0: HIPCHK(launch_f32_to_bf16((const float*)in, out, (size_t)n, s)); break;
+        case 1: HIPCHK(launch_f32_to_bf16_pad((const float*)in, out, (size_t)n, (size_t)n_total, s, aux)); break;
+        case 2: HIPCHK(launch_split_bf16((const float*)in, out, out2, (size_t)n, s)); break;
+        case 3: HIPCHK(launch_any_nonzero16(in, (size_t)n, aux, s)); break;
+        case 4: HIPCHK(launch_iota_pos((const int*)in, (int)n, (int*)out, s)); break;
+        default: HIPCHK(launch_seq_of((const int*)in, (int)n, (int*)out, s)); break;
+    }
+    return VR_OK;
+}
+
+extern "C" int vr_op_planes_sum(int device_id, const float* parts, int32_t n_parts, int64_t stride, int32_t ldp, int32_t T, int32_t N,
+                                float* out, int32_t ldo, float alpha, int32_t accumulate, void* stream) {
+    if (!parts || !out) return fail(VR_ERR_INVALID, "NULL argument");
+    VRCHK(set_dev(device_id));
+    HIPCHK(launch_planes_sum(parts, n_parts, (size_t)stride, ldp, T, N, out, ldo, alpha, accumulate != 0, (hipStream_t)stream));
+    return VR_OK;
+}
+
+extern "C" int vr_op_patch_embed(int device_id, const void* const* imgs, int32_t n, int32_t H, int32_t W, int32_t P, const float* weight,
+                                 int32_t D, int32_t K, const float* bias, const float* pos, int32_t ld_pos, float* out, int32_t ldo,
+                                 void* stream) {
+    if (!imgs || !weight || !bias || !pos || !out) return fail(VR_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n; ++i)
+        if (!imgs[i]) return fail(VR_ERR_INVALID, "NULL argument");
+    VRCHK(set_dev(device_id));
+    hipStream_t s = (hipStream_t)stream;
+    const int Kreal = 3 * P * P, patches = P > 0 ? (H / P) * (W / P) : 0;
+    // the packed weight as vr_model_load_weight keeps it: bf16 [D padded to 256 rows][K], zero where nothing is packed (the
+    // row pitch of the ALLOCATION also covers Kreal, so that the pack of a K the launcher will refuse stays inside it)
+    DevBuf wp, ptrs;
+    VRCHK(wp.alloc((size_t)pad256(D > 0 ? D : 1) * (size_t)std::max(std::max(K, Kreal), 1) * 2));
+    VRCHK(ptrs.alloc((size_t)(n > 0 ? n : 1) * sizeof(void*)));
+    HIPCHK(launch_pack_patch_weight(weight, 0, D, P, wp.p, K, s));
+    if (n > 0) HIPCHK(hipMemcpyAsync(ptrs.p, imgs, (size_t)n * sizeof(void*), hipMemcpyHostToDevice, s));
+    GemmArgs a{};
+    a.W = wp.p; a.ldw = K; a.M = n * patches; a.N = D; a.K = K; a.bias = bias; a.out = out; a.ldo = ldo; a.alpha = 1.0f;
+    a.rowbias = pos; a.rowbias_period = patches; a.rowbias_ld = ld_pos; a.rowbias_cols = D;
+    const hipError_t e = launch_patch_embed((const uint8_t* const*)ptrs.p, n, H, W, P, a, Kreal, s);
+    HIPCHK(hipStreamSynchronize(s));                        // (the temporaries are freed on return)
+    if (e != hipSuccess) return fail(VR_ERR_HIP, "launch_patch_embed(...) failed: %s", hipGetErrorString(e));
     return VR_OK;
 }
