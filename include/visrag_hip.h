@@ -307,6 +307,36 @@ int vr_index_get_search_profile(vr_index_t ix, double* ms5, int64_t* calls);
  * id_offset + rows must stay below 2^32 - 1. */
 int vr_index_search_keys(vr_index_t ix, const float* queries, int32_t nq, int32_t k, int64_t id_offset,
                          uint64_t* out_keys, int32_t on_device, void* stream);
+/* ---- document-level search: the best row per group of adjacent rows, the k best groups ---- */
+/* Partition the rows present into n_groups groups (documents) of ADJACENT rows: group g holds rows
+ * group_offsets[g] .. group_offsets[g + 1] - 1.  group_offsets (host, n_groups + 1 entries) starts at 0, is
+ * strictly increasing and ends at the row count; a NULL pointer, n_groups < 1 or offsets that break one
+ * of these rules: VR_ERR_INVALID, and the index keeps the grouping it had.  A later vr_index_add that
+ * appends rows, or vr_index_reset, drops the grouping. */
+int vr_index_set_groups(vr_index_t ix, const int64_t* group_offsets, int64_t n_groups);
+/* For every query the k best groups.  The score of a group, E_g, is the largest fp32 dot product of the
+ * query with a row of the group — the score vr_index_search returns for that row — and the group's best
+ * row is the row that attains it, the lowest row id among equal scores.  Results: larger E_g first, the
+ * lower best row id first among equal E_g.
+ *   out_scores [nq][k] float32 = E_g;  out_ids [nq][k] int64 = best row;  out_groups [nq][k] int64 = g
+ * (all host or all device per `on_device`); with fewer than k groups the tail is (-inf, -1, -1).
+ * The ids are the fp32 ranking's, as for vr_index_search, and by the same argument applied to groups: the
+ * bf16 MFMA scores b_i of all rows (|b_i - e_i| <= eps, the error model of vr_index_set_search_eps) give
+ * group maxima B_g with |B_g - E_g| <= eps; the k + 24 groups of largest B_g are candidates; in a
+ * candidate every row with b_i >= B_g - 2 eps (only such a row can attain E_g) is re-scored in fp32; the
+ * result is certified if the best B_g outside the candidates lies below E_(k) - eps, else every group with
+ * B_g >= E_(k) - eps is re-scored (up to 1024), else the query is redone from exact fp32 scores of all
+ * rows.  With certification off (eps_rel < 0) the first candidate set is re-scored (rows within the
+ * default error model of their group's B_g) and returned with no guarantee.
+ * k = 1..1000 and the dim limits of the deep path of vr_index_search: anything else is VR_ERR_INVALID
+ * before any launch; no grouping set for the rows present: VR_ERR_STATE.  Grouped searches are not counted
+ * by vr_index_search_stats and leave every state the other searches read alone. */
+int vr_index_search_groups(vr_index_t ix, const float* queries, int32_t nq, int32_t k,
+                           float* out_scores, int64_t* out_ids, int64_t* out_groups,
+                           int32_t on_device, void* stream);
+/* Grouped-search queries since the last reset: out3 = {certified from the first candidate set,
+ * certified after widening it, redone exactly}. */
+int vr_index_group_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
 /* Merge per-shard results (e.g. after an RCCL all-gather): in [n_parts][nq][k] scores and
  * global ids -> out [nq][k], same ordering rule.  Device pointers. */
 int vr_topk_merge(int device_id, const float* scores, const int64_t* ids, int32_t n_parts,

@@ -8,6 +8,7 @@
 
 #include "engine_common.h"
 
+constexpr int GRP_STATS = 2, GRP_LIST = 8, GRP_WORDS = GRP_LIST + 256;
 constexpr int CERT_WORDS = 32, CERT_FLAG = 2, CERT_FLAG2 = 3, CERT_STATS = 4, CERT_NSTATS = 6;   // (the two flag counters are consecutive: cleared together)
 struct vr_index_s {
     int device = 0, dim = 0;
@@ -22,6 +23,11 @@ struct vr_index_s {
     int64_t fcap = 0;
     int* huge_seen = nullptr;         // pinned host word: a streaming search met a band beyond search_band_max() rows (SearchArgs::huge_seen)
     float eps_rel = -2.f;             // -2: the rigorous data-dependent default; >= 0: the caller's eps_rel |q| max|d|; else off
+    // grouped search (vr_index_search_groups, search_group.hip): state of its own — the plain searches read none of it
+    int64_t n_groups = 0;             // 0: no grouping set (vr_index_add / vr_index_reset drop it)
+    DevBuf goff, gB, og, gstate;      // int first rows [n_groups + 1] | group maxima [256][ldB] | staged out_groups |
+                                      // int words: [0] flag count, [1] unused (cleared with it), u32 [2..4] the three counters of
+                                      // vr_index_group_search_stats, [GRP_LIST..] flag list of a block of <= 256 queries
     // per-stage HIP events (vr_index_set_search_profile): convert | thresholds | sweep | merge | exact pass
     bool prof_on = false;
     hipEvent_t prof_ev[SEARCH_PROF_EVENTS] = {};
@@ -52,7 +58,7 @@ extern "C" int vr_index_destroy(vr_index_t ix) {
     (void)hipSetDevice(ix->device);
     (void)hipDeviceSynchronize();
     for (DevBuf* b : {&ix->f32, &ix->bf16, &ix->q32, &ix->qbf, &ix->cs, &ix->ci, &ix->ck, &ix->os, &ix->oi, &ix->ok, &ix->thr,
-                      &ix->sbuf, &ix->cert, &ix->flags, &ix->flagq})
+                      &ix->sbuf, &ix->cert, &ix->flags, &ix->flagq, &ix->goff, &ix->gB, &ix->og, &ix->gstate})
         b->free();
     for (hipEvent_t e : ix->prof_ev) if (e) (void)hipEventDestroy(e);
     if (ix->huge_seen) (void)hipHostFree(ix->huge_seen);
@@ -66,6 +72,7 @@ extern "C" int vr_index_reset(vr_index_t ix) {
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemset(ix->cert.p, 0, 8));          // largest row norm, largest rounding residual
     ix->n = 0;
+    ix->n_groups = 0;
     if (ix->huge_seen) *ix->huge_seen = 0;
     return VR_OK;
 }
@@ -88,6 +95,7 @@ extern "C" int vr_index_add(vr_index_t ix, const float* reps, int64_t n, int32_t
     HIPCHK(launch_row_norm_max(dst, n, ix->dim, ix->cert.as<float>(), s));      // max |d|, max |d - bf16(d)|: the search's error bound
     if (!on_device) HIPCHK(hipStreamSynchronize(s));
     ix->n += n;
+    ix->n_groups = 0;                 // the grouping described the rows that were there
     return VR_OK;
 }
 
@@ -347,6 +355,117 @@ extern "C" int vr_index_search_keys(vr_index_t ix, const float* queries, int32_t
                                     uint64_t* out_keys, int32_t on_device, void* stream) {
     if (!out_keys) return fail(VR_ERR_INVALID, "out_keys is NULL");
     return search_impl(ix, queries, nq, k, nullptr, nullptr, (unsigned long long*)out_keys, id_offset, on_device, stream);
+}
+
+extern "C" int vr_index_set_groups(vr_index_t ix, const int64_t* group_offsets, int64_t n_groups) {
+    if (!ix || !group_offsets) return fail(VR_ERR_INVALID, "NULL argument");
+    if (n_groups < 1 || n_groups > ix->n) return fail(VR_ERR_INVALID, "%lld groups over %lld rows", (long long)n_groups, (long long)ix->n);
+    if (group_offsets[0] != 0) return fail(VR_ERR_INVALID, "group_offsets[0] must be 0");
+    for (int64_t g = 0; g < n_groups; ++g)
+        if (group_offsets[g + 1] <= group_offsets[g]) return fail(VR_ERR_INVALID, "group_offsets must be strictly increasing (entry %lld)", (long long)(g + 1));
+    if (group_offsets[n_groups] != ix->n)
+        return fail(VR_ERR_INVALID, "last group offset %lld is not the row count %lld", (long long)group_offsets[n_groups], (long long)ix->n);
+    VRCHK(set_dev(ix->device));
+    HIPCHK(hipDeviceSynchronize());               // (a grouped search in flight reads the offsets)
+    ix->n_groups = 0;
+    std::vector<int> off((size_t)n_groups + 1);   // rows are 32-bit (vr_index_create)
+    for (int64_t g = 0; g <= n_groups; ++g) off[(size_t)g] = (int)group_offsets[g];
+    VRCHK(ix->goff.reserve(off.size() * 4));
+    HIPCHK(hipMemcpy(ix->goff.p, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+    if (!ix->gstate.p) VRCHK(ix->gstate.alloc(GRP_WORDS * 4));
+    ix->n_groups = n_groups;
+    return VR_OK;
+}
+
+extern "C" int vr_index_group_search_stats(vr_index_t ix, int64_t* out3, int32_t reset) {
+    if (!ix || !out3) return fail(VR_ERR_INVALID, "NULL argument");
+    out3[0] = out3[1] = out3[2] = 0;
+    if (!ix->gstate.p) return VR_OK;              // no grouping was ever set: nothing counted
+    VRCHK(set_dev(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    unsigned w[3];
+    HIPCHK(hipMemcpy(w, ix->gstate.as<unsigned>() + GRP_STATS, sizeof(w), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 3; ++i) out3[i] = w[i];
+    if (reset) HIPCHK(hipMemset(ix->gstate.as<unsigned>() + GRP_STATS, 0, sizeof(w)));
+    return VR_OK;
+}
+
+// The k best groups per query (search_group.hip).  Scratch (query staging, score rows, staged outputs) is shared with the plain
+// searches; flag list, counters and group maxima are the grouped search's own.
+extern "C" int vr_index_search_groups(vr_index_t ix, const float* queries, int32_t nq, int32_t k, float* out_scores,
+                                      int64_t* out_ids, int64_t* out_groups, int32_t on_device, void* stream) {
+    if (!ix || !queries || !out_scores || !out_ids || !out_groups || nq <= 0) return fail(VR_ERR_INVALID, "bad arguments");
+    if (k <= 0 || k > search_groups_kmax() || k > search_bigk_max())
+        return fail(VR_ERR_INVALID, "k=%d unsupported (1..%d)", k, std::min(search_groups_kmax(), search_bigk_max()));
+    if (ix->n_groups <= 0 || ix->n <= 0) return fail(VR_ERR_STATE, "no grouping set for the rows of the index (vr_index_set_groups)");
+    VRCHK(set_dev(ix->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int dim = ix->dim, ng = (int)ix->n_groups;
+    const int64_t ldS = pad256l(ix->n), ldB = (ix->n_groups + 63) / 64 * 64;
+    const int64_t qblk = 256;                     // one fp32 score row per query, as on the deep path
+    const int64_t nqp = pad256l(std::min<int64_t>(nq, qblk));
+    if (ix->qcap < nqp) {
+        VRCHK(ix->qbf.alloc((size_t)nqp * dim * 2));
+        VRCHK(ix->thr.alloc((size_t)nqp * 8));
+        ix->qcap = nqp;
+    }
+    const float* q32 = queries;
+    float* os = out_scores; int64_t* oi = out_ids; int64_t* og = out_groups;
+    if (!on_device) {
+        VRCHK(ix->q32.reserve((size_t)nq * dim * 4));
+        HIPCHK(hipMemcpyAsync(ix->q32.p, queries, (size_t)nq * dim * 4, hipMemcpyHostToDevice, s));
+        q32 = ix->q32.as<float>();
+        VRCHK(ix->os.reserve((size_t)nq * k * 4));
+        VRCHK(ix->oi.reserve((size_t)nq * k * 8));
+        VRCHK(ix->og.reserve((size_t)nq * k * 8));
+        os = ix->os.as<float>(); oi = ix->oi.as<int64_t>(); og = ix->og.as<int64_t>();
+    }
+    VRCHK(ix->sbuf.reserve((size_t)qblk * ldS * 4));
+    VRCHK(ix->gB.reserve((size_t)qblk * ldB * 4));
+    const bool certify = ix->eps_rel == -2.f || ix->eps_rel >= 0.f;
+    for (int64_t q0 = 0; q0 < nq; q0 += qblk) {
+        const int nb = (int)std::min<int64_t>(qblk, nq - q0);
+        const int64_t nbp = pad256l(nb);
+        // rows >= nb: zeros; also clears the grouped search's flag counter
+        HIPCHK(launch_f32_to_bf16_pad(q32 + (size_t)q0 * dim, ix->qbf.p, (size_t)nb * dim, (size_t)nbp * dim, s, ix->gstate.as<int>()));
+        GroupSearchArgs p{};
+        SearchArgs& a = p.a;
+        a.index_bf16 = ix->bf16.p; a.index_f32 = ix->f32.as<float>(); a.n_docs = ix->n; a.dim = dim;
+        a.q_bf16 = ix->qbf.p; a.q_f32 = q32 + (size_t)q0 * dim; a.nq = nb; a.k = k;
+        // the error model also bounds which rows of a group are re-scored: with certification off, the default one does that
+        a.eps_data = ix->eps_rel >= 0.f ? 0 : 1;
+        a.eps_rel = a.eps_data ? 0.f : ix->eps_rel;
+        a.acc_rel = search_acc_rel(dim);
+        a.dmax = ix->cert.as<float>();
+        a.flag_count = ix->gstate.as<int>(); a.flag_list = ix->gstate.as<int>() + GRP_LIST;
+        a.out_scores = os + (size_t)q0 * k; a.out_ids = oi + (size_t)q0 * k;
+        p.goff = ix->goff.as<int>(); p.n_groups = ng;
+        p.B = ix->gB.as<float>(); p.ldB = (size_t)ldB;
+        p.out_groups = og + (size_t)q0 * k;
+        p.stats = ix->gstate.as<unsigned>() + GRP_STATS;
+        p.certify = certify ? 1 : 0;
+        // S[q][row] = queries x index^T on the bf16 MFMA GEMM, the deep path's launch
+        GemmArgs g{};
+        g.A = ix->qbf.p; g.lda = dim;
+        g.W = ix->bf16.p; g.ldw = dim; g.M = nb; g.N = (int)pad128l(ix->n); g.K = dim;
+        g.out = ix->sbuf.p; g.ldo = (int)ldS; g.alpha = 1.0f;
+        HIPCHK(launch_gemm(g, EPI_F32, GEMM_VARIANT_AUTO, s));
+        HIPCHK(launch_group_max(ix->sbuf.as<float>(), (size_t)ldS, p.goff, ng, p.B, p.ldB, nb, nullptr, 0, s));
+        HIPCHK(launch_group_select(p, ix->sbuf.as<float>(), (size_t)ldS, nb, s));
+        if (certify) {
+            // whatever the select flagged (nothing, normally: the three kernels leave at once): exact fp32 score rows
+            HIPCHK(launch_exact_scores(a.index_f32, a.n_docs, dim, a.q_f32, a.flag_list, a.flag_count, 0, nb, ix->sbuf.as<float>(), (size_t)ldS, s));
+            HIPCHK(launch_group_max(ix->sbuf.as<float>(), (size_t)ldS, p.goff, ng, p.B, p.ldB, nb, a.flag_count, 0, s));
+            HIPCHK(launch_group_select_exact(p, ix->sbuf.as<float>(), (size_t)ldS, 0, nb, s));
+        }
+    }
+    if (!on_device) {
+        HIPCHK(hipMemcpyAsync(out_scores, os, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(out_ids, oi, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(out_groups, og, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    return VR_OK;
 }
 
 extern "C" int vr_topk_merge(int device_id, const float* scores, const int64_t* ids, int32_t n_parts, int32_t nq,

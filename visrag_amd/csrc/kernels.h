@@ -368,5 +368,24 @@ hipError_t launch_band_select(const SearchArgs& a, const float* S, size_t ldS, i
 hipError_t launch_row_norm_max(const float* rows, int64_t n, int dim, float* dmax, hipStream_t s);
 float search_default_eps_rel(int dim);      // worst-case relative bound (a caller's yardstick; the default bound is data-dependent)
 float search_acc_rel(int dim);
+// ---- grouped search (search_group.hip): the k best groups of adjacent rows per query, each with its best row
+struct GroupSearchArgs {
+    SearchArgs a;                    // the block's view, as for launch_search_bigk: index, queries, k, out_scores / out_ids, the error
+                                     // model (eps_data / eps_rel / acc_rel / dmax: ALWAYS a valid model, it also bounds the rows re-scored
+                                     // inside a group), flag_count / flag_list (the grouped search's own); everything else unused
+    const int* goff;                 // [n_groups + 1] first row of every group; goff[n_groups] = n_docs
+    int n_groups;
+    float* B; size_t ldB;            // group maxima [slot][ldB] of the score rows at hand
+    int64_t* out_groups;             // [nq][k] group of every result (-1: none)
+    unsigned* stats;                 // [0] certified from the first candidate set [1] after widening it [2] flagged: redone exactly
+    int certify;                     // 0: the first candidate set re-scored, no guarantee
+};
+int search_groups_kmax();
+// B[slot][g] = max of S[slot][rows of group g] for n_slots score rows; slot_count set: only the first *slot_count - sub of them
+hipError_t launch_group_max(const float* S, size_t ldS, const int* goff, int n_groups, float* B, size_t ldB, int n_slots,
+                            const int* slot_count, int sub, hipStream_t s);
+hipError_t launch_group_select(const GroupSearchArgs& p, const float* S, size_t ldS, int nq_block, hipStream_t s);
+// the flagged queries from EXACT score rows / group maxima (slot i = query flag_list[sub + i]): overwrites their outputs
+hipError_t launch_group_select_exact(const GroupSearchArgs& p, const float* S, size_t ldS, int sub, int max_slots, hipStream_t s);
 
 }  // namespace vr

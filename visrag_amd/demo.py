@@ -5,6 +5,8 @@
                                                                build_index.py:14-58
   * `retrieve(knowledge_base_path, query, topk, ...)` -> paths of the top-k page images
                                                                answer.py:14-40
+  * `retrieve_documents(knowledge_base_path, query, topk, ...)` -> the best page of each of the top-k DOCUMENTS
+                                                               (no reference counterpart: its top-k is pages)
 
 Same on-disk knowledge base (`reps.npy` float32 [n_pages, 2304], `index2img_filename.txt` one file name per
 row, `<pdf>_<idx>.png`), so a base built by either side can be queried by the other.  Differences that do
@@ -20,6 +22,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
+from .documents import doc_of_page, group_rows
 from .engine import HipIndex
 from .modeling import encode  # noqa: F401  (demo/visrag_pipeline/utils.py:12-32)
 
@@ -102,3 +105,56 @@ def retrieve(knowledge_base_path: str, query: str, topk: int, model, tokenizer, 
     keep = [int(i) for i in ids[0] if i >= 0]
     paths = [os.path.join(knowledge_base_path, names[i]) for i in keep]
     return (paths, [float(s) for s in sc[0][: len(keep)]]) if return_scores else paths
+
+
+def load_document_base(knowledge_base_path: str, device: Optional[int] = None):
+    """-> (HipIndex holding reps.npy with every document's pages adjacent and the documents set as its groups, the image file
+    names in the index's row order).  The document of a page is `doc_of_page(name)`; a base whose pages are not contiguous per
+    document is reordered on load (documents in the order of their first page, pages in their order), and because the names
+    are reordered with the rows, `names[row id]` is the page whatever the order on disk."""
+    with open(os.path.join(knowledge_base_path, "index2img_filename.txt")) as f:
+        names = [n for n in f.read().split("\n") if n]
+    reps = np.load(os.path.join(knowledge_base_path, "reps.npy")).astype(np.float32)
+    if len(names) != len(reps):
+        raise ValueError(f"{len(reps)} rows but {len(names)} page names in {knowledge_base_path}")
+    order, offsets, _ = group_rows([doc_of_page(n) for n in names])
+    from .modeling import default_device
+    ix = HipIndex(reps.shape[1], max(len(reps), 1), default_device() if device is None else device)
+    if len(reps):
+        ix.add(reps[order])
+        ix.set_groups(offsets)
+    return ix, [names[i] for i in order]
+
+
+@torch.no_grad()
+def retrieve_documents(knowledge_base_path: str, query, topk: int, model, tokenizer, index=None, names=None,
+                       return_scores: bool = False):
+    """Paths of the best page of each of the `topk` most similar DOCUMENTS, best document first (None if the base does not
+    exist): a document scores as its best page does, so ten results are ten documents, not ten pages of one.  Documents are
+    the `doc_of_page` of the page names.  Pass `index, names = load_document_base(path)` to keep the index resident between
+    questions; an index of your own must hold every document's pages adjacently, `names` in its row order.  `query` is the
+    question, or its embedding ([dim] or [1, dim]) if it has been encoded already."""
+    if not os.path.exists(knowledge_base_path):
+        return None
+    own = index is None
+    if own:
+        index, names = load_document_base(knowledge_base_path, model.encoder.device if model is not None else None)
+    elif not index.n_groups:
+        order, offsets, _ = group_rows([doc_of_page(n) for n in names])
+        if not np.array_equal(order, np.arange(len(order))):
+            raise ValueError("the pages of a document are not adjacent in this index: load it with load_document_base()")
+        index.set_groups(offsets)
+    if isinstance(query, str):
+        q = encode(model, tokenizer, [QUERY_INSTRUCTION + query])
+    else:
+        q = np.asarray(query.detach().cpu() if isinstance(query, torch.Tensor) else query, dtype=np.float32).reshape(1, -1)
+    if len(index) == 0:
+        paths, scores = [], []
+    else:
+        sc, ids, _ = index.search_groups(q, max(1, min(topk, index.n_groups)))
+        keep = [int(i) for i in ids[0][:topk] if i >= 0]
+        paths = [os.path.join(knowledge_base_path, names[i]) for i in keep]
+        scores = [float(s) for s in sc[0][: len(keep)]]
+    if own:
+        index.close()
+    return (paths, scores) if return_scores else paths

@@ -240,6 +240,7 @@ class HipIndex:
         self._h = C.c_void_p()
         _lib.check(self.lib.vr_index_create(self.device, self.dim, self.capacity, C.byref(self._h)),
                    "vr_index_create")
+        self.n_groups = 0          # groups set for the rows present (set_groups); add / reset drop them
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -259,8 +260,10 @@ class HipIndex:
 
     def reset(self) -> None:
         _lib.check(self.lib.vr_index_reset(self._h))
+        self.n_groups = 0
 
     def add(self, reps) -> None:
+        self.n_groups = 0
         if isinstance(reps, torch.Tensor):
             t = reps.to(torch.float32).contiguous()
             assert t.dim() == 2 and t.shape[1] == self.dim
@@ -294,6 +297,43 @@ class HipIndex:
                                             C.c_void_p(_stream_ptr(self.device))), "vr_index_search")
         return sc, ix
 
+    def set_groups(self, offsets) -> None:
+        """Partition the rows present into groups (documents) of adjacent rows: group g = rows offsets[g] .. offsets[g + 1] - 1
+        (offsets[0] == 0, strictly increasing, offsets[-1] == len(self)).  `add` and `reset` drop the grouping."""
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        _lib.check(self.lib.vr_index_set_groups(self._h, off.ctypes.data_as(C.POINTER(C.c_int64)), len(off) - 1),
+                   "vr_index_set_groups")
+        self.n_groups = len(off) - 1
+
+    def search_groups(self, queries, k: int):
+        """The k best groups per query, each by its best row (include/visrag_hip.h: vr_index_search_groups)
+        -> (scores [nq,k] f32, best row ids [nq,k] i64, groups [nq,k] i64); cuda in -> cuda out, numpy / cpu in -> numpy out."""
+        if isinstance(queries, torch.Tensor) and queries.is_cuda:
+            q = queries.to(torch.float32).contiguous()
+            nq = q.shape[0]
+            sc = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+            ix = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+            gr = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+            _lib.check(self.lib.vr_index_search_groups(self._h, C.c_void_p(q.data_ptr()), nq, k, C.c_void_p(sc.data_ptr()),
+                                                       C.c_void_p(ix.data_ptr()), C.c_void_p(gr.data_ptr()), 1,
+                                                       C.c_void_p(_stream_ptr(self.device))), "vr_index_search_groups")
+            return sc, ix, gr
+        q = np.ascontiguousarray(queries.numpy() if isinstance(queries, torch.Tensor) else queries, dtype=np.float32)
+        nq = q.shape[0]
+        sc = np.empty((nq, max(k, 0)), dtype=np.float32)
+        ix = np.empty((nq, max(k, 0)), dtype=np.int64)
+        gr = np.empty((nq, max(k, 0)), dtype=np.int64)
+        _lib.check(self.lib.vr_index_search_groups(self._h, C.c_void_p(q.ctypes.data), nq, k, C.c_void_p(sc.ctypes.data),
+                                                   C.c_void_p(ix.ctypes.data), C.c_void_p(gr.ctypes.data), 0,
+                                                   C.c_void_p(_stream_ptr(self.device))), "vr_index_search_groups")
+        return sc, ix, gr
+
+    def group_search_stats(self, reset: bool = False) -> Dict[str, int]:
+        """Grouped-search queries since the last reset by outcome: certified from the first candidate set / after widening it /
+        redone from exact fp32 scores of every row."""
+        out = (C.c_int64 * 3)()
+        _lib.check(self.lib.vr_index_group_search_stats(self._h, out, 1 if reset else 0))
+        return {"certified": int(out[0]), "certified_widened": int(out[1]), "exact": int(out[2])}
 
     def search_keys(self, queries: torch.Tensor, k: int, id_offset: int = 0) -> torch.Tensor:
         """The same search with each result packed into ONE 64-bit word (include/visrag_hip.h:

@@ -32,6 +32,7 @@ from typing import Callable, Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
+from .documents import group_rows
 from .engine import HipIndex, topk_merge_keys
 from .utils import list_shards, read_shard, shard_rank
 
@@ -141,6 +142,45 @@ def distributed_parallel_retrieve(args, topk: int, global_topk: bool = False, sh
             if j >= 0:
                 result[q][all_ids[int(j)]] = float(s)
     return result
+
+
+def retrieve_documents(args, topk: int, doc_of: Callable[[str], str], index_factory: Optional[Callable] = None
+                       ) -> Tuple[Dict[str, Dict[str, float]], Dict[str, Dict[str, str]]]:
+    """Document-level retrieval over the same pickle shards: this rank's query shard(s) against ALL corpus shards, the corpus
+    rows being PAGES and `doc_of(page_id)` the document a page belongs to.  -> ({qid: {doc: score}}, {qid: {doc: best_page_id}}):
+    the `topk` best documents per query, a document scoring as its best page does (HipIndex.search_groups: the fp32 ranking);
+    the first dict goes to `save_as_trec` as it is.  Pages of a document need not be adjacent or in one shard: all shards are
+    loaded into ONE index, reordered so that they are (documents.group_rows).
+
+    Replicated form only: every rank holds the whole corpus.  Corpus-sharded multi-GPU grouped search is out of scope — a
+    document may straddle the shards of two ranks, and a per-rank best page is not a document's best page."""
+    make_index = index_factory or HipIndex
+    queries, qids, _ = _load_queries(args)
+    corpus_parts = list_shards(args.output_dir, "corpus")
+    if len(corpus_parts) == 0:
+        raise ValueError("No pre-computed document embeddings found")
+    reps, page_ids = [], []
+    for p in corpus_parts:
+        r, i = read_shard(p)
+        if len(i):
+            reps.append(np.asarray(r, dtype=np.float32))
+            page_ids.extend(i)
+    scores: Dict[str, Dict[str, float]] = {q: {} for q in qids}
+    pages: Dict[str, Dict[str, str]] = {q: {} for q in qids}
+    if not page_ids or topk <= 0:
+        return scores, pages
+    order, offsets, docs = group_rows([doc_of(i) for i in page_ids])
+    ix = make_index(queries.shape[1], len(page_ids), _device_index(args))
+    ix.add(np.concatenate(reps)[order])
+    ix.set_groups(offsets)
+    sc, rows, groups = ix.search_groups(queries, min(topk, len(docs)))
+    ix.close()
+    for qi, q in enumerate(qids):
+        for s, r, g in zip(sc[qi], rows[qi], groups[qi]):
+            if r >= 0:
+                scores[q][docs[int(g)]] = float(s)
+                pages[q][docs[int(g)]] = page_ids[int(order[int(r)])]
+    return scores, pages
 
 
 def _retrieve_corpus_sharded(args, topk: int, global_topk: bool, make_index: Callable, merge_keys: Optional[Callable]
