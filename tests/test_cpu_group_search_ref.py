@@ -73,6 +73,16 @@ def test_random_offsets_partition_the_rows():
         assert off[0] == 0 and off[-1] == n and (np.diff(off) >= 1).all() and (np.diff(off) < 2 * mean).all()
 
 
+def test_tie_tier_corpus_is_what_the_gpu_tests_take_it_for():
+    C, Q, ids = R.tie_tier()                                 # (its own asserts: one exact tier, gaps > 1e-2 above it, > 1e-4 among the rest)
+    assert C.shape == (3000, 64) and Q.shape == (3, 64) and ids.shape == (3, 150) and C.dtype == Q.dtype == np.float32
+    high = 7 * np.arange(100) + 3
+    assert (np.sort(ids[:, :100], axis=1) == high).all() and (ids[0, :100] != high).any()     # (score order is not id order)
+    assert (ids[:, 100:] == np.setdiff1d(np.arange(3000), high)[:50]).all()
+    _, ri, rg = R.group_topk_ref(Q, C, np.arange(3001), 150)
+    assert np.array_equal(ri, ids) and np.array_equal(rg, ids)
+
+
 def test_grouped_search_entry_points_are_declared_bound_and_exported():
     hdr = open(os.path.join(ROOT, "include", "visrag_hip.h")).read()
     lib = _lib.load()

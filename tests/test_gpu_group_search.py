@@ -182,6 +182,28 @@ def test_more_tied_groups_than_any_candidate_set():
     ix.close()
 
 
+def test_tie_tier_below_distinct_groups():
+    """R.tie_tier: 100 distinct rows above 2 900 identical ones, k = 150 — the candidates are every key above the threshold and
+    then the LOWEST of its ties.  Groups of one row: the row search, and that the expected rows; groups of three adjacent rows:
+    the reference, strictly (the input has no near-tie: R.tie_tier checks it).  The tier lies inside the error band: 2 900 tied
+    groups are beyond any candidate set (exact scores, the select with kp = k: 100 above, 50 of the ties), 900 tied groups of
+    three and the 100 above them fit the widened one (<= 1 024)."""
+    C, Q, want = R.tie_tier()
+    n, k = len(C), want.shape[1]
+    ix = _index(C, np.arange(n + 1))
+    pi = ix.search(Q, k)[1]
+    sc, ids, gr = ix.search_groups(Q, k)
+    assert np.array_equal(ids, pi) and np.array_equal(ids, want) and np.array_equal(gr, ids)
+    assert ix.group_search_stats(reset=True) == {"certified": 0, "certified_widened": 0, "exact": len(Q)}
+    off = np.arange(0, n + 1, 3)
+    ix.set_groups(off)
+    ref = R.group_topk_ref(Q, C, off, k)
+    _check(ix.search_groups(Q, k), ref, Q, C, off, strict=True)
+    _check(ix.search_groups(torch.tensor(Q).cuda(), k), ref, Q, C, off, strict=True)
+    assert ix.group_search_stats() == {"certified": 0, "certified_widened": 2 * len(Q), "exact": 0}
+    ix.close()
+
+
 def test_fewer_groups_than_k():
     C, Q = R.unit(100, 64, 1), R.unit(6, 64, 2)
     off = [0, 1, 40, 99, 100]

@@ -11,6 +11,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import visrag_ret_oracle as O  # noqa: E402
+from tests import group_search_ref as R  # noqa: E402
 from visrag_amd.engine import HipIndex, topk_merge  # noqa: E402
 from visrag_amd.retriever import merge_topk_host  # noqa: E402
 
@@ -162,6 +163,31 @@ def test_deep_retrieval_ties():
     assert np.array_equal(ids, np.tile(np.arange(k), (3, 1)))
     with pytest.raises(Exception):
         ix.search(Q, 1001)
+
+
+@pytest.mark.parametrize("eps", [None, 100.0, -1.0], ids=["default", "eps100", "uncertified"])
+@pytest.mark.parametrize("n", [3000, 9000])
+def test_deep_retrieval_tie_tier_below_distinct_rows(n, eps):
+    """A tie tier AT the selection threshold with rows above it (tests/group_search_ref.py: tie_tier): n - 100 identical rows,
+    100 distinct rows that beat them by > 1e-2.  k = 150: the 100 in fp64 order, then the 50 lowest tied ids ascending.
+    uncertified: straight from the first candidate set (kp = 174: the 100 keys above the threshold, then 74 of its ties).
+    Otherwise the tier lies inside any error band, so no error model can certify that set and the query is redone from every
+    row inside the band, which is the whole index: 3 000 rows fit the band pass (search_band.hip, <= 8 192 rows, its own sort
+    of all keys); 9 000 do not and go on to the exact pass, bigk_select_kernel with exact = 1 and kp = k — the 100 keys above
+    the threshold, then 50 of its 8 900 ties."""
+    C, Q, want = R.tie_tier(n)
+    ix = HipIndex(C.shape[1], n); ix.add(C)
+    if eps is not None:
+        ix.set_search_eps(eps)
+    ix.search_stats(reset=True)
+    sc, ids = ix.search(Q, want.shape[1])
+    st = ix.search_stats()
+    assert np.array_equal(ids, want)
+    np.testing.assert_allclose(sc, np.take_along_axis(R.scores64(Q, C), want, 1), atol=1e-5, rtol=0)
+    redone = "uncertified" if eps is not None and eps < 0 else "band_pass" if n <= 8192 else "exact_pass"
+    assert st[redone] == len(Q) and st["flagged"] == (0 if redone == "uncertified" else len(Q)), st
+    assert sum(st[w] for w in ("uncertified", "band_pass", "exact_pass", "certified", "certified_extended")) == len(Q), st
+    ix.close()
 
 
 @pytest.mark.parametrize("P,nq,k", [(4, 33, 10), (8, 17, 100), (3, 5, 1000)])

@@ -169,6 +169,66 @@ extern "C" int vr_index_get_search_profile(vr_index_t ix, double* ms5, int64_t* 
     return VR_OK;
 }
 
+// ---- what vr_index_search* and vr_index_search_groups share -----------------------------------------------------------------
+// Query staging for passes of up to `nqp` (padded) queries: capacity of the bf16 rows and thresholds, host queries to the
+// device.  *q32: the fp32 queries on the device.
+static int stage_queries(vr_index_t ix, const float* queries, int32_t nq, int64_t nqp, int32_t on_device, hipStream_t s,
+                         const float** q32) {
+    if (ix->qcap < nqp) {
+        VRCHK(ix->qbf.alloc((size_t)nqp * ix->dim * 2));
+        VRCHK(ix->thr.alloc((size_t)nqp * 8));            // thresholds | what the lists are complete down to (thr_cert)
+        ix->qcap = nqp;
+    }
+    *q32 = queries;
+    if (!on_device) {
+        VRCHK(ix->q32.reserve((size_t)nq * ix->dim * 4));
+        HIPCHK(hipMemcpyAsync(ix->q32.p, queries, (size_t)nq * ix->dim * 4, hipMemcpyHostToDevice, s));
+        *q32 = ix->q32.as<float>();
+    }
+    return VR_OK;
+}
+
+// One output array of n elements: the kernels write *dev — the caller's own array, or for a host caller the staging buffer
+// that return_output copies back (the caller synchronises the stream after the last one)
+template <typename T>
+static int stage_output(DevBuf& buf, T* out, size_t n, int32_t on_device, T** dev) {
+    *dev = out;
+    if (!on_device) { VRCHK(buf.reserve(n * sizeof(T))); *dev = buf.as<T>(); }
+    return VR_OK;
+}
+template <typename T>
+static int return_output(T* out, const T* dev, size_t n, int32_t on_device, hipStream_t s) {
+    if (!on_device) HIPCHK(hipMemcpyAsync(out, dev, n * sizeof(T), hipMemcpyDeviceToHost, s));
+    return VR_OK;
+}
+
+// S[r][row] = bf16 rows A[0, M) x index^T on the bf16 MFMA GEMM, fp32 out (m_dev set: the row count is read on the device)
+static int score_rows(vr_index_t ix, const void* A_bf16, int M, const int* m_dev, int m_sub, int variant, int64_t ldS, hipStream_t s) {
+    GemmArgs g{};
+    g.A = A_bf16; g.lda = ix->dim;
+    g.W = ix->bf16.p; g.ldw = ix->dim; g.M = M; g.N = (int)pad128l(ix->n); g.K = ix->dim;
+    g.out = ix->sbuf.p; g.ldo = (int)ldS; g.alpha = 1.0f;
+    g.m_dev = m_dev; g.m_sub = m_sub;
+    HIPCHK(launch_gemm(g, EPI_F32, variant, s));
+    return VR_OK;
+}
+
+// the error model of the certification (search_common.h: query_eps) as vr_index_set_search_eps left it
+static void fill_error_model(vr_index_t ix, SearchArgs& a) {
+    a.eps_data = ix->eps_rel == -2.f ? 1 : 0;
+    a.eps_rel = a.eps_data ? 0.f : ix->eps_rel;
+    a.acc_rel = search_acc_rel(ix->dim);
+    a.dmax = ix->cert.as<float>();
+}
+
+// entries [f0, f0 + ns) of a's flag list through the exact fp32 pass: score rows over the whole index, plain top-k of each
+static int exact_pass(vr_index_t ix, const SearchArgs& a, int f0, int ns, int64_t ldS, hipStream_t s) {
+    HIPCHK(launch_exact_scores(a.index_f32, a.n_docs, a.dim, a.q_f32, a.flag_list, a.flag_count, f0, ns, ix->sbuf.as<float>(),
+                               (size_t)ldS, s));
+    HIPCHK(launch_exact_select(a, ix->sbuf.as<float>(), (size_t)ldS, f0, ns, s));
+    return VR_OK;
+}
+
 // queries [nq][dim] -> top k per query, as (scores, ids) or as packed keys with `id_offset` added to the row ids
 static int search_impl(vr_index_t ix, const float* queries, int32_t nq, int32_t k, float* out_scores, int64_t* out_ids,
                        unsigned long long* out_keys, int64_t id_offset, int32_t on_device, void* stream) {
@@ -190,25 +250,14 @@ static int search_impl(vr_index_t ix, const float* queries, int32_t nq, int32_t 
     // score rows of the fallback passes (band pass / exact pass over the FLAGGED queries, search_band.hip): a bounded buffer
     // — at most 512 MiB of fp32 score rows (never fewer than 16 rows) — walked in passes of `slots` flagged queries
     const int64_t slots = bigk ? 256 : std::min<int64_t>(nqp, std::max<int64_t>(16, (((int64_t)1 << 27) / ldS) / 16 * 16));
-    if (ix->qcap < nqp) {
-        VRCHK(ix->qbf.alloc((size_t)nqp * dim * 2));
-        VRCHK(ix->thr.alloc((size_t)nqp * 8));            // thresholds | what the lists are complete down to (thr_cert)
-        ix->qcap = nqp;
-    }
-    const float* q32 = queries;
-    if (!on_device) {
-        VRCHK(ix->q32.reserve((size_t)nq * dim * 4));
-        HIPCHK(hipMemcpyAsync(ix->q32.p, queries, (size_t)nq * dim * 4, hipMemcpyHostToDevice, s));
-        q32 = ix->q32.as<float>();
-    }
-    float* os = out_scores; int64_t* oi = out_ids; unsigned long long* ok = out_keys;
-    if (!on_device) {
-        if (keys_out) { VRCHK(ix->ok.reserve((size_t)nq * k * 8)); ok = ix->ok.as<unsigned long long>(); }
-        else {
-            VRCHK(ix->os.reserve((size_t)nq * k * 4));
-            VRCHK(ix->oi.reserve((size_t)nq * k * 8));
-            os = ix->os.as<float>(); oi = ix->oi.as<int64_t>();
-        }
+    const float* q32 = nullptr;
+    VRCHK(stage_queries(ix, queries, nq, nqp, on_device, s, &q32));
+    const size_t n_out = (size_t)nq * k;
+    float* os = nullptr; int64_t* oi = nullptr; unsigned long long* ok = nullptr;
+    if (keys_out) VRCHK(stage_output(ix->ok, out_keys, n_out, on_device, &ok));
+    else {
+        VRCHK(stage_output(ix->os, out_scores, n_out, on_device, &os));
+        VRCHK(stage_output(ix->oi, out_ids, n_out, on_device, &oi));
     }
     if (ix->n == 0) {
         if (keys_out) HIPCHK(hipMemsetAsync(ok, 0, (size_t)nq * k * 8, s));
@@ -253,10 +302,7 @@ static int search_impl(vr_index_t ix, const float* queries, int32_t nq, int32_t 
             const bool exact_big = !conv_in_kernel && (bigk || huge_seen || !ix->huge_seen);
             a.exact_follows = (exact_small || exact_big) ? 1 : 0;
             a.huge_seen = ix->huge_seen;
-            a.eps_data = ix->eps_rel == -2.f ? 1 : 0;
-            a.eps_rel = a.eps_data ? 0.f : ix->eps_rel;
-            a.acc_rel = search_acc_rel(dim);
-            a.dmax = ix->cert.as<float>();
+            fill_error_model(ix, a);
             a.flag_count = ix->cert.as<int>() + CERT_FLAG; a.flag_list = ix->flags.as<int>();
             a.flag2_count = ix->cert.as<int>() + CERT_FLAG2; a.flag2_list = ix->flags.as<int>() + ix->fcap;
             a.flag_tau = ix->flags.as<float>() + 2 * ix->fcap; a.flag_q = ix->flagq.p;
@@ -266,12 +312,8 @@ static int search_impl(vr_index_t ix, const float* queries, int32_t nq, int32_t 
             a.prof_ev = prof ? ix->prof_ev : nullptr;
             if (bigk) {
                 // score rows of <= 256 queries at a time: S[q][doc] = queries x index^T on the bf16 MFMA GEMM
-                GemmArgs g{};
-                g.A = ix->qbf.p; g.lda = dim;
-                g.W = ix->bf16.p; g.ldw = dim; g.M = nb; g.N = (int)pad128l(ix->n); g.K = dim;
-                g.out = ix->sbuf.p; g.ldo = (int)ldS; g.alpha = 1.0f;
-                HIPCHK(launch_gemm(g, EPI_F32, GEMM_VARIANT_AUTO, s));
-                HIPCHK(launch_search_bigk(a, ix->sbuf.as<float>(), (size_t)ldS, 0, nb, s));
+                VRCHK(score_rows(ix, ix->qbf.p, nb, nullptr, 0, GEMM_VARIANT_AUTO, ldS, s));
+                HIPCHK(launch_search_bigk(a, ix->sbuf.as<float>(), (size_t)ldS, nb, s));
             } else {
                 const SearchPlan plan = search_plan(ix->n, nb, dim);
                 a.pre_own_chunks = plan.own;
@@ -300,28 +342,20 @@ static int search_impl(vr_index_t ix, const float* queries, int32_t nq, int32_t 
                 // search_band_max() rows) through the exact fp32 pass over the whole index (search_exact.hip)
                 for (int64_t f0 = 0; f0 < nb; f0 += slots) {
                     const int ns = (int)std::min<int64_t>(slots, nb - f0);
-                    GemmArgs g{};
-                    g.A = (const char*)ix->flagq.p + (size_t)f0 * dim * 2; g.lda = dim;
-                    g.W = ix->bf16.p; g.ldw = dim; g.M = ns; g.N = (int)pad128l(ix->n); g.K = dim;
-                    g.out = ix->sbuf.p; g.ldo = (int)ldS; g.alpha = 1.0f;
-                    g.m_dev = a.flag_count; g.m_sub = (int)f0;
-                    HIPCHK(launch_gemm(g, EPI_F32, GEMM_VARIANT_256IL, s));
+                    VRCHK(score_rows(ix, (const char*)ix->flagq.p + (size_t)f0 * dim * 2, ns, a.flag_count, (int)f0, GEMM_VARIANT_256IL, ldS, s));
                     HIPCHK(launch_band_select(a, ix->sbuf.as<float>(), (size_t)ldS, (int)f0, ns, s));
                 }
                 SearchArgs ax = a;
                 ax.flag_count = a.flag2_count; ax.flag_list = a.flag2_list;
                 for (int64_t f0 = 0; exact_big && f0 < nb; f0 += slots) {
                     const int ns = (int)std::min<int64_t>(slots, nb - f0);
-                    HIPCHK(launch_exact_scores(a.index_f32, a.n_docs, dim, a.q_f32, ax.flag_list, ax.flag_count, (int)f0, ns,
-                                               ix->sbuf.as<float>(), (size_t)ldS, s));
-                    HIPCHK(launch_exact_select(ax, ix->sbuf.as<float>(), (size_t)ldS, (int)f0, ns, s));
+                    VRCHK(exact_pass(ix, ax, (int)f0, ns, ldS, s));
                 }
             }
             if ((a.eps_data || a.eps_rel >= 0.f) && a.score_rows && exact_small) {
                 SearchArgs ax = a;
                 ax.flag_count = a.flag2_count; ax.flag_list = a.flag2_list;
-                HIPCHK(launch_exact_scores(a.index_f32, a.n_docs, dim, a.q_f32, ax.flag_list, ax.flag_count, 0, nb, ix->sbuf.as<float>(), (size_t)ldS, s));
-                HIPCHK(launch_exact_select(ax, ix->sbuf.as<float>(), (size_t)ldS, 0, nb, s));
+                VRCHK(exact_pass(ix, ax, 0, nb, ldS, s));
             }
             if (prof) {
                 HIPCHK(hipEventRecord(ix->prof_ev[5], s));
@@ -335,14 +369,12 @@ static int search_impl(vr_index_t ix, const float* queries, int32_t nq, int32_t 
             }
         }
     }
-    if (!on_device) {
-        if (keys_out) HIPCHK(hipMemcpyAsync(out_keys, ok, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
-        else {
-            HIPCHK(hipMemcpyAsync(out_scores, os, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(out_ids, oi, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
-        }
-        HIPCHK(hipStreamSynchronize(s));
+    if (keys_out) VRCHK(return_output(out_keys, ok, n_out, on_device, s));
+    else {
+        VRCHK(return_output(out_scores, os, n_out, on_device, s));
+        VRCHK(return_output(out_ids, oi, n_out, on_device, s));
     }
+    if (!on_device) HIPCHK(hipStreamSynchronize(s));
     return VR_OK;
 }
 
@@ -404,22 +436,13 @@ extern "C" int vr_index_search_groups(vr_index_t ix, const float* queries, int32
     const int64_t ldS = pad256l(ix->n), ldB = (ix->n_groups + 63) / 64 * 64;
     const int64_t qblk = 256;                     // one fp32 score row per query, as on the deep path
     const int64_t nqp = pad256l(std::min<int64_t>(nq, qblk));
-    if (ix->qcap < nqp) {
-        VRCHK(ix->qbf.alloc((size_t)nqp * dim * 2));
-        VRCHK(ix->thr.alloc((size_t)nqp * 8));
-        ix->qcap = nqp;
-    }
-    const float* q32 = queries;
-    float* os = out_scores; int64_t* oi = out_ids; int64_t* og = out_groups;
-    if (!on_device) {
-        VRCHK(ix->q32.reserve((size_t)nq * dim * 4));
-        HIPCHK(hipMemcpyAsync(ix->q32.p, queries, (size_t)nq * dim * 4, hipMemcpyHostToDevice, s));
-        q32 = ix->q32.as<float>();
-        VRCHK(ix->os.reserve((size_t)nq * k * 4));
-        VRCHK(ix->oi.reserve((size_t)nq * k * 8));
-        VRCHK(ix->og.reserve((size_t)nq * k * 8));
-        os = ix->os.as<float>(); oi = ix->oi.as<int64_t>(); og = ix->og.as<int64_t>();
-    }
+    const float* q32 = nullptr;
+    VRCHK(stage_queries(ix, queries, nq, nqp, on_device, s, &q32));
+    const size_t n_out = (size_t)nq * k;
+    float* os = nullptr; int64_t* oi = nullptr; int64_t* og = nullptr;
+    VRCHK(stage_output(ix->os, out_scores, n_out, on_device, &os));
+    VRCHK(stage_output(ix->oi, out_ids, n_out, on_device, &oi));
+    VRCHK(stage_output(ix->og, out_groups, n_out, on_device, &og));
     VRCHK(ix->sbuf.reserve((size_t)qblk * ldS * 4));
     VRCHK(ix->gB.reserve((size_t)qblk * ldB * 4));
     const bool certify = ix->eps_rel == -2.f || ix->eps_rel >= 0.f;
@@ -433,10 +456,8 @@ extern "C" int vr_index_search_groups(vr_index_t ix, const float* queries, int32
         a.index_bf16 = ix->bf16.p; a.index_f32 = ix->f32.as<float>(); a.n_docs = ix->n; a.dim = dim;
         a.q_bf16 = ix->qbf.p; a.q_f32 = q32 + (size_t)q0 * dim; a.nq = nb; a.k = k;
         // the error model also bounds which rows of a group are re-scored: with certification off, the default one does that
-        a.eps_data = ix->eps_rel >= 0.f ? 0 : 1;
-        a.eps_rel = a.eps_data ? 0.f : ix->eps_rel;
-        a.acc_rel = search_acc_rel(dim);
-        a.dmax = ix->cert.as<float>();
+        fill_error_model(ix, a);
+        if (!certify) { a.eps_data = 1; a.eps_rel = 0.f; }
         a.flag_count = ix->gstate.as<int>(); a.flag_list = ix->gstate.as<int>() + GRP_LIST;
         a.out_scores = os + (size_t)q0 * k; a.out_ids = oi + (size_t)q0 * k;
         p.goff = ix->goff.as<int>(); p.n_groups = ng;
@@ -445,11 +466,7 @@ extern "C" int vr_index_search_groups(vr_index_t ix, const float* queries, int32
         p.stats = ix->gstate.as<unsigned>() + GRP_STATS;
         p.certify = certify ? 1 : 0;
         // S[q][row] = queries x index^T on the bf16 MFMA GEMM, the deep path's launch
-        GemmArgs g{};
-        g.A = ix->qbf.p; g.lda = dim;
-        g.W = ix->bf16.p; g.ldw = dim; g.M = nb; g.N = (int)pad128l(ix->n); g.K = dim;
-        g.out = ix->sbuf.p; g.ldo = (int)ldS; g.alpha = 1.0f;
-        HIPCHK(launch_gemm(g, EPI_F32, GEMM_VARIANT_AUTO, s));
+        VRCHK(score_rows(ix, ix->qbf.p, nb, nullptr, 0, GEMM_VARIANT_AUTO, ldS, s));
         HIPCHK(launch_group_max(ix->sbuf.as<float>(), (size_t)ldS, p.goff, ng, p.B, p.ldB, nb, nullptr, 0, s));
         HIPCHK(launch_group_select(p, ix->sbuf.as<float>(), (size_t)ldS, nb, s));
         if (certify) {
@@ -459,12 +476,10 @@ extern "C" int vr_index_search_groups(vr_index_t ix, const float* queries, int32
             HIPCHK(launch_group_select_exact(p, ix->sbuf.as<float>(), (size_t)ldS, 0, nb, s));
         }
     }
-    if (!on_device) {
-        HIPCHK(hipMemcpyAsync(out_scores, os, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(out_ids, oi, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(out_groups, og, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
+    VRCHK(return_output(out_scores, os, n_out, on_device, s));
+    VRCHK(return_output(out_ids, oi, n_out, on_device, s));
+    VRCHK(return_output(out_groups, og, n_out, on_device, s));
+    if (!on_device) HIPCHK(hipStreamSynchronize(s));
     return VR_OK;
 }
 

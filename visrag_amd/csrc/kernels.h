@@ -342,7 +342,7 @@ bool sweep256w_ok(const SearchArgs& a);
 hipError_t launch_sweep256w(const SearchArgs& a, int kp, const float* thr, hipStream_t s);   // (honours pre_own_chunks)
 // k > 26 (search_bigk.hip): radix select over the block's score rows S + exact re-score; k <= search_bigk_max()
 int search_bigk_max();
-hipError_t launch_search_bigk(const SearchArgs& a, const float* S, size_t ldS, int q0, int nq_block, hipStream_t s);
+hipError_t launch_search_bigk(const SearchArgs& a, const float* S, size_t ldS, int nq_block, hipStream_t s);
 hipError_t launch_topk_merge_big(const float* scores, const int64_t* ids, int n_parts, int nq, int k,
                                  float* out_scores, int64_t* out_ids, hipStream_t s);   // n_parts * k <= 8192
 hipError_t launch_topk_merge(const float* scores, const int64_t* ids, int n_parts, int nq, int k,

@@ -140,11 +140,7 @@ __device__ __forceinline__ int band_pass_in_place(const SearchArgs& p, int q, fl
         // its list; when it does not (the common case: its two idle launches were 7 us of a 105 us search) the walk below is
         // done once and the host-visible word makes the engine launch the exact pass behind this index's searches from now on.
         if (p.exact_follows) {
-            if (threadIdx.x == 0) {
-                const int pos = atomicAdd(p.flag2_count, 1);
-                p.flag2_list[pos] = q;
-                if (p.stats) atomicAdd(&p.stats[5], 1u);
-            }
+            if (threadIdx.x == 0) flag2_push(p, q);
             return n_band;
         }
         if (threadIdx.x == 0) {

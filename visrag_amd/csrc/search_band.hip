@@ -24,6 +24,7 @@
 //
 // Roofline: the GEMM is MFMA-bound (2 x flagged x rows x dim), the selection HBM / L2 (score rows + union rows).
 #include "search_band.h"
+#include "search_select.h"
 
 namespace vr {
 
@@ -37,14 +38,9 @@ __global__ __launch_bounds__(BAND_NT) void band_select_kernel(SearchArgs p, cons
     BandLds& L = *reinterpret_cast<BandLds*>(smem_raw);
     __shared__ int ucnt_s;
     const int tid = threadIdx.x, lane = tid & 63;
-    const int n_slots = min(max(p.flag_count[0] - sub, 0), max_slots);
+    const int n_slots = flag_slots(p.flag_count, sub, max_slots);
     const int n_docs = (int)p.n_docs, k = p.k, dim = p.dim, nv = dim >> 2;
-#ifndef BAND_XCD
-#define BAND_XCD 0
-#endif
-    // (BAND_XCD: consecutive slots of a round on ONE XCD — workgroup b of the 256 takes slot (b % 8) * 32 + b / 8 of its round)
-    const int bslot = BAND_XCD && gridDim.x == 256 ? (int)(blockIdx.x & 7) * 32 + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-    for (int slot = bslot; slot < n_slots; slot += gridDim.x) {
+    for (int slot = blockIdx.x; slot < n_slots; slot += gridDim.x) {
         const int q = p.flag_list[sub + slot];
         const float tau = p.flag_tau[sub + slot];
         const float* row = S + (size_t)slot * ldS;
@@ -52,11 +48,7 @@ __global__ __launch_bounds__(BAND_NT) void band_select_kernel(SearchArgs p, cons
         const int n_band = band_gather<BAND_NT>(row, 0, n_docs, tau, L, &ucnt_s);
         if (n_band > BAND_MAX || !(tau > -INFINITY)) {                   // workgroup-uniform: the exact fp32 pass ...
             if (p.exact_follows || k > 64) {
-                if (tid == 0) {
-                    const int pos = atomicAdd(p.flag2_count, 1);
-                    p.flag2_list[pos] = q;
-                    if (p.stats) atomicAdd(&p.stats[5], 1u);
-                }
+                if (tid == 0) flag2_push(p, q);
                 continue;
             }
             // ... which is only launched behind an index that has shown such a band before (SearchArgs::huge_seen: its two idle

@@ -5,41 +5,33 @@
 // Deep retrieval is not the throughput case, so it takes the plain route, exact all the same:
 //   1. scores S[q][doc] of a block of <= 256 queries against the whole index with the bf16 MFMA
 //      GEMM (EPI_F32), the same arithmetic the sweeps use;
-//   2. per query (one workgroup): 3-pass radix select (11 + 11 + 10 bits of the order-preserving
-//      key, histograms in LDS) of the K'-th largest score, K' = k + 24 — the margin that keeps a
-//      true top-k row inside the candidate set although S carries bf16 rounding;
-//   3. gather the K' candidates in row order (all keys above the K'-th, then the lowest ids among
-//      its ties), re-score them against the fp32 index (exact fp32 dots: dot_lane), bitonic-sort
-//      the keys (score desc, id asc) in LDS;
+//   2. per query (one workgroup): the K' = k + 24 best bf16 scores in row order (search_select.h: radix select of the
+//      K'-th largest, then every key above it and the lowest ids among its ties) — the margin keeps a true top-k row
+//      inside the candidate set although S carries bf16 rounding;
+//   3. re-score the candidates against the fp32 index (exact fp32 dots: dot_lane), bitonic-sort the keys (score desc,
+//      id asc) in LDS;
 //   4. certify as the fused path does (search_common.h): if the K'-th bf16 score is not below
 //      tau = s_k - eps, gather and re-score EVERY row with a bf16 score >= tau (<= 1024), else
 //      flag the query for the exact fp32 pass; emit the top k.
 #include <algorithm>
 
 #include "kernels.h"
-#include "search_common.h"
+#include "search_select.h"
 
 namespace vr {
 
-constexpr int BIGK_CAND = 1024;             // K' = k + margin <= BIGK_CAND
-constexpr int BIGK_MARGIN = 24;
-
-int search_bigk_max() { return BIGK_CAND - BIGK_MARGIN; }
+int search_bigk_max() { return SEL_CAND - SEL_MARGIN; }
 
 // exact == 0: S rows are bf16-MFMA scores of queries blockIdx.x; the result is certified like the fused path's
 //   (search_common.h): tau = s_k - eps; if the radix threshold T does not lie below tau, every row with a bf16 score
-//   >= tau is gathered and re-scored instead (up to BIGK_CAND of them), else the query is flagged.
+//   >= tau is gathered and re-scored instead (up to SEL_CAND of them), else the query is flagged.
 // exact == 1: S row i holds EXACT fp32 scores of flagged query flag_list[i] (search_exact.hip); plain top-k of it.
 __global__ __launch_bounds__(256) void bigk_select_kernel(SearchArgs p, const float* __restrict__ S, size_t ldS, int kp_want,
                                                           int exact, int sub, int max_slots) {
-    __shared__ unsigned hist[2048];
-    __shared__ int cand[BIGK_CAND];
-    __shared__ uint64_t keys[BIGK_CAND];
-    __shared__ unsigned sh_prefix, sh_mask;
-    __shared__ int sh_rank, wc[4][2], run[2];
+    __shared__ SelectLds L;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // exact: a fixed grid walks entries [sub, sub + max_slots) of the flag list
-    const int n_slots = exact ? min(max(p.flag_count[0] - sub, 0), max_slots) : (int)gridDim.x;
+    const int n_slots = exact ? flag_slots(p.flag_count, sub, max_slots) : (int)gridDim.x;
     for (int slot = blockIdx.x; slot < n_slots; slot += gridDim.x) {
     const int q = exact ? p.flag_list[sub + slot] : slot;
     const float* row = S + (size_t)slot * ldS;
@@ -47,77 +39,10 @@ __global__ __launch_bounds__(256) void bigk_select_kernel(SearchArgs p, const fl
     int kp = min(n_docs, kp_want);
     __syncthreads();                                                    // (LDS of the previous slot is free)
 
-    // ---- 1. radix select: key of the kp-th largest score
-    if (tid == 0) { sh_prefix = 0u; sh_mask = 0u; sh_rank = kp; }
-    for (int pass = 0; pass < 3; ++pass) {
-        const int shift = pass == 0 ? 21 : pass == 1 ? 10 : 0;
-        const int nb = pass < 2 ? 2048 : 1024;
-        for (int i = tid; i < 2048; i += 256) hist[i] = 0u;
-        __syncthreads();
-        const unsigned prefix = sh_prefix, mask = sh_mask;
-        for (int i = tid; i < n_docs; i += 256) {
-            const unsigned key = f32_orderable(row[i]);
-            if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & (nb - 1)], 1u);
-        }
-        __syncthreads();
-        if (wave == 0) {
-            // bins from the top: lane l owns bins [hi - 32*(l+1) + ..]: do it in strides of 64 bins
-            int rank = sh_rank, sel = -1;
-            for (int b0 = nb - 64; b0 >= 0 && sel < 0; b0 -= 64) {
-                const unsigned h = hist[b0 + 63 - lane];            // lane 0 = highest bin of the stride
-                unsigned incl = h;                                   // inclusive prefix over lanes (from the top)
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
-                const unsigned total = __shfl(incl, 63, 64);
-                if ((int)total >= rank) {
-                    const unsigned long long hit = __ballot((int)incl >= rank);
-                    const int l = __ffsll((long long)hit) - 1;
-                    const unsigned before = __shfl(incl, l, 64) - __shfl(h, l, 64);
-                    sel = b0 + 63 - l;
-                    rank -= (int)before;
-                } else {
-                    rank -= (int)total;
-                }
-            }
-            if (lane == 0) {
-                sh_prefix = prefix | ((unsigned)sel << shift);
-                sh_mask = mask | ((unsigned)(nb - 1) << shift);
-                sh_rank = rank;
-            }
-        }
-        __syncthreads();
-    }
-    const unsigned T = sh_prefix;               // key of the kp-th largest
-    const int need_eq = sh_rank;                // how many keys == T belong to the kp best (lowest ids first)
-    const int G = kp - need_eq;                 // keys > T
-    // ---- 2. gather in row order: rows with key > hi_T, then the first `eq_take` rows with key == hi_T
-    auto gather = [&](unsigned hi_T, int n_gt, int eq_take, int cap) -> int {
-        if (tid < 2) run[tid] = 0;
-        __syncthreads();
-        for (int i0 = 0; i0 < n_docs; i0 += 256) {
-            const int i = i0 + tid;
-            const unsigned key = i < n_docs ? f32_orderable(row[i]) : 0u;
-            const bool gt = i < n_docs && key > hi_T, eq = i < n_docs && key == hi_T && eq_take > 0;
-            const unsigned long long bg = __ballot(gt), be = __ballot(eq);
-            if (!__syncthreads_or(gt || eq)) continue;                   // (barrier; most blocks hold no candidate)
-            if (lane == 0) { wc[wave][0] = __popcll(bg); wc[wave][1] = __popcll(be); }
-            __syncthreads();
-            int og = run[0], oe = run[1], tg = 0, te = 0;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                if (w < wave) { og += wc[w][0]; oe += wc[w][1]; }
-                tg += wc[w][0]; te += wc[w][1];
-            }
-            const unsigned long long below = (1ull << lane) - 1ull;
-            if (gt) { const int g = og + __popcll(bg & below); if (g < cap) cand[g] = i; }
-            if (eq) { const int e = oe + __popcll(be & below); if (e < eq_take && n_gt + e < cap) cand[n_gt + e] = i; }
-            __syncthreads();
-            if (tid == 0) { run[0] += tg; run[1] += te; }
-            __syncthreads();
-        }
-        return run[0];                             // rows with key > hi_T
-    };
-    gather(T, G, need_eq, BIGK_CAND);
+    // ---- 2. the kp best bf16 scores' rows in row order (search_select.h)
+    const KthKey kth = select_kth(row, n_docs, kp, L);
+    const unsigned T = kth.T;
+    gather_ordered(row, n_docs, T, kp - kth.need_eq, kth.need_eq, SEL_CAND, L);
     // ---- 3. exact fp32 re-scoring, sort
     const int nv = dim >> 2;
     f32x4 qv[MERGE_MAXV];
@@ -125,14 +50,14 @@ __global__ __launch_bounds__(256) void bigk_select_kernel(SearchArgs p, const fl
     auto rescore_sort = [&](int m) {
         int n2 = 1;
         while (n2 < m) n2 <<= 1;
-        for (int c = m + tid; c < n2; c += 256) keys[c] = KEY_NONE;
+        for (int c = m + tid; c < n2; c += 256) L.keys[c] = KEY_NONE;
         for (int c = wave; c < m; c += 4) {
-            const int id = cand[c];
+            const int id = L.cand[c];
             const float a = wave_sum(dot_lane(qv, p.index_f32 + (size_t)id * dim, nv, lane));
-            if (lane == 0) keys[c] = make_key(a, (uint32_t)id);
+            if (lane == 0) L.keys[c] = make_key(a, (uint32_t)id);
         }
         __syncthreads();
-        block_bitonic_desc(keys, n2, tid, 256);
+        block_bitonic_desc(L.keys, n2, tid, 256);
     };
     rescore_sort(kp);
     // ---- 4. certification (rows outside the re-scored set have a bf16 score <= T's)
@@ -141,41 +66,40 @@ __global__ __launch_bounds__(256) void bigk_select_kernel(SearchArgs p, const fl
         float tau = -INFINITY;
         if (kp < n_docs) {
             const float eps = query_eps(p, qv);
-            tau = key_score(keys[k - 1]) - eps;                       // kp >= k here (kp < n_docs => kp = k + margin)
+            tau = key_score(L.keys[k - 1]) - eps;                       // kp >= k here (kp < n_docs => kp = k + margin)
             if (!(orderable_f32(T) < tau)) {
                 // every row whose bf16 score is >= tau (strictly above the key just below tau's)
                 __syncthreads();
                 const unsigned tk = f32_orderable(tau);
-                const int m = gather(tk ? tk - 1u : 0u, 0, 0, BIGK_CAND);
+                const int m = gather_ordered(row, n_docs, tk ? tk - 1u : 0u, 0, 0, SEL_CAND, L);
                 __syncthreads();
-                if (m <= BIGK_CAND && m >= kp) { rescore_sort(m); kp = m; what = 1; }
+                if (m <= SEL_CAND && m >= kp) { rescore_sort(m); kp = m; what = 1; }
                 else what = 2;
             }
         }
         if (tid == 0 && p.stats) atomicAdd(&p.stats[what], 1u);
         __syncthreads();
-        flag_query(p, q, what == 2, tau, &sh_rank);
+        flag_query(p, q, what == 2, tau, &L.rank);
     } else if (!exact && tid == 0 && p.stats) {
         atomicAdd(&p.stats[3], 1u);
     }
-    for (int c = tid; c < k; c += 256) emit_slot(p, q, c, c < kp ? keys[c] : KEY_NONE);
+    for (int c = tid; c < k; c += 256) emit_slot(p, q, c, c < kp ? L.keys[c] : KEY_NONE);
     }
 }
 
-// queries [q0, q0 + nq_block) of the call: S holds their bf16-MFMA scores, one row of ldS floats each.
+// a block of nq_block queries of the call: S holds their bf16-MFMA scores, one row of ldS floats each.
 // `a` is the BLOCK's view (q_f32 / outputs / flag lists start at the block's first query).
-hipError_t launch_search_bigk(const SearchArgs& a, const float* S, size_t ldS, int q0, int nq_block, hipStream_t s) {
-    (void)q0;
+hipError_t launch_search_bigk(const SearchArgs& a, const float* S, size_t ldS, int nq_block, hipStream_t s) {
     if (nq_block <= 0) return hipSuccess;
     if (a.k > search_bigk_max() || a.dim % 4 || a.dim > 64 * 4 * MERGE_MAXV) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(bigk_select_kernel, dim3(nq_block), dim3(256), 0, s, a, S, ldS, a.k + BIGK_MARGIN, 0, 0, 0);
+    hipLaunchKernelGGL(bigk_select_kernel, dim3(nq_block), dim3(256), 0, s, a, S, ldS, a.k + SEL_MARGIN, 0, 0, 0);
     return hipGetLastError();
 }
 
 // exact top-k of the flagged queries from their exact score rows (slot i of S = query flag_list[i])
 hipError_t launch_exact_select(const SearchArgs& a, const float* S, size_t ldS, int sub, int max_slots, hipStream_t s) {
     if (max_slots <= 0) return hipSuccess;
-    if (a.k > BIGK_CAND || a.dim % 4 || a.dim > 64 * 4 * MERGE_MAXV || !a.flag_count || !a.flag_list) return hipErrorInvalidValue;
+    if (a.k > SEL_CAND || a.dim % 4 || a.dim > 64 * 4 * MERGE_MAXV || !a.flag_count || !a.flag_list) return hipErrorInvalidValue;
     hipLaunchKernelGGL(bigk_select_kernel, dim3(max_slots < 128 ? max_slots : 128), dim3(256), 0, s, a, S, ldS, a.k, 1, sub, max_slots);
     return hipGetLastError();
 }

@@ -173,6 +173,13 @@ __device__ __forceinline__ void flag_query(const SearchArgs& p, int q, bool flag
     }
 }
 
+// a flagged query whose band the band pass cannot hold goes on the second list: the exact fp32 pass redoes it (ONE thread calls)
+__device__ __forceinline__ void flag2_push(const SearchArgs& p, int q) {
+    const int pos = atomicAdd(p.flag2_count, 1);
+    p.flag2_list[pos] = q;
+    if (p.stats) atomicAdd(&p.stats[5], 1u);
+}
+
 // descending bitonic sort of n (power of two) keys in LDS by the whole workgroup
 __device__ __forceinline__ void block_bitonic_desc(uint64_t* keys, int n, int tid, int nthreads) {
     for (int k = 2; k <= n; k <<= 1) {

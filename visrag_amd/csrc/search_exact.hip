@@ -18,7 +18,7 @@
 // Also here: the largest row norm and the largest bf16 rounding residual of the index rows (vr_index_add): the |d| and
 // |d - bf16(d)| of the error bound.
 #include "kernels.h"
-#include "search_common.h"
+#include "search_select.h"
 
 namespace vr {
 
@@ -31,7 +31,7 @@ __global__ __launch_bounds__(256) void exact_scores_kernel(const float* __restri
                                                            const int* __restrict__ flag_count, int sub, int max_slots,
                                                            float* __restrict__ S, size_t ldS) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int nf = min(flag_count[0] - sub, max_slots);     // this launch: entries [sub, sub + nf) of the list = slots 0..
+    const int nf = flag_slots(flag_count, sub, max_slots);  // this launch: entries [sub, sub + nf) of the list = slots 0..
     if (nf <= 0) return;
     flag_list += sub;
     f32x4* qs = reinterpret_cast<f32x4*>(smem);                 // [EX_QB][nv]

@@ -6,7 +6,8 @@
 // path (search_bigk.hip) carries over with groups in the place of rows:
 //   1. score rows S[q][row] of a block of <= 256 queries on the bf16 MFMA GEMM (the deep path's launch, index.hip);
 //   2. group_max_kernel: B[q][g] = max of S[q] over the group's rows (columns < n_docs only: the padding never wins);
-//   3. group_select_kernel, one workgroup per query: radix select of the K' = k + 24 largest B_g; inside every candidate group
+//   3. group_select_kernel, one workgroup per query: the K' = k + 24 largest B_g in group order (search_select.h: the deep
+//      path's radix select and ordered gather, over B in the place of S); inside every candidate group
 //      each row with b_i >= B_g - 2 eps — only such a row can attain E_g, ties included — is re-scored in fp32 (dot_lane), the
 //      largest key (score, then LOWER row id) is the group's (E_g, best row); the keys are sorted and certified:
 //      tau = E_(k) - eps; a group outside the candidates has B_g <= the K'-th B, so if that lies below tau none of them can
@@ -16,18 +17,11 @@
 #include <algorithm>
 
 #include "kernels.h"
-#include "search_common.h"
+#include "search_select.h"
 
 namespace vr {
 
-constexpr int GRP_CAND = 1024;              // K' = k + margin <= GRP_CAND; cap of the widened candidate set
-constexpr int GRP_MARGIN = 24;
 constexpr int GRP_SHORT = 64;               // a group of up to this many rows is reduced by its own thread
-
-// rows of S this launch works on: all of gridDim.y, or (slot_count set) entries [sub, sub + gridDim.y) of a flag list
-__device__ __forceinline__ int group_slots(const int* slot_count, int sub, int max_slots) {
-    return slot_count ? min(max(slot_count[0] - sub, 0), max_slots) : max_slots;
-}
 
 // the next float below x: a bound computed by one rounded subtraction, lowered so that the rounding cannot have raised it
 __device__ __forceinline__ float one_ulp_down(float x) {
@@ -43,7 +37,7 @@ __global__ __launch_bounds__(256) void group_max_kernel(const float* __restrict_
     __shared__ int s_lo[256], s_hi[256];
     __shared__ float red[4];
     const int slot = blockIdx.y;
-    if (slot >= group_slots(slot_count, sub, (int)gridDim.y)) return;       // (workgroup-uniform)
+    if (slot >= flag_slots(slot_count, sub, (int)gridDim.y)) return;       // (workgroup-uniform)
     const float* row = S + (size_t)slot * ldS;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = blockIdx.x * 256 + tid;
@@ -74,14 +68,10 @@ __global__ __launch_bounds__(256) void group_max_kernel(const float* __restrict_
 // exact == 1: S / B row i hold EXACT fp32 scores of flagged query flag_list[sub + i] (search_exact.hip): eps = 0, plain top-k.
 __global__ __launch_bounds__(256) void group_select_kernel(GroupSearchArgs p, const float* __restrict__ S, size_t ldS,
                                                            int kp_want, int exact, int sub, int max_slots) {
-    __shared__ unsigned hist[2048];
-    __shared__ int cand[GRP_CAND];
-    __shared__ uint64_t keys[GRP_CAND];
-    __shared__ unsigned sh_prefix, sh_mask;
-    __shared__ int sh_rank, wc[4][2], run[2];
+    __shared__ SelectLds L;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const SearchArgs& a = p.a;
-    const int n_slots = exact ? group_slots(a.flag_count, sub, max_slots) : (int)gridDim.x;
+    const int n_slots = exact ? flag_slots(a.flag_count, sub, max_slots) : (int)gridDim.x;
     for (int slot = blockIdx.x; slot < n_slots; slot += gridDim.x) {
     const int q = exact ? a.flag_list[sub + slot] : slot;
     const float* srow = S + (size_t)slot * ldS;
@@ -90,77 +80,11 @@ __global__ __launch_bounds__(256) void group_select_kernel(GroupSearchArgs p, co
     int kp = min(n_groups, kp_want);
     __syncthreads();                                                    // (LDS of the previous slot is free)
 
-    // ---- 1. radix select (search_bigk.hip): key of the kp-th largest group maximum
-    if (tid == 0) { sh_prefix = 0u; sh_mask = 0u; sh_rank = kp; }
-    for (int pass = 0; pass < 3; ++pass) {
-        const int shift = pass == 0 ? 21 : pass == 1 ? 10 : 0;
-        const int nb = pass < 2 ? 2048 : 1024;
-        for (int i = tid; i < 2048; i += 256) hist[i] = 0u;
-        __syncthreads();
-        const unsigned prefix = sh_prefix, mask = sh_mask;
-        for (int i = tid; i < n_groups; i += 256) {
-            const unsigned key = f32_orderable(brow[i]);
-            if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & (nb - 1)], 1u);
-        }
-        __syncthreads();
-        if (wave == 0) {
-            int rank = sh_rank, sel = -1;
-            for (int b0 = nb - 64; b0 >= 0 && sel < 0; b0 -= 64) {
-                const unsigned h = hist[b0 + 63 - lane];            // lane 0 = highest bin of the stride
-                unsigned incl = h;                                   // inclusive prefix over lanes (from the top)
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
-                const unsigned total = __shfl(incl, 63, 64);
-                if ((int)total >= rank) {
-                    const unsigned long long hit = __ballot((int)incl >= rank);
-                    const int l = __ffsll((long long)hit) - 1;
-                    const unsigned before = __shfl(incl, l, 64) - __shfl(h, l, 64);
-                    sel = b0 + 63 - l;
-                    rank -= (int)before;
-                } else {
-                    rank -= (int)total;
-                }
-            }
-            if (lane == 0) {
-                sh_prefix = prefix | ((unsigned)sel << shift);
-                sh_mask = mask | ((unsigned)(nb - 1) << shift);
-                sh_rank = rank;
-            }
-        }
-        __syncthreads();
-    }
-    const unsigned T = sh_prefix;               // key of the kp-th largest B
-    const int need_eq = sh_rank;                // how many groups with key == T belong to the kp best (lowest groups first)
-    const int G = kp - need_eq;                 // groups with key > T
-    // ---- 2. gather in group order: groups with key > hi_T, then the first `eq_take` groups with key == hi_T
-    auto gather = [&](unsigned hi_T, int n_gt, int eq_take, int cap) -> int {
-        if (tid < 2) run[tid] = 0;
-        __syncthreads();
-        for (int i0 = 0; i0 < n_groups; i0 += 256) {
-            const int i = i0 + tid;
-            const unsigned key = i < n_groups ? f32_orderable(brow[i]) : 0u;
-            const bool gt = i < n_groups && key > hi_T, eq = i < n_groups && key == hi_T && eq_take > 0;
-            const unsigned long long bg = __ballot(gt), be = __ballot(eq);
-            if (!__syncthreads_or(gt || eq)) continue;                   // (barrier; most blocks hold no candidate)
-            if (lane == 0) { wc[wave][0] = __popcll(bg); wc[wave][1] = __popcll(be); }
-            __syncthreads();
-            int og = run[0], oe = run[1], tg = 0, te = 0;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                if (w < wave) { og += wc[w][0]; oe += wc[w][1]; }
-                tg += wc[w][0]; te += wc[w][1];
-            }
-            const unsigned long long below = (1ull << lane) - 1ull;
-            if (gt) { const int o = og + __popcll(bg & below); if (o < cap) cand[o] = i; }
-            if (eq) { const int e = oe + __popcll(be & below); if (e < eq_take && n_gt + e < cap) cand[n_gt + e] = i; }
-            __syncthreads();
-            if (tid == 0) { run[0] += tg; run[1] += te; }
-            __syncthreads();
-        }
-        return run[0];                             // groups with key > hi_T
-    };
-    gather(T, G, need_eq, GRP_CAND);
-    // ---- 3. per candidate group: exact fp32 score of every row that can be the group's best; sort the groups' keys
+    // ---- 3a. the kp largest group maxima's groups in group order (search_select.h)
+    const KthKey kth = select_kth(brow, n_groups, kp, L);
+    const unsigned T = kth.T;
+    gather_ordered(brow, n_groups, T, kp - kth.need_eq, kth.need_eq, SEL_CAND, L);
+    // ---- 3b. per candidate group: exact fp32 score of every row that can be the group's best; sort the groups' keys
     const int nv = dim >> 2;
     f32x4 qv[MERGE_MAXV];
     load_query_regs(qv, a.q_f32 + (size_t)q * dim, nv, lane);
@@ -169,9 +93,9 @@ __global__ __launch_bounds__(256) void group_select_kernel(GroupSearchArgs p, co
     auto rescore_sort = [&](int m) {
         int n2 = 1;
         while (n2 < m) n2 <<= 1;
-        for (int c = m + tid; c < n2; c += 256) keys[c] = KEY_NONE;
+        for (int c = m + tid; c < n2; c += 256) L.keys[c] = KEY_NONE;
         for (int c = wave; c < m; c += 4) {                              // one wave per candidate group
-            const int g = cand[c];
+            const int g = L.cand[c];
             const int lo = p.goff[g], hi = p.goff[g + 1];
             const float lim = one_ulp_down(brow[g] - band);               // (the subtraction may have rounded up)
             uint64_t best = KEY_NONE;
@@ -186,33 +110,33 @@ __global__ __launch_bounds__(256) void group_select_kernel(GroupSearchArgs p, co
                     best = key > best ? key : best;
                 }
             }
-            if (lane == 0) keys[c] = best;
+            if (lane == 0) L.keys[c] = best;
         }
         __syncthreads();
-        block_bitonic_desc(keys, n2, tid, 256);
+        block_bitonic_desc(L.keys, n2, tid, 256);
     };
     rescore_sort(kp);
-    // ---- 4. certification (a group outside the re-scored set has B <= T's score)
+    // ---- 3c. certification (a group outside the re-scored set has B <= T's score)
     if (!exact && p.certify) {
         int what = 0;
         if (kp < n_groups) {
-            const float tau = one_ulp_down(key_score(keys[k - 1]) - eps);  // kp >= k here (kp < n_groups => kp = k + margin)
+            const float tau = one_ulp_down(key_score(L.keys[k - 1]) - eps);  // kp >= k here (kp < n_groups => kp = k + margin)
             if (!(orderable_f32(T) < tau)) {
                 // every group whose B is >= tau (strictly above the key just below tau's)
                 __syncthreads();
                 const unsigned tk = f32_orderable(tau);
-                const int m = gather(tk ? tk - 1u : 0u, 0, 0, GRP_CAND);
+                const int m = gather_ordered(brow, n_groups, tk ? tk - 1u : 0u, 0, 0, SEL_CAND, L);
                 __syncthreads();
-                if (m <= GRP_CAND && m >= kp) { rescore_sort(m); kp = m; what = 1; }
+                if (m <= SEL_CAND && m >= kp) { rescore_sort(m); kp = m; what = 1; }
                 else what = 2;
             }
         }
         if (tid == 0) atomicAdd(&p.stats[what], 1u);
         __syncthreads();
-        flag_query(a, q, what == 2, 0.f, &sh_rank);
+        flag_query(a, q, what == 2, 0.f, &L.rank);
     }
     for (int c = tid; c < k; c += 256) {
-        const uint64_t key = c < kp ? keys[c] : KEY_NONE;
+        const uint64_t key = c < kp ? L.keys[c] : KEY_NONE;
         emit_slot(a, q, c, key);
         int g = -1;
         if (key != KEY_NONE) {                                           // the group of the row: last g with goff[g] <= row
@@ -229,7 +153,7 @@ __global__ __launch_bounds__(256) void group_select_kernel(GroupSearchArgs p, co
     }
 }
 
-int search_groups_kmax() { return GRP_CAND - GRP_MARGIN; }
+int search_groups_kmax() { return SEL_CAND - SEL_MARGIN; }
 
 static bool group_args_ok(const GroupSearchArgs& p) {
     const SearchArgs& a = p.a;
@@ -251,7 +175,7 @@ hipError_t launch_group_max(const float* S, size_t ldS, const int* goff, int n_g
 hipError_t launch_group_select(const GroupSearchArgs& p, const float* S, size_t ldS, int nq_block, hipStream_t s) {
     if (nq_block <= 0) return hipSuccess;
     if (!group_args_ok(p)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(group_select_kernel, dim3(nq_block), dim3(256), 0, s, p, S, ldS, p.a.k + GRP_MARGIN, 0, 0, 0);
+    hipLaunchKernelGGL(group_select_kernel, dim3(nq_block), dim3(256), 0, s, p, S, ldS, p.a.k + SEL_MARGIN, 0, 0, 0);
     return hipGetLastError();
 }
 

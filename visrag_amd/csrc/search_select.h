@@ -1,0 +1,114 @@
+// Selection of the K' best of a row of n fp32 values by ONE workgroup of 256 threads, shared by the deep path
+// (search_bigk.hip: values = a query's score row) and the grouped search (search_group.hip: values = its group maxima):
+//   select_kth      3-pass radix select (11 + 11 + 10 bits of the order-preserving key, histograms in LDS) of the key of
+//                   the kp-th largest value, and how many of its ties belong to the kp best;
+//   gather_ordered  the positions of the candidates in ascending order: every key above a threshold, then the LOWEST positions
+//                   among the keys equal to it — the one place where "lowest ids first at the threshold" is decided.
+// What is done with the candidates (re-scoring, certification, output) is the kernels' own.
+// Also here: flag_slots, the part of a flag list that one launch of a fallback kernel walks.
+#pragma once
+#include "kernels.h"
+#include "search_common.h"
+
+namespace vr {
+
+constexpr int SEL_CAND = 1024;              // K' = k + margin <= SEL_CAND; cap of a widened candidate set
+constexpr int SEL_MARGIN = 24;              // keeps a true top-k entry inside the candidate set although the values carry bf16 rounding
+
+struct SelectLds {                          // static LDS of a selecting kernel: declared once, __shared__
+    unsigned hist[2048];
+    int cand[SEL_CAND];                     // gathered positions
+    uint64_t keys[SEL_CAND];                // their exact keys (the kernels' re-scoring)
+    unsigned prefix;                        // radix select: the key bits fixed so far (those above the pass's own)
+    int rank;                               // ... and the rank wanted among the keys that share them (also flag_query's scratch)
+    int wc[4][2], run[2];                   // gather_ordered: per-wave and running counts {above, equal}
+};
+
+// slots this launch works on: all max_slots, or (count set) entries [sub, sub + max_slots) of a flag list of count[0] queries
+__device__ __forceinline__ int flag_slots(const int* count, int sub, int max_slots) {
+    return count ? min(max(count[0] - sub, 0), max_slots) : max_slots;
+}
+
+struct KthKey {
+    unsigned T;                             // key of the kp-th largest value
+    int need_eq;                            // how many keys == T belong to the kp best (lowest positions first); kp - need_eq keys are > T
+};
+
+// Called by the whole workgroup, 1 <= kp <= n; the LDS must be free (barrier) when it is entered.
+__device__ __forceinline__ KthKey select_kth(const float* __restrict__ vals, int n, int kp, SelectLds& L) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) { L.prefix = 0u; L.rank = kp; }
+    for (int pass = 0; pass < 3; ++pass) {
+        const int shift = pass == 0 ? 21 : pass == 1 ? 10 : 0;
+        const int nb = pass < 2 ? 2048 : 1024;
+        for (int i = tid; i < 2048; i += 256) L.hist[i] = 0u;
+        __syncthreads();
+        const int top = shift + (pass < 2 ? 11 : 10);                // the pass's digit: key bits [shift, top)
+        const unsigned prefix = L.prefix, mask = top < 32 ? ~0u << top : 0u;    // ... the bits above it: fixed by the passes before
+        for (int i = tid; i < n; i += 256) {
+            const unsigned key = f32_orderable(vals[i]);
+            if ((key & mask) == prefix) atomicAdd(&L.hist[(key >> shift) & (nb - 1)], 1u);
+        }
+        __syncthreads();
+        if (wave == 0) {
+            // bins from the top in strides of 64: lane 0 owns the highest bin of the stride
+            int rank = L.rank, sel = -1;
+            for (int b0 = nb - 64; b0 >= 0 && sel < 0; b0 -= 64) {
+                const unsigned h = L.hist[b0 + 63 - lane];
+                unsigned incl = h;                                   // inclusive prefix over lanes (from the top)
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
+                const unsigned total = __shfl(incl, 63, 64);
+                if ((int)total >= rank) {
+                    const unsigned long long hit = __ballot((int)incl >= rank);
+                    const int l = __ffsll((long long)hit) - 1;
+                    const unsigned before = __shfl(incl, l, 64) - __shfl(h, l, 64);
+                    sel = b0 + 63 - l;
+                    rank -= (int)before;
+                } else {
+                    rank -= (int)total;
+                }
+            }
+            if (lane == 0) {
+                L.prefix = prefix | ((unsigned)sel << shift);
+                L.rank = rank;
+            }
+        }
+        __syncthreads();
+    }
+    return KthKey{L.prefix, L.rank};
+}
+
+// Positions i of vals[0, n) in ascending order into L.cand: those with key > hi_T from slot 0, then the first `eq_take` with
+// key == hi_T from slot n_gt (n_gt = how many are above); nothing is written at or beyond slot `cap`.  Returns the number of
+// keys > hi_T (may exceed cap).  Called by the whole workgroup.
+__device__ __forceinline__ int gather_ordered(const float* __restrict__ vals, int n, unsigned hi_T, int n_gt, int eq_take, int cap,
+                                              SelectLds& L) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid < 2) L.run[tid] = 0;
+    __syncthreads();
+    for (int i0 = 0; i0 < n; i0 += 256) {
+        const int i = i0 + tid;
+        const unsigned key = i < n ? f32_orderable(vals[i]) : 0u;
+        const bool gt = i < n && key > hi_T, eq = i < n && key == hi_T && eq_take > 0;
+        const unsigned long long bg = __ballot(gt), be = __ballot(eq);
+        if (!__syncthreads_or(gt || eq)) continue;                   // (barrier; most blocks hold no candidate)
+        if (lane == 0) { L.wc[wave][0] = __popcll(bg); L.wc[wave][1] = __popcll(be); }
+        __syncthreads();
+        int og = L.run[0], oe = L.run[1], tg = 0, te = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            if (w < wave) { og += L.wc[w][0]; oe += L.wc[w][1]; }
+            tg += L.wc[w][0]; te += L.wc[w][1];
+        }
+        const unsigned long long below = (1ull << lane) - 1ull;
+        if (gt) { const int g = og + __popcll(bg & below); if (g < cap) L.cand[g] = i; }
+        if (eq) { const int e = oe + __popcll(be & below); if (e < eq_take && n_gt + e < cap) L.cand[n_gt + e] = i; }
+        __syncthreads();
+        if (tid == 0) { L.run[0] += tg; L.run[1] += te; }
+        __syncthreads();
+    }
+    return L.run[0];
+}
+
+}  // namespace vr

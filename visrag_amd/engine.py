@@ -275,27 +275,26 @@ class HipIndex:
             _lib.check(self.lib.vr_index_add(self._h, C.c_void_p(a.ctypes.data), a.shape[0], 0,
                                              C.c_void_p(_stream_ptr(self.device))), "vr_index_add")
 
+    def _search(self, fn, what: str, queries, k: int, n_int_out: int):
+        """One call of a library search that writes scores [nq,k] f32 and `n_int_out` arrays [nq,k] i64: torch cuda tensors in ->
+        cuda tensors out, numpy / cpu in -> numpy out (sized with max(k, 0): a negative k reaches the library's own error)."""
+        cuda = isinstance(queries, torch.Tensor) and queries.is_cuda
+        if cuda:
+            q = queries.to(torch.float32).contiguous()
+            outs = [torch.empty((q.shape[0], k), dtype=d, device=q.device) for d in [torch.float32] + [torch.int64] * n_int_out]
+            ptrs = [x.data_ptr() for x in [q] + outs]
+        else:
+            q = np.ascontiguousarray(queries.numpy() if isinstance(queries, torch.Tensor) else queries, dtype=np.float32)
+            outs = [np.empty((q.shape[0], max(k, 0)), dtype=d) for d in [np.float32] + [np.int64] * n_int_out]
+            ptrs = [x.ctypes.data for x in [q] + outs]
+        _lib.check(fn(self._h, C.c_void_p(ptrs[0]), q.shape[0], k, *[C.c_void_p(p) for p in ptrs[1:]], 1 if cuda else 0,
+                      C.c_void_p(_stream_ptr(self.device))), what)
+        return tuple(outs)
+
     def search(self, queries, k: int):
         """-> (scores [nq,k] f32, ids [nq,k] i64); torch cuda tensors in -> cuda tensors out,
         numpy / cpu in -> numpy out."""
-        if isinstance(queries, torch.Tensor) and queries.is_cuda:
-            q = queries.to(torch.float32).contiguous()
-            nq = q.shape[0]
-            sc = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-            ix = torch.empty((nq, k), dtype=torch.int64, device=q.device)
-            _lib.check(self.lib.vr_index_search(self._h, C.c_void_p(q.data_ptr()), nq, k,
-                                                C.c_void_p(sc.data_ptr()), C.c_void_p(ix.data_ptr()), 1,
-                                                C.c_void_p(_stream_ptr(self.device))), "vr_index_search")
-            return sc, ix
-        q = np.ascontiguousarray(queries.numpy() if isinstance(queries, torch.Tensor) else queries,
-                                 dtype=np.float32)
-        nq = q.shape[0]
-        sc = np.empty((nq, k), dtype=np.float32)
-        ix = np.empty((nq, k), dtype=np.int64)
-        _lib.check(self.lib.vr_index_search(self._h, C.c_void_p(q.ctypes.data), nq, k,
-                                            C.c_void_p(sc.ctypes.data), C.c_void_p(ix.ctypes.data), 0,
-                                            C.c_void_p(_stream_ptr(self.device))), "vr_index_search")
-        return sc, ix
+        return self._search(self.lib.vr_index_search, "vr_index_search", queries, k, 1)
 
     def set_groups(self, offsets) -> None:
         """Partition the rows present into groups (documents) of adjacent rows: group g = rows offsets[g] .. offsets[g + 1] - 1
@@ -308,25 +307,7 @@ class HipIndex:
     def search_groups(self, queries, k: int):
         """The k best groups per query, each by its best row (include/visrag_hip.h: vr_index_search_groups)
         -> (scores [nq,k] f32, best row ids [nq,k] i64, groups [nq,k] i64); cuda in -> cuda out, numpy / cpu in -> numpy out."""
-        if isinstance(queries, torch.Tensor) and queries.is_cuda:
-            q = queries.to(torch.float32).contiguous()
-            nq = q.shape[0]
-            sc = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-            ix = torch.empty((nq, k), dtype=torch.int64, device=q.device)
-            gr = torch.empty((nq, k), dtype=torch.int64, device=q.device)
-            _lib.check(self.lib.vr_index_search_groups(self._h, C.c_void_p(q.data_ptr()), nq, k, C.c_void_p(sc.data_ptr()),
-                                                       C.c_void_p(ix.data_ptr()), C.c_void_p(gr.data_ptr()), 1,
-                                                       C.c_void_p(_stream_ptr(self.device))), "vr_index_search_groups")
-            return sc, ix, gr
-        q = np.ascontiguousarray(queries.numpy() if isinstance(queries, torch.Tensor) else queries, dtype=np.float32)
-        nq = q.shape[0]
-        sc = np.empty((nq, max(k, 0)), dtype=np.float32)
-        ix = np.empty((nq, max(k, 0)), dtype=np.int64)
-        gr = np.empty((nq, max(k, 0)), dtype=np.int64)
-        _lib.check(self.lib.vr_index_search_groups(self._h, C.c_void_p(q.ctypes.data), nq, k, C.c_void_p(sc.ctypes.data),
-                                                   C.c_void_p(ix.ctypes.data), C.c_void_p(gr.ctypes.data), 0,
-                                                   C.c_void_p(_stream_ptr(self.device))), "vr_index_search_groups")
-        return sc, ix, gr
+        return self._search(self.lib.vr_index_search_groups, "vr_index_search_groups", queries, k, 2)
 
     def group_search_stats(self, reset: bool = False) -> Dict[str, int]:
         """Grouped-search queries since the last reset by outcome: certified from the first candidate set / after widening it /
