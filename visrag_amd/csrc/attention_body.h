@@ -1,5 +1,4 @@
-// Flash-attention workgroup body shared by attention.hip (the grid form) and gen_persist.hip (the decode step's persistent
-// kernel).  Design notes: attention.hip.
+// Flash-attention workgroup body shared by attention.hip and attention_small.hip.  Design notes: attention.hip.
 #pragma once
 #include <type_traits>
 
@@ -47,14 +46,11 @@ __device__ __forceinline__ float col4_sum(float v) {
 }
 
 // The kernel's body as a device function: `unit` = the (q tile, head, batch item) index a workgroup of the grid form takes
-// from blockIdx, `smem` = attn_smem_bytes<HD, PIPE>() of LDS.  The decode step's persistent kernel (gen_persist.hip) calls it
-// per (KV range, KV head) unit with q_lds = the group's query rows built in LDS (read instead of p.q) and COH = true: the
-// partial rows and log-sum-exps leave as device-scope relaxed atomics (sc1), because workgroups on OTHER XCDs read them
-// later in the same launch.
+// from blockIdx, `smem` = attn_smem_bytes<HD, PIPE>() of LDS.
 template <int HD, int PIPE> constexpr int attn_smem_bytes() { return 2 * (PIPE ? 2 : 1) * ATT_KV * AttnCfg<HD>::PITCH; }
 
-template <int HD, int QF, int PIPE, bool COH = false>
-__device__ __forceinline__ void attention_body(const AttnArgs& p, int unit, char* smem, const bf16_t* q_lds = nullptr) {
+template <int HD, int QF, int PIPE>
+__device__ __forceinline__ void attention_body(const AttnArgs& p, int unit, char* smem) {
     static_assert(PIPE == 0 || PIPE == 3, "PIPE 0: one K/V slot staged through registers; PIPE 3: two slots staged by LDS-DMA");
     using C = AttnCfg<HD>;
     constexpr int K32 = C::K32, DFRAGS = C::DFRAGS, PITCH = C::PITCH;
@@ -85,8 +81,8 @@ __device__ __forceinline__ void attention_body(const AttnArgs& p, int unit, char
     const int qs = qt * QT;                            // first query of this tile (seq-relative)
     if (qs >= q_len || kv_len <= 0) return;
 
-    const bf16_t* qbase = q_lds ? q_lds : (const bf16_t*)p.q + (size_t)(p.q_in_rows ? p.q_in_rows[b] : (p.q_shared ? 0 : q_row0)) * p.ldq +
-                                          h * (p.q_head_stride ? p.q_head_stride : HD);
+    const bf16_t* qbase = (const bf16_t*)p.q + (size_t)(p.q_in_rows ? p.q_in_rows[b] : (p.q_shared ? 0 : q_row0)) * p.ldq +
+                          h * (p.q_head_stride ? p.q_head_stride : HD);
     const int hkv = p.kv_group > 1 ? h / p.kv_group : h;          // grouped-query attention: K/V head of this query head
     const bf16_t* kbase = (const bf16_t*)p.k + (size_t)kv0 * p.ldk + hkv * HD;
     const bf16_t* vbase = (const bf16_t*)p.v + (size_t)kv0 * p.ldv + hkv * HD;
@@ -422,9 +418,7 @@ __device__ __forceinline__ void attention_body(const AttnArgs& p, int unit, char
         if constexpr (ONES) l = __shfl(o[f][DFRAGS - 1][0], 32 + fr, 64);   // O^T[72][q]: lane (fq=2, fr=q), reg 0 (all lanes active here)
         if (q >= q_len) continue;
         if (p.lse && fq == 0) {                                       // sum_k 2^(s_k * sc) = 2^m * l
-            const float lv = m_run[f] + __log2f(l);
-            if constexpr (COH) __hip_atomic_store(p.lse + (size_t)(q_row0 + q) * p.heads + h, lv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else p.lse[(size_t)(q_row0 + q) * p.heads + h] = lv;
+            p.lse[(size_t)(q_row0 + q) * p.heads + h] = m_run[f] + __log2f(l);
         }
         const float inv = 1.0f / l;
         bf16_t* orow = (bf16_t*)p.out + (size_t)(q_row0 + q) * p.ldo + h * HD;
@@ -435,13 +429,7 @@ __device__ __forceinline__ void attention_body(const AttnArgs& p, int unit, char
                 bf16x4 ov;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) ov[r] = f2bf(o[f][d][r] * inv);
-                if constexpr (COH) {
-                    const u32x2 w2 = __builtin_bit_cast(u32x2, ov);
-                    __hip_atomic_store(reinterpret_cast<unsigned*>(orow + dd), w2[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(reinterpret_cast<unsigned*>(orow + dd) + 1, w2[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                } else {
-                    *reinterpret_cast<bf16x4*>(orow + dd) = ov;
-                }
+                *reinterpret_cast<bf16x4*>(orow + dd) = ov;
             }
         }
     }

@@ -28,93 +28,6 @@ static void drop_graph(vg_model_s* m) {
     if (m->graph) { (void)hipGraphDestroy(m->graph); m->graph = nullptr; }
 }
 
-// decode (gemm_skinny.hip): how many K ranges a GEMM's 256-column tiles are cut into.  One workgroup fits on a CU (its
-// four LDS stages), so the fastest shape is ONE balanced round of workgroups with K loops as long as that allows —
-// measured on the 7B layer (ms per token): gate/up 148 tiles as 148 x 56 K-steps 3.74, 296 x 28 (a second round of 40)
-// 3.94, 592 x 14 3.80; down 14 tiles as 252 x 17 3.74, 112 x 37 3.94, 518 x 8 4.08.  The splits need not divide the
-// K-steps (the last range is shorter); every range keeps >= 4 steps; more tiles than CUs: no split.
-static int choose_ksplit(int n, int k) { return skinny_ksplit(n, k, GEN_KS_MAX); }
-
-// The persistent layer kernel of the decode step (gen_persist.hip): decide whether this model / device takes it and build
-// its layer table for the CURRENT slot (the caches are per slot).  It is OPT-IN — VR_DECODE_PERSIST=1 in the environment
-// when the model is finalized / a slot is selected (or -DVR_DECODE_PERSIST=1) — because on MI355X it only draws level with
-// the separate launches (3.33 against 3.29 ms per token at the 7B shape: its weight streams run at 6.5 TB/s instead of
-// 5.4-5.7, but seven grid barriers per layer cost 4.3 us each under the prefetch traffic).
-#ifndef VR_DECODE_PERSIST
-#define VR_DECODE_PERSIST 0
-#endif
-static int persist_setup(vg_model_s* m) {
-    m->p_grid = 0;
-    const char* env = getenv("VR_DECODE_PERSIST");
-    if (env ? atoi(env) == 0 : !VR_DECODE_PERSIST) return VR_OK;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, m->device) != hipSuccess || decode_persist_occupancy() < 1) return VR_OK;
-    const int grid = prop.multiProcessorCount;
-    const int E = m->E, QD = m->QD, QKV = m->QKV, G = m->H / m->KV;
-    const GenLayer& L0 = m->layers[0];
-    const int ks_qkv = choose_ksplit(QKV, E), ks_o = choose_ksplit(E, QD);
-    const int ks_d = choose_ksplit(E, L0.down.k_pad), ks_gu = choose_ksplit(L0.gu.n_pad, E);
-    auto per64 = [](int k, int ks) { return ((k / 64 + ks - 1) / ks) * 64; };
-    const bool fits =
-        E <= 4096 && (E / 4 + 63) / 64 <= 16 && (E / 4 + 63) / 64 <= grid && G <= 16 && GEN_ATT_SPLITS * m->KV <= grid && ks_gu == 1 &&
-        L0.qkv.n_pad == QKV && L0.qkv.k_pad == E && L0.o.n_pad == E && L0.o.k_pad == QD && L0.gu.k_pad == E && L0.down.n_pad == E &&
-        L0.down.k_pad == pad128(m->I) && !L0.o.has_b && !L0.gu.has_b && !L0.down.has_b &&
-        (QKV + 255) / 256 * ks_qkv <= grid && (E + 255) / 256 * ks_o <= grid && (E + 255) / 256 * ks_d <= grid && (L0.gu.n_pad + 255) / 256 <= grid &&
-        per64(E, ks_qkv) <= 4096 && per64(QD, ks_o) <= 4096 && per64(L0.down.k_pad, ks_d) <= 4096 &&
-        (size_t)std::max(ks_qkv, std::max(ks_o, ks_d)) * std::max(QKV, E) * 4 <= m->w_part.bytes;
-    if (!fits) return VR_OK;
-    std::vector<PersistLayer> t(m->layers.size());
-    for (size_t l = 0; l < t.size(); ++l) {
-        GenLayer& L = m->layers[l];
-        t[l] = PersistLayer{L.qkv.w.p, L.o.w.p, L.gu.w.p, L.down.w.p, L.qkv.has_b ? L.qkv.b.as<float>() : nullptr,
-                            L.ln1.v.as<float>(), L.ln2.v.as<float>(), gen_kc(m, (int)l, m->cur), gen_vc(m, (int)l, m->cur)};
-    }
-    if (!m->p_table.p) {
-        VRCHK(m->p_table.alloc(t.size() * sizeof(PersistLayer)));
-        VRCHK(m->p_sync.alloc(128 * 8));
-        VRCHK(m->p_ss.alloc(16 * 4));
-        HIPCHK(hipMemset(m->p_sync.p, 0, 128 * 8));
-        HIPCHK(hipMemset(m->p_ss.p, 0, 16 * 4));
-        HIPCHK(hipHostMalloc((void**)&m->p_abort, 64, hipHostMallocMapped));
-        *m->p_abort = 0;
-    }
-    HIPCHK(hipMemcpy(m->p_table.p, t.data(), t.size() * sizeof(PersistLayer), hipMemcpyHostToDevice));
-    m->p_grid = grid;
-    return VR_OK;
-}
-static int persist_layers(vg_model_s* m, hipStream_t s) {
-    const GenLayer& L0 = m->layers[0];
-    PersistArgs a{};
-    a.layers = m->p_table.as<PersistLayer>(); a.n_layers = (int)m->layers.size();
-    a.E = m->E; a.QKV = m->QKV; a.QD = m->QD; a.KVD = m->KVD; a.H = m->H; a.KV = m->KV; a.Ip = L0.down.k_pad; a.N2 = L0.gu.n_pad;
-    a.ldw_qkv = L0.qkv.k_pad; a.ldw_o = L0.o.k_pad; a.ldw_gu = L0.gu.k_pad; a.ldw_d = L0.down.k_pad;
-    a.ks_qkv = choose_ksplit(m->QKV, m->E); a.ks_o = choose_ksplit(m->E, m->QD);
-    a.ks_d = choose_ksplit(m->E, L0.down.k_pad);
-    a.eps = m->c.rms_norm_eps; a.g_final = m->final_norm.v.as<float>();
-    a.h = m->w_h.as<float>(); a.xn = m->w_xn.p; a.planes = m->w_part.as<float>(); a.act = m->w_act.p;
-    a.attp = m->w_attp.p; a.lse = m->w_lse.as<float>(); a.ss = m->p_ss.as<float>();
-    a.st = m->w_state.as<GenState>(); a.inv_freq = m->inv_freq.as<float>();
-    a.sec_t = m->c.mrope_section[0]; a.sec_h = m->c.mrope_section[1];
-    a.sync = m->p_sync.as<unsigned long long>(); a.abort_host = m->p_abort;
-    HIPCHK(launch_decode_persist(a, m->p_grid, s));
-    return VR_OK;
-}
-// a barrier of the persistent kernel timed out (the workgroups were not all resident): everything after it is garbage
-// The kernel's abort flag and its barrier counters are sticky: leave the persistent path for good — the step that timed out
-// is reported as failed (its logits are garbage), every later step runs as separate launches (p_grid = 0) on clean state.
-static int persist_check(vg_model_s* m) {
-    if (m->p_abort && *m->p_abort) {
-        *m->p_abort = 0;
-        m->p_grid = 0;
-        if (m->p_sync.p) (void)hipMemset(m->p_sync.p, 0, 128 * 8);
-        if (m->p_ss.p) (void)hipMemset(m->p_ss.p, 0, 16 * 4);
-        return fail(VR_ERR_HIP, "the decode kernel's grid barrier timed out (its workgroups must all be resident: one per CU — "
-                                "another kernel was running on the device?); this step's result is invalid, the model has fallen "
-                                "back to separate launches for the steps that follow: prefill again and continue");
-    }
-    return VR_OK;
-}
-
 extern "C" int vg_create(int device_id, const vg_config_t* cfg, vg_model_t* out) {
     if (!cfg || !out) return fail(VR_ERR_INVALID, "cfg/out is NULL");
     const vg_config_t& c = *cfg;
@@ -175,7 +88,6 @@ extern "C" int vg_destroy(vg_model_t m) {
     for (auto& e : m->run_ev)
         if (e) (void)hipEventDestroy(e);
     if (m->h_tokens) (void)hipHostFree(m->h_tokens);
-    if (m->p_abort) (void)hipHostFree(m->p_abort);
     vision_destroy(m);
     delete m;                           // DevBuf destructors release everything
     return VR_OK;
@@ -258,109 +170,142 @@ extern "C" int vg_finalize(vg_model_t m) {
     }
     if (m->vis) VRCHK(vision_check_complete(m));
     VRCHK(set_dev(m->device));
-    VRCHK(persist_setup(m));
+    const GenLayer& L0 = m->layers[0];
+    auto choose_ksplit = [](int n, int k) { return skinny_ksplit(n, k, GEN_KS_MAX); };
+    DecodePlan& dp = m->plan;
+    dp.ks_qkv = choose_ksplit(m->QKV, m->E); dp.ks_o = choose_ksplit(m->E, m->QD);
+    dp.ks_gu = choose_ksplit(L0.gu.n_pad, m->E); dp.ks_d = choose_ksplit(m->E, L0.down.k_pad);
+    dp.Ip = L0.down.k_pad; dp.N2 = L0.gu.n_pad;
+    // The single-sequence step merges the attention's KV ranges inside the o projection (SkinnyCombine), which builds a K range's
+    // A row in the four-stage ring: at most 4 K-steps per range.  vg_create admits hidden = heads * 128, a multiple of 256, up to
+    // 3584, so QD = E, the o projection has tiles = E / 256 <= 14 column tiles over nk = E / 64 = 4 * tiles K-steps, and
+    // skinny_ksplit returns exactly `tiles` (tiles * tiles <= 196 workgroups fit the one round of 256; 4 steps each) — or 1 at
+    // E = 256, again 4 steps.  So this holds for every shape the handle accepts; it is checked because the launch relies on it.
+    const int per_o = (m->QD / 64 + dp.ks_o - 1) / dp.ks_o;
+    if (per_o > 4) return fail(VR_ERR_STATE, "o projection: %d K-steps per range (split %d) are beyond the fused range merge's 4", per_o, dp.ks_o);
     m->finalized = true;
     return VR_OK;
 }
 
-// one decoder layer over T rows that already sit (normalised, bf16) in w_xn; cache rows [len, len + T)
-static int gen_layer(vg_model_s* m, int l, int T, bool decode, const float* next_norm, hipStream_t s) {
+// one decoder layer of the prefill over T rows that already sit (normalised, bf16) in w_xn; cache rows [len, len + T) of the
+// current slot; attention causal within the prompt
+static int gen_layer_prefill(vg_model_s* m, int l, int T, const float* next_norm, hipStream_t s) {
     const vg_config_t& c = m->c;
     GenLayer& L = m->layers[l];
     const int E = m->E, QD = m->QD, QKV = m->QKV, Ip = pad128(m->I);
     float* h = m->w_h.as<float>();
-    float* part = m->w_part.as<float>();
     int* cu = m->w_cu.as<int>();
     // ---- q | k | v
-    if (decode) {
-        GemmArgs a = gen_gemm_args(m->w_xn.p, E, L.qkv, T, part, QKV);
-        a.bias = nullptr;
-        a.ksplit = choose_ksplit(QKV, E);
-        a.split_stride = (size_t)QKV * T;
-        HIPCHK(launch_gemm_skinny(a, s));
-        GenState* st = m->w_state.as<GenState>();          // position and cache row of the step: on the device
-        HIPCHK(launch_mrope_cache(nullptr, part, a.ksplit, (size_t)QKV * T, L.qkv.b.as<float>(), QKV, T, m->H, m->KV, st->pos,
-                                  1, c.mrope_section[0], c.mrope_section[1], m->inv_freq.as<float>(), m->w_q.p, QD,
-                                  gen_kc(m, l, m->cur), gen_vc(m, l, m->cur), m->KVD, 0, nullptr, s, &st->len));
-    } else {
+    {
         GemmArgs a = gen_gemm_args(m->w_xn.p, E, L.qkv, T, m->w_qkv.p, QKV);
         HIPCHK(launch_gemm(a, EPI_BF16, GEMM_VARIANT_AUTO, s));
         HIPCHK(launch_mrope_cache(m->w_qkv.p, nullptr, 0, 0, nullptr, QKV, T, m->H, m->KV, m->w_pos.as<int>(), m->Tcap,
                                   c.mrope_section[0], c.mrope_section[1], m->inv_freq.as<float>(), m->w_q.p, QD, gen_kc(m, l, m->cur),
                                   gen_vc(m, l, m->cur), m->KVD, m->len, nullptr, s));
     }
-    // ---- grouped-query attention over the cache.  Prefill: causal within the prompt.  Decode: the new row sees the
-    //      whole cache; one query row x 28 heads would be 28 workgroups, so the cache is cut into KV ranges
-    //      (decode_begin_kernel, GenState::cu_kv) that run as independent "sequences" sharing the query row (q_shared) —
-    //      always GEN_ATT_SPLITS of them on the grid, the ones past the end empty — and a small kernel merges the
-    //      GenState::splits real ones by their log-sum-exps.  Nothing here depends on a host-side length.
+    // ---- grouped-query attention over the cache
     {
         AttnArgs a{};
         a.q = m->w_q.p; a.ldq = QD; a.k = gen_kc(m, l, m->cur); a.ldk = m->KVD; a.v = gen_vc(m, l, m->cur); a.ldv = m->KVD;
         a.heads = m->H; a.head_dim = 128; a.scale = 1.0f / sqrtf(128.0f); a.kv_group = m->H / m->KV;
-        if (decode) {
-            // the G = H / KV query heads that share a KV head are the ROWS of one tile (q_head_stride): a KV range is read
-            // once per group instead of once per query head, on KV x ranges workgroups
-            const int G = m->H / m->KV;
-            GenState* st = m->w_state.as<GenState>();
-            a.cu_q = st->cu_q; a.cu_kv = st->cu_kv;
-            a.heads = m->KV; a.kv_group = 1; a.ldq = 128; a.q_head_stride = G * 128;
-            a.out = m->w_attp.p; a.ldo = m->KVD; a.B = GEN_ATT_SPLITS; a.max_q = G; a.causal = 0; a.q_shared = 1;
-            a.lse = m->w_lse.as<float>();
-            HIPCHK(launch_attention(a, s));
-            // (the ranges are merged by the o projection below as it builds its A row: no launch of its own)
-        } else {
-            a.cu_q = cu; a.cu_kv = cu + 2;
-            a.out = m->w_att.p; a.ldo = QD; a.B = 1; a.max_q = T; a.causal = 1; a.q_shared = 0;
-            HIPCHK(launch_attention(a, s));
-        }
+        a.cu_q = cu; a.cu_kv = cu + 2;
+        a.out = m->w_att.p; a.ldo = QD; a.B = 1; a.max_q = T; a.causal = 1; a.q_shared = 0;
+        HIPCHK(launch_attention(a, s));
     }
     // ---- o projection + residual, post-attention norm
-    if (decode) {
-        GemmArgs a = gen_gemm_args(m->w_att.p, QD, L.o, T, part, E);
-        a.ksplit = choose_ksplit(E, QD);
-        a.split_stride = (size_t)E * T;
-        const int per = (QD / 64 + a.ksplit - 1) / a.ksplit;
-        if (T == 1 && per <= 4) {
-            GenState* st = m->w_state.as<GenState>();
-            SkinnyCombine cb{m->w_attp.p, m->w_lse.as<float>(), 0, m->H, m->H / m->KV, &st->splits};
-            HIPCHK(launch_gemm_skinny(a, s, false, &cb));
-        } else {                                    // (a K range longer than the stage ring: merge with its own launch)
-            GenState* st = m->w_state.as<GenState>();
-            HIPCHK(launch_attn_combine(m->w_attp.p, m->w_lse.as<float>(), 0, m->H, m->H / m->KV, m->w_att.p, s, &st->splits));
-            HIPCHK(launch_gemm_skinny(a, s));
-        }
-        HIPCHK(launch_rmsnorm_accum(h, T, E, E, part, a.ksplit, (size_t)E * T, E, 1.0f, L.ln2.v.as<float>(), c.rms_norm_eps, m->w_xn.p, E, s));
-    } else {
+    {
         GemmArgs a = gen_gemm_args(m->w_att.p, QD, L.o, T, h, E);
         a.resid = h;
         HIPCHK(launch_gemm(a, EPI_RESID, GEMM_VARIANT_AUTO, s));
         HIPCHK(launch_rmsnorm(h, T, E, E, L.ln2.v.as<float>(), c.rms_norm_eps, m->w_xn.p, E, s));
     }
-    // ---- SwiGLU MLP + residual; the next layer's (or the final) norm closes the layer
-    if (decode) {
-        const int N2 = L.gu.n_pad;
-        GemmArgs g = gen_gemm_args(m->w_xn.p, E, L.gu, T, part, N2);
-        g.ksplit = choose_ksplit(N2, E);
+    // ---- SwiGLU MLP + residual; the next layer's norm closes the layer (the last layer's row goes to gen_head)
+    { GemmArgs a = gen_gemm_args(m->w_xn.p, E, L.gu, T, m->w_act.p, Ip); HIPCHK(launch_gemm(a, EPI_SWIGLU, GEMM_VARIANT_AUTO, s)); }
+    GemmArgs a = gen_gemm_args(m->w_act.p, Ip, L.down, T, h, E);
+    a.resid = h;
+    HIPCHK(launch_gemm(a, EPI_RESID, GEMM_VARIANT_AUTO, s));
+    if (l + 1 < (int)m->layers.size()) HIPCHK(launch_rmsnorm(h, T, E, E, next_norm, c.rms_norm_eps, m->w_xn.p, E, s));
+    return VR_OK;
+}
+
+// What the two decode steps hand their layers: the single-sequence step (enqueue_decode) reads everything from GenState, the
+// batched one (vg_decode_batch) from GenBatch.
+struct DecodeRows {
+    int n;                              // rows of the step: one per sequence
+    const int* pos; int pos_stride;     // mRoPE positions [3][pos_stride]
+    const int* row0_dev;                // the cache row of the one new row, on the device (&GenState::len) ...
+    const int* cache_rows;              // ... or [n] cache rows (GenBatch::cache_row), counted from `slot`'s base
+    int slot;                           // the caches' base: the current slot's, or slot 0 = the whole cache
+    const int *cu_q, *cu_kv, *kv_end, *q_in;    // attention items (AttnArgs): (row, KV range); kv_end / q_in null: GenState's form
+    int q_shared, B;
+    const int* splits;                  // [n] KV ranges per row, on the device
+    bool fused_merge;                   // the ranges are merged by the o projection itself (n = 1) instead of a launch of their own
+};
+
+// one decoder layer of a decode step: d.n rows, one per sequence, already (normalised, bf16) in w_xn.  Every GEMM is one pass
+// over its weights into fp32 split-K planes (m->plan) that the next kernel sums.
+static int gen_layer_decode(vg_model_s* m, int l, const DecodeRows& d, const float* next_norm, hipStream_t s) {
+    const vg_config_t& c = m->c;
+    const DecodePlan& dp = m->plan;
+    GenLayer& L = m->layers[l];
+    const int E = m->E, QD = m->QD, QKV = m->QKV, G = m->H / m->KV, n = d.n;
+    float* h = m->w_h.as<float>();
+    float* part = m->w_part.as<float>();
+    void* kc = gen_kc(m, l, d.slot);
+    void* vc = gen_vc(m, l, d.slot);
+    {   // ---- q | k | v, then rotate + append to each row's cache
+        GemmArgs a = gen_gemm_args(m->w_xn.p, E, L.qkv, n, part, QKV);
+        a.bias = nullptr;
+        a.ksplit = dp.ks_qkv;
+        a.split_stride = (size_t)QKV * n;
+        HIPCHK(launch_gemm_skinny(a, s));
+        HIPCHK(launch_mrope_cache(nullptr, part, a.ksplit, (size_t)QKV * n, L.qkv.b.as<float>(), QKV, n, m->H, m->KV, d.pos, d.pos_stride,
+                                  c.mrope_section[0], c.mrope_section[1], m->inv_freq.as<float>(), m->w_q.p, QD, kc, vc, m->KVD, 0, nullptr, s,
+                                  d.row0_dev, d.cache_rows));
+    }
+    {   // ---- grouped-query attention: a new row sees the whole cache; one query row x 28 heads would be 28 workgroups, so the
+        //      cache is cut into KV ranges (gen_kv_split) that run as independent items — always GEN_ATT_SPLITS per row on the
+        //      grid, the ones past the end empty — and d.splits real ones are merged by their log-sum-exps.  The G = H / KV query
+        //      heads that share a KV head are the ROWS of one tile (q_head_stride): a KV range is read once per group instead of
+        //      once per query head.  Nothing here depends on a host-side length.
+        AttnArgs a{};
+        a.q = m->w_q.p; a.ldq = 128; a.q_head_stride = G * 128; a.q_in_rows = d.q_in;
+        a.k = kc; a.ldk = m->KVD; a.v = vc; a.ldv = m->KVD;
+        a.cu_q = d.cu_q; a.cu_kv = d.cu_kv; a.kv_end = d.kv_end;
+        a.heads = m->KV; a.kv_group = 1; a.head_dim = 128; a.scale = 1.0f / sqrtf(128.0f);
+        a.out = m->w_attp.p; a.ldo = m->KVD; a.B = d.B; a.max_q = G; a.causal = 0; a.q_shared = d.q_shared;
+        a.lse = m->w_lse.as<float>();
+        HIPCHK(launch_attention(a, s));
+    }
+    {   // ---- o projection (+ the range merge), residual and post-attention norm
+        GemmArgs a = gen_gemm_args(m->w_att.p, QD, L.o, n, part, E);
+        a.ksplit = dp.ks_o;
+        a.split_stride = (size_t)E * n;
+        if (d.fused_merge) {                        // its A row is built from the partial rows (vg_finalize: a K range fits the stage ring)
+            SkinnyCombine cb{m->w_attp.p, m->w_lse.as<float>(), 0, m->H, G, d.splits};
+            HIPCHK(launch_gemm_skinny(a, s, false, &cb));
+        } else {
+            HIPCHK(launch_attn_combine(m->w_attp.p, m->w_lse.as<float>(), 0, m->H, G, m->w_att.p, s, d.splits, n, QD));
+            HIPCHK(launch_gemm_skinny(a, s));
+        }
+        HIPCHK(launch_rmsnorm_accum(h, n, E, E, part, a.ksplit, (size_t)E * n, E, 1.0f, L.ln2.v.as<float>(), c.rms_norm_eps, m->w_xn.p, E, s));
+    }
+    {   // ---- SwiGLU MLP + residual; the next layer's (or the final) norm closes the layer
+        GemmArgs g = gen_gemm_args(m->w_xn.p, E, L.gu, n, part, dp.N2);
+        g.ksplit = dp.ks_gu;
         if (g.ksplit == 1) {                        // the usual case (more tiles than a split would help): SwiGLU in the tile's epilogue
-            g.out = m->w_act.p; g.ldo = Ip;
+            g.out = m->w_act.p; g.ldo = dp.Ip;
             HIPCHK(launch_gemm_skinny(g, s, true));
         } else {
-            g.split_stride = (size_t)N2 * T;
+            g.split_stride = (size_t)dp.N2 * n;
             HIPCHK(launch_gemm_skinny(g, s));
-            HIPCHK(launch_swiglu_sum(part, g.ksplit, (size_t)N2 * T, N2, T, m->I, m->w_act.p, Ip, s));
+            HIPCHK(launch_swiglu_sum(part, g.ksplit, (size_t)dp.N2 * n, dp.N2, n, m->I, m->w_act.p, dp.Ip, s));
         }
-        GemmArgs a = gen_gemm_args(m->w_act.p, Ip, L.down, T, part, E);
-        a.ksplit = choose_ksplit(E, L.down.k_pad);
-        a.split_stride = (size_t)E * T;
+        GemmArgs a = gen_gemm_args(m->w_act.p, dp.Ip, L.down, n, part, E);
+        a.ksplit = dp.ks_d;
+        a.split_stride = (size_t)E * n;
         HIPCHK(launch_gemm_skinny(a, s));
-        HIPCHK(launch_rmsnorm_accum(h, T, E, E, part, a.ksplit, (size_t)E * T, E, 1.0f, next_norm, c.rms_norm_eps, m->w_xn.p, E, s));
-    } else {
-        { GemmArgs a = gen_gemm_args(m->w_xn.p, E, L.gu, T, m->w_act.p, Ip); HIPCHK(launch_gemm(a, EPI_SWIGLU, GEMM_VARIANT_AUTO, s)); }
-        GemmArgs a = gen_gemm_args(m->w_act.p, Ip, L.down, T, h, E);
-        a.resid = h;
-        HIPCHK(launch_gemm(a, EPI_RESID, GEMM_VARIANT_AUTO, s));
-        if (l + 1 < (int)m->layers.size()) HIPCHK(launch_rmsnorm(h, T, E, E, next_norm, c.rms_norm_eps, m->w_xn.p, E, s));
+        HIPCHK(launch_rmsnorm_accum(h, n, E, E, part, a.ksplit, (size_t)E * n, E, 1.0f, next_norm, c.rms_norm_eps, m->w_xn.p, E, s));
     }
     return VR_OK;
 }
@@ -418,7 +363,7 @@ extern "C" int vg_prefill(vg_model_t m, const int32_t* ids, int32_t T, const int
     HIPCHK(launch_rmsnorm(m->w_h.as<float>(), T, E, E, m->layers[0].ln1.v.as<float>(), m->c.rms_norm_eps, m->w_xn.p, E, s));
     const int nl = (int)m->layers.size();
     for (int l = 0; l < nl; ++l)
-        VRCHK(gen_layer(m, l, T, false, l + 1 < nl ? m->layers[l + 1].ln1.v.as<float>() : nullptr, s));
+        VRCHK(gen_layer_prefill(m, l, T, l + 1 < nl ? m->layers[l + 1].ln1.v.as<float>() : nullptr, s));
     m->len = T;
     return gen_head(m, m->w_h.as<float>() + (size_t)(T - 1) * E, false, s);
 }
@@ -432,13 +377,14 @@ static int enqueue_decode(vg_model_s* m, hipStream_t s, bool sampled, float temp
     HIPCHK(launch_decode_begin(st, m->H / m->KV, s));
     HIPCHK(launch_embed_gather(&st->token, 1, m->embed.p, E, 1.0f, m->w_h.as<float>(), s));
     HIPCHK(launch_rmsnorm(m->w_h.as<float>(), 1, E, E, m->layers[0].ln1.v.as<float>(), m->c.rms_norm_eps, m->w_xn.p, E, s));
+    // position, cache row and KV ranges of the step are on the device; the ranges share the one query row
+    DecodeRows d{};
+    d.n = 1; d.pos = st->pos; d.pos_stride = 1; d.row0_dev = &st->len; d.slot = m->cur;
+    d.cu_q = st->cu_q; d.cu_kv = st->cu_kv; d.q_shared = 1; d.B = GEN_ATT_SPLITS;
+    d.splits = &st->splits; d.fused_merge = true;
     const int nl = (int)m->layers.size();
-    if (m->p_grid > 0) {
-        VRCHK(persist_layers(m, s));               // all layers in one launch; leaves the lm_head's A row in w_xn like the loop below
-    } else {
-        for (int l = 0; l < nl; ++l)
-            VRCHK(gen_layer(m, l, 1, true, l + 1 < nl ? m->layers[l + 1].ln1.v.as<float>() : m->final_norm.v.as<float>(), s));
-    }
+    for (int l = 0; l < nl; ++l)
+        VRCHK(gen_layer_decode(m, l, d, l + 1 < nl ? m->layers[l + 1].ln1.v.as<float>() : m->final_norm.v.as<float>(), s));
     VRCHK(gen_head(m, nullptr, true, s));
     if (sampled)
         HIPCHK(launch_sample(gen_logits(m, m->cur), m->V, gen_seen(m, m->cur), penalty, temperature, seed, 0, m->w_tok.as<int>(),
@@ -483,7 +429,7 @@ extern "C" int vg_sample(vg_model_t m, float temperature, float repetition_penal
     HIPCHK(hipMemcpyAsync(token_out, m->w_tok.p, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     m->tok_on_device = true;
-    return persist_check(m);
+    return VR_OK;
 }
 
 // ---- free-running generation ------------------------------------------------------------------------------------
@@ -549,7 +495,7 @@ extern "C" int vg_run_token(vg_model_t m, int32_t index, int32_t* token) {
     VRCHK(set_dev(m->device));
     HIPCHK(hipEventSynchronize(m->run_ev[index % GEN_RUN_RING]));
     *token = m->h_tokens[index % GEN_RUN_RING];
-    return persist_check(m);
+    return VR_OK;
 }
 
 extern "C" int vg_run_end(vg_model_t m) {
@@ -570,63 +516,6 @@ extern "C" int vg_select(vg_model_t m, int32_t slot) {
     m->len = m->slot_len[slot]; m->have_logits = m->slot_logits[slot] != 0;
     m->tok_on_device = false;
     drop_graph(m);
-    return persist_setup(m);                       // the layer table points at the slot's caches
-}
-
-// one decoder layer of a batched decode step: n rows, one per sequence, each with its own cache rows
-static int gen_layer_batch(vg_model_s* m, int l, int n, const float* next_norm, hipStream_t s) {
-    const vg_config_t& c = m->c;
-    GenLayer& L = m->layers[l];
-    const int E = m->E, QD = m->QD, QKV = m->QKV, Ip = pad128(m->I), G = m->H / m->KV;
-    float* h = m->w_h.as<float>();
-    float* part = m->w_part.as<float>();
-    GenBatch* bt = m->w_batch.as<GenBatch>();
-    {   // q | k | v: one pass over the weights for the n rows, then rotate + append to each sequence's cache
-        GemmArgs a = gen_gemm_args(m->w_xn.p, E, L.qkv, n, part, QKV);
-        a.bias = nullptr;
-        a.ksplit = choose_ksplit(QKV, E);
-        a.split_stride = (size_t)QKV * n;
-        HIPCHK(launch_gemm_skinny(a, s));
-        HIPCHK(launch_mrope_cache(nullptr, part, a.ksplit, (size_t)QKV * n, L.qkv.b.as<float>(), QKV, n, m->H, m->KV, &bt->pos[0][0], 16,
-                                  c.mrope_section[0], c.mrope_section[1], m->inv_freq.as<float>(), m->w_q.p, QD, m->kc[l].p, m->vc[l].p,
-                                  m->KVD, 0, nullptr, s, nullptr, bt->cache_row));
-    }
-    {   // attention: item (r, range) = the group's query heads of row r against one KV range of ITS cache
-        AttnArgs a{};
-        a.q = m->w_q.p; a.ldq = 128; a.q_head_stride = G * 128; a.q_in_rows = bt->q_in;
-        a.k = m->kc[l].p; a.ldk = m->KVD; a.v = m->vc[l].p; a.ldv = m->KVD;
-        a.cu_q = bt->cu_q; a.cu_kv = bt->kv_lo; a.kv_end = bt->kv_hi;
-        a.heads = m->KV; a.kv_group = 1; a.head_dim = 128; a.scale = 1.0f / sqrtf(128.0f);
-        a.out = m->w_attp.p; a.ldo = m->KVD; a.B = n * GEN_ATT_SPLITS; a.max_q = G; a.causal = 0; a.q_shared = 0;
-        a.lse = m->w_lse.as<float>();
-        HIPCHK(launch_attention(a, s));
-        HIPCHK(launch_attn_combine(m->w_attp.p, m->w_lse.as<float>(), 0, m->H, G, m->w_att.p, s, bt->splits, n, QD));
-    }
-    {
-        GemmArgs a = gen_gemm_args(m->w_att.p, QD, L.o, n, part, E);
-        a.ksplit = choose_ksplit(E, QD);
-        a.split_stride = (size_t)E * n;
-        HIPCHK(launch_gemm_skinny(a, s));
-        HIPCHK(launch_rmsnorm_accum(h, n, E, E, part, a.ksplit, (size_t)E * n, E, 1.0f, L.ln2.v.as<float>(), c.rms_norm_eps, m->w_xn.p, E, s));
-    }
-    {
-        const int N2 = L.gu.n_pad;
-        GemmArgs g = gen_gemm_args(m->w_xn.p, E, L.gu, n, part, N2);
-        g.ksplit = choose_ksplit(N2, E);
-        if (g.ksplit == 1) {
-            g.out = m->w_act.p; g.ldo = Ip;
-            HIPCHK(launch_gemm_skinny(g, s, true));
-        } else {
-            g.split_stride = (size_t)N2 * n;
-            HIPCHK(launch_gemm_skinny(g, s));
-            HIPCHK(launch_swiglu_sum(part, g.ksplit, (size_t)N2 * n, N2, n, m->I, m->w_act.p, Ip, s));
-        }
-        GemmArgs a = gen_gemm_args(m->w_act.p, Ip, L.down, n, part, E);
-        a.ksplit = choose_ksplit(E, L.down.k_pad);
-        a.split_stride = (size_t)E * n;
-        HIPCHK(launch_gemm_skinny(a, s));
-        HIPCHK(launch_rmsnorm_accum(h, n, E, E, part, a.ksplit, (size_t)E * n, E, 1.0f, next_norm, c.rms_norm_eps, m->w_xn.p, E, s));
-    }
     return VR_OK;
 }
 
@@ -640,8 +529,9 @@ extern "C" int vg_decode_batch(vg_model_t m, int32_t n, const int32_t* slots, co
     const int G = m->H / m->KV;
     {   // the widest split-K plane set of the step must fit the partial buffer
         const size_t cap = m->w_part.bytes / 4;
-        const size_t need = (size_t)n * std::max({(size_t)choose_ksplit(m->QKV, m->E) * m->QKV, (size_t)choose_ksplit(m->E, m->QD) * m->E,
-                                                  (size_t)choose_ksplit(m->E, pad128(m->I)) * m->E});
+        const DecodePlan& dp = m->plan;
+        const size_t need = (size_t)n * std::max({(size_t)dp.ks_qkv * m->QKV, (size_t)dp.ks_o * m->E, (size_t)dp.ks_d * m->E,
+                                                  dp.ks_gu > 1 ? (size_t)dp.ks_gu * dp.N2 : (size_t)0});     // (unsplit gate | up writes no plane)
         if (need > cap) return fail(VR_ERR_CAPACITY, "%d rows need %zu partial-sum floats (%zu available)", n, need, cap);
     }
     GenBatch b{};
@@ -658,16 +548,13 @@ extern "C" int vg_decode_batch(vg_model_t m, int32_t n, const int32_t* slots, co
         for (int c = 0; c < 3; ++c) b.pos[c][r] = pos[3 * r + c];
         const int base = sl * m->c.max_len;
         b.cache_row[r] = base + len;
-        // KV ranges of the row's attention: decode_begin_kernel's split of its L = len + 1 cache rows
-        const int L = len + 1;
-        int splits = std::min(GEN_ATT_SPLITS, std::max(1, (L + 127) / 128));
-        const int chunk = ((L + splits - 1) / splits + 63) / 64 * 64;
-        splits = (L + chunk - 1) / chunk;
-        b.splits[r] = splits;
+        const int L = len + 1;                          // the row's attention sees its new cache row
+        const KvSplit kv = gen_kv_split(L);
+        b.splits[r] = kv.splits;
         for (int t = 0; t < GEN_ATT_SPLITS; ++t) {
             const int it = r * GEN_ATT_SPLITS + t;
-            b.kv_lo[it] = base + std::min(L, t * chunk);
-            b.kv_hi[it] = base + std::min(L, (t + 1) * chunk);
+            b.kv_lo[it] = base + std::min(L, t * kv.chunk);
+            b.kv_hi[it] = base + std::min(L, (t + 1) * kv.chunk);
             b.q_in[it] = r * m->H;                       // q rows are 128 wide: row r's heads start at r * H
         }
     }
@@ -679,9 +566,14 @@ extern "C" int vg_decode_batch(vg_model_t m, int32_t n, const int32_t* slots, co
     const int E = m->E;
     HIPCHK(launch_embed_gather(bt->token, n, m->embed.p, E, 1.0f, m->w_h.as<float>(), s));
     HIPCHK(launch_rmsnorm(m->w_h.as<float>(), n, E, E, m->layers[0].ln1.v.as<float>(), m->c.rms_norm_eps, m->w_xn.p, E, s));
+    // item (r, range) = the group's query heads of row r against one KV range of ITS cache (rows of the whole cache)
+    DecodeRows d{};
+    d.n = n; d.pos = &bt->pos[0][0]; d.pos_stride = 16; d.cache_rows = bt->cache_row; d.slot = 0;
+    d.cu_q = bt->cu_q; d.cu_kv = bt->kv_lo; d.kv_end = bt->kv_hi; d.q_in = bt->q_in; d.q_shared = 0; d.B = n * GEN_ATT_SPLITS;
+    d.splits = bt->splits; d.fused_merge = false;
     const int nl = (int)m->layers.size();
     for (int l = 0; l < nl; ++l)
-        VRCHK(gen_layer_batch(m, l, n, l + 1 < nl ? m->layers[l + 1].ln1.v.as<float>() : m->final_norm.v.as<float>(), s));
+        VRCHK(gen_layer_decode(m, l, d, l + 1 < nl ? m->layers[l + 1].ln1.v.as<float>() : m->final_norm.v.as<float>(), s));
     {   // lm_head over the n normed rows, then every row to its slot's logits
         GemmArgs a = gen_gemm_args(m->w_xn.p, E, m->lm_head, n, m->w_logits_b.p, m->lm_head.n_pad);
         HIPCHK(launch_gemm_skinny(a, s));
@@ -723,7 +615,7 @@ extern "C" int vg_logits(vg_model_t m, float* out, void* stream) {
     VRCHK(end_run(m));
     HIPCHK(hipMemcpyAsync(out, gen_logits(m, m->cur), (size_t)m->V * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    return persist_check(m);
+    return VR_OK;
 }
 
 extern "C" int vg_cache_len(vg_model_t m, int32_t* len) {

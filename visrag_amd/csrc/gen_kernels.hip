@@ -228,11 +228,9 @@ hipError_t launch_sample(const float* logits, int vocab, unsigned* seen, float p
 __global__ void decode_begin_kernel(GenState* __restrict__ st, int q_rows) {
     if (threadIdx.x != 0) return;
     const int L = st->len + 1;
-    int splits = min(GEN_ATT_SPLITS, max(1, (L + 127) / 128));
-    const int chunk = ((L + splits - 1) / splits + 63) / 64 * 64;
-    splits = (L + chunk - 1) / chunk;
-    st->splits = splits;
-    for (int i = 0; i <= GEN_ATT_SPLITS; ++i) { st->cu_q[i] = i * q_rows; st->cu_kv[i] = min(L, i * chunk); }
+    const KvSplit kv = gen_kv_split(L);
+    st->splits = kv.splits;
+    for (int i = 0; i <= GEN_ATT_SPLITS; ++i) { st->cu_q[i] = i * q_rows; st->cu_kv[i] = min(L, i * kv.chunk); }
 }
 hipError_t launch_decode_begin(GenState* st, int q_rows, hipStream_t s) {
     hipLaunchKernelGGL(decode_begin_kernel, dim3(1), dim3(64), 0, s, st, q_rows);

@@ -1,5 +1,5 @@
-// Small arithmetic of the generator's decode step that more than one kernel performs (the separate launches of gen.hip and
-// the persistent kernel of gen_persist.hip must produce the same bits): spelled out operation by operation, because left to
+// Small arithmetic of the decode steps that more than one kernel performs and that must give the same bits wherever it runs
+// (the range merge: fused into gemm_skinny.hip's o projection and on its own in attn_combine_kernel): spelled out operation by operation, because left to
 // -ffp-contract=fast hipcc fuses `a * b + c * d` one way in one kernel and the other way in the next (seen: a rotated q / k
 // element one ulp apart, a bf16 rounding flipped, logits 2e-3 of their scale apart at one decode step in a few hundred).
 #pragma once

@@ -15,6 +15,15 @@ struct GenLayer {
 constexpr int GEN_KS_MAX = 64;      // split-K planes of the decode path
 constexpr int GEN_RUN_RING = 8;     // most free-running steps in flight before their tokens are collected
 
+
+// The decode step's GEMM shapes, fixed once the weights are loaded (vg_finalize): how many K ranges each GEMM's 256-column tiles
+// are cut into (gemm_skinny.hip; skinny_ksplit with GEN_KS_MAX), the SwiGLU row's length and the gate | up rows (both padded).
+// One workgroup fits on a CU (its four LDS stages), so the fastest shape is ONE balanced round of workgroups with K loops as
+// long as that allows — measured on the 7B layer (ms per token): gate/up 148 tiles as 148 x 56 K-steps 3.74, 296 x 28 (a
+// second round of 40) 3.94, 592 x 14 3.80; down 14 tiles as 252 x 17 3.74, 112 x 37 3.94, 518 x 8 4.08.  The splits need not
+// divide the K-steps (the last range is shorter); every range keeps >= 4 steps; more tiles than CUs: no split.
+struct DecodePlan { int ks_qkv = 1, ks_o = 1, ks_gu = 1, ks_d = 1, Ip = 0, N2 = 0; };
+
 struct VisionTower;                 // gen_vision.hip
 
 struct vg_model_s {
@@ -25,6 +34,7 @@ struct vg_model_s {
     DevBuf embed;
     bool has_embed = false;
     std::vector<GenLayer> layers;
+    DecodePlan plan;
     Vec final_norm;
     Linear lm_head;
     DevBuf inv_freq;
@@ -51,10 +61,6 @@ struct vg_model_s {
     int run_steps = 0;                  // steps enqueued in the current run
     int* h_tokens = nullptr;            // pinned ring [GEN_RUN_RING] the sampled tokens are copied into
     hipEvent_t run_ev[8] = {};          // run_ev[i % 8]: step i's token has landed
-    // the decode step's persistent layer kernel (gen_persist.hip): layer table for the CURRENT slot, barrier words, host-mapped abort flag
-    DevBuf p_table, p_sync, p_ss;
-    unsigned* p_abort = nullptr;        // hipHostMalloc'd
-    int p_grid = 0;                     // 0: the shape / device does not take the kernel (separate launches instead)
     VisionTower* vis = nullptr;         // attached by vg_vision_create
     int vis_tokens = 0;                 // embedding rows the last vg_vision_encode left in w_emb (image-token order)
 };
