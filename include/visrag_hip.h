@@ -337,6 +337,37 @@ int vr_index_search_groups(vr_index_t ix, const float* queries, int32_t nq, int3
 /* Grouped-search queries since the last reset: out3 = {certified from the first candidate set,
  * certified after widening it, redone exactly}. */
 int vr_index_group_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
+/* ---- filtered search: the top k among the rows a query's filter allows ---- */
+/* Set n_filters row filters over the rows present.  bits (host or device per `on_device`) is [n_filters][words] uint32,
+ * words = ceil(rows / 32): filter f allows row r iff bit r & 31 of word r >> 5 of filter f is set.  Bits at or beyond
+ * the row count are ignored (cleared in the library's copy).  The library copies the filters into memory it owns and
+ * counts every filter's allowed rows once, here.  NULL, n_filters < 1 or an empty index: VR_ERR_INVALID, and the index
+ * keeps the filters it had.  A later vr_index_add that appends rows, or vr_index_reset, drops the filters.  Filters and
+ * groups are independent. */
+int vr_index_set_filters(vr_index_t ix, const uint32_t* bits, int32_t n_filters, int32_t on_device, void* stream);
+/* For every query the k ALLOWED rows of largest fp32 dot product, larger score first and the lower row id first among
+ * equal scores: what vr_index_search returns on an index that holds only the allowed rows, with the original row ids.
+ * filter_of_query [nq] int32 (host or device as `queries`): the filter of query q, -1 = no filter (all rows).
+ *   out_scores [nq][k] float32;  out_ids [nq][k] int64;  fewer than k allowed rows (none included): the tail is (-inf, -1).
+ * The allowed rows are a sub-index for which the error model of vr_index_set_search_eps holds as it does for the whole
+ * index (the index-wide max |d| and max |d - bf16(d)| can only be looser), so the certification of the deep path
+ * applies with na = the filter's allowed rows in the place of the row count: the bf16 MFMA scores of all rows are
+ * computed, the disallowed ones set to -inf, the min(na, k + 24) best are re-scored in fp32; the result is certified if
+ * every allowed row was re-scored or the best bf16 score outside the candidates lies below E_(k) - eps, else every
+ * allowed row with a bf16 score >= E_(k) - eps is re-scored (up to 1024), else the query is redone from exact fp32 scores
+ * of all rows, masked the same way.  With certification off (eps_rel < 0) the first candidate set is re-scored and
+ * returned with no guarantee, and nothing is counted.
+ * k = 1..1000 and the dim limits of the deep path of vr_index_search; a HOST filter_of_query entry outside
+ * [-1, n_filters): VR_ERR_INVALID before any launch.  On the device such an entry cannot be seen before the launch: it
+ * allows nothing (an all-empty result row) and nothing outside the filter store is read.  No filters set for the rows
+ * present: VR_ERR_STATE.  Filtered searches are not counted by vr_index_search_stats or vr_index_group_search_stats and
+ * leave every state the other searches read alone. */
+int vr_index_search_filtered(vr_index_t ix, const float* queries, int32_t nq, int32_t k,
+                             const int32_t* filter_of_query,
+                             float* out_scores, int64_t* out_ids, int32_t on_device, void* stream);
+/* Filtered-search queries since the last reset: out3 = {certified from the first candidate set (a query with no
+ * allowed row included), certified after widening it, redone exactly}. */
+int vr_index_filter_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
 /* Merge per-shard results (e.g. after an RCCL all-gather): in [n_parts][nq][k] scores and
  * global ids -> out [nq][k], same ordering rule.  Device pointers. */
 int vr_topk_merge(int device_id, const float* scores, const int64_t* ids, int32_t n_parts,

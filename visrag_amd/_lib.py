@@ -106,6 +106,9 @@ SIGNATURES = {
     "vr_index_set_groups": (C.c_int, [_vp, C.POINTER(_i64), _i64]),
     "vr_index_search_groups": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
     "vr_index_group_search_stats": (C.c_int, [_vp, C.POINTER(_i64), _i32]),
+    "vr_index_set_filters": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
+    "vr_index_search_filtered": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "vr_index_filter_search_stats": (C.c_int, [_vp, C.POINTER(_i64), _i32]),
     "vr_topk_merge_keys": (C.c_int, [C.c_int, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "vr_resize_bicubic": (C.c_int, [C.c_int, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
     "vr_op_gemm": (C.c_int, [C.c_int, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _f32,

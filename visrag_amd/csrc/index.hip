@@ -9,6 +9,7 @@
 #include "engine_common.h"
 
 constexpr int GRP_STATS = 2, GRP_LIST = 8, GRP_WORDS = GRP_LIST + 256;
+constexpr int FLT_STATS = 2, FLT_LIST = 8, FLT_WORDS = FLT_LIST + 256;
 constexpr int CERT_WORDS = 32, CERT_FLAG = 2, CERT_FLAG2 = 3, CERT_STATS = 4, CERT_NSTATS = 6;   // (the two flag counters are consecutive: cleared together)
 struct vr_index_s {
     int device = 0, dim = 0;
@@ -28,6 +29,11 @@ struct vr_index_s {
     DevBuf goff, gB, og, gstate;      // int first rows [n_groups + 1] | group maxima [256][ldB] | staged out_groups |
                                       // int words: [0] flag count, [1] unused (cleared with it), u32 [2..4] the three counters of
                                       // vr_index_group_search_stats, [GRP_LIST..] flag list of a block of <= 256 queries
+    // filtered search (vr_index_search_filtered, search_filter.hip): state of its own, independent of the grouping
+    int64_t n_filters = 0;            // 0: no filters set (vr_index_add / vr_index_reset drop them)
+    DevBuf fbits, fcount, ffq, fstate;   // u32 [n_filters][ceil(n / 32)] the library's copy | int allowed rows [n_filters] | staged
+                                      // filter_of_query of a host caller | int words laid out as gstate's: [0] flag count, [1] unused,
+                                      // u32 [2..4] the counters of vr_index_filter_search_stats, [FLT_LIST..] flag list of a block
     // per-stage HIP events (vr_index_set_search_profile): convert | thresholds | sweep | merge | exact pass
     bool prof_on = false;
     hipEvent_t prof_ev[SEARCH_PROF_EVENTS] = {};
@@ -58,7 +64,8 @@ extern "C" int vr_index_destroy(vr_index_t ix) {
     (void)hipSetDevice(ix->device);
     (void)hipDeviceSynchronize();
     for (DevBuf* b : {&ix->f32, &ix->bf16, &ix->q32, &ix->qbf, &ix->cs, &ix->ci, &ix->ck, &ix->os, &ix->oi, &ix->ok, &ix->thr,
-                      &ix->sbuf, &ix->cert, &ix->flags, &ix->flagq, &ix->goff, &ix->gB, &ix->og, &ix->gstate})
+                      &ix->sbuf, &ix->cert, &ix->flags, &ix->flagq, &ix->goff, &ix->gB, &ix->og, &ix->gstate,
+                      &ix->fbits, &ix->fcount, &ix->ffq, &ix->fstate})
         b->free();
     for (hipEvent_t e : ix->prof_ev) if (e) (void)hipEventDestroy(e);
     if (ix->huge_seen) (void)hipHostFree(ix->huge_seen);
@@ -73,6 +80,7 @@ extern "C" int vr_index_reset(vr_index_t ix) {
     HIPCHK(hipMemset(ix->cert.p, 0, 8));          // largest row norm, largest rounding residual
     ix->n = 0;
     ix->n_groups = 0;
+    ix->n_filters = 0;
     if (ix->huge_seen) *ix->huge_seen = 0;
     return VR_OK;
 }
@@ -96,6 +104,7 @@ extern "C" int vr_index_add(vr_index_t ix, const float* reps, int64_t n, int32_t
     if (!on_device) HIPCHK(hipStreamSynchronize(s));
     ix->n += n;
     ix->n_groups = 0;                 // the grouping described the rows that were there
+    ix->n_filters = 0;                // ... and so did the filters
     return VR_OK;
 }
 
@@ -479,6 +488,104 @@ extern "C" int vr_index_search_groups(vr_index_t ix, const float* queries, int32
     VRCHK(return_output(out_scores, os, n_out, on_device, s));
     VRCHK(return_output(out_ids, oi, n_out, on_device, s));
     VRCHK(return_output(out_groups, og, n_out, on_device, s));
+    if (!on_device) HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
+}
+
+extern "C" int vr_index_set_filters(vr_index_t ix, const uint32_t* bits, int32_t n_filters, int32_t on_device, void* stream) {
+    if (!ix || !bits) return fail(VR_ERR_INVALID, "NULL argument");
+    if (n_filters < 1) return fail(VR_ERR_INVALID, "%d filters", (int)n_filters);
+    if (ix->n <= 0) return fail(VR_ERR_INVALID, "filters over an empty index");
+    VRCHK(set_dev(ix->device));
+    HIPCHK(hipDeviceSynchronize());               // (a filtered search in flight reads the filters)
+    hipStream_t s = (hipStream_t)stream;
+    const size_t words = (size_t)((ix->n + 31) / 32), total = words * (size_t)n_filters;
+    ix->n_filters = 0;
+    VRCHK(ix->fbits.reserve(total * 4));
+    VRCHK(ix->fcount.reserve((size_t)n_filters * 4));
+    if (!ix->fstate.p) VRCHK(ix->fstate.alloc(FLT_WORDS * 4));
+    HIPCHK(hipMemcpyAsync(ix->fbits.p, bits, total * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    // the caller's bits at or beyond the row count are garbage: cleared in the copy; allowed rows per filter counted once, here
+    HIPCHK(launch_filter_prepare(ix->fbits.as<uint32_t>(), words, n_filters, ix->n, ix->fcount.as<int>(), s));
+    if (!on_device) HIPCHK(hipStreamSynchronize(s));
+    ix->n_filters = n_filters;
+    return VR_OK;
+}
+
+extern "C" int vr_index_filter_search_stats(vr_index_t ix, int64_t* out3, int32_t reset) {
+    if (!ix || !out3) return fail(VR_ERR_INVALID, "NULL argument");
+    out3[0] = out3[1] = out3[2] = 0;
+    if (!ix->fstate.p) return VR_OK;              // no filters were ever set: nothing counted
+    VRCHK(set_dev(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    unsigned w[3];
+    HIPCHK(hipMemcpy(w, ix->fstate.as<unsigned>() + FLT_STATS, sizeof(w), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 3; ++i) out3[i] = w[i];
+    if (reset) HIPCHK(hipMemset(ix->fstate.as<unsigned>() + FLT_STATS, 0, sizeof(w)));
+    return VR_OK;
+}
+
+// The k best rows per query among the rows its filter allows (search_filter.hip).  Scratch (query staging, score rows, staged
+// outputs) is shared with the other searches; filters, flag list and counters are the filtered search's own.
+extern "C" int vr_index_search_filtered(vr_index_t ix, const float* queries, int32_t nq, int32_t k, const int32_t* filter_of_query,
+                                        float* out_scores, int64_t* out_ids, int32_t on_device, void* stream) {
+    if (!ix || !queries || !filter_of_query || !out_scores || !out_ids || nq <= 0) return fail(VR_ERR_INVALID, "bad arguments");
+    if (k <= 0 || k > search_bigk_max()) return fail(VR_ERR_INVALID, "k=%d unsupported (1..%d)", k, search_bigk_max());
+    if (ix->n_filters <= 0 || ix->n <= 0) return fail(VR_ERR_STATE, "no filters set for the rows of the index (vr_index_set_filters)");
+    if (!on_device)
+        for (int32_t q = 0; q < nq; ++q)
+            if (filter_of_query[q] < -1 || filter_of_query[q] >= ix->n_filters)
+                return fail(VR_ERR_INVALID, "filter_of_query[%d] = %d outside [-1, %lld)", (int)q, (int)filter_of_query[q], (long long)ix->n_filters);
+    VRCHK(set_dev(ix->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int dim = ix->dim;
+    const int64_t ldS = pad256l(ix->n);
+    const int64_t qblk = 256;                     // one fp32 score row per query, as on the deep path
+    const int64_t nqp = pad256l(std::min<int64_t>(nq, qblk));
+    const float* q32 = nullptr;
+    VRCHK(stage_queries(ix, queries, nq, nqp, on_device, s, &q32));
+    const int* foq = filter_of_query;
+    if (!on_device) {
+        VRCHK(ix->ffq.reserve((size_t)nq * 4));
+        HIPCHK(hipMemcpyAsync(ix->ffq.p, filter_of_query, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+        foq = ix->ffq.as<int>();
+    }
+    const size_t n_out = (size_t)nq * k;
+    float* os = nullptr; int64_t* oi = nullptr;
+    VRCHK(stage_output(ix->os, out_scores, n_out, on_device, &os));
+    VRCHK(stage_output(ix->oi, out_ids, n_out, on_device, &oi));
+    VRCHK(ix->sbuf.reserve((size_t)qblk * ldS * 4));
+    const bool certify = ix->eps_rel == -2.f || ix->eps_rel >= 0.f;
+    for (int64_t q0 = 0; q0 < nq; q0 += qblk) {
+        const int nb = (int)std::min<int64_t>(qblk, nq - q0);
+        const int64_t nbp = pad256l(nb);
+        // rows >= nb: zeros; also clears the filtered search's flag counter
+        HIPCHK(launch_f32_to_bf16_pad(q32 + (size_t)q0 * dim, ix->qbf.p, (size_t)nb * dim, (size_t)nbp * dim, s, ix->fstate.as<int>()));
+        FilterSearchArgs p{};
+        SearchArgs& a = p.a;
+        a.index_bf16 = ix->bf16.p; a.index_f32 = ix->f32.as<float>(); a.n_docs = ix->n; a.dim = dim;
+        a.q_bf16 = ix->qbf.p; a.q_f32 = q32 + (size_t)q0 * dim; a.nq = nb; a.k = k;
+        fill_error_model(ix, a);
+        a.flag_count = ix->fstate.as<int>(); a.flag_list = ix->fstate.as<int>() + FLT_LIST;
+        a.out_scores = os + (size_t)q0 * k; a.out_ids = oi + (size_t)q0 * k;
+        p.bits = ix->fbits.as<uint32_t>(); p.words = (size_t)((ix->n + 31) / 32); p.n_filters = (int)ix->n_filters;
+        p.allowed = ix->fcount.as<int>();
+        p.filter_of_query = foq + q0;
+        p.stats = ix->fstate.as<unsigned>() + FLT_STATS;
+        p.certify = certify ? 1 : 0;
+        // S[q][row] = queries x index^T on the bf16 MFMA GEMM, the deep path's launch; disallowed columns -> -inf
+        VRCHK(score_rows(ix, ix->qbf.p, nb, nullptr, 0, GEMM_VARIANT_AUTO, ldS, s));
+        HIPCHK(launch_filter_mask(p, ix->sbuf.as<float>(), (size_t)ldS, nb, nullptr, 0, s));
+        HIPCHK(launch_filter_select(p, ix->sbuf.as<float>(), (size_t)ldS, nb, s));
+        if (certify) {
+            // whatever the select flagged (nothing, normally: the three kernels leave at once): exact fp32 score rows, masked
+            HIPCHK(launch_exact_scores(a.index_f32, a.n_docs, dim, a.q_f32, a.flag_list, a.flag_count, 0, nb, ix->sbuf.as<float>(), (size_t)ldS, s));
+            HIPCHK(launch_filter_mask(p, ix->sbuf.as<float>(), (size_t)ldS, nb, a.flag_count, 0, s));
+            HIPCHK(launch_filter_select_exact(p, ix->sbuf.as<float>(), (size_t)ldS, 0, nb, s));
+        }
+    }
+    VRCHK(return_output(out_scores, os, n_out, on_device, s));
+    VRCHK(return_output(out_ids, oi, n_out, on_device, s));
     if (!on_device) HIPCHK(hipStreamSynchronize(s));
     return VR_OK;
 }

@@ -374,5 +374,27 @@ hipError_t launch_group_max(const float* S, size_t ldS, const int* goff, int n_g
 hipError_t launch_group_select(const GroupSearchArgs& p, const float* S, size_t ldS, int nq_block, hipStream_t s);
 // the flagged queries from EXACT score rows / group maxima (slot i = query flag_list[sub + i]): overwrites their outputs
 hipError_t launch_group_select_exact(const GroupSearchArgs& p, const float* S, size_t ldS, int sub, int max_slots, hipStream_t s);
+// ---- filtered search (search_filter.hip): the k best rows per query among the rows its filter allows
+struct FilterSearchArgs {
+    SearchArgs a;                    // the block's view, as for launch_search_bigk: index, queries, k, out_scores / out_ids, the error
+                                     // model, flag_count / flag_list (the filtered search's own); everything else unused
+    const uint32_t* bits;            // [n_filters][words] the library's copy: bit r & 31 of word r >> 5 = row r allowed, bits >= n_docs clear
+    size_t words;                    // (n_docs + 31) / 32
+    int n_filters;
+    const int* allowed;              // [n_filters] allowed rows of every filter
+    const int* filter_of_query;      // [nq] device: the filter of every query of the block, -1 = all rows; an entry outside
+                                     // [-1, n_filters) allows nothing
+    unsigned* stats;                 // [0] certified from the first candidate set [1] after widening it [2] flagged: redone exactly
+    int certify;                     // 0: the first candidate set re-scored, no guarantee, nothing counted
+};
+// the library's copy of the filters as the caller's words arrived: spare bits of the last word cleared, allowed[f] = popcount
+hipError_t launch_filter_prepare(uint32_t* bits, size_t words, int n_filters, int64_t n_rows, int* allowed, hipStream_t s);
+// disallowed columns of score rows [0, n_slots) of S -> -inf (row i = query i of the block; slot_count set: the first
+// *slot_count - sub rows only, row i = query p.a.flag_list[sub + i])
+hipError_t launch_filter_mask(const FilterSearchArgs& p, float* S, size_t ldS, int n_slots, const int* slot_count, int sub,
+                              hipStream_t s);
+hipError_t launch_filter_select(const FilterSearchArgs& p, const float* S, size_t ldS, int nq_block, hipStream_t s);
+// the flagged queries from masked EXACT score rows (slot i = query flag_list[sub + i]): overwrites their outputs
+hipError_t launch_filter_select_exact(const FilterSearchArgs& p, const float* S, size_t ldS, int sub, int max_slots, hipStream_t s);
 
 }  // namespace vr

@@ -5,6 +5,7 @@
                                                                build_index.py:14-58
   * `retrieve(knowledge_base_path, query, topk, ...)` -> paths of the top-k page images
                                                                answer.py:14-40
+    (`documents=[...]`: only the pages of those documents are ranked — HipIndex.search_filtered)
   * `retrieve_documents(knowledge_base_path, query, topk, ...)` -> the best page of each of the top-k DOCUMENTS
                                                                (no reference counterpart: its top-k is pages)
 
@@ -22,7 +23,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from .documents import doc_of_page, group_rows
+from .documents import doc_of_page, group_rows, label_filters
 from .engine import HipIndex
 from .modeling import encode  # noqa: F401  (demo/visrag_pipeline/utils.py:12-32)
 
@@ -90,11 +91,17 @@ def load_knowledge_base(knowledge_base_path: str, device: Optional[int] = None):
 
 @torch.no_grad()
 def retrieve(knowledge_base_path: str, query: str, topk: int, model, tokenizer, index=None, names=None,
-             return_scores: bool = False):
+             return_scores: bool = False, documents=None):
     """answer.py:14-40: paths of the `topk` most similar page images (None if the base does not exist).
-    Pass `index, names = load_knowledge_base(path)` to keep the index resident between questions."""
+    Pass `index, names = load_knowledge_base(path)` to keep the index resident between questions.
+    `documents`: an iterable of document names (the `doc_of_page` of the page names) — only their pages are ranked
+    (HipIndex.search_filtered: the true top-k of those pages, however few they are); a name no page carries contributes
+    nothing, and with no page allowed the result is [].  Works on a `load_knowledge_base` index and on a `load_document_base`
+    one; `query` may then also be the query's embedding ([dim] or [1, dim])."""
     if not os.path.exists(knowledge_base_path):
         return None
+    if documents is not None:
+        return _retrieve_filtered(knowledge_base_path, query, topk, model, tokenizer, index, names, return_scores, documents)
     own = index is None
     if own:
         index, names = load_knowledge_base(knowledge_base_path, model.encoder.device)
@@ -105,6 +112,31 @@ def retrieve(knowledge_base_path: str, query: str, topk: int, model, tokenizer, 
     keep = [int(i) for i in ids[0] if i >= 0]
     paths = [os.path.join(knowledge_base_path, names[i]) for i in keep]
     return (paths, [float(s) for s in sc[0][: len(keep)]]) if return_scores else paths
+
+
+def _retrieve_filtered(knowledge_base_path, query, topk, model, tokenizer, index, names, return_scores, documents):
+    """retrieve() among the pages of `documents`: one filter, set for this question (it replaces the index's filters)"""
+    own = index is None
+    if own:
+        index, names = load_knowledge_base(knowledge_base_path, model.encoder.device if model is not None else None)
+    n = len(index)
+    mask = label_filters([doc_of_page(nm) for nm in names[:n]], [documents])
+    if isinstance(query, str):
+        q = encode(model, tokenizer, [QUERY_INSTRUCTION + query])
+    else:
+        q = np.asarray(query.detach().cpu() if isinstance(query, torch.Tensor) else query, dtype=np.float32).reshape(1, -1)
+    allowed = int(mask.sum())
+    if allowed == 0 or topk <= 0:
+        paths, scores = [], []
+    else:
+        index.set_filters(mask)
+        sc, ids = index.search_filtered(q, min(topk, allowed), 0)
+        keep = [int(i) for i in ids[0] if i >= 0]
+        paths = [os.path.join(knowledge_base_path, names[i]) for i in keep]
+        scores = [float(s) for s in sc[0][: len(keep)]]
+    if own:
+        index.close()
+    return (paths, scores) if return_scores else paths
 
 
 def load_document_base(knowledge_base_path: str, device: Optional[int] = None):

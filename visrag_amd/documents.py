@@ -2,11 +2,15 @@
 
 The index ranks rows (pages); a corpus is usually documents embedded page after page.  `search_groups` wants every document
 to be ONE run of adjacent rows.  `group_rows` turns per-row labels into that layout, `doc_of_page` is the label rule of the demo's
-knowledge base (`<pdf>_<idx>.png`).  Pure numpy: nothing here touches the GPU.
+knowledge base (`<pdf>_<idx>.png`).
+
+The filtered search (HipIndex.set_filters / search_filtered) ranks inside a subset of the rows: `pack_filters` is the bit layout
+the library takes, `group_filter` allows the rows of some groups, `label_filters` the rows whose label is in a wanted set.
+Pure numpy: nothing here touches the GPU.
 """
 from __future__ import annotations
 
-from typing import Hashable, List, Sequence, Tuple
+from typing import Hashable, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -39,3 +43,39 @@ def doc_of_page(name: str) -> str:
     underscore (`my_report.pdf_12.png` -> `my_report.pdf`); a name without an underscore is its own document."""
     head, sep, _ = name.rpartition("_")
     return head if sep else name
+
+
+def pack_filters(masks) -> np.ndarray:
+    """bool [n_filters][rows] (or [rows]: one filter) -> uint32 [n_filters][ceil(rows / 32)]: row r is bit r & 31 of word r >> 5,
+    the spare bits of the last word are 0 — what `HipIndex.set_filters` hands to the library."""
+    m = np.atleast_2d(np.asarray(masks, dtype=bool))
+    nf, n = m.shape
+    words = (n + 31) // 32
+    padded = np.zeros((nf, words * 32), dtype=bool)
+    padded[:, :n] = m
+    return np.ascontiguousarray(np.packbits(padded, axis=1, bitorder="little")).view("<u4").astype(np.uint32).reshape(nf, words)
+
+
+def group_filter(offsets, groups: Iterable[int]) -> np.ndarray:
+    """bool [rows]: exactly the rows of the listed groups of `offsets` (group g = rows offsets[g] .. offsets[g + 1] - 1)."""
+    off = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    out = np.zeros(int(off[-1]), dtype=bool)
+    for g in groups:
+        g = int(g)
+        if not 0 <= g < len(off) - 1:
+            raise ValueError(f"group {g} outside [0, {len(off) - 1})")
+        out[off[g]:off[g + 1]] = True
+    return out
+
+
+def label_filters(labels: Sequence[Hashable], wanted_sets: Sequence[Optional[Iterable[Hashable]]]) -> np.ndarray:
+    """bool [len(wanted_sets)][rows]: filter j allows the rows whose label is in wanted_sets[j] (None: every row).  A wanted
+    label that no row carries allows nothing."""
+    out = np.zeros((len(wanted_sets), len(labels)), dtype=bool)
+    for j, wanted in enumerate(wanted_sets):
+        if wanted is None:
+            out[j] = True
+            continue
+        w = set(wanted)
+        out[j] = [lab in w for lab in labels]
+    return out

@@ -241,6 +241,7 @@ class HipIndex:
         _lib.check(self.lib.vr_index_create(self.device, self.dim, self.capacity, C.byref(self._h)),
                    "vr_index_create")
         self.n_groups = 0          # groups set for the rows present (set_groups); add / reset drop them
+        self.n_filters = 0         # filters set for the rows present (set_filters); add / reset drop them
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -261,9 +262,11 @@ class HipIndex:
     def reset(self) -> None:
         _lib.check(self.lib.vr_index_reset(self._h))
         self.n_groups = 0
+        self.n_filters = 0
 
     def add(self, reps) -> None:
         self.n_groups = 0
+        self.n_filters = 0
         if isinstance(reps, torch.Tensor):
             t = reps.to(torch.float32).contiguous()
             assert t.dim() == 2 and t.shape[1] == self.dim
@@ -314,6 +317,75 @@ class HipIndex:
         redone from exact fp32 scores of every row."""
         out = (C.c_int64 * 3)()
         _lib.check(self.lib.vr_index_group_search_stats(self._h, out, 1 if reset else 0))
+        return {"certified": int(out[0]), "certified_widened": int(out[1]), "exact": int(out[2])}
+
+    def set_filters(self, masks) -> None:
+        """Row filters for `search_filtered` over the rows present: `masks` is bool [n_filters][len(self)] (True = the row is
+        allowed) or already packed uint32 [n_filters][ceil(len(self) / 32)] (documents.pack_filters: bit r & 31 of word r >> 5;
+        bits beyond the last row are ignored), numpy or torch, host or cuda — a cuda tensor is packed and handed over on the
+        device.  The library keeps its own copy.  `add` and `reset` drop the filters; filters and groups are independent."""
+        n, words = len(self), (len(self) + 31) // 32
+        if isinstance(masks, torch.Tensor) and masks.is_cuda:
+            m = masks
+            if m.dtype == torch.bool:
+                if m.dim() != 2 or m.shape[1] != n:
+                    raise ValueError(f"bool masks must be [n_filters][{n}]")
+                m = torch.nn.functional.pad(m, (0, words * 32 - n)).reshape(m.shape[0], words, 32).to(torch.int64)
+                m = (m << torch.arange(32, device=m.device)).sum(-1)                 # 0 .. 2^32 - 1: the word's value
+                m = torch.where(m >= 2 ** 31, m - 2 ** 32, m).to(torch.int32)        # ... as the int32 of the same bits
+            elif m.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+                raise ValueError("cuda masks must be bool, or packed words as int32 / uint32")
+            m = m.contiguous()
+            if m.dim() != 2 or m.shape[1] != words:
+                raise ValueError(f"packed masks must be [n_filters][{words}]")
+            ptr, nf, dev = m.data_ptr(), m.shape[0], 1
+        else:
+            from .documents import pack_filters
+            m = np.asarray(masks.numpy() if isinstance(masks, torch.Tensor) else masks)
+            m = pack_filters(m) if m.dtype == np.bool_ and m.ndim == 2 and m.shape[1] == n else m
+            if m.dtype == np.int32:
+                m = m.view(np.uint32)
+            if m.dtype != np.uint32 or m.ndim != 2 or m.shape[1] != words:
+                raise ValueError(f"masks must be bool [n_filters][{n}] or packed uint32 [n_filters][{words}]")
+            m = np.ascontiguousarray(m)
+            ptr, nf, dev = m.ctypes.data, m.shape[0], 0
+        _lib.check(self.lib.vr_index_set_filters(self._h, C.c_void_p(ptr), nf, dev, C.c_void_p(_stream_ptr(self.device))),
+                   "vr_index_set_filters")
+        self.n_filters = int(nf)
+
+    def search_filtered(self, queries, k: int, filter_of_query=None):
+        """The k best rows per query among the rows its filter allows (include/visrag_hip.h: vr_index_search_filtered)
+        -> (scores [nq,k] f32, ids [nq,k] i64), tail (-inf, -1) where fewer than k rows are allowed; cuda in -> cuda out, numpy / cpu
+        in -> numpy out.  `filter_of_query`: one filter index per query (any int sequence or tensor), an int = that filter for
+        every query, None or -1 = no filter (all rows).  Entries outside [-1, n_filters) raise ValueError."""
+        nq = int(queries.shape[0])
+        if filter_of_query is None:
+            filter_of_query = -1
+        if isinstance(filter_of_query, (int, np.integer)):
+            fq = np.full(nq, int(filter_of_query), dtype=np.int64)
+        elif isinstance(filter_of_query, torch.Tensor):
+            fq = filter_of_query.detach().cpu().numpy().astype(np.int64).reshape(-1)
+        else:
+            fq = np.asarray(filter_of_query, dtype=np.int64).reshape(-1)
+        if len(fq) != nq:
+            raise ValueError(f"{len(fq)} filter_of_query entries for {nq} queries")
+        if self.n_filters and ((fq < -1) | (fq >= self.n_filters)).any():
+            raise ValueError(f"filter_of_query entries must lie in [-1, {self.n_filters})")
+        fq = np.ascontiguousarray(fq, dtype=np.int32)
+        cuda = isinstance(queries, torch.Tensor) and queries.is_cuda
+        keep = torch.from_numpy(fq).to(queries.device) if cuda else fq
+        fptr = C.c_void_p(keep.data_ptr() if cuda else keep.ctypes.data)
+
+        def fn(h, q, n, kk, out_scores, out_ids, on_device, stream):
+            return self.lib.vr_index_search_filtered(h, q, n, kk, fptr, out_scores, out_ids, on_device, stream)
+
+        return self._search(fn, "vr_index_search_filtered", queries, k, 1)
+
+    def filter_search_stats(self, reset: bool = False) -> Dict[str, int]:
+        """Filtered-search queries since the last reset by outcome: certified from the first candidate set (or no row allowed) /
+        after widening it / redone from exact fp32 scores of every row."""
+        out = (C.c_int64 * 3)()
+        _lib.check(self.lib.vr_index_filter_search_stats(self._h, out, 1 if reset else 0))
         return {"certified": int(out[0]), "certified_widened": int(out[1]), "exact": int(out[2])}
 
     def search_keys(self, queries: torch.Tensor, k: int, id_offset: int = 0) -> torch.Tensor:

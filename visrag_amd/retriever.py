@@ -32,7 +32,7 @@ from typing import Callable, Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
-from .documents import group_rows
+from .documents import group_rows, label_filters
 from .engine import HipIndex, topk_merge_keys
 from .utils import list_shards, read_shard, shard_rank
 
@@ -181,6 +181,51 @@ def retrieve_documents(args, topk: int, doc_of: Callable[[str], str], index_fact
                 scores[q][docs[int(g)]] = float(s)
                 pages[q][docs[int(g)]] = page_ids[int(order[int(r)])]
     return scores, pages
+
+
+def retrieve_filtered(args, topk: int, label_of: Callable[[str], object], labels_of_query: Callable[[str], Optional[set]],
+                      index_factory: Optional[Callable] = None) -> Dict[str, Dict[str, float]]:
+    """Retrieval inside a subset of the corpus, over the same pickle shards: this rank's query shard(s) against ALL corpus
+    shards in ONE index, query `qid` ranked only against the rows whose `label_of(docid)` is in `labels_of_query(qid)` (None =
+    every row) — a dataset, a tenant, a few documents.  -> {qid: {docid: score}}: the `topk` best ALLOWED rows per query
+    (HipIndex.search_filtered: the fp32 ranking inside the subset, fewer entries when fewer rows are allowed); it goes to
+    `save_as_trec` as it is.  One filter is built per distinct label set.
+
+    Replicated form only, like retrieve_documents: every rank holds the whole corpus."""
+    make_index = index_factory or HipIndex
+    queries, qids, _ = _load_queries(args)
+    corpus_parts = list_shards(args.output_dir, "corpus")
+    if len(corpus_parts) == 0:
+        raise ValueError("No pre-computed document embeddings found")
+    reps, doc_ids = [], []
+    for p in corpus_parts:
+        r, i = read_shard(p)
+        if len(i):
+            reps.append(np.asarray(r, dtype=np.float32))
+            doc_ids.extend(i)
+    result: Dict[str, Dict[str, float]] = {q: {} for q in qids}
+    if not doc_ids or topk <= 0:
+        return result
+    sets: List[Optional[frozenset]] = []
+    which: Dict[Optional[frozenset], int] = {}
+    filter_of_query = np.empty(len(qids), dtype=np.int32)
+    for qi, q in enumerate(qids):
+        wanted = labels_of_query(q)
+        key = None if wanted is None else frozenset(wanted)
+        if key not in which:
+            which[key] = len(sets)
+            sets.append(key)
+        filter_of_query[qi] = which[key]
+    ix = make_index(queries.shape[1], len(doc_ids), _device_index(args))
+    ix.add(np.concatenate(reps))
+    ix.set_filters(label_filters([label_of(i) for i in doc_ids], sets))
+    sc, rows = ix.search_filtered(queries, min(topk, len(doc_ids)), filter_of_query)
+    ix.close()
+    for qi, q in enumerate(qids):
+        for s, r in zip(sc[qi], rows[qi]):
+            if r >= 0:
+                result[q][doc_ids[int(r)]] = float(s)
+    return result
 
 
 def _retrieve_corpus_sharded(args, topk: int, global_topk: bool, make_index: Callable, merge_keys: Optional[Callable]
