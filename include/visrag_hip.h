@@ -368,6 +368,31 @@ int vr_index_search_filtered(vr_index_t ix, const float* queries, int32_t nq, in
 /* Filtered-search queries since the last reset: out3 = {certified from the first candidate set (a query with no
  * allowed row included), certified after widening it, redone exactly}. */
 int vr_index_filter_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
+/* ---- diversified search: k rows picked by maximal marginal relevance (MMR) from a pool of the best rows ---- */
+/* For every query, k rows that are relevant AND unlike each other — what a caller wants who hands the k pages to a
+ * generator, where near-duplicate pages (one slide template across many decks) spend its context on one page.
+ *   1. The pool is the first `pool` rows of the fp32 ranking: exactly what vr_index_search(k = pool) returns, or with
+ *      filter_of_query (as for vr_index_search_filtered; NULL = no filter for any query) exactly what
+ *      vr_index_search_filtered(k = pool) returns — produced by those code paths as they stand, and so certified as they
+ *      are.  The (-inf, -1) tail entries are not members; P' = the number of members.  Pool position = rank in that
+ *      result: higher fp32 score first, lower row id among equal scores.
+ *   2. Pick 0 is pool position 0.
+ *   3. Pick t >= 1 is the unselected member i that maximises
+ *          v_i = lambda r_i - (1 - lambda) max_{j selected} <d_i, d_j>
+ *      with r_i the member's fp32 score as the search returned it and <d_i, d_j> the fp32 dot product of the index's fp32
+ *      rows (unit rows: their cosine, the measure the index ranks by), computed like every score the library returns and
+ *      never in bf16.  Among equal v the lower pool position wins; bit-identical rows have bit-identical v.
+ *   4. out_ids [nq][k] int64 = the picks in pick order, out_scores [nq][k] float32 = their r_i — the relevance, not
+ *      monotone in general (all host or all device per `on_device`).  With P' < k the tail is (-inf, -1).
+ * lambda = 1 gives the first k of the pool; lambda = 0 only avoids what was picked.
+ * 1 <= k <= pool <= 1000, 0 <= lambda <= 1 (NaN refused) and the dim limits of the deep path of vr_index_search: anything
+ * else is VR_ERR_INVALID before any launch, the outputs untouched.  A HOST filter_of_query entry outside [-1, n_filters):
+ * VR_ERR_INVALID likewise; filter_of_query given while no filters are set for the rows present: VR_ERR_STATE.
+ * The pool stage IS the plain or the filtered search and counts in that search's statistics; the MMR stage keeps no
+ * counters and leaves every state the other searches read alone.  Work: (k - 1) P' fp32 row dots per query. */
+int vr_index_search_diverse(vr_index_t ix, const float* queries, int32_t nq, int32_t k, int32_t pool, float lambda,
+                            const int32_t* filter_of_query /* NULL: no filter for any query */,
+                            float* out_scores, int64_t* out_ids, int32_t on_device, void* stream);
 /* Merge per-shard results (e.g. after an RCCL all-gather): in [n_parts][nq][k] scores and
  * global ids -> out [nq][k], same ordering rule.  Device pointers. */
 int vr_topk_merge(int device_id, const float* scores, const int64_t* ids, int32_t n_parts,

@@ -34,6 +34,9 @@ struct vr_index_s {
     DevBuf fbits, fcount, ffq, fstate;   // u32 [n_filters][ceil(n / 32)] the library's copy | int allowed rows [n_filters] | staged
                                       // filter_of_query of a host caller | int words laid out as gstate's: [0] flag count, [1] unused,
                                       // u32 [2..4] the counters of vr_index_filter_search_stats, [FLT_LIST..] flag list of a block
+    // diversified search (vr_index_search_diverse, search_diverse.hip): its pool — the result of the plain or the filtered search for
+    // k = pool — in buffers of its own, because that very search overwrites the shared scratch
+    DevBuf dps, dpi;                  // f32 pool scores [nq][pool] | int64 pool ids [nq][pool]
     // per-stage HIP events (vr_index_set_search_profile): convert | thresholds | sweep | merge | exact pass
     bool prof_on = false;
     hipEvent_t prof_ev[SEARCH_PROF_EVENTS] = {};
@@ -65,7 +68,7 @@ extern "C" int vr_index_destroy(vr_index_t ix) {
     (void)hipDeviceSynchronize();
     for (DevBuf* b : {&ix->f32, &ix->bf16, &ix->q32, &ix->qbf, &ix->cs, &ix->ci, &ix->ck, &ix->os, &ix->oi, &ix->ok, &ix->thr,
                       &ix->sbuf, &ix->cert, &ix->flags, &ix->flagq, &ix->goff, &ix->gB, &ix->og, &ix->gstate,
-                      &ix->fbits, &ix->fcount, &ix->ffq, &ix->fstate})
+                      &ix->fbits, &ix->fcount, &ix->ffq, &ix->fstate, &ix->dps, &ix->dpi})
         b->free();
     for (hipEvent_t e : ix->prof_ev) if (e) (void)hipEventDestroy(e);
     if (ix->huge_seen) (void)hipHostFree(ix->huge_seen);
@@ -584,6 +587,56 @@ extern "C" int vr_index_search_filtered(vr_index_t ix, const float* queries, int
             HIPCHK(launch_filter_select_exact(p, ix->sbuf.as<float>(), (size_t)ldS, 0, nb, s));
         }
     }
+    VRCHK(return_output(out_scores, os, n_out, on_device, s));
+    VRCHK(return_output(out_ids, oi, n_out, on_device, s));
+    if (!on_device) HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
+}
+
+// k rows per query picked by maximal marginal relevance from the pool of its `pool` best rows (search_diverse.hip).  The pool
+// is the plain or the filtered search's own result, produced by that search as it stands on the staged queries with device
+// outputs of the diverse search's own; the selection kernel writes the (staged) outputs.  No state of its own but the pool.
+extern "C" int vr_index_search_diverse(vr_index_t ix, const float* queries, int32_t nq, int32_t k, int32_t pool, float lambda,
+                                       const int32_t* filter_of_query, float* out_scores, int64_t* out_ids, int32_t on_device,
+                                       void* stream) {
+    if (!ix || !queries || !out_scores || !out_ids || nq <= 0) return fail(VR_ERR_INVALID, "bad arguments");
+    if (k < 1 || k > pool || pool > search_bigk_max())
+        return fail(VR_ERR_INVALID, "k=%d pool=%d unsupported (1 <= k <= pool <= %d)", k, pool, search_bigk_max());
+    if (!(lambda >= 0.f && lambda <= 1.f)) return fail(VR_ERR_INVALID, "lambda=%g outside [0, 1]", (double)lambda);
+    if (!mmr_dim_ok(ix->dim)) return fail(VR_ERR_INVALID, "dim %d unsupported", ix->dim);
+    if (filter_of_query) {
+        if (ix->n_filters <= 0 || ix->n <= 0) return fail(VR_ERR_STATE, "no filters set for the rows of the index (vr_index_set_filters)");
+        if (!on_device)
+            for (int32_t q = 0; q < nq; ++q)
+                if (filter_of_query[q] < -1 || filter_of_query[q] >= ix->n_filters)
+                    return fail(VR_ERR_INVALID, "filter_of_query[%d] = %d outside [-1, %lld)", (int)q, (int)filter_of_query[q], (long long)ix->n_filters);
+    }
+    VRCHK(set_dev(ix->device));
+    hipStream_t s = (hipStream_t)stream;
+    const float* q32 = nullptr;
+    VRCHK(stage_queries(ix, queries, nq, pad256l(std::min<int64_t>(nq, 256)), on_device, s, &q32));
+    const int* foq = filter_of_query;
+    if (foq && !on_device) {
+        VRCHK(ix->ffq.reserve((size_t)nq * 4));
+        HIPCHK(hipMemcpyAsync(ix->ffq.p, filter_of_query, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+        foq = ix->ffq.as<int>();
+    }
+    // ---- the pool: the staged queries are device queries to the search, which then stages nothing and writes the pool buffers
+    const size_t n_pool = (size_t)nq * pool, n_out = (size_t)nq * k;
+    VRCHK(ix->dps.reserve(n_pool * 4));
+    VRCHK(ix->dpi.reserve(n_pool * 8));
+    if (foq) VRCHK(vr_index_search_filtered(ix, q32, nq, pool, foq, ix->dps.as<float>(), ix->dpi.as<int64_t>(), 1, stream));
+    else VRCHK(search_impl(ix, q32, nq, pool, ix->dps.as<float>(), ix->dpi.as<int64_t>(), nullptr, 0, 1, stream));
+    // ---- the picks
+    float* os = nullptr; int64_t* oi = nullptr;
+    VRCHK(stage_output(ix->os, out_scores, n_out, on_device, &os));
+    VRCHK(stage_output(ix->oi, out_ids, n_out, on_device, &oi));
+    MmrArgs m{};
+    m.index_f32 = ix->f32.as<float>(); m.n_docs = ix->n; m.dim = ix->dim;
+    m.pool_scores = ix->dps.as<float>(); m.pool_ids = ix->dpi.as<int64_t>();
+    m.nq = nq; m.pool = pool; m.k = k; m.lambda = lambda;
+    m.out_scores = os; m.out_ids = oi;
+    HIPCHK(launch_mmr_select(m, s));
     VRCHK(return_output(out_scores, os, n_out, on_device, s));
     VRCHK(return_output(out_ids, oi, n_out, on_device, s));
     if (!on_device) HIPCHK(hipStreamSynchronize(s));

@@ -396,5 +396,18 @@ hipError_t launch_filter_mask(const FilterSearchArgs& p, float* S, size_t ldS, i
 hipError_t launch_filter_select(const FilterSearchArgs& p, const float* S, size_t ldS, int nq_block, hipStream_t s);
 // the flagged queries from masked EXACT score rows (slot i = query flag_list[sub + i]): overwrites their outputs
 hipError_t launch_filter_select_exact(const FilterSearchArgs& p, const float* S, size_t ldS, int sub, int max_slots, hipStream_t s);
+// ---- diversified search (search_diverse.hip): k rows per query picked by maximal marginal relevance from a pool of its best rows
+struct MmrArgs {
+    const float* index_f32;          // [n_docs][dim] f32
+    int64_t n_docs;
+    int dim;
+    const float* pool_scores;        // [nq][pool] a search's result for k = pool: fp32 scores, best first ...
+    const int64_t* pool_ids;         // ... and row ids; the (-inf, -1) tail of a query with fewer rows is not part of its pool
+    int nq, pool, k;                 // 1 <= k <= pool <= 1000
+    float lambda;                    // 0..1: weight of the relevance; 1 - lambda weighs the largest dot with a picked row
+    float* out_scores; int64_t* out_ids;               // [nq][k] the picks in pick order, their pool scores; tail (-inf, -1)
+};
+bool mmr_dim_ok(int dim);            // the dim limits of the fp32 re-scoring (search_common.h: dot_lane)
+hipError_t launch_mmr_select(const MmrArgs& p, hipStream_t s);
 
 }  // namespace vr

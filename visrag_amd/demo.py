@@ -91,15 +91,21 @@ def load_knowledge_base(knowledge_base_path: str, device: Optional[int] = None):
 
 @torch.no_grad()
 def retrieve(knowledge_base_path: str, query: str, topk: int, model, tokenizer, index=None, names=None,
-             return_scores: bool = False, documents=None):
+             return_scores: bool = False, documents=None, diverse=None, pool=None):
     """answer.py:14-40: paths of the `topk` most similar page images (None if the base does not exist).
     Pass `index, names = load_knowledge_base(path)` to keep the index resident between questions.
     `documents`: an iterable of document names (the `doc_of_page` of the page names) — only their pages are ranked
     (HipIndex.search_filtered: the true top-k of those pages, however few they are); a name no page carries contributes
     nothing, and with no page allowed the result is [].  Works on a `load_knowledge_base` index and on a `load_document_base`
-    one; `query` may then also be the query's embedding ([dim] or [1, dim])."""
+    one; `query` may then also be the query's embedding ([dim] or [1, dim]).
+    `diverse`: a lambda in [0, 1] — the pages are picked by maximal marginal relevance from the `pool` best ones
+    (HipIndex.search_diverse; `pool=None`: its default) and come in PICK order with their relevance scores, so near-duplicate
+    pages do not fill the generator's context; with `documents` the pool holds only their pages.  `query` may be an embedding."""
     if not os.path.exists(knowledge_base_path):
         return None
+    if diverse is not None:
+        return _retrieve_diverse(knowledge_base_path, query, topk, model, tokenizer, index, names, return_scores, documents,
+                                 float(diverse), pool)
     if documents is not None:
         return _retrieve_filtered(knowledge_base_path, query, topk, model, tokenizer, index, names, return_scores, documents)
     own = index is None
@@ -131,6 +137,34 @@ def _retrieve_filtered(knowledge_base_path, query, topk, model, tokenizer, index
     else:
         index.set_filters(mask)
         sc, ids = index.search_filtered(q, min(topk, allowed), 0)
+        keep = [int(i) for i in ids[0] if i >= 0]
+        paths = [os.path.join(knowledge_base_path, names[i]) for i in keep]
+        scores = [float(s) for s in sc[0][: len(keep)]]
+    if own:
+        index.close()
+    return (paths, scores) if return_scores else paths
+
+
+def _retrieve_diverse(knowledge_base_path, query, topk, model, tokenizer, index, names, return_scores, documents, lam, pool):
+    """retrieve() with MMR picks; `documents` given: among their pages, through one filter set for this question"""
+    own = index is None
+    if own:
+        index, names = load_knowledge_base(knowledge_base_path, model.encoder.device if model is not None else None)
+    n = len(index)
+    if isinstance(query, str):
+        q = encode(model, tokenizer, [QUERY_INSTRUCTION + query])
+    else:
+        q = np.asarray(query.detach().cpu() if isinstance(query, torch.Tensor) else query, dtype=np.float32).reshape(1, -1)
+    mask = None if documents is None else label_filters([doc_of_page(nm) for nm in names[:n]], [documents])
+    rows = n if mask is None else int(mask.sum())
+    k = min(topk, rows)
+    if k <= 0:
+        paths, scores = [], []
+    else:
+        if mask is not None:
+            index.set_filters(mask)
+        sc, ids = index.search_diverse(q, k, None if pool is None else max(int(pool), k), lam, None if mask is None else 0)
+        sc, ids = (x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in (sc, ids))
         keep = [int(i) for i in ids[0] if i >= 0]
         paths = [os.path.join(knowledge_base_path, names[i]) for i in keep]
         scores = [float(s) for s in sc[0][: len(keep)]]

@@ -353,11 +353,8 @@ class HipIndex:
                    "vr_index_set_filters")
         self.n_filters = int(nf)
 
-    def search_filtered(self, queries, k: int, filter_of_query=None):
-        """The k best rows per query among the rows its filter allows (include/visrag_hip.h: vr_index_search_filtered)
-        -> (scores [nq,k] f32, ids [nq,k] i64), tail (-inf, -1) where fewer than k rows are allowed; cuda in -> cuda out, numpy / cpu
-        in -> numpy out.  `filter_of_query`: one filter index per query (any int sequence or tensor), an int = that filter for
-        every query, None or -1 = no filter (all rows).  Entries outside [-1, n_filters) raise ValueError."""
+    def _filter_of_query(self, queries, filter_of_query):
+        """`filter_of_query` of search_filtered / search_diverse as int32 [nq] where the queries live -> (keep-alive, pointer)"""
         nq = int(queries.shape[0])
         if filter_of_query is None:
             filter_of_query = -1
@@ -374,12 +371,35 @@ class HipIndex:
         fq = np.ascontiguousarray(fq, dtype=np.int32)
         cuda = isinstance(queries, torch.Tensor) and queries.is_cuda
         keep = torch.from_numpy(fq).to(queries.device) if cuda else fq
-        fptr = C.c_void_p(keep.data_ptr() if cuda else keep.ctypes.data)
+        return keep, C.c_void_p(keep.data_ptr() if cuda else keep.ctypes.data)
+
+    def search_filtered(self, queries, k: int, filter_of_query=None):
+        """The k best rows per query among the rows its filter allows (include/visrag_hip.h: vr_index_search_filtered)
+        -> (scores [nq,k] f32, ids [nq,k] i64), tail (-inf, -1) where fewer than k rows are allowed; cuda in -> cuda out, numpy / cpu
+        in -> numpy out.  `filter_of_query`: one filter index per query (any int sequence or tensor), an int = that filter for
+        every query, None or -1 = no filter (all rows).  Entries outside [-1, n_filters) raise ValueError."""
+        keep, fptr = self._filter_of_query(queries, filter_of_query)
 
         def fn(h, q, n, kk, out_scores, out_ids, on_device, stream):
             return self.lib.vr_index_search_filtered(h, q, n, kk, fptr, out_scores, out_ids, on_device, stream)
 
         return self._search(fn, "vr_index_search_filtered", queries, k, 1)
+
+    def search_diverse(self, queries, k: int, pool: Optional[int] = None, lambda_: float = 0.5, filter_of_query=None):
+        """k rows per query picked by maximal marginal relevance from the pool of its `pool` best rows (include/visrag_hip.h:
+        vr_index_search_diverse): pick 0 is the best row, every later pick maximises lambda_ * score - (1 - lambda_) * (largest
+        dot product with a row already picked).  -> (scores [nq,k] f32 the picks' relevance, ids [nq,k] i64) in PICK order — the
+        scores are not monotone — tail (-inf, -1) where the pool has fewer than k rows; cuda in -> cuda out, numpy / cpu in ->
+        numpy out.  `pool=None`: min(1000, max(4 * k, 32)).  `filter_of_query` as in `search_filtered`, None = the pool of the
+        plain search (no filters need to be set)."""
+        if pool is None:
+            pool = min(1000, max(4 * k, 32))
+        keep, fptr = (None, C.c_void_p(None)) if filter_of_query is None else self._filter_of_query(queries, filter_of_query)
+
+        def fn(h, q, n, kk, out_scores, out_ids, on_device, stream):
+            return self.lib.vr_index_search_diverse(h, q, n, kk, int(pool), float(lambda_), fptr, out_scores, out_ids, on_device, stream)
+
+        return self._search(fn, "vr_index_search_diverse", queries, k, 1)
 
     def filter_search_stats(self, reset: bool = False) -> Dict[str, int]:
         """Filtered-search queries since the last reset by outcome: certified from the first candidate set (or no row allowed) /
