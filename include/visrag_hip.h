@@ -393,6 +393,53 @@ int vr_index_filter_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
 int vr_index_search_diverse(vr_index_t ix, const float* queries, int32_t nq, int32_t k, int32_t pool, float lambda,
                             const int32_t* filter_of_query /* NULL: no filter for any query */,
                             float* out_scores, int64_t* out_ids, int32_t on_device, void* stream);
+/* ---- range search: every row at or above a score threshold, exact ---- */
+/* For query q the result is the SET of rows i with e_i >= thresholds[q] — with filter_of_query (as for
+ * vr_index_search_filtered; NULL = no filter for any query) only rows the query's filter allows.  e_i is the fp32 dot product
+ * of the fp32 rows, computed by the library's one re-scoring dot product: a row returned both here and by vr_index_search
+ * for the same query carries the same score bits, and the comparison with the threshold is an fp32 compare of that value.
+ * The size of the answer is the answer: nothing is cut at a k.
+ *   Layout: CSR.  out_lims [nq + 1] int64: entries out_lims[q] .. out_lims[q + 1] - 1 are query q's, out_lims[0] = 0,
+ * out_lims[nq] = *total; inside a query the entries are in ASCENDING ROW ID (deterministic, no sort).  queries [nq][dim]
+ * float32, thresholds [nq] float32, filter_of_query [nq] int32 and out_lims are all host or all device per `on_device`;
+ * `total` is always a host pointer.
+ *   Ownership: scores and ids are written to device buffers the library owns; they stay valid until the next range search,
+ * vr_index_reset or vr_index_destroy.  vr_index_range_results copies the first n entries (n <= the last total) to the
+ * caller's arrays (out_scores [n] float32, out_ids [n] int64, host or device per `on_device`); n larger than the last total,
+ * or no range search since the last reset: VR_ERR_STATE.
+ *   Exactness: with b_i the bf16 MFMA score and |b_i - e_i| <= eps (the error model of vr_index_set_search_eps) every row
+ * with e_i >= t has b_i >= t - eps.  The bf16 scores of all rows are computed, disallowed ones set to -inf, exactly the rows
+ * with b_i >= t - eps (the bound lowered by one ulp) are re-scored in fp32 and those with e_i >= t kept: the fp32 answer, with
+ * no candidate margin, no widening and no flagged query; a query costs what its band holds.  A range search always uses a
+ * valid model: with certification off (eps_rel < 0) the default data-dependent bound, so the result is exact in every
+ * setting.  Columns at or past the row count are never looked at.
+ *   Checks, all before any launch, the outputs and the previous result untouched: NULL pointers, nq < 1, max_total < 1 or a
+ * dim outside the limits of the deep path of vr_index_search: VR_ERR_INVALID; a HOST threshold that is NaN or +-inf:
+ * VR_ERR_INVALID (a caller that wants every row passes a finite threshold below every score); a HOST filter_of_query entry
+ * outside [-1, n_filters): VR_ERR_INVALID; filter_of_query given while no filters are set for the rows present:
+ * VR_ERR_STATE.  On the device such values cannot be seen before the launch: a non-finite threshold or an out-of-range
+ * filter yields an empty segment, and nothing outside the library's buffers is read.  An empty index: all-zero lims and
+ * total 0 without a launch.
+ *   Capacity: if the running total would exceed max_total the call returns VR_ERR_CAPACITY (the text names the first block of
+ * 256 queries that overran); the previous result is gone — vr_index_range_results then returns VR_ERR_STATE — and nothing
+ * else of the index changes but the range search's own counters, which have counted the blocks that ran.
+ *   The call synchronises the stream, because the sizes of its result are host values: once per block of 256 queries and
+ * once at the end.  It leaves every state the other searches read alone and counts in none of their statistics.
+ * Not offered: sorted output (sort a segment by score on the caller's side: the Python wrapper does), groups (a thresholded
+ * document search is vr_index_search_groups plus a cut), an exact count without the rows, corpus-sharded ranks (a range
+ * result over shards is the union of the shards' results). */
+int vr_index_search_range(vr_index_t ix, const float* queries, int32_t nq,
+                          const float* thresholds,          /* [nq] */
+                          const int32_t* filter_of_query,   /* NULL: no filter for any query */
+                          int64_t max_total,
+                          int64_t* out_lims,                /* [nq + 1] */
+                          int64_t* total,                   /* host */
+                          int32_t on_device, void* stream);
+int vr_index_range_results(vr_index_t ix, float* out_scores, int64_t* out_ids, int64_t n,
+                           int32_t on_device, void* stream);
+/* Range searches since the last reset: out3 = {queries, candidate rows re-scored in fp32, rows returned} — 64-bit counters
+ * in device memory. */
+int vr_index_range_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
 /* Merge per-shard results (e.g. after an RCCL all-gather): in [n_parts][nq][k] scores and
  * global ids -> out [nq][k], same ordering rule.  Device pointers. */
 int vr_topk_merge(int device_id, const float* scores, const int64_t* ids, int32_t n_parts,

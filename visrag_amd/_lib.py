@@ -109,6 +109,9 @@ SIGNATURES = {
     "vr_index_set_filters": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
     "vr_index_search_filtered": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
     "vr_index_filter_search_stats": (C.c_int, [_vp, C.POINTER(_i64), _i32]),
+    "vr_index_search_range": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i64, _vp, C.POINTER(_i64), _i32, _vp]),
+    "vr_index_range_results": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp]),
+    "vr_index_range_search_stats": (C.c_int, [_vp, C.POINTER(_i64), _i32]),
     "vr_index_search_diverse": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _i32, _vp]),
     "vr_topk_merge_keys": (C.c_int, [C.c_int, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "vr_resize_bicubic": (C.c_int, [C.c_int, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),

@@ -37,6 +37,13 @@ struct vr_index_s {
     // diversified search (vr_index_search_diverse, search_diverse.hip): its pool — the result of the plain or the filtered search for
     // k = pool — in buffers of its own, because that very search overwrites the shared scratch
     DevBuf dps, dpi;                  // f32 pool scores [nq][pool] | int64 pool ids [nq][pool]
+    // range search (vr_index_search_range, search_range.hip): its result and state of its own — no other search reads any of it
+    DevBuf rs, ri;                    // the result: f32 scores [rcap] | int64 row ids [rcap], valid entries [0, range_total)
+    int64_t rcap = 0, range_total = -1;   // -1: no result (none yet, vr_index_reset, or the last range search failed)
+    DevBuf rthr, rlims, rcnt, roff, rstate;   // staged thresholds / lims of a host caller | int rows kept [256][slots] | int their
+                                      // exclusive scan per query | u64 words: [0..2] the counters of vr_index_range_search_stats, [3] a block's
+                                      // total, [4..] never written: the flag words launch_filter_mask's argument check wants to see
+    int64_t* range_host = nullptr;    // pinned host word: the block total as the host reads it
     // per-stage HIP events (vr_index_set_search_profile): convert | thresholds | sweep | merge | exact pass
     bool prof_on = false;
     hipEvent_t prof_ev[SEARCH_PROF_EVENTS] = {};
@@ -68,8 +75,10 @@ extern "C" int vr_index_destroy(vr_index_t ix) {
     (void)hipDeviceSynchronize();
     for (DevBuf* b : {&ix->f32, &ix->bf16, &ix->q32, &ix->qbf, &ix->cs, &ix->ci, &ix->ck, &ix->os, &ix->oi, &ix->ok, &ix->thr,
                       &ix->sbuf, &ix->cert, &ix->flags, &ix->flagq, &ix->goff, &ix->gB, &ix->og, &ix->gstate,
-                      &ix->fbits, &ix->fcount, &ix->ffq, &ix->fstate, &ix->dps, &ix->dpi})
+                      &ix->fbits, &ix->fcount, &ix->ffq, &ix->fstate, &ix->dps, &ix->dpi, &ix->rs, &ix->ri, &ix->rthr, &ix->rlims,
+                      &ix->rcnt, &ix->roff, &ix->rstate})
         b->free();
+    if (ix->range_host) (void)hipHostFree(ix->range_host);
     for (hipEvent_t e : ix->prof_ev) if (e) (void)hipEventDestroy(e);
     if (ix->huge_seen) (void)hipHostFree(ix->huge_seen);
     delete ix;
@@ -84,6 +93,7 @@ extern "C" int vr_index_reset(vr_index_t ix) {
     ix->n = 0;
     ix->n_groups = 0;
     ix->n_filters = 0;
+    ix->range_total = -1;
     if (ix->huge_seen) *ix->huge_seen = 0;
     return VR_OK;
 }
@@ -589,6 +599,168 @@ extern "C" int vr_index_search_filtered(vr_index_t ix, const float* queries, int
     }
     VRCHK(return_output(out_scores, os, n_out, on_device, s));
     VRCHK(return_output(out_ids, oi, n_out, on_device, s));
+    if (!on_device) HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
+}
+
+constexpr int RNG_TOTAL = 3, RNG_SPARE = 4, RNG_WORDS = 16;
+
+extern "C" int vr_index_range_search_stats(vr_index_t ix, int64_t* out3, int32_t reset) {
+    if (!ix || !out3) return fail(VR_ERR_INVALID, "NULL argument");
+    out3[0] = out3[1] = out3[2] = 0;
+    if (!ix->rstate.p) return VR_OK;              // no range search ever ran: nothing counted
+    VRCHK(set_dev(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    unsigned long long w[3];
+    HIPCHK(hipMemcpy(w, ix->rstate.p, sizeof(w), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 3; ++i) out3[i] = (int64_t)w[i];
+    if (reset) HIPCHK(hipMemset(ix->rstate.p, 0, sizeof(w)));
+    return VR_OK;
+}
+
+// room for `need` entries of the range result, the first `keep` of which are kept (what earlier blocks of the call packed)
+static int range_reserve(vr_index_t ix, int64_t need, int64_t keep, int64_t max_total, hipStream_t s) {
+    if (need <= ix->rcap && ix->rs.p && ix->ri.p) return VR_OK;
+    const int64_t cap = std::max<int64_t>(std::min(max_total, std::max(need, 2 * ix->rcap)), std::max<int64_t>(need, 1));
+    DevBuf ns, ni;
+    VRCHK(ns.reserve((size_t)cap * 4));
+    VRCHK(ni.reserve((size_t)cap * 8));
+    if (keep > 0) {
+        HIPCHK(hipMemcpyAsync(ns.p, ix->rs.p, (size_t)keep * 4, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(ni.p, ix->ri.p, (size_t)keep * 8, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    ix->rs = std::move(ns);
+    ix->ri = std::move(ni);
+    ix->rcap = cap;
+    return VR_OK;
+}
+
+// Every row at or above a query's threshold (search_range.hip).  Scratch (query staging, score rows, the staged filter_of_query)
+// is shared with the other searches; result, counts, offsets and counters are the range search's own.
+extern "C" int vr_index_search_range(vr_index_t ix, const float* queries, int32_t nq, const float* thresholds,
+                                     const int32_t* filter_of_query, int64_t max_total, int64_t* out_lims, int64_t* total,
+                                     int32_t on_device, void* stream) {
+    if (!ix || !queries || !thresholds || !out_lims || !total || nq < 1) return fail(VR_ERR_INVALID, "bad arguments");
+    if (max_total < 1) return fail(VR_ERR_INVALID, "max_total=%lld must be at least 1", (long long)max_total);
+    if (!range_dim_ok(ix->dim)) return fail(VR_ERR_INVALID, "dim %d unsupported", ix->dim);
+    if (!on_device)
+        for (int32_t q = 0; q < nq; ++q)
+            if (!std::isfinite(thresholds[q])) return fail(VR_ERR_INVALID, "thresholds[%d] = %g is not finite", (int)q, (double)thresholds[q]);
+    if (filter_of_query) {
+        if (ix->n_filters <= 0 || ix->n <= 0) return fail(VR_ERR_STATE, "no filters set for the rows of the index (vr_index_set_filters)");
+        if (!on_device)
+            for (int32_t q = 0; q < nq; ++q)
+                if (filter_of_query[q] < -1 || filter_of_query[q] >= ix->n_filters)
+                    return fail(VR_ERR_INVALID, "filter_of_query[%d] = %d outside [-1, %lld)", (int)q, (int)filter_of_query[q], (long long)ix->n_filters);
+    }
+    VRCHK(set_dev(ix->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (ix->n == 0) {                             // no row: no launch
+        if (on_device) {
+            HIPCHK(hipMemsetAsync(out_lims, 0, ((size_t)nq + 1) * 8, s));
+            HIPCHK(hipStreamSynchronize(s));
+        } else {
+            std::fill(out_lims, out_lims + nq + 1, (int64_t)0);
+        }
+        *total = 0;
+        ix->range_total = 0;
+        return VR_OK;
+    }
+    if (!ix->rstate.p) VRCHK(ix->rstate.alloc(RNG_WORDS * 8));
+    if (!ix->range_host && hipHostMalloc((void**)&ix->range_host, 64, hipHostMallocDefault) != hipSuccess) {
+        ix->range_host = nullptr;
+        return fail(VR_ERR_HIP, "hipHostMalloc");
+    }
+    ix->range_total = -1;                         // from here on the previous result is gone
+    const int dim = ix->dim;
+    const int64_t ldS = pad256l(ix->n), slots = range_scan_slots(ix->n);
+    const int64_t qblk = 256;                     // one fp32 score row per query, as on the deep path
+    const float* q32 = nullptr;
+    VRCHK(stage_queries(ix, queries, nq, pad256l(std::min<int64_t>(nq, qblk)), on_device, s, &q32));
+    const float* thr = thresholds;
+    const int* foq = filter_of_query;
+    int64_t* lims = out_lims;
+    if (!on_device) {
+        VRCHK(ix->rthr.reserve((size_t)nq * 4));
+        HIPCHK(hipMemcpyAsync(ix->rthr.p, thresholds, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+        thr = ix->rthr.as<float>();
+        if (foq) {
+            VRCHK(ix->ffq.reserve((size_t)nq * 4));
+            HIPCHK(hipMemcpyAsync(ix->ffq.p, filter_of_query, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+            foq = ix->ffq.as<int>();
+        }
+        VRCHK(ix->rlims.reserve(((size_t)nq + 1) * 8));
+        lims = ix->rlims.as<int64_t>();
+    }
+    VRCHK(ix->sbuf.reserve((size_t)qblk * ldS * 4));
+    VRCHK(ix->rcnt.reserve((size_t)qblk * slots * 4));
+    VRCHK(ix->roff.reserve((size_t)qblk * slots * 4));
+    VRCHK(range_reserve(ix, std::min<int64_t>(max_total, 65536), 0, max_total, s));
+    unsigned long long* words = ix->rstate.as<unsigned long long>();
+    const bool certify = ix->eps_rel == -2.f || ix->eps_rel >= 0.f;
+    int64_t base = 0;
+    for (int64_t q0 = 0; q0 < nq; q0 += qblk) {
+        const int nb = (int)std::min<int64_t>(qblk, nq - q0);
+        const int64_t nbp = pad256l(nb);
+        HIPCHK(launch_f32_to_bf16_pad(q32 + (size_t)q0 * dim, ix->qbf.p, (size_t)nb * dim, (size_t)nbp * dim, s));   // rows >= nb: zeros
+        RangeSearchArgs p{};
+        SearchArgs& a = p.a;
+        a.index_bf16 = ix->bf16.p; a.index_f32 = ix->f32.as<float>(); a.n_docs = ix->n; a.dim = dim;
+        a.q_bf16 = ix->qbf.p; a.q_f32 = q32 + (size_t)q0 * dim; a.nq = nb; a.k = 1;
+        // the band is defined by the error model: with certification off, the default one defines it
+        fill_error_model(ix, a);
+        if (!certify) { a.eps_data = 1; a.eps_rel = 0.f; }
+        p.thresholds = thr + q0;
+        p.filter_of_query = foq ? foq + q0 : nullptr;
+        p.n_filters = (int)ix->n_filters;
+        p.stats = words;
+        // S[q][row] = queries x index^T on the bf16 MFMA GEMM, the deep path's launch; disallowed columns -> -inf
+        VRCHK(score_rows(ix, ix->qbf.p, nb, nullptr, 0, GEMM_VARIANT_AUTO, ldS, s));
+        if (foq) {
+            FilterSearchArgs f{};                 // the mask reads bits, words, n_filters and filter_of_query; the rest passes its argument check
+            f.a = a;
+            f.a.out_scores = ix->rs.as<float>(); f.a.out_ids = ix->ri.as<int64_t>();
+            f.a.flag_count = reinterpret_cast<int*>(words + RNG_SPARE); f.a.flag_list = f.a.flag_count + 2;
+            f.bits = ix->fbits.as<uint32_t>(); f.words = (size_t)((ix->n + 31) / 32); f.n_filters = (int)ix->n_filters;
+            f.allowed = ix->fcount.as<int>();
+            f.filter_of_query = p.filter_of_query;
+            f.stats = reinterpret_cast<unsigned*>(words + RNG_SPARE) + 4;
+            HIPCHK(launch_filter_mask(f, ix->sbuf.as<float>(), (size_t)ldS, nb, nullptr, 0, s));
+        }
+        HIPCHK(launch_range_rescore(p, ix->sbuf.as<float>(), (size_t)ldS, nb, ix->rcnt.as<int>(), s));
+        HIPCHK(launch_range_scan(ix->rcnt.as<int>(), ix->roff.as<int>(), ix->n, nb, base, q0 == 0 ? 1 : 0, lims + q0,
+                                 reinterpret_cast<int64_t*>(words + RNG_TOTAL), s));
+        // the size of the block's result is a host value: capacity check, growth of the result arrays
+        HIPCHK(hipMemcpyAsync(ix->range_host, words + RNG_TOTAL, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        const int64_t bt = *ix->range_host;
+        if (bt < 0 || base + bt > max_total)
+            return fail(VR_ERR_CAPACITY, "range result exceeds max_total=%lld in query block %lld (queries %lld..%lld): %lld entries by then",
+                        (long long)max_total, (long long)(q0 / qblk), (long long)q0, (long long)(q0 + nb - 1), (long long)(base + bt));
+        VRCHK(range_reserve(ix, base + bt, base, max_total, s));
+        p.out_scores = ix->rs.as<float>(); p.out_ids = ix->ri.as<int64_t>();
+        if (bt > 0)
+            HIPCHK(launch_range_pack(p, ix->sbuf.as<float>(), (size_t)ldS, nb, ix->rcnt.as<int>(), ix->roff.as<int>(), lims + q0, s));
+        base += bt;
+    }
+    if (!on_device) HIPCHK(hipMemcpyAsync(out_lims, lims, ((size_t)nq + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *total = base;
+    ix->range_total = base;
+    return VR_OK;
+}
+
+extern "C" int vr_index_range_results(vr_index_t ix, float* out_scores, int64_t* out_ids, int64_t n, int32_t on_device, void* stream) {
+    if (!ix || n < 0 || (n > 0 && (!out_scores || !out_ids))) return fail(VR_ERR_INVALID, "bad arguments");
+    if (ix->range_total < 0) return fail(VR_ERR_STATE, "no range result (vr_index_search_range)");
+    if (n > ix->range_total) return fail(VR_ERR_STATE, "%lld entries asked for, the last range search found %lld", (long long)n, (long long)ix->range_total);
+    if (n == 0) return VR_OK;
+    VRCHK(set_dev(ix->device));
+    hipStream_t s = (hipStream_t)stream;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    HIPCHK(hipMemcpyAsync(out_scores, ix->rs.p, (size_t)n * 4, kind, s));
+    HIPCHK(hipMemcpyAsync(out_ids, ix->ri.p, (size_t)n * 8, kind, s));
     if (!on_device) HIPCHK(hipStreamSynchronize(s));
     return VR_OK;
 }

@@ -396,6 +396,27 @@ hipError_t launch_filter_mask(const FilterSearchArgs& p, float* S, size_t ldS, i
 hipError_t launch_filter_select(const FilterSearchArgs& p, const float* S, size_t ldS, int nq_block, hipStream_t s);
 // the flagged queries from masked EXACT score rows (slot i = query flag_list[sub + i]): overwrites their outputs
 hipError_t launch_filter_select_exact(const FilterSearchArgs& p, const float* S, size_t ldS, int sub, int max_slots, hipStream_t s);
+// ---- range search (search_range.hip): every row whose fp32 score reaches the query's threshold, CSR, ascending row id
+struct RangeSearchArgs {
+    SearchArgs a;                    // the block's view, as for launch_search_bigk: index_f32, n_docs, dim, q_f32, nq and the error
+                                     // model (ALWAYS a valid one, as for GroupSearchArgs); everything else unused
+    const float* thresholds;         // [nq] device: the threshold of every query of the block; not finite: an empty segment
+    const int* filter_of_query;      // [nq] device or null (no filter for any query): as FilterSearchArgs'; the score rows have been
+    int n_filters;                   //   masked by launch_filter_mask; an entry outside [-1, n_filters): an empty segment
+    float* out_scores; int64_t* out_ids;   // the result arrays of the whole call (the pack writes at lims[q] + scanned offset)
+    unsigned long long* stats;       // [0] queries [1] candidate rows re-scored in fp32 [2] rows kept
+};
+bool range_dim_ok(int dim);          // the dim limits of the fp32 re-scoring (search_common.h: dot_lane)
+int64_t range_scan_slots(int64_t n_docs);   // counts / offsets per query: one per 1024 columns
+// S rows [0, nq_block): the band b >= t - eps re-scored in place (e where e >= t, else -inf); counts [nq_block][slots] = rows kept
+hipError_t launch_range_rescore(const RangeSearchArgs& p, float* S, size_t ldS, int nq_block, int* counts, hipStream_t s);
+// offs [nq_block][slots] = exclusive scan of a query's counts; lims[q + 1] = base + entries of the block's queries <= q (lims: the
+// block's first query's entry of the call's lims; first: lims[0] = 0); *block_total = entries of the block
+hipError_t launch_range_scan(const int* counts, int* offs, int64_t n_docs, int nq_block, int64_t base, int first, int64_t* lims,
+                             int64_t* block_total, hipStream_t s);
+// (score, id) of every column with S >= t -> p.out_scores / p.out_ids [lims[q] + offs ...], in column order
+hipError_t launch_range_pack(const RangeSearchArgs& p, const float* S, size_t ldS, int nq_block, const int* counts, const int* offs,
+                             const int64_t* lims, hipStream_t s);
 // ---- diversified search (search_diverse.hip): k rows per query picked by maximal marginal relevance from a pool of its best rows
 struct MmrArgs {
     const float* index_f32;          // [n_docs][dim] f32

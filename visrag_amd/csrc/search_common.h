@@ -18,6 +18,11 @@ __device__ __forceinline__ float orderable_f32(uint32_t o) {
     const uint32_t u = o ^ ((o >> 31) ? 0x80000000u : 0xFFFFFFFFu);
     return __uint_as_float(u);
 }
+// the next float below x: a bound computed by one rounded subtraction, lowered so that the rounding cannot have raised it
+__device__ __forceinline__ float one_ulp_down(float x) {
+    const uint32_t o = f32_orderable(x);
+    return o ? orderable_f32(o - 1u) : x;
+}
 // sort key: larger key = better candidate (higher score, then LOWER id)
 __device__ __forceinline__ uint64_t make_key(float score, uint32_t id) {
     return ((uint64_t)f32_orderable(score) << 32) | (uint32_t)(~id);

@@ -32,12 +32,6 @@ namespace vr {
 
 constexpr int FILT_COLS = 4;                // columns per thread of the mask kernel (one 16-byte store)
 
-// the next float below x: a bound computed by one rounded subtraction, lowered so that the rounding cannot have raised it
-__device__ __forceinline__ float one_ulp_down(float x) {
-    const uint32_t o = f32_orderable(x);
-    return o ? orderable_f32(o - 1u) : x;
-}
-
 // rows a query may see: all of them (-1), its filter's count, or none (an entry outside [-1, n_filters))
 __device__ __forceinline__ int filter_allowed(const FilterSearchArgs& p, int f) {
     return f == -1 ? (int)p.a.n_docs : ((unsigned)f < (unsigned)p.n_filters ? p.allowed[f] : 0);

@@ -23,12 +23,6 @@ namespace vr {
 
 constexpr int GRP_SHORT = 64;               // a group of up to this many rows is reduced by its own thread
 
-// the next float below x: a bound computed by one rounded subtraction, lowered so that the rounding cannot have raised it
-__device__ __forceinline__ float one_ulp_down(float x) {
-    const uint32_t o = f32_orderable(x);
-    return o ? orderable_f32(o - 1u) : x;
-}
-
 // B[slot][g] = max over rows [goff[g], goff[g + 1]) of S[slot][row].  Thread t of a workgroup owns group blockIdx.x * 256 + t;
 // a group longer than GRP_SHORT rows is reduced by the whole workgroup instead (a group may be the whole index).
 __global__ __launch_bounds__(256) void group_max_kernel(const float* __restrict__ S, size_t ldS, const int* __restrict__ goff,

@@ -8,6 +8,9 @@
     (`documents=[...]`: only the pages of those documents are ranked — HipIndex.search_filtered)
   * `retrieve_documents(knowledge_base_path, query, topk, ...)` -> the best page of each of the top-k DOCUMENTS
                                                                (no reference counterpart: its top-k is pages)
+  * `retrieve_above(knowledge_base_path, query, min_score, ...)` -> EVERY page at or above a score, best first
+  * `duplicate_pages(knowledge_base_path, threshold, ...)` -> groups of near-duplicate pages
+                                                               (HipIndex.search_range; no reference counterpart either)
 
 Same on-disk knowledge base (`reps.npy` float32 [n_pages, 2304], `index2img_filename.txt` one file name per
 row, `<pdf>_<idx>.png`), so a base built by either side can be queried by the other.  Differences that do
@@ -23,7 +26,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from .documents import doc_of_page, group_rows, label_filters
+from .documents import doc_of_page, duplicate_groups, group_rows, label_filters
 from .engine import HipIndex
 from .modeling import encode  # noqa: F401  (demo/visrag_pipeline/utils.py:12-32)
 
@@ -224,3 +227,63 @@ def retrieve_documents(knowledge_base_path: str, query, topk: int, model, tokeni
     if own:
         index.close()
     return (paths, scores) if return_scores else paths
+
+
+@torch.no_grad()
+def retrieve_above(knowledge_base_path: str, query, min_score: float, model, tokenizer, index=None, names=None, documents=None,
+                   max_pages: Optional[int] = None, return_scores: bool = False):
+    """Paths of EVERY page whose score is at least `min_score`, best first (None if the base does not exist): the similarity
+    threshold of a RAG stack — a question with one relevant page gets one page, and a family of a thousand near-duplicates comes
+    back whole (HipIndex.search_range: the exact fp32 answer, no cap at a k).  `documents`: only the pages of those documents,
+    as in `retrieve` (one filter, set for this question).  `max_pages`, if given, cuts the sorted result.  `query` is the
+    question, or its embedding ([dim] or [1, dim]).  Pass `index, names = load_knowledge_base(path)` to keep the index resident."""
+    if not os.path.exists(knowledge_base_path):
+        return None
+    own = index is None
+    if own:
+        index, names = load_knowledge_base(knowledge_base_path, model.encoder.device if model is not None else None)
+    n = len(index)
+    if isinstance(query, str):
+        q = encode(model, tokenizer, [QUERY_INSTRUCTION + query])
+    else:
+        q = np.asarray(query.detach().cpu() if isinstance(query, torch.Tensor) else query, dtype=np.float32).reshape(1, -1)
+    mask = None if documents is None else label_filters([doc_of_page(nm) for nm in names[:n]], [documents])
+    if n == 0 or (mask is not None and not mask.any()) or (max_pages is not None and max_pages <= 0):
+        paths, scores = [], []
+    else:
+        if mask is not None:
+            index.set_filters(mask)
+        _, sc, ids = index.search_range(q, float(min_score), None if mask is None else 0)
+        if max_pages is not None:
+            sc, ids = sc[:max_pages], ids[:max_pages]
+        paths = [os.path.join(knowledge_base_path, names[int(i)]) for i in ids]
+        scores = [float(s) for s in sc]
+    if own:
+        index.close()
+    return (paths, scores) if return_scores else paths
+
+
+def duplicate_pages(knowledge_base_path: str, threshold: float, index=None, names=None, batch: int = 256) -> Optional[List[List[str]]]:
+    """Groups of page names whose embeddings are chained by a dot product >= `threshold` (None if the base does not exist): the
+    near-duplicate pages of a knowledge base, found before they reach the generator.  The base's own rows are the queries of a
+    range search, `batch` of them per call; page a and page c land in one group when a-b and b-c match, even if a-c does not.
+    Groups come ordered by their first page, pages in row order; a page that matches only itself is in no group.  An index
+    passed in must hold the rows of reps.npy in their order on disk (`load_knowledge_base`)."""
+    if not os.path.exists(knowledge_base_path):
+        return None
+    own = index is None
+    if own:
+        index, names = load_knowledge_base(knowledge_base_path)
+    reps = np.load(os.path.join(knowledge_base_path, "reps.npy")).astype(np.float32)
+    n = len(index)
+    if len(reps) != n:
+        raise ValueError(f"{len(reps)} rows in {knowledge_base_path} but {n} in the index")
+    lims, ids = [np.zeros(1, np.int64)], []
+    for lo in range(0, n, max(int(batch), 1)):
+        l, _, i = index.search_range(reps[lo:lo + batch], float(threshold), sort=False)
+        lims.append(l[1:] + lims[-1][-1])
+        ids.append(i)
+    if own:
+        index.close()
+    groups = duplicate_groups(np.concatenate(lims), np.concatenate(ids) if ids else np.zeros(0, np.int64), n)
+    return [[names[r] for r in g] for g in groups]

@@ -6,6 +6,9 @@ knowledge base (`<pdf>_<idx>.png`).
 
 The filtered search (HipIndex.set_filters / search_filtered) ranks inside a subset of the rows: `pack_filters` is the bit layout
 the library takes, `group_filter` allows the rows of some groups, `label_filters` the rows whose label is in a wanted set.
+
+The range search (HipIndex.search_range) returns a CSR result (lims, scores, ids): `split_ranges` cuts it into per-query pairs,
+`duplicate_groups` reads it — the index's own rows as queries — as a graph and returns its components.
 Pure numpy: nothing here touches the GPU.
 """
 from __future__ import annotations
@@ -79,3 +82,46 @@ def label_filters(labels: Sequence[Hashable], wanted_sets: Sequence[Optional[Ite
         w = set(wanted)
         out[j] = [lab in w for lab in labels]
     return out
+
+
+def split_ranges(lims, scores, ids) -> List[Tuple[np.ndarray, np.ndarray]]:
+    """A range result (HipIndex.search_range) -> [(scores, ids)] per query: views of entries lims[q] .. lims[q + 1] - 1."""
+    lims = np.asarray(lims, dtype=np.int64).reshape(-1)
+    scores, ids = np.asarray(scores), np.asarray(ids)
+    if len(lims) < 1 or lims[0] != 0 or (np.diff(lims) < 0).any() or lims[-1] != len(ids) or len(scores) != len(ids):
+        raise ValueError("lims must start at 0, be non-decreasing and end at the number of entries")
+    return [(scores[lims[q]:lims[q + 1]], ids[lims[q]:lims[q + 1]]) for q in range(len(lims) - 1)]
+
+
+def duplicate_groups(lims, ids, n_rows: int) -> List[List[int]]:
+    """The connected components with more than one row of the graph "row q - row ids[j]" for every entry j of query q's segment
+    (lims[q] <= j < lims[q + 1]): the rows of an index chained by a score at or above the threshold of a range search whose
+    queries were the index's own rows 0, 1, ...  A row's match with itself joins nothing.  -> sorted lists of rows, ordered by
+    their first row.  Union-find over n_rows rows, pure host code."""
+    lims = np.asarray(lims, dtype=np.int64).reshape(-1)
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    parent = np.arange(int(n_rows), dtype=np.int64)
+
+    def find(x: int) -> int:
+        root = x
+        while parent[root] != root:
+            root = parent[root]
+        while parent[x] != root:                       # path compression
+            parent[x], x = root, parent[x]
+        return int(root)
+
+    for q in range(len(lims) - 1):
+        row = q
+        if row >= n_rows:
+            raise ValueError(f"query {q} is no row of [0, {n_rows})")
+        for j in ids[lims[q]:lims[q + 1]]:
+            j = int(j)
+            if not 0 <= j < n_rows:
+                raise ValueError(f"row id {j} outside [0, {n_rows})")
+            a, b = find(row), find(j)
+            if a != b:                                 # the smaller row is the root: a component is named by its first row
+                parent[max(a, b)] = min(a, b)
+    members: dict = {}
+    for r in range(int(n_rows)):
+        members.setdefault(find(r), []).append(r)
+    return [m for _, m in sorted(members.items()) if len(m) > 1]

@@ -408,6 +408,70 @@ class HipIndex:
         _lib.check(self.lib.vr_index_filter_search_stats(self._h, out, 1 if reset else 0))
         return {"certified": int(out[0]), "certified_widened": int(out[1]), "exact": int(out[2])}
 
+    def search_range(self, queries, threshold, filter_of_query=None, max_total: Optional[int] = None, sort: bool = True):
+        """Every row whose fp32 score is >= the query's threshold (include/visrag_hip.h: vr_index_search_range) -> (lims int64
+        [nq + 1], scores f32 [total], ids i64 [total]): entries lims[q] .. lims[q + 1] - 1 are query q's; cuda in -> cuda out,
+        numpy / cpu in -> numpy out.  `threshold`: a scalar or one per query.  `filter_of_query` as in `search_filtered`, None =
+        no filter (none need to be set).  `max_total=None`: min(nq * rows, 2 ** 26) entries; a larger result raises
+        (VR_ERR_CAPACITY).  `sort=True`: every segment by score descending, then id ascending — the library's ranking order;
+        `sort=False`: the ABI's ascending-id order."""
+        cuda = isinstance(queries, torch.Tensor) and queries.is_cuda
+        if cuda:
+            q = queries.to(torch.float32).contiguous()
+        else:
+            q = np.ascontiguousarray(queries.numpy() if isinstance(queries, torch.Tensor) else queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"queries must be [nq][{self.dim}]")
+        nq = int(q.shape[0])
+        if isinstance(threshold, torch.Tensor):
+            threshold = threshold.detach().cpu().numpy()
+        thr = np.array(threshold, dtype=np.float32).reshape(-1)          # (a copy: the caller's array may be read-only)
+        thr = np.full(nq, thr[0], dtype=np.float32) if thr.size == 1 else np.ascontiguousarray(thr)
+        if len(thr) != nq:
+            raise ValueError(f"{len(thr)} thresholds for {nq} queries")
+        keep, fptr = (None, C.c_void_p(None)) if filter_of_query is None else self._filter_of_query(q, filter_of_query)
+        if max_total is None:
+            max_total = max(1, min(nq * len(self), 2 ** 26))
+        total = C.c_int64(0)
+        stream = C.c_void_p(_stream_ptr(self.device))
+        if cuda:
+            thr_d = torch.from_numpy(thr).to(q.device)
+            lims = torch.empty(nq + 1, dtype=torch.int64, device=q.device)
+            ptrs = (q.data_ptr(), thr_d.data_ptr(), lims.data_ptr())
+        else:
+            lims = np.empty(nq + 1, dtype=np.int64)
+            ptrs = (q.ctypes.data, thr.ctypes.data, lims.ctypes.data)
+        _lib.check(self.lib.vr_index_search_range(self._h, C.c_void_p(ptrs[0]), nq, C.c_void_p(ptrs[1]), fptr, int(max_total),
+                                                  C.c_void_p(ptrs[2]), C.byref(total), 1 if cuda else 0, stream), "vr_index_search_range")
+        n = int(total.value)
+        if cuda:
+            scores = torch.empty(n, dtype=torch.float32, device=q.device)
+            ids = torch.empty(n, dtype=torch.int64, device=q.device)
+            optrs = (scores.data_ptr(), ids.data_ptr())
+        else:
+            scores, ids = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.int64)
+            optrs = (scores.ctypes.data, ids.ctypes.data)
+        _lib.check(self.lib.vr_index_range_results(self._h, C.c_void_p(optrs[0]), C.c_void_p(optrs[1]), n, 1 if cuda else 0, stream),
+                   "vr_index_range_results")
+        del keep
+        if sort and n > 1:
+            if cuda:
+                seg = torch.repeat_interleave(torch.arange(nq, device=q.device), lims[1:] - lims[:-1])
+                o1 = torch.sort(scores, descending=True, stable=True)[1]     # ids ascend already: the stable sorts keep that
+                order = o1[torch.sort(seg[o1], stable=True)[1]]
+            else:
+                seg = np.repeat(np.arange(nq), np.diff(lims))
+                order = np.lexsort((ids, -scores.astype(np.float64), seg))
+            scores, ids = scores[order], ids[order]
+        return lims, scores, ids
+
+    def range_search_stats(self, reset: bool = False) -> Dict[str, int]:
+        """Range searches since the last reset: queries, candidate rows re-scored in fp32 (the rows inside the error band below
+        the thresholds and everything above), rows returned."""
+        out = (C.c_int64 * 3)()
+        _lib.check(self.lib.vr_index_range_search_stats(self._h, out, 1 if reset else 0))
+        return {"queries": int(out[0]), "candidates": int(out[1]), "returned": int(out[2])}
+
     def search_keys(self, queries: torch.Tensor, k: int, id_offset: int = 0) -> torch.Tensor:
         """The same search with each result packed into ONE 64-bit word (include/visrag_hip.h:
         vr_index_search_keys): orderable(score) << 32 | ~(row + id_offset); 0 = empty slot.  -> int64 [nq, k]

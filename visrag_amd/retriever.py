@@ -228,6 +228,41 @@ def retrieve_filtered(args, topk: int, label_of: Callable[[str], object], labels
     return result
 
 
+def retrieve_range(args, threshold: float, max_per_query: Optional[int] = None, index_factory: Optional[Callable] = None
+                   ) -> Dict[str, Dict[str, float]]:
+    """A run of variable depth over the same pickle shards: this rank's query shard(s) against ALL corpus shards, every row
+    whose score is at least `threshold` (HipIndex.search_range: the exact fp32 answer, not cut at a k).  -> {qid: {docid:
+    score}}, a query's entries best first; it goes to `save_as_trec` as it is.  The corpus is taken shard by shard: a range
+    result is the union of the shard results, so no merge kernel is involved and the index never holds more than one shard.
+    `max_per_query`, if given, keeps a query's best entries only (score descending, then shard and row order).
+
+    Replicated form only, like retrieve_documents: every rank sees the whole corpus."""
+    make_index = index_factory or HipIndex
+    queries, qids, _ = _load_queries(args)
+    corpus_parts = list_shards(args.output_dir, "corpus")
+    if len(corpus_parts) == 0:
+        raise ValueError("No pre-computed document embeddings found")
+    dev = _device_index(args)
+    found: List[List[Tuple[float, str]]] = [[] for _ in qids]
+    for p in corpus_parts:
+        reps, ids = read_shard(p)
+        if len(ids) == 0:
+            continue
+        ix = make_index(queries.shape[1], len(ids), dev)
+        ix.add(np.asarray(reps, dtype=np.float32))
+        lims, sc, rows = ix.search_range(queries, float(threshold))
+        ix.close()
+        for qi in range(len(qids)):
+            found[qi].extend((float(s), ids[int(r)]) for s, r in zip(sc[lims[qi]:lims[qi + 1]], rows[lims[qi]:lims[qi + 1]]))
+    result: Dict[str, Dict[str, float]] = {}
+    for q, entries in zip(qids, found):
+        entries.sort(key=lambda e: -e[0])                # stable: equal scores keep shard and row order
+        if max_per_query is not None:
+            entries = entries[:max(int(max_per_query), 0)]
+        result[q] = {d: s for s, d in entries}
+    return result
+
+
 def _retrieve_corpus_sharded(args, topk: int, global_topk: bool, make_index: Callable, merge_keys: Optional[Callable]
                              ) -> Dict[str, Dict[str, float]]:
     """The corpus-sharded form (module docstring).  Row ids are global: files in sorted order (the order the
