@@ -440,6 +440,36 @@ int vr_index_range_results(vr_index_t ix, float* out_scores, int64_t* out_ids, i
 /* Range searches since the last reset: out3 = {queries, candidate rows re-scored in fp32, rows returned} — 64-bit counters
  * in device memory. */
 int vr_index_range_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
+/* ---- editing in place: remove rows, overwrite rows, read rows back ---- */
+/* After any of the calls below every search behaves exactly — score bits, ids, groups, lims — as on an index freshly built
+ * (vr_index_create, vr_index_add, vr_index_set_filters / vr_index_set_groups) from the rows that remain.  Ids are positions, as
+ * everywhere in this ABI.  `ids` is always a HOST array: the list is small, and everything is checked before anything changes.
+ *   Checks, all before any launch and with the index unchanged: a NULL ix, NULL ids with n > 0, n < 0 or an id outside
+ * [0, rows): VR_ERR_INVALID; vr_index_update: NULL reps with n > 0 or an id named twice: VR_ERR_INVALID; vr_index_get_rows: both
+ * outputs NULL: VR_ERR_INVALID.  n == 0: VR_OK and nothing is touched — not the grouping, the filters or the range result.
+ *   All three calls synchronise the stream before they return (the id list is the caller's host memory); vr_index_remove also
+ * waits for the device first, as vr_index_reset does, because a search in flight on another stream reads the rows it moves. */
+/* Remove the rows ids[0..n) (host int64, any order, duplicates count once).  The remaining rows keep their relative order and
+ * close up: a surviving row's new id = old id - (removed ids below it).  *removed (host, may be NULL) = distinct rows removed.
+ * What is left is the state of vr_index_reset + vr_index_add of the surviving rows: both stores hold survivor j at row j; the row
+ * count drops, so capacity comes back; max|d| and max|d - bf16(d)| of the error model are RECOMPUTED over the survivors (a stale
+ * larger maximum would still bound the error, but would leave the certification looser than a fresh index's for ever); the
+ * exact-pass hint of vr_index_search_plan is cleared.  The FILTERS ARE CARRIED: bit j of every filter becomes the old bit of the
+ * row now at j, and the allowed rows are recounted (a filter may end up allowing nothing: legal).  The GROUPING IS DROPPED, as by
+ * vr_index_add: a removal can empty a group, and the offsets are the host's to rebuild.  The range result is gone
+ * (vr_index_range_results: VR_ERR_STATE).  The searches' counters stay.
+ *   Rows below the first removed id are not touched.  The rest move in ascending windows, each either straight into place (when
+ * the rows removed so far make the window's source lie wholly behind it) or through a scratch of at most 64 MiB: never a second
+ * copy of the store, and no kernel waits for another workgroup — stream order between launches is the only ordering. */
+int vr_index_remove(vr_index_t ix, const int64_t* ids, int64_t n, int64_t* removed, void* stream);
+/* Row ids[i] becomes reps[i] (float32 [n][dim], host or device per on_device); ids host, distinct.  The bf16 rows are converted
+ * as vr_index_add converts them and the two maxima of the error model are recomputed over all rows (an overwritten row may have
+ * been the largest).  No row moves: grouping and filters stay.  The range result is gone and the exact-pass hint is cleared. */
+int vr_index_update(vr_index_t ix, const int64_t* ids, const float* reps, int64_t n, int32_t on_device, void* stream);
+/* Rows by id: out_f32 [n][dim] float32 and / or out_bf16 [n][dim] uint16 (the MFMA copy; tests), either may be NULL, not both;
+ * host or device per on_device; ids host, duplicates allowed.  Changes nothing. */
+int vr_index_get_rows(vr_index_t ix, const int64_t* ids, int64_t n, float* out_f32, uint16_t* out_bf16, int32_t on_device,
+                      void* stream);
 /* Merge per-shard results (e.g. after an RCCL all-gather): in [n_parts][nq][k] scores and
  * global ids -> out [nq][k], same ordering rule.  Device pointers. */
 int vr_topk_merge(int device_id, const float* scores, const int64_t* ids, int32_t n_parts,

@@ -113,6 +113,9 @@ SIGNATURES = {
     "vr_index_range_results": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp]),
     "vr_index_range_search_stats": (C.c_int, [_vp, C.POINTER(_i64), _i32]),
     "vr_index_search_diverse": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _i32, _vp]),
+    "vr_index_remove": (C.c_int, [_vp, C.POINTER(_i64), _i64, C.POINTER(_i64), _vp]),
+    "vr_index_update": (C.c_int, [_vp, C.POINTER(_i64), _vp, _i64, _i32, _vp]),
+    "vr_index_get_rows": (C.c_int, [_vp, C.POINTER(_i64), _i64, _vp, _vp, _i32, _vp]),
     "vr_topk_merge_keys": (C.c_int, [C.c_int, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "vr_resize_bicubic": (C.c_int, [C.c_int, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
     "vr_op_gemm": (C.c_int, [C.c_int, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _f32,

@@ -430,5 +430,19 @@ struct MmrArgs {
 };
 bool mmr_dim_ok(int dim);            // the dim limits of the fp32 re-scoring (search_common.h: dot_lane)
 hipError_t launch_mmr_select(const MmrArgs& p, hipStream_t s);
+// ---- editing in place (index_edit.hip): whole rows of `row_bytes` (a multiple of 16) moved by whole waves.  rem: the removed rows,
+// sorted and distinct (device, nr ints); src(j) = j + #{i : rem[i] - i <= j} = the old row that becomes row j
+// out rows [0, n_rows) = store rows src(j0) .. src(j0 + n_rows - 1).  `out` may lie inside `store` if the rows written (all below
+// j0 + n_rows) and the rows read (all >= src(j0)) are apart: workgroups are not ordered, only launches are
+hipError_t launch_rows_compact(const void* store, size_t row_bytes, const int* rem, int nr, int64_t j0, int64_t n_rows, void* out,
+                               hipStream_t s);
+// out row i = store row ids[i] (device ints, in range — the caller has checked them; duplicates allowed)
+hipError_t launch_rows_gather(const void* store, size_t row_bytes, const int* ids, int64_t n_rows, void* out, hipStream_t s);
+// f32 row ids[i] = reps row i and bf16 row ids[i] = its conversion (as launch_f32_to_bf16); ids distinct and in range, dim % 8 == 0
+hipError_t launch_rows_update(const float* reps, const int* ids, int64_t n, int dim, float* f32, void* bf16, hipStream_t s);
+// out [n_filters][ceil(new_n / 32)]: bit j of a filter = bit src(j) of bits [n_filters][words] (words = ceil((new_n + nr) / 32)),
+// bits at or beyond new_n clear; out is another buffer
+hipError_t launch_filter_compact(const uint32_t* bits, size_t words, int n_filters, const int* rem, int nr, int64_t new_n,
+                                 uint32_t* out, hipStream_t s);
 
 }  // namespace vr

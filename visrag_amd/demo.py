@@ -11,6 +11,8 @@
   * `retrieve_above(knowledge_base_path, query, min_score, ...)` -> EVERY page at or above a score, best first
   * `duplicate_pages(knowledge_base_path, threshold, ...)` -> groups of near-duplicate pages
                                                                (HipIndex.search_range; no reference counterpart either)
+  * `remove_documents(knowledge_base_path, documents, ...)` / `update_pages(...)`: withdraw documents, re-embed pages — on disk
+                                                               and in a resident index, in place (HipIndex.remove / update)
 
 Same on-disk knowledge base (`reps.npy` float32 [n_pages, 2304], `index2img_filename.txt` one file name per
 row, `<pdf>_<idx>.png`), so a base built by either side can be queried by the other.  Differences that do
@@ -26,7 +28,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from .documents import doc_of_page, duplicate_groups, group_rows, label_filters
+from .documents import doc_of_page, duplicate_groups, group_rows, label_filters, rows_of_documents
 from .engine import HipIndex
 from .modeling import encode  # noqa: F401  (demo/visrag_pipeline/utils.py:12-32)
 
@@ -274,16 +276,96 @@ def duplicate_pages(knowledge_base_path: str, threshold: float, index=None, name
     own = index is None
     if own:
         index, names = load_knowledge_base(knowledge_base_path)
-    reps = np.load(os.path.join(knowledge_base_path, "reps.npy")).astype(np.float32)
+    n_disk = len(np.load(os.path.join(knowledge_base_path, "reps.npy"), mmap_mode="r"))
     n = len(index)
-    if len(reps) != n:
-        raise ValueError(f"{len(reps)} rows in {knowledge_base_path} but {n} in the index")
+    if n_disk != n:
+        raise ValueError(f"{n_disk} rows in {knowledge_base_path} but {n} in the index")
     lims, ids = [np.zeros(1, np.int64)], []
-    for lo in range(0, n, max(int(batch), 1)):
-        l, _, i = index.search_range(reps[lo:lo + batch], float(threshold), sort=False)
+    batch = max(int(batch), 1)
+    for lo in range(0, n, batch):                  # the queries are the index's own fp32 rows, read back: no host copy of the base
+        l, _, i = index.search_range(index.rows(np.arange(lo, min(lo + batch, n))), float(threshold), sort=False)
         lims.append(l[1:] + lims[-1][-1])
         ids.append(i)
     if own:
         index.close()
     groups = duplicate_groups(np.concatenate(lims), np.concatenate(ids) if ids else np.zeros(0, np.int64), n)
     return [[names[r] for r in g] for g in groups]
+
+
+def _read_names(knowledge_base_path: str) -> List[str]:
+    with open(os.path.join(knowledge_base_path, "index2img_filename.txt")) as f:
+        return [n for n in f.read().split("\n") if n]
+
+
+def _write_base(knowledge_base_path: str, reps: np.ndarray, names: Sequence[str]) -> None:
+    np.save(os.path.join(knowledge_base_path, "reps.npy"), reps)
+    with open(os.path.join(knowledge_base_path, "index2img_filename.txt"), "w") as f:
+        f.write("\n".join(names))
+
+
+def remove_documents(knowledge_base_path: str, documents, index=None, names=None, delete_images: bool = True) -> Optional[List[str]]:
+    """Withdraw the documents `documents` (the `doc_of_page` of the page names) from the base: their rows leave `reps.npy` and
+    `index2img_filename.txt`, and with `delete_images` their cached PNGs are deleted — files inside the base directory only.
+    With a resident `index` / `names` (`load_knowledge_base`, rows in the order on disk) the rows are removed from the index in
+    place (HipIndex.remove: no rebuild, no upload) and `names` is edited in place, so the next `retrieve(..., index=, names=)`
+    sees the edited base; a grouping is dropped with the rows (`retrieve_documents` sets it again).  -> the removed file names
+    (None if the base does not exist); a document no page belongs to removes nothing."""
+    if not os.path.exists(knowledge_base_path):
+        return None
+    disk_names = _read_names(knowledge_base_path)
+    if names is not None and [n for n in names if n] != disk_names:
+        raise ValueError("`names` is not the page list of the base on disk: withdraw documents from an index in the disk's row order")
+    ids = rows_of_documents(disk_names, documents)
+    gone = [disk_names[i] for i in ids]
+    if not len(ids):
+        return gone
+    keep = np.ones(len(disk_names), dtype=bool)
+    keep[ids] = False
+    reps = np.load(os.path.join(knowledge_base_path, "reps.npy"))
+    if len(reps) != len(disk_names):
+        raise ValueError(f"{len(reps)} rows but {len(disk_names)} page names in {knowledge_base_path}")
+    left = [n for n, k in zip(disk_names, keep) if k]
+    _write_base(knowledge_base_path, np.ascontiguousarray(reps[keep]), left)
+    if index is not None:
+        index.remove(ids)
+    if names is not None:
+        names[:] = left
+    if delete_images:
+        base = os.path.realpath(knowledge_base_path)
+        for nm in gone:
+            path = os.path.realpath(os.path.join(base, nm))
+            if os.path.dirname(path) == base and os.path.isfile(path):
+                os.remove(path)
+    return gone
+
+
+@torch.no_grad()
+def update_pages(model, tokenizer, pages: Sequence, knowledge_base_path: str, names: Sequence[str], index=None,
+                 batch_size: int = 32) -> np.ndarray:
+    """Re-embed pages that are in the base already (a re-scanned page): `names[i]` is the file name of PIL image `pages[i]`.
+    Their rows are replaced in `reps.npy` and, with a resident `index` (rows in the order on disk), overwritten in place
+    (HipIndex.update); their PNGs are overwritten.  A name the base does not hold, or one given twice, raises ValueError
+    before anything changes.  -> the new [n, D] float32 reps."""
+    names = list(names)
+    if len(names) != len(pages):
+        raise ValueError("names and pages must have the same length")
+    disk_names = _read_names(knowledge_base_path)
+    row_of = {n: i for i, n in enumerate(disk_names)}
+    unknown = [n for n in names if n not in row_of]
+    if unknown:
+        raise ValueError(f"not in the knowledge base: {unknown[:5]}")
+    if len(set(names)) != len(names):
+        raise ValueError("a page is named more than once")
+    reps = np.load(os.path.join(knowledge_base_path, "reps.npy")).astype(np.float32)
+    if not names:
+        return np.zeros((0, reps.shape[1]), np.float32)
+    new = np.concatenate([encode(model, tokenizer, list(pages[lo:lo + batch_size]))
+                          for lo in range(0, len(pages), batch_size)]).astype(np.float32)
+    ids = np.asarray([row_of[n] for n in names], dtype=np.int64)
+    reps[ids] = new
+    _write_base(knowledge_base_path, reps, disk_names)
+    if index is not None:
+        index.update(ids, new)
+    for img, nm in zip(pages, names):
+        img.save(os.path.join(knowledge_base_path, nm))
+    return new

@@ -9,6 +9,10 @@ the library takes, `group_filter` allows the rows of some groups, `label_filters
 
 The range search (HipIndex.search_range) returns a CSR result (lims, scores, ids): `split_ranges` cuts it into per-query pairs,
 `duplicate_groups` reads it — the index's own rows as queries — as a graph and returns its components.
+
+Editing in place (HipIndex.remove / update): `rows_of_documents` names the rows of documents to withdraw, `new_id_of_old` is the
+map a removal applies to the row ids, `remap_rows` carries ids a caller holds across it, and `compact_filters` states what the
+library does to the filters it keeps.
 Pure numpy: nothing here touches the GPU.
 """
 from __future__ import annotations
@@ -125,3 +129,40 @@ def duplicate_groups(lims, ids, n_rows: int) -> List[List[int]]:
     for r in range(int(n_rows)):
         members.setdefault(find(r), []).append(r)
     return [m for _, m in sorted(members.items()) if len(m) > 1]
+
+
+def rows_of_documents(names: Sequence[str], documents: Iterable[str]) -> np.ndarray:
+    """int64, ascending: the rows (pages `names[i]` of the demo's knowledge base) whose `doc_of_page` is one of `documents` — what
+    `HipIndex.remove` takes to withdraw those documents.  A document that no page belongs to names no row."""
+    wanted = set(documents)
+    return np.asarray([i for i, nm in enumerate(names) if doc_of_page(nm) in wanted], dtype=np.int64)
+
+
+def new_id_of_old(n_rows: int, removed) -> np.ndarray:
+    """int64 [n_rows]: where every row of an index of `n_rows` rows is after `HipIndex.remove(removed)` — the survivors keep their
+    order and close up (new id = old id - removed ids below it), a removed row maps to -1.  `removed`: any order, duplicates count
+    once; an id outside [0, n_rows) raises ValueError."""
+    rem = np.asarray(removed, dtype=np.int64).reshape(-1)
+    if len(rem) and (rem.min() < 0 or rem.max() >= n_rows):
+        raise ValueError(f"row ids must lie in [0, {n_rows})")
+    keep = np.ones(int(n_rows), dtype=bool)
+    keep[rem] = False
+    out = np.cumsum(keep, dtype=np.int64) - 1
+    out[~keep] = -1
+    return out
+
+
+def remap_rows(new_id_of_old, ids) -> np.ndarray:
+    """Row ids a caller holds from before a removal -> their ids after it, in the same order; ids of removed rows are dropped."""
+    m = np.asarray(new_id_of_old, dtype=np.int64)[np.asarray(ids, dtype=np.int64).reshape(-1)]
+    return m[m >= 0]
+
+
+def compact_filters(masks, new_id_of_old) -> np.ndarray:
+    """bool [n_filters][old rows] -> bool [n_filters][rows left]: the filters an index keeps across `HipIndex.remove` — entry j of
+    a filter is its old entry for the row now at j.  A filter may end up allowing nothing."""
+    m = np.atleast_2d(np.asarray(masks, dtype=bool))
+    nid = np.asarray(new_id_of_old, dtype=np.int64).reshape(-1)
+    if m.shape[1] != len(nid):
+        raise ValueError(f"masks over {m.shape[1]} rows, a map over {len(nid)}")
+    return np.ascontiguousarray(m[:, nid >= 0])

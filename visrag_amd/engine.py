@@ -278,6 +278,62 @@ class HipIndex:
             _lib.check(self.lib.vr_index_add(self._h, C.c_void_p(a.ctypes.data), a.shape[0], 0,
                                              C.c_void_p(_stream_ptr(self.device))), "vr_index_add")
 
+    # ---- editing in place (include/visrag_hip.h: vr_index_remove / vr_index_update / vr_index_get_rows) ----
+    @staticmethod
+    def _row_ids(ids) -> np.ndarray:
+        if isinstance(ids, torch.Tensor):
+            ids = ids.detach().cpu().numpy()
+        return np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+
+    def remove(self, ids) -> np.ndarray:
+        """Remove the rows `ids` (any int sequence or tensor, any order, duplicates count once).  The rows that remain keep their
+        order and close up; every search then answers as on an index freshly built from them.  The filters are carried along
+        (`n_filters` stays), the grouping is dropped (`n_groups = 0`: set the offsets of the rows that remain).
+        -> new_id_of_old, int64 [len before]: the new id of every old row, -1 for a removed one (documents.remap_rows carries
+        ids across it, documents.compact_filters states what became of the filters)."""
+        from .documents import new_id_of_old
+        a = self._row_ids(ids)
+        n_old = len(self)
+        removed = C.c_int64(0)
+        _lib.check(self.lib.vr_index_remove(self._h, a.ctypes.data_as(C.POINTER(C.c_int64)), len(a), C.byref(removed),
+                                            C.c_void_p(_stream_ptr(self.device))), "vr_index_remove")
+        if len(a):
+            self.n_groups = 0
+        return new_id_of_old(n_old, a)
+
+    def update(self, ids, reps) -> None:
+        """Rows `ids` (distinct) become `reps` [len(ids)][dim]: numpy, a cpu tensor or a cuda tensor.  No row moves: groups and
+        filters stay."""
+        a = self._row_ids(ids)
+        if isinstance(reps, torch.Tensor) and reps.is_cuda:
+            r = reps.to(torch.float32).contiguous()
+            ptr, dev = r.data_ptr(), 1
+        else:
+            r = np.ascontiguousarray(reps.numpy() if isinstance(reps, torch.Tensor) else reps, dtype=np.float32)
+            ptr, dev = r.ctypes.data, 0
+        if r.ndim != 2 or tuple(r.shape) != (len(a), self.dim):
+            raise ValueError(f"reps must be [{len(a)}][{self.dim}]")
+        _lib.check(self.lib.vr_index_update(self._h, a.ctypes.data_as(C.POINTER(C.c_int64)), C.c_void_p(ptr), len(a), dev,
+                                            C.c_void_p(_stream_ptr(self.device))), "vr_index_update")
+
+    def rows(self, ids=None, bf16: bool = False, device: bool = False):
+        """The rows `ids` (None: all; duplicates allowed) as stored: float32 [n][dim], or with `bf16` the MFMA copy as its raw
+        bits, uint16 [n][dim] (int16 of the same bits on the device).  -> numpy, or a cuda tensor with `device=True`."""
+        a = self._row_ids(np.arange(len(self)) if ids is None else ids)
+        n = len(a)
+        if device:
+            out = torch.empty((n, self.dim), dtype=torch.int16 if bf16 else torch.float32, device=f"cuda:{self.device}")
+            ptr = out.data_ptr()
+        else:
+            out = np.empty((n, self.dim), dtype=np.uint16 if bf16 else np.float32)
+            ptr = out.ctypes.data
+        if n == 0:
+            return out
+        _lib.check(self.lib.vr_index_get_rows(self._h, a.ctypes.data_as(C.POINTER(C.c_int64)), n,
+                                              C.c_void_p(None if bf16 else ptr), C.c_void_p(ptr if bf16 else None),
+                                              1 if device else 0, C.c_void_p(_stream_ptr(self.device))), "vr_index_get_rows")
+        return out
+
     def _search(self, fn, what: str, queries, k: int, n_int_out: int):
         """One call of a library search that writes scores [nq,k] f32 and `n_int_out` arrays [nq,k] i64: torch cuda tensors in ->
         cuda tensors out, numpy / cpu in -> numpy out (sized with max(k, 0): a negative k reaches the library's own error)."""
