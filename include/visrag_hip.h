@@ -426,8 +426,8 @@ int vr_index_search_diverse(vr_index_t ix, const float* queries, int32_t nq, int
  *   The call synchronises the stream, because the sizes of its result are host values: once per block of 256 queries and
  * once at the end.  It leaves every state the other searches read alone and counts in none of their statistics.
  * Not offered: sorted output (sort a segment by score on the caller's side: the Python wrapper does), groups (a thresholded
- * document search is vr_index_search_groups plus a cut), an exact count without the rows, corpus-sharded ranks (a range
- * result over shards is the union of the shards' results). */
+ * document search is vr_index_search_groups plus a cut), corpus-sharded ranks (a range result over shards is the union of the
+ * shards' results).  An exact count without the rows: vr_index_count_range below. */
 int vr_index_search_range(vr_index_t ix, const float* queries, int32_t nq,
                           const float* thresholds,          /* [nq] */
                           const int32_t* filter_of_query,   /* NULL: no filter for any query */
@@ -440,6 +440,46 @@ int vr_index_range_results(vr_index_t ix, float* out_scores, int64_t* out_ids, i
 /* Range searches since the last reset: out3 = {queries, candidate rows re-scored in fp32, rows returned} — 64-bit counters
  * in device memory. */
 int vr_index_range_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
+/* ---- rank search: the exact rank and score of named rows, exact counts against thresholds ---- */
+/* vr_index_rank_rows: for query q and target row i, out_scores = e_i, the fp32 score of the library's one re-scoring dot product
+ * (the bits vr_index_search returns for that (query, row)), and out_ranks = the number of rows j — allowed by the query's filter
+ * if filter_of_query is given — whose key is greater than the target's: score descending, then lower id first.  A target of
+ * rank r is therefore at position r of vr_index_search for every k > r (of vr_index_search_filtered under the filter), rows
+ * with identical bits get consecutive ranks in id order, and duplicate targets are allowed.  The rank is defined whether or
+ * not the filter allows the target itself: it is then the position the row WOULD take among the allowed rows.
+ *   vr_index_count_range: for query q and threshold t the number of (allowed) rows with e >= t, or with e > t when strict:
+ * the non-strict count is exactly the size of vr_index_search_range's segment for the same threshold.  -0.0 counts as +0.0.
+ *   Layout: targets / thresholds in CSR form: query q's are entries lims[q] .. lims[q + 1] - 1.  lims [nq + 1] int64, ids int64
+ * and thresholds float32 are always HOST arrays (as the ids of vr_index_remove are); queries [nq][dim] float32, filter_of_query
+ * [nq] int32 and the outputs (lims[nq] entries each) are all host or all device per `on_device`.
+ *   Exactness: as for the range search.  With |b_j - e_j| <= eps a row with b_j > t + eps is certainly ahead of a bar t (t = e_i
+ * for a rank) and one with b_j < t - eps certainly behind it; exactly the rows of the band between are re-scored in fp32 and
+ * compared — by key for a rank, by the fp32 compare for a count.  No candidate margin, no widening, no flagged query; a pair
+ * costs what its band holds.  With certification off the default error model defines the band.  Counts are additive over
+ * shards of a corpus, which no top-k result is.
+ *   Checks, all before any launch and with the outputs untouched: NULL pointers, nq < 0, lims[0] != 0 or decreasing lims, an
+ * id outside [0, rows), a threshold that is NaN or +-inf, an unsupported dim (as vr_index_search_range): VR_ERR_INVALID; the
+ * filter checks are those of vr_index_search_range (on the device an out-of-range filter index gives a count of 0).  Zero
+ * pairs: VR_OK, nothing is launched.  An empty index: vr_index_count_range writes zeros, vr_index_rank_rows with pairs is
+ * VR_ERR_INVALID (no id is in range).  Nothing is stored: a later vr_index_remove / update / add has nothing to invalidate.
+ * A host caller's call synchronises the stream.  Not offered: corpus-sharded ranks inside the library (add per-shard counts),
+ * ranks of groups, ranks under MMR. */
+int vr_index_rank_rows(vr_index_t ix, const float* queries, int32_t nq,
+                       const int64_t* lims,              /* host [nq + 1] */
+                       const int64_t* ids,               /* host [lims[nq]] */
+                       const int32_t* filter_of_query,   /* NULL: no filter for any query */
+                       float* out_scores, int64_t* out_ranks,   /* [lims[nq]] */
+                       int32_t on_device, void* stream);
+int vr_index_count_range(vr_index_t ix, const float* queries, int32_t nq,
+                         const int64_t* lims,            /* host [nq + 1] */
+                         const float* thresholds,        /* host [lims[nq]] */
+                         int32_t strict,                 /* 0: e >= t, 1: e > t */
+                         const int32_t* filter_of_query, /* NULL: no filter for any query */
+                         int64_t* out_counts,            /* [lims[nq]] */
+                         int32_t on_device, void* stream);
+/* Rank searches since the last reset: out3 = {pairs, band candidates re-scored in fp32, rows counted} — 64-bit counters in
+ * device memory. */
+int vr_index_rank_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
 /* ---- editing in place: remove rows, overwrite rows, read rows back ---- */
 /* After any of the calls below every search behaves exactly — score bits, ids, groups, lims — as on an index freshly built
  * (vr_index_create, vr_index_add, vr_index_set_filters / vr_index_set_groups) from the rows that remain.  Ids are positions, as

@@ -44,6 +44,9 @@ struct vr_index_s {
                                       // exclusive scan per query | u64 words: [0..2] the counters of vr_index_range_search_stats, [3] a block's
                                       // total, [4..] never written: the flag words launch_filter_mask's argument check wants to see
     int64_t* range_host = nullptr;    // pinned host word: the block total as the host reads it
+    // rank search (vr_index_rank_rows / vr_index_count_range, search_rank.hip): scratch and counters of its own, no stored result
+    DevBuf kq, kv, kbar, keps, kstate;   // int query of every pair | int target rows or f32 thresholds | u64 bars | f32 eps per pair | u64
+                                      // words: [0..2] the counters of vr_index_rank_search_stats, [4..] never written (as rstate's)
     // editing in place (vr_index_remove / vr_index_update / vr_index_get_rows, index_edit.hip)
     DevBuf eids, erows, fbits2;       // int row ids of the call | rows of a host caller, staged (<= EDIT_SCRATCH bytes for get_rows) |
                                       // the filters compacted out of place: swapped with fbits
@@ -79,7 +82,7 @@ extern "C" int vr_index_destroy(vr_index_t ix) {
     for (DevBuf* b : {&ix->f32, &ix->bf16, &ix->q32, &ix->qbf, &ix->cs, &ix->ci, &ix->ck, &ix->os, &ix->oi, &ix->ok, &ix->thr,
                       &ix->sbuf, &ix->cert, &ix->flags, &ix->flagq, &ix->goff, &ix->gB, &ix->og, &ix->gstate,
                       &ix->fbits, &ix->fcount, &ix->ffq, &ix->fstate, &ix->dps, &ix->dpi, &ix->rs, &ix->ri, &ix->rthr, &ix->rlims,
-                      &ix->rcnt, &ix->roff, &ix->rstate, &ix->eids, &ix->erows, &ix->fbits2})
+                      &ix->rcnt, &ix->roff, &ix->rstate, &ix->kq, &ix->kv, &ix->kbar, &ix->keps, &ix->kstate, &ix->eids, &ix->erows, &ix->fbits2})
         b->free();
     if (ix->range_host) (void)hipHostFree(ix->range_host);
     for (hipEvent_t e : ix->prof_ev) if (e) (void)hipEventDestroy(e);
@@ -766,6 +769,145 @@ extern "C" int vr_index_range_results(vr_index_t ix, float* out_scores, int64_t*
     HIPCHK(hipMemcpyAsync(out_ids, ix->ri.p, (size_t)n * 8, kind, s));
     if (!on_device) HIPCHK(hipStreamSynchronize(s));
     return VR_OK;
+}
+
+constexpr int RNK_SPARE = 4, RNK_WORDS = 16;
+
+extern "C" int vr_index_rank_search_stats(vr_index_t ix, int64_t* out3, int32_t reset) {
+    if (!ix || !out3) return fail(VR_ERR_INVALID, "NULL argument");
+    out3[0] = out3[1] = out3[2] = 0;
+    if (!ix->kstate.p) return VR_OK;              // no rank search ever ran: nothing counted
+    VRCHK(set_dev(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    unsigned long long w[3];
+    HIPCHK(hipMemcpy(w, ix->kstate.p, sizeof(w), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 3; ++i) out3[i] = (int64_t)w[i];
+    if (reset) HIPCHK(hipMemset(ix->kstate.p, 0, sizeof(w)));
+    return VR_OK;
+}
+
+// What vr_index_rank_rows (ids set) and vr_index_count_range (thresholds set) share: every check first, then per block of <= 256
+// queries the score rows, the mask, the bars of the block's pairs and their counts (search_rank.hip).  Scratch (query staging,
+// score rows, the staged filter_of_query and outputs) is shared with the other searches; nothing is stored.
+static int rank_impl(vr_index_t ix, bool ranks, const float* queries, int32_t nq, const int64_t* lims, const int64_t* ids,
+                     const float* thresholds, int32_t strict, const int32_t* filter_of_query, float* out_scores, int64_t* out_counts, int32_t on_device,
+                     void* stream) {
+    if (!ix || !lims || nq < 0 || (nq > 0 && !queries)) return fail(VR_ERR_INVALID, "bad arguments");
+    if (!range_dim_ok(ix->dim)) return fail(VR_ERR_INVALID, "dim %d unsupported", ix->dim);
+    if (lims[0] != 0) return fail(VR_ERR_INVALID, "lims[0] = %lld must be 0", (long long)lims[0]);
+    for (int32_t q = 0; q < nq; ++q)
+        if (lims[q + 1] < lims[q]) return fail(VR_ERR_INVALID, "lims[%d] = %lld decreases", (int)q + 1, (long long)lims[q + 1]);
+    const int64_t np = lims[nq];
+    if (np >= ((int64_t)1 << 31)) return fail(VR_ERR_INVALID, "%lld pairs: too many for one call", (long long)np);
+    if (np > 0 && (!out_counts || (ranks ? !ids || !out_scores : !thresholds))) return fail(VR_ERR_INVALID, "bad arguments");
+    if (ranks) {
+        for (int64_t i = 0; i < np; ++i)
+            if (ids[i] < 0 || ids[i] >= ix->n)
+                return fail(VR_ERR_INVALID, "ids[%lld] = %lld outside [0, %lld)", (long long)i, (long long)ids[i], (long long)ix->n);
+    } else {
+        for (int64_t i = 0; i < np; ++i)
+            if (!std::isfinite(thresholds[i])) return fail(VR_ERR_INVALID, "thresholds[%lld] = %g is not finite", (long long)i, (double)thresholds[i]);
+    }
+    if (filter_of_query) {
+        if (ix->n_filters <= 0 || ix->n <= 0) return fail(VR_ERR_STATE, "no filters set for the rows of the index (vr_index_set_filters)");
+        if (!on_device)
+            for (int32_t q = 0; q < nq; ++q)
+                if (filter_of_query[q] < -1 || filter_of_query[q] >= ix->n_filters)
+                    return fail(VR_ERR_INVALID, "filter_of_query[%d] = %d outside [-1, %lld)", (int)q, (int)filter_of_query[q], (long long)ix->n_filters);
+    }
+    if (np == 0) return VR_OK;                    // no pair: no launch
+    VRCHK(set_dev(ix->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (ix->n == 0) {                             // (counts only: a target row would have been out of range) no row: no launch
+        if (on_device) HIPCHK(hipMemsetAsync(out_counts, 0, (size_t)np * 8, s));
+        else std::fill(out_counts, out_counts + np, (int64_t)0);
+        return VR_OK;
+    }
+    if (!ix->kstate.p) VRCHK(ix->kstate.alloc(RNK_WORDS * 8));
+    const int dim = ix->dim;
+    const int64_t ldS = pad256l(ix->n);
+    const int64_t qblk = 256;                     // one fp32 score row per query, as on the deep path
+    const float* q32 = nullptr;
+    VRCHK(stage_queries(ix, queries, nq, pad256l(std::min<int64_t>(nq, qblk)), on_device, s, &q32));
+    const int* foq = filter_of_query;
+    if (foq && !on_device) {
+        VRCHK(ix->ffq.reserve((size_t)nq * 4));
+        HIPCHK(hipMemcpyAsync(ix->ffq.p, filter_of_query, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+        foq = ix->ffq.as<int>();
+    }
+    // the pairs: their query inside its block and their target row or threshold, 4 bytes each
+    std::vector<int> pq((size_t)np), pv(ids ? (size_t)np : 0);
+    for (int32_t q = 0; q < nq; ++q)
+        for (int64_t i = lims[q]; i < lims[q + 1]; ++i) pq[(size_t)i] = (int)(q % qblk);
+    if (ids) for (int64_t i = 0; i < np; ++i) pv[(size_t)i] = (int)ids[i];
+    VRCHK(ix->kq.reserve((size_t)np * 4));
+    VRCHK(ix->kv.reserve((size_t)np * 4));
+    VRCHK(ix->kbar.reserve((size_t)np * 8));
+    VRCHK(ix->keps.reserve((size_t)np * 4));
+    HIPCHK(hipMemcpyAsync(ix->kq.p, pq.data(), (size_t)np * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ix->kv.p, ids ? (const void*)pv.data() : (const void*)thresholds, (size_t)np * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));              // (the host arrays are free from here on)
+    float* os = nullptr; int64_t* oc = nullptr;
+    if (ids) VRCHK(stage_output(ix->os, out_scores, (size_t)np, on_device, &os));
+    VRCHK(stage_output(ix->oi, out_counts, (size_t)np, on_device, &oc));
+    VRCHK(ix->sbuf.reserve((size_t)qblk * ldS * 4));
+    unsigned long long* words = ix->kstate.as<unsigned long long>();
+    const bool certify = ix->eps_rel == -2.f || ix->eps_rel >= 0.f;
+    for (int64_t q0 = 0; q0 < nq; q0 += qblk) {
+        const int nb = (int)std::min<int64_t>(qblk, nq - q0);
+        const int64_t p0 = lims[q0], pn = lims[q0 + nb] - p0;
+        if (pn == 0) continue;                    // a block without pairs: no launch
+        const int64_t nbp = pad256l(nb);
+        HIPCHK(launch_f32_to_bf16_pad(q32 + (size_t)q0 * dim, ix->qbf.p, (size_t)nb * dim, (size_t)nbp * dim, s));   // rows >= nb: zeros
+        RankSearchArgs p{};
+        SearchArgs& a = p.a;
+        a.index_bf16 = ix->bf16.p; a.index_f32 = ix->f32.as<float>(); a.n_docs = ix->n; a.dim = dim;
+        a.q_bf16 = ix->qbf.p; a.q_f32 = q32 + (size_t)q0 * dim; a.nq = nb; a.k = 1;
+        // the band is defined by the error model: with certification off, the default one defines it
+        fill_error_model(ix, a);
+        if (!certify) { a.eps_data = 1; a.eps_rel = 0.f; }
+        p.pair_query = ix->kq.as<int>() + p0;
+        p.pair_id = ids ? ix->kv.as<int>() + p0 : nullptr;
+        p.pair_thr = ids ? nullptr : ix->kv.as<float>() + p0;
+        p.strict = strict ? 1 : 0;
+        p.filter_of_query = foq ? foq + q0 : nullptr;
+        p.n_filters = (int)ix->n_filters;
+        p.bars = ix->kbar.as<unsigned long long>() + p0;
+        p.bar_eps = ix->keps.as<float>() + p0;
+        p.out_scores = ids ? os + p0 : nullptr;
+        p.out_counts = reinterpret_cast<unsigned long long*>(oc) + p0;
+        p.stats = words;
+        // S[q][row] = queries x index^T on the bf16 MFMA GEMM, the deep path's launch; disallowed columns -> -inf
+        VRCHK(score_rows(ix, ix->qbf.p, nb, nullptr, 0, GEMM_VARIANT_AUTO, ldS, s));
+        if (foq) {
+            FilterSearchArgs f{};                 // the mask reads bits, words, n_filters and filter_of_query; the rest passes its argument check
+            f.a = a;
+            f.a.out_scores = ix->keps.as<float>(); f.a.out_ids = oc;
+            f.a.flag_count = reinterpret_cast<int*>(words + RNK_SPARE); f.a.flag_list = f.a.flag_count + 2;
+            f.bits = ix->fbits.as<uint32_t>(); f.words = (size_t)((ix->n + 31) / 32); f.n_filters = (int)ix->n_filters;
+            f.allowed = ix->fcount.as<int>();
+            f.filter_of_query = p.filter_of_query;
+            f.stats = reinterpret_cast<unsigned*>(words + RNK_SPARE) + 4;
+            HIPCHK(launch_filter_mask(f, ix->sbuf.as<float>(), (size_t)ldS, nb, nullptr, 0, s));
+        }
+        HIPCHK(launch_rank_bars(p, (size_t)ldS, nb, pn, s));
+        HIPCHK(launch_rank_count(p, ix->sbuf.as<float>(), (size_t)ldS, nb, pn, s));
+    }
+    if (ids) VRCHK(return_output(out_scores, os, (size_t)np, on_device, s));
+    VRCHK(return_output(out_counts, oc, (size_t)np, on_device, s));
+    if (!on_device) HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
+}
+
+extern "C" int vr_index_rank_rows(vr_index_t ix, const float* queries, int32_t nq, const int64_t* lims, const int64_t* ids,
+                                  const int32_t* filter_of_query, float* out_scores, int64_t* out_ranks, int32_t on_device, void* stream) {
+    return rank_impl(ix, true, queries, nq, lims, ids, nullptr, 0, filter_of_query, out_scores, out_ranks, on_device, stream);
+}
+
+extern "C" int vr_index_count_range(vr_index_t ix, const float* queries, int32_t nq, const int64_t* lims, const float* thresholds,
+                                    int32_t strict, const int32_t* filter_of_query, int64_t* out_counts, int32_t on_device, void* stream) {
+    return rank_impl(ix, false, queries, nq, lims, nullptr, thresholds, strict, filter_of_query, nullptr, out_counts,
+                     on_device, stream);
 }
 
 // k rows per query picked by maximal marginal relevance from the pool of its `pool` best rows (search_diverse.hip).  The pool

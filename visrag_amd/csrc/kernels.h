@@ -417,6 +417,25 @@ hipError_t launch_range_scan(const int* counts, int* offs, int64_t n_docs, int n
 // (score, id) of every column with S >= t -> p.out_scores / p.out_ids [lims[q] + offs ...], in column order
 hipError_t launch_range_pack(const RangeSearchArgs& p, const float* S, size_t ldS, int nq_block, const int* counts, const int* offs,
                              const int64_t* lims, hipStream_t s);
+// ---- rank search (search_rank.hip): the exact rank and score of named rows, exact counts against thresholds; a pair = (query, bar)
+struct RankSearchArgs {
+    SearchArgs a;                    // the block's view, as RangeSearchArgs': index_f32, n_docs, dim, q_f32, nq and a valid error model
+    const int* pair_query;           // [pairs] device: the pair's query inside the block, 0 .. nq - 1
+    const int* pair_id;              // [pairs] device: the target row of a rank, in [0, n_docs) ... (exactly one of the two is set)
+    const float* pair_thr;           // [pairs] device: ... or the threshold of a count, finite
+    int strict;                      // counts: 0 = rows with e >= t, 1 = rows with e > t
+    const int* filter_of_query;      // [nq] device or null, as RangeSearchArgs': the score rows have been masked; an entry outside
+    int n_filters;                   //   [-1, n_filters): the pair's count is 0
+    unsigned long long* bars;        // [pairs] scratch: make_key(target's fp32 score, id), or the threshold's bits
+    float* bar_eps;                  // [pairs] scratch: query_eps of the pair's query (NaN: nothing to count)
+    float* out_scores;               // [pairs] ranks: the target's fp32 score; counts: unused
+    unsigned long long* out_counts;  // [pairs] rows ahead of the bar
+    unsigned long long* stats;       // [0] pairs [1] band candidates re-scored in fp32 [2] rows counted
+};
+// the bars (and the scores of the targets) of the block's pairs; their counts start at 0
+hipError_t launch_rank_bars(const RankSearchArgs& p, size_t ldS, int nq_block, int64_t n_pairs, hipStream_t s);
+// out_counts[pair] += rows of S row pair_query[pair] ahead of the pair's bar, the band around it decided by fp32 re-scoring; S is only read
+hipError_t launch_rank_count(const RankSearchArgs& p, const float* S, size_t ldS, int nq_block, int64_t n_pairs, hipStream_t s);
 // ---- diversified search (search_diverse.hip): k rows per query picked by maximal marginal relevance from a pool of its best rows
 struct MmrArgs {
     const float* index_f32;          // [n_docs][dim] f32

@@ -1,0 +1,169 @@
+// vr_index_rank_rows / vr_index_count_range: WHERE a named row stands in a query's fp32 ranking, and HOW MANY rows reach a
+// threshold — exact counts, no row lists.  A pair is (query, bar): the bar of a rank is the 64-bit key make_key(e, id) of the
+// target row (e its fp32 score: dot_lane + wave_sum, the bits vr_index_search returns for that (query, row)), the bar of a count
+// is the threshold t.  With b_j the bf16-MFMA score of row j, e_j its fp32 score and |b_j - e_j| <= eps (search_common.h:
+// query_eps), a row with b_j > t + eps lies certainly ahead of the bar and one with b_j < t - eps certainly behind it (t = e for
+// a rank): only the rows of the band between need their fp32 dot product.  No candidate margin, no widening, no flagged queries;
+// exact under the conditions of the range search (search_range.hip).  Per block of <= 256 queries (index.hip):
+//   1. score rows S[q][row] on the bf16 MFMA GEMM (the deep path's launch); with filters launch_filter_mask turns the columns a
+//      query may not see into -inf: below every finite bar, never counted;
+//   2. rank_bar_kernel, one wave per pair: eps of the pair's query; for a rank the target's fp32 score from the fp32 store ->
+//      out_scores and the bar key; for a count the bar is the threshold (-0.0 taken as +0.0); the pair's count starts at 0.  A
+//      filter index outside [-1, n_filters) (a device caller's: it cannot be seen before the launch) leaves the count at 0;
+//   3. rank_count_kernel, one workgroup per (column chunk of 4096, pair): lo = one_ulp_down(t - eps), hi = the next float above
+//      t + eps.  b > hi: counted from the bf16 score alone; b < lo: skipped; the columns in [lo, hi] are compacted into an LDS
+//      list (ballot + popcount, as range_rescore_kernel does) and re-scored one candidate per wave, the row's loads issued in
+//      front of dot_lane's fma chain (profiles/diverse_search_bench.txt): a rank compares keys (score descending, then lower id
+//      first), a count compares floats (>= t, or > t when strict).  The target lies in its own band and compares equal: it never
+//      counts itself.  S is only read — several pairs share a score row.  The workgroup's total is added to the pair's 64-bit
+//      count: integer adds commute, the result does not depend on the order; no workgroup waits for another.
+// Pairs are laid along the grid's x dimension (chunk fastest), a launch holds at most 2^22 workgroups: no pair count is assumed
+// to fit a grid's y or z.  No kernel looks at or past column n_docs of a score row: the padded columns hold zeros.
+#include "kernels.h"
+#include "search_common.h"
+
+namespace vr {
+
+constexpr int RANK_CHUNK = 4096;            // columns per workgroup (the range search's chunk)
+constexpr int64_t RANK_MAX_WGS = (int64_t)1 << 22;   // workgroups per launch of the counting kernel
+
+struct RankLds {
+    int cand[RANK_CHUNK];                   // columns inside the band, any order
+    int n_cand;
+    unsigned ahead;                         // rows of this chunk ahead of the bar
+};
+
+__device__ __forceinline__ float one_ulp_up(float x) {
+    const uint32_t o = f32_orderable(x);
+    return o != 0xFFFFFFFFu ? orderable_f32(o + 1u) : x;
+}
+
+__global__ __launch_bounds__(256) void rank_bar_kernel(RankSearchArgs p, int n_pairs) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const SearchArgs& a = p.a;
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&p.stats[0], (unsigned long long)n_pairs);
+    const int pair = blockIdx.x * 4 + wave;
+    if (pair >= n_pairs) return;                                           // (wave-uniform; no barrier below)
+    const int q = p.pair_query[pair], nv = a.dim >> 2;
+    f32x4 qv[MERGE_MAXV];
+    load_query_regs(qv, a.q_f32 + (size_t)q * a.dim, nv, lane);
+    float eps = query_eps(a, qv);
+    const int f = p.filter_of_query ? p.filter_of_query[q] : -1;
+    if (!(f == -1 || (unsigned)f < (unsigned)p.n_filters)) eps = __builtin_nanf("");   // nothing is allowed: the count stays 0
+    unsigned long long bar;
+    if (p.pair_id) {
+        const uint32_t id = (uint32_t)p.pair_id[pair];                     // (in [0, n_docs): the host checked it)
+        const float e = wave_sum(dot_lane(qv, a.index_f32 + (size_t)id * a.dim, nv, lane));
+        bar = make_key(e, id);
+        if (lane == 0) p.out_scores[pair] = e;
+    } else {
+        const float t = p.pair_thr[pair];
+        bar = (unsigned long long)__float_as_uint(t == 0.f ? 0.f : t);     // -0.0 counts as +0.0
+    }
+    if (lane == 0) {
+        p.bars[pair] = bar;
+        p.bar_eps[pair] = eps;
+        p.out_counts[pair] = 0ull;
+    }
+}
+
+__global__ __launch_bounds__(256) void rank_count_kernel(RankSearchArgs p, const float* __restrict__ S, size_t ldS, int pair0,
+                                                         int chunks) {
+    __shared__ RankLds L;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const SearchArgs& a = p.a;
+    const int pair = pair0 + (int)(blockIdx.x / (unsigned)chunks), chunk = (int)(blockIdx.x % (unsigned)chunks);
+    const float eps = p.bar_eps[pair];
+    if (eps != eps) return;                                                // (workgroup-uniform) a filter index out of range
+    const int q = p.pair_query[pair], n_docs = (int)a.n_docs, nv = a.dim >> 2;
+    const int c0 = chunk * RANK_CHUNK, c1 = min(c0 + RANK_CHUNK, n_docs);
+    const unsigned long long bar = p.bars[pair];
+    const bool by_key = p.pair_id != nullptr;
+    const float t = by_key ? key_score(bar) : __uint_as_float((uint32_t)bar);
+    const float lo = one_ulp_down(t - eps), hi = one_ulp_up(t + eps);
+    if (tid == 0) { L.n_cand = 0; L.ahead = 0u; }
+    __syncthreads();
+    // ---- certainly ahead: b > hi; the band: lo <= b <= hi (a masked column is -inf, lo is finite)
+    const float* row = S + (size_t)q * ldS;
+    unsigned mine = 0;                      // rows ahead of the bar this wave found (complete in lane 0: it leaves the loop last)
+    for (int i0 = c0 + tid * 4; i0 < c1; i0 += 256 * 4) {                  // (c0 and ldS are multiples of 4: aligned; < ldS)
+        const f32x4 b = *reinterpret_cast<const f32x4*>(row + i0);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const bool valid = i0 + e < c1;
+            mine += (unsigned)__popcll(__ballot(valid && b[e] > hi));
+            const bool in = valid && b[e] >= lo && b[e] <= hi;
+            const unsigned long long m = __ballot(in);
+            if (m == 0ull) continue;                                       // (wave-uniform)
+            int base = 0;
+            if (lane == 0) base = atomicAdd(&L.n_cand, __popcll(m));
+            base = __shfl(base, 0, 64);
+            if (in) L.cand[base + __popcll(m & ((1ull << lane) - 1ull))] = i0 + e;     // (< RANK_CHUNK: one slot per column)
+        }
+    }
+    __syncthreads();
+    // ---- fp32 re-scoring of the band, one candidate per wave
+    const int m = L.n_cand;
+    if (m > 0) {                                                           // (workgroup-uniform)
+        f32x4 qv[MERGE_MAXV];
+        load_query_regs(qv, a.q_f32 + (size_t)q * a.dim, nv, lane);
+        for (int c = wave; c < m; c += 4) {
+            const int id = L.cand[c];
+            const f32x4* dr = reinterpret_cast<const f32x4*>(a.index_f32 + (size_t)id * a.dim);
+            f32x4 dv[MERGE_MAXV];
+#pragma unroll
+            for (int i = 0; i < MERGE_MAXV; ++i) {
+                const int cc = lane + i * 64;
+                dv[i] = (cc < nv) ? dr[cc] : f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+            float s = 0.f;
+#pragma unroll
+            for (int i = 0; i < MERGE_MAXV; ++i) {
+                const int cc = lane + i * 64;
+                if (cc < nv) s = dot_chunk(qv[i], dv[i], s);               // the chain of dot_lane(query, row)
+            }
+            s = wave_sum(s);
+            const bool ahead = by_key ? make_key(s, (uint32_t)id) > bar : (p.strict ? s > t : s >= t);
+            mine += ahead ? 1u : 0u;                                       // (every lane holds the same s)
+        }
+    }
+    if (lane == 0 && mine) atomicAdd(&L.ahead, mine);
+    __syncthreads();
+    if (tid == 0) {
+        if (m > 0) atomicAdd(&p.stats[1], (unsigned long long)m);
+        const unsigned n = L.ahead;
+        if (n > 0) {
+            atomicAdd(&p.out_counts[pair], (unsigned long long)n);
+            atomicAdd(&p.stats[2], (unsigned long long)n);
+        }
+    }
+}
+
+static bool rank_args_ok(const RankSearchArgs& p, size_t ldS, int nq_block, int64_t n_pairs) {
+    const SearchArgs& a = p.a;
+    return nq_block >= 1 && nq_block <= 256 && n_pairs >= 1 && n_pairs < ((int64_t)1 << 31) && a.n_docs >= 1 &&
+           a.n_docs < ((int64_t)1 << 31) && range_dim_ok(a.dim) && a.index_f32 && a.q_f32 && a.dmax && (a.eps_data || a.eps_rel >= 0.f) &&
+           p.pair_query && ((p.pair_id != nullptr) != (p.pair_thr != nullptr)) && (!p.pair_id || p.out_scores) && p.bars && p.bar_eps &&
+           p.out_counts && p.stats && ldS % 4 == 0 && (int64_t)ldS >= a.n_docs && (!p.filter_of_query || p.n_filters >= 1);
+}
+
+hipError_t launch_rank_bars(const RankSearchArgs& p, size_t ldS, int nq_block, int64_t n_pairs, hipStream_t s) {
+    if (!rank_args_ok(p, ldS, nq_block, n_pairs)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rank_bar_kernel, dim3((unsigned)((n_pairs + 3) / 4)), dim3(256), 0, s, p, (int)n_pairs);
+    return hipGetLastError();
+}
+
+hipError_t launch_rank_count(const RankSearchArgs& p, const float* S, size_t ldS, int nq_block, int64_t n_pairs, hipStream_t s) {
+    if (!rank_args_ok(p, ldS, nq_block, n_pairs) || !S) return hipErrorInvalidValue;
+    const int64_t chunks = (p.a.n_docs + RANK_CHUNK - 1) / RANK_CHUNK;
+    const int64_t per_launch = RANK_MAX_WGS / chunks;                      // (chunks < 2^19: at least 8 pairs)
+    for (int64_t p0 = 0; p0 < n_pairs; p0 += per_launch) {
+        const int64_t np = n_pairs - p0 < per_launch ? n_pairs - p0 : per_launch;
+        hipLaunchKernelGGL(rank_count_kernel, dim3((unsigned)(np * chunks)), dim3(256), 0, s, p, S, ldS, (int)p0, (int)chunks);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+}  // namespace vr

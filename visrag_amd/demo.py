@@ -11,6 +11,8 @@
   * `retrieve_above(knowledge_base_path, query, min_score, ...)` -> EVERY page at or above a score, best first
   * `duplicate_pages(knowledge_base_path, threshold, ...)` -> groups of near-duplicate pages
                                                                (HipIndex.search_range; no reference counterpart either)
+  * `explain(knowledge_base_path, query, pages, ...)` -> the score and the rank of named pages for a question: "why was my page
+                                                               not retrieved?" (HipIndex.rank_rows)
   * `remove_documents(knowledge_base_path, documents, ...)` / `update_pages(...)`: withdraw documents, re-embed pages — on disk
                                                                and in a resident index, in place (HipIndex.remove / update)
 
@@ -263,6 +265,46 @@ def retrieve_above(knowledge_base_path: str, query, min_score: float, model, tok
     if own:
         index.close()
     return (paths, scores) if return_scores else paths
+
+
+@torch.no_grad()
+def explain(knowledge_base_path: str, query, pages, documents=None, index=None, names=None, model=None, tokenizer=None):
+    """Where named pages stand for a question: -> [(score, rank)] for the page names `pages` (one name: one pair; None if the base
+    does not exist).  `score` is the page's fp32 score as `retrieve` reports it, `rank` its position in the ranking of ALL
+    pages (0 = the best; HipIndex.rank_rows: exact, however deep) — `retrieve(topk)` returns the page iff rank < topk.  With
+    `documents=[...]` the rank is among the pages of those documents, as `retrieve(documents=...)` ranks them (one filter, set
+    for this question); for a page outside them it is the position the page would take.  A name the base does not hold raises
+    ValueError.  `query` is the question (`model`, `tokenizer` encode it) or its embedding ([dim] or [1, dim]).  Pass `index,
+    names = load_knowledge_base(path)` to keep the index resident."""
+    if not os.path.exists(knowledge_base_path):
+        return None
+    own = index is None
+    if own:
+        index, names = load_knowledge_base(knowledge_base_path, model.encoder.device if model is not None else None)
+    try:
+        n = len(index)
+        one = isinstance(pages, str)
+        wanted = [pages] if one else list(pages)
+        row_of = {nm: i for i, nm in enumerate(names[:n])}
+        missing = [nm for nm in wanted if nm not in row_of]
+        if missing:
+            raise ValueError(f"no such page in {knowledge_base_path}: {missing[0]}")
+        if isinstance(query, str):
+            q = encode(model, tokenizer, [QUERY_INSTRUCTION + query])
+        else:
+            q = np.asarray(query.detach().cpu() if isinstance(query, torch.Tensor) else query, dtype=np.float32).reshape(1, -1)
+        if not wanted:
+            return []
+        foq = None
+        if documents is not None:
+            index.set_filters(label_filters([doc_of_page(nm) for nm in names[:n]], [documents]))
+            foq = 0
+        sc, rk = index.rank_rows(q, np.asarray([[row_of[nm] for nm in wanted]], dtype=np.int64), filter_of_query=foq)
+        out = [(float(s), int(r)) for s, r in zip(sc[0], rk[0])]
+        return out[0] if one else out
+    finally:
+        if own:
+            index.close()
 
 
 def duplicate_pages(knowledge_base_path: str, threshold: float, index=None, names=None, batch: int = 256) -> Optional[List[List[str]]]:

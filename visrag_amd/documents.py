@@ -13,6 +13,10 @@ The range search (HipIndex.search_range) returns a CSR result (lims, scores, ids
 Editing in place (HipIndex.remove / update): `rows_of_documents` names the rows of documents to withdraw, `new_id_of_old` is the
 map a removal applies to the row ids, `remap_rows` carries ids a caller holds across it, and `compact_filters` states what the
 library does to the filters it keeps.
+
+The rank search (HipIndex.rank_rows) returns the rank of every qrel positive, in CSR form (query q's positives are entries
+lims[q] .. lims[q + 1] - 1): `reciprocal_ranks` / `mrr_from_ranks` and `recall_at` turn them into the metrics a run of fixed
+depth cannot give — MRR without a cut-off, recall at any k.
 Pure numpy: nothing here touches the GPU.
 """
 from __future__ import annotations
@@ -166,3 +170,48 @@ def compact_filters(masks, new_id_of_old) -> np.ndarray:
     if m.shape[1] != len(nid):
         raise ValueError(f"masks over {m.shape[1]} rows, a map over {len(nid)}")
     return np.ascontiguousarray(m[:, nid >= 0])
+
+
+def _ranks_csr(ranks, lims) -> Tuple[np.ndarray, np.ndarray]:
+    ranks = np.asarray(ranks, dtype=np.int64).reshape(-1)
+    lims = np.asarray(lims, dtype=np.int64).reshape(-1)
+    if len(lims) < 1 or lims[0] != 0 or (np.diff(lims) < 0).any() or lims[-1] != len(ranks):
+        raise ValueError("lims must start at 0, be non-decreasing and end at the number of ranks")
+    if len(ranks) and ranks.min() < 0:
+        raise ValueError("ranks are positions: 0 is the best row")
+    return ranks, lims
+
+
+def reciprocal_ranks(ranks, lims, cutoff: Optional[int] = None) -> np.ndarray:
+    """float64 [nq]: 1 / (1 + the best rank among query q's positives `ranks[lims[q]:lims[q + 1]]`) (HipIndex.rank_rows: rank 0 is
+    the best row); 0 for a query without positives, and with `cutoff` for one whose best positive has a rank >= cutoff."""
+    ranks, lims = _ranks_csr(ranks, lims)
+    out = np.zeros(len(lims) - 1, dtype=np.float64)
+    for q in range(len(out)):
+        if lims[q + 1] > lims[q]:
+            best = int(ranks[lims[q]:lims[q + 1]].min())
+            if cutoff is None or best < cutoff:
+                out[q] = 1.0 / (best + 1)
+    return out
+
+
+def mrr_from_ranks(ranks, lims, cutoff: Optional[int] = None) -> float:
+    """Mean reciprocal rank over all queries of `lims` from the ranks of their positives: with `cutoff=k` what `utils.eval_mrr`
+    computes from a run of depth k, with `cutoff=None` the MRR no run of fixed depth can give."""
+    rr = reciprocal_ranks(ranks, lims, cutoff)
+    return float(rr.mean()) if len(rr) else 0.0
+
+
+def recall_at(ranks, lims, ks) -> np.ndarray:
+    """float64 [len(ks)]: recall@k for every k of `ks` — the share of a query's positives with a rank < k, averaged over the queries
+    that have a positive (trec_eval's convention; 0 if none has)."""
+    ranks, lims = _ranks_csr(ranks, lims)
+    ks = np.asarray(ks, dtype=np.int64).reshape(-1)
+    out = np.zeros(len(ks), dtype=np.float64)
+    n = 0
+    for q in range(len(lims) - 1):
+        r = ranks[lims[q]:lims[q + 1]]
+        if len(r):
+            n += 1
+            out += (r[None, :] < ks[:, None]).sum(1) / len(r)
+    return out / n if n else out

@@ -528,6 +528,86 @@ class HipIndex:
         _lib.check(self.lib.vr_index_range_search_stats(self._h, out, 1 if reset else 0))
         return {"queries": int(out[0]), "candidates": int(out[1]), "returned": int(out[2])}
 
+    # ---- rank search (include/visrag_hip.h: vr_index_rank_rows / vr_index_count_range) ----
+    @staticmethod
+    def _pairs(values, lims, nq: int, dtype, what: str):
+        """The targets / thresholds of nq queries -> (flat [pairs] of `dtype`, lims int64 [nq + 1], shape of the outputs).  `values`:
+        a scalar (one for every query), [nq], [nq][T], or flat with `lims`."""
+        if isinstance(values, torch.Tensor):
+            values = values.detach().cpu().numpy()
+        v = np.asarray(values)
+        if lims is not None:
+            if isinstance(lims, torch.Tensor):
+                lims = lims.detach().cpu().numpy()
+            lims = np.ascontiguousarray(np.asarray(lims, dtype=np.int64).reshape(-1))
+            v = v.reshape(-1)
+            if len(lims) != nq + 1 or lims[-1] != len(v):
+                raise ValueError(f"lims must hold {nq + 1} entries and end at the {len(v)} {what}")
+            shape = (len(v),)
+        else:
+            if v.ndim == 0:
+                v = np.full(nq, v)
+            if v.ndim not in (1, 2) or v.shape[0] != nq:
+                raise ValueError(f"{what} must be [{nq}] or [{nq}][T], or flat with lims")
+            shape = v.shape
+            lims = np.arange(nq + 1, dtype=np.int64) * (1 if v.ndim == 1 else v.shape[1])
+        return np.ascontiguousarray(v.reshape(-1), dtype=dtype), lims, shape
+
+    def _rank_call(self, queries, flat, lims, shape, filter_of_query, strict):
+        """vr_index_rank_rows (int64 targets) or vr_index_count_range (float32 thresholds) -> (scores or None, counts)"""
+        cuda = isinstance(queries, torch.Tensor) and queries.is_cuda
+        if cuda:
+            q = queries.to(torch.float32).contiguous()
+        else:
+            q = np.ascontiguousarray(queries.numpy() if isinstance(queries, torch.Tensor) else queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"queries must be [nq][{self.dim}]")
+        nq, n = int(q.shape[0]), len(flat)
+        ranks = flat.dtype == np.int64
+        keep, fptr = (None, C.c_void_p(None)) if filter_of_query is None else self._filter_of_query(q, filter_of_query)
+        if cuda:
+            scores = torch.empty(n, dtype=torch.float32, device=q.device)
+            counts = torch.empty(n, dtype=torch.int64, device=q.device)
+            ptrs = (q.data_ptr(), scores.data_ptr(), counts.data_ptr())
+        else:
+            scores, counts = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.int64)
+            ptrs = (q.ctypes.data, scores.ctypes.data, counts.ctypes.data)
+        stream = C.c_void_p(_stream_ptr(self.device))
+        if ranks:
+            _lib.check(self.lib.vr_index_rank_rows(self._h, C.c_void_p(ptrs[0]), nq, C.c_void_p(lims.ctypes.data), C.c_void_p(flat.ctypes.data),
+                                                   fptr, C.c_void_p(ptrs[1]), C.c_void_p(ptrs[2]), 1 if cuda else 0, stream),
+                       "vr_index_rank_rows")
+        else:
+            _lib.check(self.lib.vr_index_count_range(self._h, C.c_void_p(ptrs[0]), nq, C.c_void_p(lims.ctypes.data),
+                                                     C.c_void_p(flat.ctypes.data), 1 if strict else 0, fptr, C.c_void_p(ptrs[2]),
+                                                     1 if cuda else 0, stream), "vr_index_count_range")
+        del keep
+        return (scores.reshape(shape) if ranks else None), counts.reshape(shape)
+
+    def rank_rows(self, queries, ids, lims=None, filter_of_query=None):
+        """Where the named rows stand (include/visrag_hip.h: vr_index_rank_rows) -> (scores f32, ranks i64) shaped as `ids`: the
+        fp32 score `search` returns for that (query, row) and the number of rows ahead of it — score descending, then lower id
+        first — so a row of rank r is at position r of `search(k)` for every k > r.  `ids`: [nq] (one target per query), [nq][T],
+        or flat with `lims` [nq + 1] (query q's targets are ids[lims[q]:lims[q + 1]]); duplicates allowed.  `filter_of_query`
+        as in `search_filtered`: the rank among the rows the filter allows — for a target the filter forbids, the position it
+        WOULD take.  cuda queries -> cuda tensors, numpy / cpu -> numpy."""
+        flat, lims, shape = self._pairs(ids, lims, int(queries.shape[0]), np.int64, "ids")
+        return self._rank_call(queries, flat, lims, shape, filter_of_query, False)
+
+    def count_range(self, queries, thresholds, lims=None, filter_of_query=None, strict: bool = False):
+        """How many rows reach a threshold (include/visrag_hip.h: vr_index_count_range) -> counts i64 shaped as `thresholds`
+        (a scalar: [nq]): rows with fp32 score >= t, with `strict` > t — exactly `np.diff(search_range(queries, t)[0])`, without
+        the rows.  `thresholds`: a scalar, [nq], [nq][T], or flat with `lims`.  `filter_of_query` as in `search_filtered`.
+        cuda queries -> a cuda tensor, numpy / cpu -> numpy."""
+        flat, lims, shape = self._pairs(thresholds, lims, int(queries.shape[0]), np.float32, "thresholds")
+        return self._rank_call(queries, flat, lims, shape, filter_of_query, strict)[1]
+
+    def rank_search_stats(self, reset: bool = False) -> Dict[str, int]:
+        """Rank searches and counts since the last reset: (query, bar) pairs, rows of the error bands re-scored in fp32, rows counted."""
+        out = (C.c_int64 * 3)()
+        _lib.check(self.lib.vr_index_rank_search_stats(self._h, out, 1 if reset else 0))
+        return {"pairs": int(out[0]), "candidates": int(out[1]), "counted": int(out[2])}
+
     def search_keys(self, queries: torch.Tensor, k: int, id_offset: int = 0) -> torch.Tensor:
         """The same search with each result packed into ONE 64-bit word (include/visrag_hip.h:
         vr_index_search_keys): orderable(score) << 32 | ~(row + id_offset); 0 = empty slot.  -> int64 [nq, k]

@@ -263,6 +263,69 @@ def retrieve_range(args, threshold: float, max_per_query: Optional[int] = None, 
     return result
 
 
+def rank_rows(args, targets_of_query, index_factory: Optional[Callable] = None) -> Dict[str, Dict[str, Tuple[float, int]]]:
+    """Where named rows stand, over the same pickle shards: `targets_of_query` is {qid: [docid, ...]} (the qrel positives, say) or
+    a callable qid -> docids; -> {qid: {docid: (score, rank)}} with `score` the row's fp32 score and `rank` its position (0 = the
+    best) in the ranking of the WHOLE corpus — score descending, then shard and row order — however deep it lies
+    (HipIndex.rank_rows / count_range: exact counts, no run of fixed depth).  `documents.mrr_from_ranks` / `recall_at` take the
+    ranks.  The corpus is taken shard by shard, twice, and the index never holds more than one shard: the shard that holds a
+    target gives its score and its rank inside the shard; every EARLIER shard adds its rows with a score >= that score (on equal
+    scores the earlier position is ahead), every LATER shard its rows with a score > it.  Counts add up over shards, which no
+    top-k list does: the sum is the global rank.  A docid in no shard raises ValueError; a query without targets gets {}.
+
+    Replicated form only, like retrieve_documents: every rank sees the whole corpus."""
+    make_index = index_factory or HipIndex
+    queries, qids, _ = _load_queries(args)
+    corpus_parts = list_shards(args.output_dir, "corpus")
+    if len(corpus_parts) == 0:
+        raise ValueError("No pre-computed document embeddings found")
+    dev = _device_index(args)
+    get = targets_of_query if callable(targets_of_query) else (lambda q: targets_of_query.get(q, ()))
+    wanted = [list(dict.fromkeys(get(q))) for q in qids]                  # a docid named twice counts once
+    lims = np.concatenate([np.zeros(1, np.int64), np.cumsum([len(w) for w in wanted])]).astype(np.int64)
+    query_of = np.repeat(np.arange(len(qids)), np.diff(lims))
+    flat = [d for w in wanted for d in w]
+    n = len(flat)
+    shard_of, scores, ranks = np.full(n, -1, dtype=np.int64), np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.int64)
+    if n:
+        # pass 1: a target's own shard: its score and the rows of that shard ahead of it
+        for si, p in enumerate(corpus_parts):
+            reps, ids = read_shard(p)
+            row_of: Dict[str, int] = {}
+            for r, d in enumerate(ids):
+                row_of.setdefault(d, r)
+            here = np.asarray([j for j in range(n) if shard_of[j] < 0 and flat[j] in row_of], dtype=np.int64)
+            if len(here) == 0:
+                continue
+            ix = make_index(queries.shape[1], len(ids), dev)
+            ix.add(np.asarray(reps, dtype=np.float32))
+            sub = np.concatenate([np.zeros(1, np.int64), np.cumsum(np.bincount(query_of[here], minlength=len(qids)))]).astype(np.int64)
+            sc, rk = ix.rank_rows(queries, np.asarray([row_of[flat[j]] for j in here], dtype=np.int64), sub)
+            ix.close()
+            shard_of[here], scores[here], ranks[here] = si, sc, rk
+        if (shard_of < 0).any():
+            raise ValueError(f"no such document in the corpus shards: {flat[int(np.argmax(shard_of < 0))]}")
+        # pass 2: every other shard: its rows at or above (earlier shard) / above (later shard) the target's score
+        for si, p in enumerate(corpus_parts):
+            ix = None
+            for strict in (False, True):
+                there = np.flatnonzero(shard_of < si) if strict else np.flatnonzero(shard_of > si)
+                if len(there) == 0:
+                    continue
+                if ix is None:
+                    reps, ids = read_shard(p)
+                    if len(ids) == 0:
+                        break
+                    ix = make_index(queries.shape[1], len(ids), dev)
+                    ix.add(np.asarray(reps, dtype=np.float32))
+                sub = np.concatenate([np.zeros(1, np.int64), np.cumsum(np.bincount(query_of[there], minlength=len(qids)))]).astype(np.int64)
+                ranks[there] += ix.count_range(queries, scores[there], sub, strict=strict)
+            if ix is not None:
+                ix.close()
+    return {q: {d: (float(scores[j]), int(ranks[j])) for j, d in zip(range(lims[qi], lims[qi + 1]), wanted[qi])}
+            for qi, q in enumerate(qids)}
+
+
 def _retrieve_corpus_sharded(args, topk: int, global_topk: bool, make_index: Callable, merge_keys: Optional[Callable]
                              ) -> Dict[str, Dict[str, float]]:
     """The corpus-sharded form (module docstring).  Row ids are global: files in sorted order (the order the
