@@ -591,6 +591,18 @@ int vr_op_gemm_ex(int device_id, const void* A, int32_t lda, const void* W, int3
                   const float* resid, float alpha, void* out, int32_t ldo,
                   const int32_t* rope_pos, const float* rope_table, int32_t rope_cols,
                   int32_t variant, const vr_gemm_extras_t* extras, void* stream);
+/* vr_op_gemm_ex with one more launch argument, under the same rule:
+ *   warm, warm_bytes   (a device region the launch only REQUESTS while it runs: one dword of each of its 128-byte lines, counted from
+ *                   its first byte, each line once, so that the launch behind this one finds the region in the memory-side cache —
+ *                   nothing is computed from it, nothing outside it is read, no output bit depends on it) honoured by 12 for
+ *                   every epilogue; refused by 0, 7, 9, 13, 14, 15 (and by 3 where the engine's choice lands on one of them) and for a region of
+ *                   2 GiB or more; warm NULL or
+ *                   warm_bytes 0: absent, i.e. vr_op_gemm_ex */
+int vr_op_gemm_warm(int device_id, const void* A, int32_t lda, const void* W, int32_t ldw,
+                    int32_t M, int32_t N, int32_t K, int32_t epilogue, const float* bias,
+                    const float* resid, float alpha, void* out, int32_t ldo,
+                    const int32_t* rope_pos, const float* rope_table, int32_t rope_cols,
+                    int32_t variant, const vr_gemm_extras_t* extras, const void* warm, uint64_t warm_bytes, void* stream);
 /* y = LN(x) (kind 0, affine, eps) or RMSNorm(x) (kind 1): x f32 [rows][dim] -> bf16 [rows][ldo]. */
 int vr_op_norm(int device_id, int32_t kind, const float* x, int32_t rows, int32_t dim,
                const float* weight, const float* bias, float eps, void* out, int32_t ldo,

@@ -432,6 +432,15 @@ int encode_impl(vr_model_t m, const uint8_t* const* slices, const int32_t* slice
         }
         return VR_OK;
     };
+    // The half-height projections wait on every K-step for weight lines that come from HBM (the 4.9 GB of decoder weights never
+    // survive a step in any cache; gemm128w.hip has the arithmetic).  The MFMA-bound launch IN FRONT of each — q|k|v + RoPE in front
+    // of o, gate|up + SwiGLU in front of down — requests the projection's (padded) matrix while it runs (GemmArgs::warm): the bytes
+    // are the ones the projection fetches anyway, asked for some tens of microseconds earlier, and wait for it in the memory-side cache.
+    // (not under a hook: a chat prefill puts a launch of its own between q|k|v and o.)
+    auto warm_for = [&](GemmArgs& a, int epi, const Linear& next) {
+        const size_t bytes = (size_t)next.n_pad * next.k_pad * 2;
+        if (route.proj_128w && !hook && bytes < WARM_MAX_BYTES && gemm_auto_variant(a, epi) == GEMM_VARIANT_256W) { a.warm = next.w.p; a.warm_bytes = bytes; }
+    };
     double attn_flops = 0;
     for (int i = 0; i < B; ++i) { const double Li = seq_offsets[i + 1] - seq_offsets[i]; attn_flops += 4.0 * Li * Li * E; }
     for (int l = 0; l < c.num_layers; ++l) {
@@ -440,6 +449,7 @@ int encode_impl(vr_model_t m, const uint8_t* const* slices, const int32_t* slice
         {
             GemmArgs a = gemm_args(m->w_dxn.p, E, L.qkv, T, m->w_dqkv.p, 3 * E);
             a.rope_pos = m->w_pos.as<int>(); a.rope_table = m->rope.as<float>(); a.rope_cols = 2 * E;
+            warm_for(a, EPI_ROPE, L.o);
             VRCHK(prof_begin(m, VR_PROF_DEC_QKV, s));
             HIPCHK(launch_gemm(a, EPI_ROPE, GEMM_VARIANT_AUTO, s));
             VRCHK(prof_end(m, VR_PROF_DEC_QKV, 6.0 * T * (double)E * E, s));
@@ -462,6 +472,7 @@ int encode_impl(vr_model_t m, const uint8_t* const* slices, const int32_t* slice
         VRCHK(prof_begin(m, VR_PROF_DEC_GU, s));
         {
             GemmArgs a = gemm_args(m->w_dxn.p, E, L.gu, T, m->w_dact.p, m->Ip);
+            warm_for(a, EPI_SWIGLU, L.down);
             HIPCHK(launch_gemm(a, EPI_SWIGLU, GEMM_VARIANT_AUTO, s));
         }
         VRCHK(prof_end(m, VR_PROF_DEC_GU, 4.0 * T * (double)E * m->I, s));

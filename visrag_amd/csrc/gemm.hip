@@ -151,44 +151,47 @@ bool gemm_args_refused(const GemmArgs& a, int epi, int variant) {
     if (a.ksplit > 1 && (!split_tile || epi != EPI_F32 || a.K % (a.ksplit * GEMM_BK) || a.rowmap || a.rowbias)) return true;
     // a device-side row count is read by the 8-wave 256-tile kernel only
     if (a.m_dev && variant != GEMM_VARIANT_256IL) return true;
+    // a region to warm is requested by the one-wave 256^2 kernel only, through one descriptor and 32-bit offsets
+    if (a.warm && a.warm_bytes && (variant != GEMM_VARIANT_256W || a.warm_bytes >= WARM_MAX_BYTES)) return true;
     return false;
+}
+
+int gemm_auto_variant(const GemmArgs& a, int epi) {
+    // N = 1152 (SigLIP proj / fc2): 6 x 192 columns, big M -> the 256x192 kernel
+    if (a.N % 192 == 0 && a.N % 256 != 0 && a.N <= 1536 && a.M >= 4096 && epi <= EPI_RESID) {
+        if (epi == EPI_RESID && !a.rowmap && gemm256w_fits(a, 192)) return GEMM_VARIANT_192W;
+        return GEMM_VARIANT_192;
+    }
+    // 256x256 tiles when N is a multiple of 256 or wide enough that one partial tile column costs
+    // little (3456 -> 14 tiles, +3.7 %); N = 1152 (4.5 tiles) goes to the 256x192 kernel above.
+    // Small grids (decoder, M ~ 2k) are decided by wave quantisation: 256 one-per-CU slots for the
+    // big tile vs 512 two-per-CU slots for the 128x128 one, whose flops cost ~1.45x the time and
+    // ~1.25x the energy of the one-wave-per-SIMD kernel's (tools/op_energy.py, decoder gate/up:
+    // 405 big tiles in two rounds 107 us / 134 mJ, 1530 small tiles in three rounds 121 us / 168 mJ).
+    const bool n_ok = (a.N % 256 == 0) || a.N >= 2048;
+    const long t256 = (long)((a.N + 255) / 256) * ((a.M + 255) / 256);
+    const long t128 = (long)(a.N / 128) * ((a.M + 127) / 128);
+    const double e256 = 1.45 * (double)t256 / (double)(((t256 + 255) / 256) * 256);
+    const double e128 = (double)t128 / (double)(((t128 + 511) / 512) * 512);
+    // Which 256x256 kernel: the one-wave-per-SIMD kernel (gemm256w.hip) is faster and leaner in isolation
+    // everywhere (ViT qkv 230 vs 255 us, 302 vs 326 mJ), but its denser matrix-core stream pulls the shader
+    // clock down (1.9 vs 2.1 GHz sustained, well below the 1400 W cap) and the clock recovers slowly, so in
+    // the model the kernels that FOLLOW it lose part of what it gains: decide in-model, on one box
+    // (tools/ab_libs.sh).  Round 2: every epilogue on
+    // it 48.1 ms/step, all but the ViT qkv GEMM 48.7, none (8-wave kernel, 128x128 gate/up) 50.5.
+    const bool w_ok = gemm256w_fits(a, 256);     // (else: the 8-wave kernel, 64-bit addresses)
+    return (n_ok && e256 > e128) ? (w_ok ? GEMM_VARIANT_256W : GEMM_VARIANT_256IL) : GEMM_VARIANT_GLDS;
 }
 
 hipError_t launch_gemm(const GemmArgs& a, int epi, int variant, hipStream_t s) {
     if (a.M <= 0) return hipSuccess;
     // (each variant launcher applies gemm_args_refused to itself; AUTO is judged as the variant it picks)
+    if (variant == GEMM_VARIANT_AUTO) variant = gemm_auto_variant(a, epi);
     if (variant == GEMM_VARIANT_192) return launch_gemm192(a, epi, s);
     if (variant == GEMM_VARIANT_256W) return launch_gemm256w(a, epi, s);
     if (variant == GEMM_VARIANT_192W) return launch_gemm192w(a, epi, s);
     if (variant == GEMM_VARIANT_128W_192) return launch_gemm128w(a, epi, 192, s);
     if (variant == GEMM_VARIANT_128W_256) return launch_gemm128w(a, epi, 256, s);
-    if (variant == GEMM_VARIANT_AUTO) {
-        // N = 1152 (SigLIP proj / fc2): 6 x 192 columns, big M -> the 256x192 kernel
-        if (a.N % 192 == 0 && a.N % 256 != 0 && a.N <= 1536 && a.M >= 4096 && epi <= EPI_RESID) {
-            if (epi == EPI_RESID && !a.rowmap && gemm256w_fits(a, 192)) return launch_gemm192w(a, epi, s);
-            return launch_gemm192(a, epi, s);
-        }
-        // 256x256 tiles when N is a multiple of 256 or wide enough that one partial tile column costs
-        // little (3456 -> 14 tiles, +3.7 %); N = 1152 (4.5 tiles) goes to the 256x192 kernel above.
-        // Small grids (decoder, M ~ 2k) are decided by wave quantisation: 256 one-per-CU slots for the
-        // big tile vs 512 two-per-CU slots for the 128x128 one, whose flops cost ~1.45x the time and
-        // ~1.25x the energy of the one-wave-per-SIMD kernel's (tools/op_energy.py, decoder gate/up:
-        // 405 big tiles in two rounds 107 us / 134 mJ, 1530 small tiles in three rounds 121 us / 168 mJ).
-        const bool n_ok = (a.N % 256 == 0) || a.N >= 2048;
-        const long t256 = (long)((a.N + 255) / 256) * ((a.M + 255) / 256);
-        const long t128 = (long)(a.N / 128) * ((a.M + 127) / 128);
-        const double e256 = 1.45 * (double)t256 / (double)(((t256 + 255) / 256) * 256);
-        const double e128 = (double)t128 / (double)(((t128 + 511) / 512) * 512);
-        // Which 256x256 kernel: the one-wave-per-SIMD kernel (gemm256w.hip) is faster and leaner in isolation
-        // everywhere (ViT qkv 230 vs 255 us, 302 vs 326 mJ), but its denser matrix-core stream pulls the shader
-        // clock down (1.9 vs 2.1 GHz sustained, well below the 1400 W cap) and the clock recovers slowly, so in
-        // the model the kernels that FOLLOW it lose part of what it gains: decide in-model, on one box
-        // (tools/ab_libs.sh).  Round 2: every epilogue on
-        // it 48.1 ms/step, all but the ViT qkv GEMM 48.7, none (8-wave kernel, 128x128 gate/up) 50.5.
-        const bool w_ok = gemm256w_fits(a, 256);     // (else: the 8-wave kernel, 64-bit addresses)
-        variant = (n_ok && e256 > e128) ? (w_ok ? GEMM_VARIANT_256W : GEMM_VARIANT_256IL) : GEMM_VARIANT_GLDS;
-        if (variant == GEMM_VARIANT_256W) return launch_gemm256w(a, epi, s);
-    }
     if (gemm_args_refused(a, epi, variant)) return hipErrorInvalidValue;
     switch (epi) {
         case EPI_BF16: return launch_epi<EPI_BF16>(a, variant, s);

@@ -67,7 +67,37 @@ constexpr unsigned W_OOB = 0x80000000u;            // per-lane offset beyond the
 // PLAIN: the host has checked that the bf16-output epilogue needs no per-row lookups (no row map / row bias,
 // N and ldo multiples of 8) — the kernel then carries only the lookup-free staged epilogue.
 constexpr int W_STAGING = 4096;                            // epilogue staging per wave: one piece of 32 rows x 64 bf16
-constexpr int W_SMEM_BYTES = 2 * W_STAGE + 4 * W_STAGING;  // two stages + staging = 144 KiB
+constexpr int W_WARM_DUMP = 256;                           // where a wave's GemmArgs::warm requests land: 64 lanes x 4 bytes nobody reads
+constexpr int W_SMEM_BYTES = 2 * W_STAGE + 4 * W_STAGING + 4 * W_WARM_DUMP;  // two stages + staging + dump slots = 145 KiB
+
+// GemmArgs::warm: walking the workgroups and their waves in order, each share starts where the one before ended (ordered, disjoint,
+// no gap) and the last one ends with the region's last line — every line is requested exactly once, whatever the grid
+constexpr bool warm_shares_tile(size_t bytes, unsigned total) {
+    unsigned at = 0;
+    for (unsigned w = 0; w < total; ++w)
+        for (unsigned v = 0; v < WARM_WAVES; ++v) {
+            const WarmShare s = warm_share(bytes, w, total, v);
+            if (s.first != at || s.end < s.first) return false;
+            at = s.end;
+        }
+    return at == warm_lines(bytes) && (size_t)at * WARM_LINE >= bytes && (bytes == 0 || (size_t)(at - 1) * WARM_LINE < bytes);
+}
+static_assert(warm_shares_tile(0, 1) && warm_shares_tile(0, 243), "no lines");
+static_assert(warm_shares_tile(1, 1) && warm_shares_tile(WARM_LINE, 4) && warm_shares_tile(WARM_LINE + 1, 4), "1 and 2 lines");
+static_assert(warm_shares_tile(63 * WARM_LINE, 1) && warm_shares_tile(64 * WARM_LINE, 1) && warm_shares_tile(65 * WARM_LINE, 1), "63 / 64 / 65 lines, one workgroup");
+static_assert(warm_shares_tile(63 * WARM_LINE, 4) && warm_shares_tile(64 * WARM_LINE, 4) && warm_shares_tile(65 * WARM_LINE - 3, 4), "63 / 64 / 65 lines, four");
+static_assert(warm_shares_tile(100 * WARM_LINE, 243) && warm_shares_tile(5 * WARM_LINE, 405), "a region of fewer lines than the grid has waves");
+static_assert(warm_shares_tile((size_t)2304 * 2304 * 2, 243), "W_o (10.6 MB) over the decoder's q|k|v grid");
+static_assert(warm_shares_tile((size_t)2304 * 5760 * 2, 405), "W_down (26.5 MB) over the decoder's gate|up grid");
+static_assert(warm_shares_tile(WARM_MAX_BYTES - 1, 1021), "the largest region");
+static_assert(warm_cut((1u << 24) - 1, 65534, 65535) == (unsigned)(((1ull << 24) - 1) * 65534 / 65535) && warm_cut(65534, 65534, 65535) == 65533 &&
+              warm_cut((1u << 24) - 1, 65535, 65535) == (1u << 24) - 1, "the largest grid of the 32-bit form");
+static_assert(warm_part(0, warm_lines(WARM_MAX_BYTES - 1), 65536, 65537).end == warm_lines(WARM_MAX_BYTES - 1) &&
+              warm_cut(1u << 24, 70001, 70003) == (unsigned)((1ull << 24) * 70001 / 70003) && warm_cut(82944, 100, 243) == 82944ull * 100 / 243, "both forms of the cut");
+#if VR_WARM_LINE == 128
+static_assert(warm_instructions(warm_share((size_t)2304 * 2304 * 2, 0, 243, 0)) == 2 &&
+              warm_instructions(warm_share((size_t)2304 * 5760 * 2, 404, 405, 3)) == 2, "two requests per wave in the decoder");
+#endif
 
 #define W_KERNEL_TEMPLATE template <int EPI, bool PLAIN, int NJ>
 #define W_KERNEL_NAME gemm256w_bf16_kernel

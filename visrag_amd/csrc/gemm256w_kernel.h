@@ -80,6 +80,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     int m0, n0, split;
     coords(my_first, m0, n0, split);
     unsigned curA = tile_off_a(m0, split), curW = tile_off_w(n0, split);
+    unsigned warm_lo = 0, warm_hi = 0;
 
     // ---- prologue: K-steps 0 and 1 in flight, the accumulators zeroed under their latency (256 register writes:
     //      half a microsecond), k-half-0 fragments of step 0 requested
@@ -89,6 +90,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         for (int d = 0; d < NR; ++d) dma(0, d, lofA + curA, lofW + curW);
 #pragma unroll
         for (int d = 0; d < NR; ++d) dma(1, d, lofA + curA + k1, lofW + curW + k1);
+        if constexpr (NJ == 8) {     // GemmArgs::warm: this wave's lines of the region (gemm_warm.h; a few 32-bit divisions, under the loads' latency)
+            if (p.warm && p.warm_bytes) {
+                const WarmShare sh = warm_share(p.warm_bytes, (unsigned)my_first, (unsigned)total, (unsigned)wave);
+                warm_lo = (unsigned)__builtin_amdgcn_readfirstlane((int)sh.first);
+                warm_hi = (unsigned)__builtin_amdgcn_readfirstlane((int)sh.end);
+            }
+        }
         W_FOR_EACH_ACC(W_ZERO)
         if constexpr (NJ == 8) VR_WAIT_VM_BARRIER(16); else VR_WAIT_VM_BARRIER(14);
 #pragma unroll
@@ -184,6 +192,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             const unsigned long long a = (unsigned long long)q;
             return (void*)(((unsigned long long)uni32((unsigned)(a >> 32)) << 32) | uni32((unsigned)a));
         };
+        // GemmArgs::warm: lane l of request i asks for ONE dword of line warm_lo + 64 i + l — the line comes into the memory-side cache,
+        // the dword into a dump slot nobody reads (LDS-DMA: no register is written).  The descriptor ends with the region, a lane past
+        // the wave's share is pointed out of its range: no predicate, nothing read outside.  Each epilogue form below calls this
+        // BEHIND the loads it waits for first (bias, residual pieces, RoPE positions and rows: loads return in order, and these
+        // requests are the cold ones) and in front of its first accumulator read-back; never from the K-loop, whose waits are
+        // counted.  The first two requests (all the decoder's launches need) sit between scheduling barriers, so that hipcc keeps
+        // the epilogue's own loads in front of them (check the listing when this moves: with the requests in a loop alone it sank the
+        // RoPE rows' loads behind them).  Nothing waits for the requests: the epilogue's later loads and stores queue behind them,
+        // and s_endpgm itself waits for every counter of the wave, so the dump slot outlives them.
+        auto warm_requests = [&]() {
+            if constexpr (NJ == 8) {
+                if (warm_lo < warm_hi) {       // (wave-uniform; a launch without a region skips all of it)
+                    const unsigned long long wa = (unsigned long long)uni_ptr(p.warm);
+                    const auto wrs = __builtin_amdgcn_make_buffer_rsrc((void*)wa, 0, uni32((unsigned)p.warm_bytes), 0x00020000);
+                    const unsigned pad = (0u - (unsigned)wa) & 3u;      // (a region that starts off a dword: the requests are aligned ones)
+                    char* const dump = smem + 2 * W_STAGE + 4 * W_STAGING + wave * W_WARM_DUMP;
+                    auto request = [&](unsigned l) {
+                        const unsigned line = l + (unsigned)lane;
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, VR_LDS(dump), 4, line < warm_hi ? line * WARM_LINE + pad : W_OOB, 0, 0, 0);
+                    };
+                    __builtin_amdgcn_sched_barrier(0);
+                    request(warm_lo);
+                    request(warm_lo + 64);
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma nounroll
+                    for (unsigned l = warm_lo + 128; l < warm_hi; l += 64) request(l);
+                }
+            }
+        };
         bool buf_tile = false;
         if constexpr (EPI == EPI_RESID) buf_tile = plain_resid && n0 + BN <= p.N;
         if constexpr (EPI == EPI_F32) buf_tile = !p.rowmap && !p.rowbias && n0 + BN <= p.N;
@@ -220,6 +257,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     };
 #pragma unroll
                     for (int q = 0; q < RD; ++q) load_piece(q, rs[q]);
+                    warm_requests();
 #pragma unroll
                     for (int q = 0; q < 8; ++q) {
                         const int h = q & 1, sg = q >> 1;
@@ -241,6 +279,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     }
                 } else {
                     // fp32 outputs, incl. the split-K partial products (split s writes its own plane, the bias goes with split 0)
+                    warm_requests();
 #pragma unroll
                     for (int q = 0; q < 8; ++q) {
                         const int h = q & 1, sg = q >> 1;
@@ -288,6 +327,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
                 for (int j = 0; j < NJ; ++j)
                     bias[j] = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + min(nb0 + j * 16 + fq * 4, p.N - 4)) : f32x4{0.f, 0.f, 0.f, 0.f};
+                warm_requests();
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
                     const int h = q & 1, sg = q >> 1;
@@ -348,6 +388,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             };
             if constexpr (EPI == EPI_ROPE && PLAIN) load_rope(0, rt[0]);
             (void)ors16; (void)ldo2; (void)biasw; (void)rbrs; (void)rb_row0; (void)posw; (void)rt;
+            warm_requests();
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 constexpr int MI = 2;

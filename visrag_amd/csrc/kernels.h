@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gemm_warm.h"
+
 namespace vr {
 
 // ---- GEMM (gemm.hip) ---------------------------------------------------------------------
@@ -36,6 +38,10 @@ struct GemmArgs {
                                      // head_dim^-0.5 * log2(e) into the attention kernel with ONE rounding (attention_w.hip)
     const int* m_dev; int m_sub;     // optional, GEMM_VARIANT_256IL only (refused elsewhere): rows < *m_dev - m_sub exist (a row count known on the
                                      // device only: tiles at or past it leave at once — the search's band pass)
+    const void* warm; size_t warm_bytes;   // optional, GEMM_VARIANT_256W only (refused elsewhere): "while you run, request every 128-byte line of
+                                     // this region once" — the bytes are not used, only brought into the memory-side cache for the launch
+                                     // behind this one (the decoder's o / down weights ride the q|k|v and gate|up launches); null or 0
+                                     // bytes: absent.  Each workgroup requests its share (gemm_warm.h) between its K-loop and its epilogue
 };
 hipError_t launch_gemm(const GemmArgs& a, int epilogue, int variant, hipStream_t s);
 // The rule of the optional fields: each is HONOURED by the kernel a launch reaches or the launch is REFUSED (hipErrorInvalidValue)
@@ -43,6 +49,8 @@ hipError_t launch_gemm(const GemmArgs& a, int epilogue, int variant, hipStream_t
 // launcher below asks this itself, so a direct caller gets the same answer as launch_gemm's.  (include/visrag_hip.h,
 // vr_op_gemm_ex, has the table.)
 bool gemm_args_refused(const GemmArgs& a, int epilogue, int variant);
+// the concrete variant GEMM_VARIANT_AUTO resolves to for this launch (a caller that sets a field only one variant honours asks first)
+int gemm_auto_variant(const GemmArgs& a, int epilogue);
 // 256x192 tile (gemm192.hip): N % 192 == 0, epilogues BF16 / GELU / F32 / RESID only
 hipError_t launch_gemm192(const GemmArgs& a, int epilogue, hipStream_t s);
 // 256x256 tile, one wave per SIMD (gemm256w.hip): same contract as the 256-tile path of launch_gemm

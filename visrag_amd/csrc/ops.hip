@@ -115,10 +115,10 @@ extern "C" int vr_streams_overlap(int device_id, void* stream_a, void* stream_b,
 
 // ------------------------------------------------------------------------------ op-level ---
 // (extras: the fields of GemmArgs beyond vr_op_gemm's arguments, copied as they are — what is legal is the launchers' decision)
-extern "C" int vr_op_gemm_ex(int device_id, const void* A, int32_t lda, const void* W, int32_t ldw, int32_t M, int32_t N,
-                             int32_t K, int32_t epilogue, const float* bias, const float* resid, float alpha, void* out,
-                             int32_t ldo, const int32_t* rope_pos, const float* rope_table, int32_t rope_cols,
-                             int32_t variant, const vr_gemm_extras_t* extras, void* stream) {
+extern "C" int vr_op_gemm_warm(int device_id, const void* A, int32_t lda, const void* W, int32_t ldw, int32_t M, int32_t N,
+                               int32_t K, int32_t epilogue, const float* bias, const float* resid, float alpha, void* out,
+                               int32_t ldo, const int32_t* rope_pos, const float* rope_table, int32_t rope_cols,
+                               int32_t variant, const vr_gemm_extras_t* extras, const void* warm, uint64_t warm_bytes, void* stream) {
     if (!A || !W || !out) return fail(VR_ERR_INVALID, "NULL argument");
     if (variant != GEMM_VARIANT_GLDS && variant != GEMM_VARIANT_AUTO && variant != GEMM_VARIANT_192 && variant != GEMM_VARIANT_256IL && variant != GEMM_VARIANT_256W && variant != GEMM_VARIANT_192W &&
         variant != GEMM_VARIANT_128W_192 && variant != GEMM_VARIANT_128W_256)
@@ -138,8 +138,17 @@ extern "C" int vr_op_gemm_ex(int device_id, const void* A, int32_t lda, const vo
         a.m_dev = extras->m_dev; a.m_sub = extras->m_sub;
         a.raster_gm = extras->raster_gm;
     }
+    a.warm = warm; a.warm_bytes = (size_t)warm_bytes;
     HIPCHK(launch_gemm(a, epilogue, variant, (hipStream_t)stream));
     return VR_OK;
+}
+
+extern "C" int vr_op_gemm_ex(int device_id, const void* A, int32_t lda, const void* W, int32_t ldw, int32_t M, int32_t N,
+                             int32_t K, int32_t epilogue, const float* bias, const float* resid, float alpha, void* out,
+                             int32_t ldo, const int32_t* rope_pos, const float* rope_table, int32_t rope_cols,
+                             int32_t variant, const vr_gemm_extras_t* extras, void* stream) {
+    return vr_op_gemm_warm(device_id, A, lda, W, ldw, M, N, K, epilogue, bias, resid, alpha, out, ldo, rope_pos, rope_table, rope_cols,
+                           variant, extras, nullptr, 0, stream);
 }
 
 extern "C" int vr_op_gemm(int device_id, const void* A, int32_t lda, const void* W, int32_t ldw, int32_t M, int32_t N,
