@@ -480,6 +480,37 @@ int vr_index_count_range(vr_index_t ix, const float* queries, int32_t nq,
 /* Rank searches since the last reset: out3 = {pairs, band candidates re-scored in fp32, rows counted} — 64-bit counters in
  * device memory. */
 int vr_index_rank_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
+/* ---- windowed search: the rows at ranks [offset, offset + k) of a query's ranking, any offset ---- */
+/* vr_index_search_window: entry j of query q is the row at rank offsets[q] + j of q's fp32 ranking — fp32 score descending, then
+ * lower id first, over the rows q's filter allows (filter_of_query NULL or an entry of -1: all rows) — with e, the fp32 score of
+ * the library's one re-scoring dot product (the bits every other search returns for that (query, row)).  Slots at or past the
+ * number of allowed rows are (-inf, -1); an offset at or past that number gives a row of them.  In every setting of
+ * vr_index_set_search_eps the result equals entries offsets[q] .. offsets[q] + k - 1 of vr_index_search / _search_filtered for
+ * k' = offsets[q] + k wherever that search reaches, the same entries of the sorted segment of vr_index_search_range for a
+ * threshold below every score, and vr_index_rank_rows of the ids returned is offsets[q] + j: the inverse of the rank search.
+ *   Layout: offsets [nq] int64 is always a HOST array (as the ids and lims of vr_index_rank_rows are), each >= 0, with no upper
+ * limit; 1 <= k <= 1000 (page for more); queries [nq][dim] float32, filter_of_query [nq] int32 and the outputs [nq][k] are all
+ * host or all device per `on_device`.
+ *   Exactness: as for the range and the rank search.  With |b_j - e_j| <= eps the r-th largest bf16 score lies within eps of
+ * the r-th largest fp32 score, so the window's rows have b within 2 eps of the bf16 scores at ranks offset + 1 and offset + k:
+ * rows above that band are certainly ahead of the window, rows below it certainly behind; exactly the band is re-scored in
+ * fp32 and ranked by key.  No candidate margin, no widening, no flagged query; a query costs what its band holds.  With
+ * certification off the default error model defines the band.
+ *   Checks, all before any launch and with the outputs untouched: NULL pointers with nq > 0, nq < 0, k outside 1..1000, a
+ * negative offset, an unsupported dim (as vr_index_search_range): VR_ERR_INVALID; the filter checks are those of
+ * vr_index_search_range (on the device an out-of-range filter index gives a row of tails).  nq == 0: VR_OK, nothing is
+ * launched.  An empty index: tails, nothing is launched.  Nothing is stored: a later vr_index_remove / update / add has nothing
+ * to invalidate.  A host caller's call synchronises the stream.  Not offered: corpus-sharded ranks inside the library (merge
+ * per-shard pages on the host), windows of groups, windows under MMR, k > 1000 in one call, a k per query. */
+int vr_index_search_window(vr_index_t ix, const float* queries, int32_t nq,
+                           const int64_t* offsets,           /* host [nq] */
+                           int32_t k,
+                           const int32_t* filter_of_query,   /* NULL: no filter for any query */
+                           float* out_scores, int64_t* out_ids,   /* [nq][k] */
+                           int32_t on_device, void* stream);
+/* Windowed searches since the last reset: out3 = {queries, band candidates re-scored in fp32, rows certainly ahead of their
+ * window} — 64-bit counters in device memory. */
+int vr_index_window_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
 /* ---- editing in place: remove rows, overwrite rows, read rows back ---- */
 /* After any of the calls below every search behaves exactly — score bits, ids, groups, lims — as on an index freshly built
  * (vr_index_create, vr_index_add, vr_index_set_filters / vr_index_set_groups) from the rows that remain.  Ids are positions, as

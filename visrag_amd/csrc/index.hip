@@ -47,6 +47,9 @@ struct vr_index_s {
     // rank search (vr_index_rank_rows / vr_index_count_range, search_rank.hip): scratch and counters of its own, no stored result
     DevBuf kq, kv, kbar, keps, kstate;   // int query of every pair | int target rows or f32 thresholds | u64 bars | f32 eps per pair | u64
                                       // words: [0..2] the counters of vr_index_rank_search_stats, [4..] never written (as rstate's)
+    // windowed search (vr_index_search_window, search_window.hip): scratch and counters of its own, no stored result
+    DevBuf woff, wedge, wstate;       // int64 offsets of the call's queries | f32 band edges {lo, hi} of a block's queries | u64 words:
+                                      // [0..2] the counters of vr_index_window_search_stats, [4..] never written (as rstate's)
     // editing in place (vr_index_remove / vr_index_update / vr_index_get_rows, index_edit.hip)
     DevBuf eids, erows, fbits2;       // int row ids of the call | rows of a host caller, staged (<= EDIT_SCRATCH bytes for get_rows) |
                                       // the filters compacted out of place: swapped with fbits
@@ -82,7 +85,8 @@ extern "C" int vr_index_destroy(vr_index_t ix) {
     for (DevBuf* b : {&ix->f32, &ix->bf16, &ix->q32, &ix->qbf, &ix->cs, &ix->ci, &ix->ck, &ix->os, &ix->oi, &ix->ok, &ix->thr,
                       &ix->sbuf, &ix->cert, &ix->flags, &ix->flagq, &ix->goff, &ix->gB, &ix->og, &ix->gstate,
                       &ix->fbits, &ix->fcount, &ix->ffq, &ix->fstate, &ix->dps, &ix->dpi, &ix->rs, &ix->ri, &ix->rthr, &ix->rlims,
-                      &ix->rcnt, &ix->roff, &ix->rstate, &ix->kq, &ix->kv, &ix->kbar, &ix->keps, &ix->kstate, &ix->eids, &ix->erows, &ix->fbits2})
+                      &ix->rcnt, &ix->roff, &ix->rstate, &ix->kq, &ix->kv, &ix->kbar, &ix->keps, &ix->kstate, &ix->woff, &ix->wedge, &ix->wstate,
+                      &ix->eids, &ix->erows, &ix->fbits2})
         b->free();
     if (ix->range_host) (void)hipHostFree(ix->range_host);
     for (hipEvent_t e : ix->prof_ev) if (e) (void)hipEventDestroy(e);
@@ -908,6 +912,115 @@ extern "C" int vr_index_count_range(vr_index_t ix, const float* queries, int32_t
                                     int32_t strict, const int32_t* filter_of_query, int64_t* out_counts, int32_t on_device, void* stream) {
     return rank_impl(ix, false, queries, nq, lims, nullptr, thresholds, strict, filter_of_query, nullptr, out_counts,
                      on_device, stream);
+}
+
+constexpr int WIN_SPARE = 4, WIN_WORDS = 16;
+
+extern "C" int vr_index_window_search_stats(vr_index_t ix, int64_t* out3, int32_t reset) {
+    if (!ix || !out3) return fail(VR_ERR_INVALID, "NULL argument");
+    out3[0] = out3[1] = out3[2] = 0;
+    if (!ix->wstate.p) return VR_OK;              // no windowed search ever ran: nothing counted
+    VRCHK(set_dev(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    unsigned long long w[3];
+    HIPCHK(hipMemcpy(w, ix->wstate.p, sizeof(w), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 3; ++i) out3[i] = (int64_t)w[i];
+    if (reset) HIPCHK(hipMemset(ix->wstate.p, 0, sizeof(w)));
+    return VR_OK;
+}
+
+// The rows at ranks [offsets[q], offsets[q] + k) of every query's fp32 ranking (search_window.hip): every check first, then per
+// block of <= 256 queries the score rows, the mask, the band edges, the rewritten rows and the select.  Scratch (query staging,
+// score rows, the staged filter_of_query and outputs) is shared with the other searches; nothing is stored.
+extern "C" int vr_index_search_window(vr_index_t ix, const float* queries, int32_t nq, const int64_t* offsets, int32_t k,
+                                      const int32_t* filter_of_query, float* out_scores, int64_t* out_ids, int32_t on_device,
+                                      void* stream) {
+    if (!ix || nq < 0 || (nq > 0 && (!queries || !offsets || !out_scores || !out_ids))) return fail(VR_ERR_INVALID, "bad arguments");
+    if (k <= 0 || k > search_bigk_max()) return fail(VR_ERR_INVALID, "k=%d unsupported (1..%d)", k, search_bigk_max());
+    if (!range_dim_ok(ix->dim)) return fail(VR_ERR_INVALID, "dim %d unsupported", ix->dim);
+    for (int32_t q = 0; q < nq; ++q)
+        if (offsets[q] < 0) return fail(VR_ERR_INVALID, "offsets[%d] = %lld is negative", (int)q, (long long)offsets[q]);
+    if (filter_of_query) {
+        if (ix->n_filters <= 0 || ix->n <= 0) return fail(VR_ERR_STATE, "no filters set for the rows of the index (vr_index_set_filters)");
+        if (!on_device)
+            for (int32_t q = 0; q < nq; ++q)
+                if (filter_of_query[q] < -1 || filter_of_query[q] >= ix->n_filters)
+                    return fail(VR_ERR_INVALID, "filter_of_query[%d] = %d outside [-1, %lld)", (int)q, (int)filter_of_query[q], (long long)ix->n_filters);
+    }
+    if (nq == 0) return VR_OK;                    // no query: no launch
+    VRCHK(set_dev(ix->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n_out = (size_t)nq * k;
+    if (ix->n == 0) {                             // no row: tails, no launch
+        if (on_device) {
+            HIPCHK(hipMemsetD32Async((hipDeviceptr_t)out_scores, (int)0xFF800000u, n_out, s));     // -inf
+            HIPCHK(hipMemsetAsync(out_ids, 0xFF, n_out * 8, s));                                   // -1
+        } else {
+            std::fill(out_scores, out_scores + n_out, -INFINITY);
+            std::fill(out_ids, out_ids + n_out, (int64_t)-1);
+        }
+        return VR_OK;
+    }
+    if (!ix->wstate.p) VRCHK(ix->wstate.alloc(WIN_WORDS * 8));
+    const int dim = ix->dim;
+    const int64_t ldS = pad256l(ix->n);
+    const int64_t qblk = 256;                     // one fp32 score row per query, as on the deep path
+    const float* q32 = nullptr;
+    VRCHK(stage_queries(ix, queries, nq, pad256l(std::min<int64_t>(nq, qblk)), on_device, s, &q32));
+    const int* foq = filter_of_query;
+    if (foq && !on_device) {
+        VRCHK(ix->ffq.reserve((size_t)nq * 4));
+        HIPCHK(hipMemcpyAsync(ix->ffq.p, filter_of_query, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+        foq = ix->ffq.as<int>();
+    }
+    VRCHK(ix->woff.reserve((size_t)nq * 8));
+    VRCHK(ix->wedge.reserve((size_t)qblk * 8));
+    HIPCHK(hipMemcpyAsync(ix->woff.p, offsets, (size_t)nq * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));              // (the host array is free from here on)
+    float* os = nullptr; int64_t* oi = nullptr;
+    VRCHK(stage_output(ix->os, out_scores, n_out, on_device, &os));
+    VRCHK(stage_output(ix->oi, out_ids, n_out, on_device, &oi));
+    VRCHK(ix->sbuf.reserve((size_t)qblk * ldS * 4));
+    unsigned long long* words = ix->wstate.as<unsigned long long>();
+    const bool certify = ix->eps_rel == -2.f || ix->eps_rel >= 0.f;
+    for (int64_t q0 = 0; q0 < nq; q0 += qblk) {
+        const int nb = (int)std::min<int64_t>(qblk, nq - q0);
+        const int64_t nbp = pad256l(nb);
+        HIPCHK(launch_f32_to_bf16_pad(q32 + (size_t)q0 * dim, ix->qbf.p, (size_t)nb * dim, (size_t)nbp * dim, s));   // rows >= nb: zeros
+        WindowSearchArgs p{};
+        SearchArgs& a = p.a;
+        a.index_bf16 = ix->bf16.p; a.index_f32 = ix->f32.as<float>(); a.n_docs = ix->n; a.dim = dim;
+        a.q_bf16 = ix->qbf.p; a.q_f32 = q32 + (size_t)q0 * dim; a.nq = nb; a.k = k;
+        // the band is defined by the error model: with certification off, the default one defines it
+        fill_error_model(ix, a);
+        if (!certify) { a.eps_data = 1; a.eps_rel = 0.f; }
+        a.out_scores = os + (size_t)q0 * k; a.out_ids = oi + (size_t)q0 * k;
+        p.offsets = ix->woff.as<int64_t>() + q0;
+        p.filter_of_query = foq ? foq + q0 : nullptr;
+        p.n_filters = (int)ix->n_filters;
+        p.allowed = foq ? ix->fcount.as<int>() : nullptr;
+        p.edges = ix->wedge.as<float>();
+        p.stats = words;
+        // S[q][row] = queries x index^T on the bf16 MFMA GEMM, the deep path's launch; disallowed columns -> -inf
+        VRCHK(score_rows(ix, ix->qbf.p, nb, nullptr, 0, GEMM_VARIANT_AUTO, ldS, s));
+        if (foq) {
+            FilterSearchArgs f{};                 // the mask reads bits, words, n_filters and filter_of_query; the rest passes its argument check
+            f.a = a;
+            f.a.flag_count = reinterpret_cast<int*>(words + WIN_SPARE); f.a.flag_list = f.a.flag_count + 2;
+            f.bits = ix->fbits.as<uint32_t>(); f.words = (size_t)((ix->n + 31) / 32); f.n_filters = (int)ix->n_filters;
+            f.allowed = ix->fcount.as<int>();
+            f.filter_of_query = p.filter_of_query;
+            f.stats = reinterpret_cast<unsigned*>(words + WIN_SPARE) + 4;
+            HIPCHK(launch_filter_mask(f, ix->sbuf.as<float>(), (size_t)ldS, nb, nullptr, 0, s));
+        }
+        HIPCHK(launch_window_edges(p, ix->sbuf.as<float>(), (size_t)ldS, nb, s));
+        HIPCHK(launch_window_rescore(p, ix->sbuf.as<float>(), (size_t)ldS, nb, s));
+        HIPCHK(launch_window_select(p, ix->sbuf.as<float>(), (size_t)ldS, nb, s));
+    }
+    VRCHK(return_output(out_scores, os, n_out, on_device, s));
+    VRCHK(return_output(out_ids, oi, n_out, on_device, s));
+    if (!on_device) HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
 }
 
 // k rows per query picked by maximal marginal relevance from the pool of its `pool` best rows (search_diverse.hip).  The pool

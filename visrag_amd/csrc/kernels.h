@@ -444,6 +444,23 @@ struct RankSearchArgs {
 hipError_t launch_rank_bars(const RankSearchArgs& p, size_t ldS, int nq_block, int64_t n_pairs, hipStream_t s);
 // out_counts[pair] += rows of S row pair_query[pair] ahead of the pair's bar, the band around it decided by fp32 re-scoring; S is only read
 hipError_t launch_rank_count(const RankSearchArgs& p, const float* S, size_t ldS, int nq_block, int64_t n_pairs, hipStream_t s);
+// ---- windowed search (search_window.hip): the rows at ranks [offset, offset + k) of a query's fp32 ranking, any offset
+struct WindowSearchArgs {
+    SearchArgs a;                    // the block's view, as RangeSearchArgs': index_f32, n_docs, dim, q_f32, nq and a valid error model;
+                                     // k, out_scores / out_ids [nq][k]: the block's part of the result (no out_keys)
+    const int64_t* offsets;          // [nq] device: the first rank of every query's window, >= 0
+    const int* filter_of_query;      // [nq] device or null, as RangeSearchArgs': the score rows have been masked; an entry outside
+    int n_filters;                   //   [-1, n_filters): a row of tails
+    const int* allowed;              // [n_filters] device (filter_of_query set): the rows every filter allows
+    float* edges;                    // [nq][2] scratch: the band {lo, hi} of bf16 scores the window's rows lie in (NaN: an empty window)
+    unsigned long long* stats;       // [0] queries [1] band candidates re-scored in fp32 [2] rows certainly ahead of their window
+};
+// edges[q] from two radix selects over S row q (masked bf16-MFMA scores); S is only read
+hipError_t launch_window_edges(const WindowSearchArgs& p, const float* S, size_t ldS, int nq_block, hipStream_t s);
+// S rows [0, nq_block) rewritten in place: +inf certainly ahead, -inf certainly behind or masked, the fp32 score inside the band
+hipError_t launch_window_rescore(const WindowSearchArgs& p, float* S, size_t ldS, int nq_block, hipStream_t s);
+// ranks [offset, offset + k) of the rewritten rows -> a.out_scores / a.out_ids, (-inf, -1) past the allowed rows
+hipError_t launch_window_select(const WindowSearchArgs& p, const float* S, size_t ldS, int nq_block, hipStream_t s);
 // ---- diversified search (search_diverse.hip): k rows per query picked by maximal marginal relevance from a pool of its best rows
 struct MmrArgs {
     const float* index_f32;          // [n_docs][dim] f32

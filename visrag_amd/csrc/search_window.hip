@@ -1,0 +1,269 @@
+// vr_index_search_window: WHICH rows stand at ranks [o, o + k) of a query's fp32 ranking (fp32 score descending, then lower id
+// first, over the rows the query's filter allows) — the inverse of vr_index_rank_rows, any offset o, k <= search_bigk_max().
+// Let b_j be row j's bf16-MFMA score, e_j its fp32 score (dot_lane + wave_sum, the bits vr_index_search returns for that pair)
+// and |b_j - e_j| <= eps for every allowed j (search_common.h: query_eps).  Order statistics are 1-Lipschitz under a sup-norm
+// perturbation: with b_(r) the r-th largest bf16 score and e_(r) the r-th largest fp32 score, |b_(r) - e_(r)| <= eps for every
+// rank r.  With na the allowed rows, v_a = b_(o + 1) and v_z = b_(min(o + k, na)):
+//   - every row of the window has e in [v_z - eps, v_a + eps], hence b in [v_z - 2 eps, v_a + 2 eps]: the BAND;
+//   - a row with b > v_a + 2 eps has e > v_a + eps >= e_(o + 1): strictly ahead of the whole window, whatever its id;
+//   - a row with b < v_z - 2 eps is strictly behind the whole window.
+// With A the rows certainly ahead (A <= o always: fewer than o + 1 rows have b > b_(o + 1)), the window is positions
+// o - A .. o - A + k - 1 of the band rows sorted by make_key(e, id).  Both bounds are rounded outward by one ulp (the rounded
+// subtraction / addition cannot have narrowed the band).  No candidate margin, no widening, no flagged queries; with
+// certification off the default error model defines the band.  Per block of <= 256 queries (index.hip):
+//   1. score rows S[q][row] on the bf16 MFMA GEMM (the deep path's launch); with filters launch_filter_mask turns the columns a
+//      query may not see into -inf;
+//   2. window_edge_kernel, one workgroup per query: eps, na; o >= na (or a filter index outside [-1, n_filters), which a device
+//      caller's cannot be checked for before the launch): the query is empty (lo = NaN).  Otherwise two radix selects over the
+//      row give v_a and v_z (both ranks <= na: neither is a masked -inf) and lo = one_ulp_down(v_z - 2 eps), hi = the next
+//      float above v_a + 2 eps;
+//   3. window_rescore_kernel, grid (column chunk of 4096, query): the row is REWRITTEN in place so that it alone defines the
+//      answer: +inf for b > hi (certainly ahead), -inf for b < lo (certainly behind, or masked), and for the columns in
+//      [lo, hi] — compacted into an LDS list by ballot + popcount, re-scored one candidate per wave with the row's loads issued
+//      in front of the fma chain (profiles/diverse_search_bench.txt) — their fp32 score e.  The A rows of +inf then occupy
+//      ranks 0 .. A - 1 of the rewritten row (id order), every band row stands where its key puts it, and the window is ranks
+//      o .. o + k - 1 of the rewritten row: no per-query counter to subtract.  A column is written by one thread only;
+//   4. window_select_kernel, one workgroup per query: radix selects for rank o (when o > 0) and rank min(o + k, na) of the
+//      rewritten row, then gather_window: the positions NOT among the first o and among the first o + k, "lowest ids first
+//      among equals" being the tie rule at both edges (T_a == T_z: both edges inside one tie tier, equal-positions
+//      [need_a, need_z)).  At most k <= 1000 positions: keys make_key(S[i], i), block_bitonic_desc, k slots emitted,
+//      (-inf, -1) past the allowed rows.
+// No kernel waits for another workgroup; stream order between the launches is the only ordering.  No kernel reads a column at
+// or past n_docs as a value or writes one: the padded columns hold zeros.
+#include "kernels.h"
+#include "search_select.h"
+
+namespace vr {
+
+constexpr int WIN_CHUNK = 4096;             // columns per workgroup of the re-scoring (the range and the rank search's chunk)
+
+struct WindowLds {
+    int cand[WIN_CHUNK];                    // columns inside the band, any order
+    int n_cand;
+    unsigned ahead;                         // rows of this chunk certainly ahead of the window
+};
+
+struct WindowSelectLds {
+    SelectLds s;
+    int wc[4][3], run[3];                   // gather_window: per-wave and running counts {== T_a, == T_z, selected}
+};
+
+__device__ __forceinline__ float one_ulp_up(float x) {
+    const uint32_t o = f32_orderable(x);
+    return o != 0xFFFFFFFFu ? orderable_f32(o + 1u) : x;
+}
+
+// rows query q may see: all of them, its filter's count, or none (an entry outside [-1, n_filters))
+__device__ __forceinline__ int window_allowed(const WindowSearchArgs& p, int q) {
+    const int f = p.filter_of_query ? p.filter_of_query[q] : -1;
+    return f == -1 ? (int)p.a.n_docs : ((unsigned)f < (unsigned)p.n_filters ? p.allowed[f] : 0);
+}
+
+__global__ __launch_bounds__(256) void window_edge_kernel(WindowSearchArgs p, const float* __restrict__ S, size_t ldS) {
+    __shared__ SelectLds L;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const SearchArgs& a = p.a;
+    const int q = blockIdx.x, n_docs = (int)a.n_docs, nv = a.dim >> 2;
+    if (q == 0 && tid == 0) atomicAdd(&p.stats[0], (unsigned long long)gridDim.x);
+    const int na = window_allowed(p, q);
+    const int64_t o = p.offsets[q];
+    if (o >= (int64_t)na) {                                                // (workgroup-uniform) an empty window: a row of tails
+        if (tid == 0) { p.edges[2 * q] = __builtin_nanf(""); p.edges[2 * q + 1] = __builtin_nanf(""); }
+        return;
+    }
+    f32x4 qv[MERGE_MAXV];
+    load_query_regs(qv, a.q_f32 + (size_t)q * a.dim, nv, lane);
+    const float eps = query_eps(a, qv);                                    // (every wave computes the same value)
+    const float* row = S + (size_t)q * ldS;
+    const int kz = (int)min(o + (int64_t)a.k, (int64_t)na);                // 1 <= o + 1 <= kz <= na
+    const KthKey ka = select_kth(row, n_docs, (int)o + 1, L);
+    __syncthreads();
+    const KthKey kz_key = select_kth(row, n_docs, kz, L);
+    if (tid == 0) {
+        const float va = orderable_f32(ka.T), vz = orderable_f32(kz_key.T);
+        p.edges[2 * q] = one_ulp_down(vz - 2.f * eps);
+        p.edges[2 * q + 1] = one_ulp_up(va + 2.f * eps);
+    }
+}
+
+__global__ __launch_bounds__(256) void window_rescore_kernel(WindowSearchArgs p, float* __restrict__ S, size_t ldS) {
+    __shared__ WindowLds L;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const SearchArgs& a = p.a;
+    const int q = blockIdx.y, n_docs = (int)a.n_docs, nv = a.dim >> 2;
+    const float lo = p.edges[2 * q], hi = p.edges[2 * q + 1];
+    if (lo != lo) return;                                                  // (workgroup-uniform) an empty window
+    const int c0 = blockIdx.x * WIN_CHUNK, c1 = min(c0 + WIN_CHUNK, n_docs);
+    if (tid == 0) { L.n_cand = 0; L.ahead = 0u; }
+    __syncthreads();
+    // ---- certainly ahead: b > hi -> +inf; certainly behind or masked: b < lo -> -inf; the band lo <= b <= hi: listed
+    float* row = S + (size_t)q * ldS;
+    unsigned mine = 0;                      // rows certainly ahead this wave found (complete in lane 0: it leaves the loop last)
+    for (int i0 = c0 + tid * 4; i0 < c1; i0 += 256 * 4) {                  // (c0 and ldS are multiples of 4: aligned; < ldS)
+        const f32x4 b = *reinterpret_cast<const f32x4*>(row + i0);
+        f32x4 w;
+        bool any_band = false;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const bool valid = i0 + e < c1;
+            const bool up = valid && b[e] > hi;
+            const bool in = valid && b[e] >= lo && b[e] <= hi;
+            w[e] = up ? INFINITY : -INFINITY;
+            any_band |= in;
+            mine += (unsigned)__popcll(__ballot(up));
+            const unsigned long long m = __ballot(in);
+            if (m == 0ull) continue;                                       // (wave-uniform)
+            int base = 0;
+            if (lane == 0) base = atomicAdd(&L.n_cand, __popcll(m));
+            base = __shfl(base, 0, 64);
+            if (in) L.cand[base + __popcll(m & ((1ull << lane) - 1ull))] = i0 + e;     // (< WIN_CHUNK: one slot per column)
+        }
+        // a band column is written by the wave that re-scores it, a column at or past n_docs by nobody
+        if (i0 + 4 <= c1 && !any_band) {
+            *reinterpret_cast<f32x4*>(row + i0) = w;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (i0 + e < c1 && !(b[e] >= lo && b[e] <= hi)) row[i0 + e] = w[e];
+        }
+    }
+    if (lane == 0 && mine) atomicAdd(&L.ahead, mine);
+    __syncthreads();
+    // ---- fp32 re-scoring of the band, one candidate per wave
+    const int m = L.n_cand;
+    if (m > 0) {                                                           // (workgroup-uniform)
+        f32x4 qv[MERGE_MAXV];
+        load_query_regs(qv, a.q_f32 + (size_t)q * a.dim, nv, lane);
+        for (int c = wave; c < m; c += 4) {
+            const int id = L.cand[c];
+            const f32x4* dr = reinterpret_cast<const f32x4*>(a.index_f32 + (size_t)id * a.dim);
+            f32x4 dv[MERGE_MAXV];
+#pragma unroll
+            for (int i = 0; i < MERGE_MAXV; ++i) {
+                const int cc = lane + i * 64;
+                dv[i] = (cc < nv) ? dr[cc] : f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+            float s = 0.f;
+#pragma unroll
+            for (int i = 0; i < MERGE_MAXV; ++i) {
+                const int cc = lane + i * 64;
+                if (cc < nv) s = dot_chunk(qv[i], dv[i], s);               // the chain of dot_lane(query, row)
+            }
+            s = wave_sum(s);
+            if (lane == 0) row[id] = s;
+        }
+    }
+    if (tid == 0) {
+        if (m > 0) atomicAdd(&p.stats[1], (unsigned long long)m);
+        const unsigned n = L.ahead;
+        if (n > 0) atomicAdd(&p.stats[2], (unsigned long long)n);
+    }
+}
+
+// Positions i of vals[0, n) that are NOT among the first o of the ranking (value descending, then lower position) and ARE among
+// its first kz, into L.s.cand in ascending order; returns how many (kz - o when both keys come from select_kth over vals).
+//   first o:  key > a.T, or key == a.T at equal-position < a.need_eq      (skip_a == false: o == 0, nothing is excluded)
+//   first kz: key > z.T, or key == z.T at equal-position < z.need_eq
+// Nothing is written at or beyond slot SEL_CAND.  Called by the whole workgroup; the LDS must be free (barrier).
+__device__ __forceinline__ int gather_window(const float* __restrict__ vals, int n, KthKey a, bool skip_a, KthKey z, WindowSelectLds& L) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid < 3) L.run[tid] = 0;
+    __syncthreads();
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int i0 = 0; i0 < n; i0 += 256) {
+        const int i = i0 + tid;
+        const unsigned key = i < n ? f32_orderable(vals[i]) : 0u;
+        const bool eqa = i < n && skip_a && key == a.T, eqz = i < n && key == z.T;
+        const bool span = i < n && key >= z.T && (!skip_a || key <= a.T);  // every selected position, and every tie of an edge
+        if (!__syncthreads_or(span)) continue;                             // (barrier; most blocks hold none)
+        const unsigned long long ba = __ballot(eqa), bz = __ballot(eqz);
+        if (lane == 0) { L.wc[wave][0] = __popcll(ba); L.wc[wave][1] = __popcll(bz); }
+        __syncthreads();
+        int pa = L.run[0] + __popcll(ba & below), pz = L.run[1] + __popcll(bz & below), ta = 0, tz = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            if (w < wave) { pa += L.wc[w][0]; pz += L.wc[w][1]; }
+            ta += L.wc[w][0]; tz += L.wc[w][1];
+        }
+        const bool past_o = !skip_a || key < a.T || (eqa && pa >= a.need_eq);
+        const bool in_kz = key > z.T || (eqz && pz < z.need_eq);
+        const bool sel = span && past_o && in_kz;
+        const unsigned long long bs = __ballot(sel);
+        if (lane == 0) L.wc[wave][2] = __popcll(bs);
+        __syncthreads();
+        int ps = L.run[2] + __popcll(bs & below), ts = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            if (w < wave) ps += L.wc[w][2];
+            ts += L.wc[w][2];
+        }
+        if (sel && ps < SEL_CAND) L.s.cand[ps] = i;
+        __syncthreads();
+        if (tid == 0) { L.run[0] += ta; L.run[1] += tz; L.run[2] += ts; }
+        __syncthreads();
+    }
+    return L.run[2];
+}
+
+__global__ __launch_bounds__(256) void window_select_kernel(WindowSearchArgs p, const float* __restrict__ S, size_t ldS, int n_sort) {
+    __shared__ WindowSelectLds L;
+    const int tid = threadIdx.x;
+    const SearchArgs& a = p.a;
+    const int q = blockIdx.x, n_docs = (int)a.n_docs, k = a.k;
+    const float lo = p.edges[2 * q];
+    if (lo != lo) {                                                        // (workgroup-uniform) an empty window: k tails
+        for (int c = tid; c < k; c += 256) emit_slot(a, q, c, KEY_NONE);
+        return;
+    }
+    const int na = window_allowed(p, q);
+    const int o = (int)p.offsets[q];                                       // (< na: the edge kernel saw it)
+    const int kz = (int)min((int64_t)o + k, (int64_t)na);
+    const float* row = S + (size_t)q * ldS;
+    KthKey ka{0xFFFFFFFFu, 0};
+    if (o > 0) {
+        ka = select_kth(row, n_docs, o, L.s);
+        __syncthreads();
+    }
+    const KthKey kzk = select_kth(row, n_docs, kz, L.s);
+    __syncthreads();
+    const int n_sel = min(gather_window(row, n_docs, ka, o > 0, kzk, L), SEL_CAND);
+    for (int c = tid; c < n_sort; c += 256) {
+        uint64_t key = KEY_NONE;
+        if (c < n_sel) { const int i = L.s.cand[c]; key = make_key(row[i], (uint32_t)i); }
+        L.s.keys[c] = key;
+    }
+    __syncthreads();
+    block_bitonic_desc(L.s.keys, n_sort, tid, 256);
+    for (int c = tid; c < k; c += 256) emit_slot(a, q, c, L.s.keys[c]);
+}
+
+static bool window_args_ok(const WindowSearchArgs& p, size_t ldS, int nq_block) {
+    const SearchArgs& a = p.a;
+    return nq_block >= 1 && nq_block <= 256 && a.n_docs >= 1 && a.n_docs < ((int64_t)1 << 31) && range_dim_ok(a.dim) && a.index_f32 &&
+           a.q_f32 && a.dmax && (a.eps_data || a.eps_rel >= 0.f) && a.k >= 1 && a.k <= SEL_CAND - SEL_MARGIN && a.out_scores &&
+           a.out_ids && !a.out_keys && p.offsets && p.edges && p.stats && ldS % 4 == 0 && (int64_t)ldS >= a.n_docs &&
+           (!p.filter_of_query || (p.n_filters >= 1 && p.allowed));
+}
+
+hipError_t launch_window_edges(const WindowSearchArgs& p, const float* S, size_t ldS, int nq_block, hipStream_t s) {
+    if (!window_args_ok(p, ldS, nq_block) || !S) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(window_edge_kernel, dim3((unsigned)nq_block), dim3(256), 0, s, p, S, ldS);
+    return hipGetLastError();
+}
+
+hipError_t launch_window_rescore(const WindowSearchArgs& p, float* S, size_t ldS, int nq_block, hipStream_t s) {
+    if (!window_args_ok(p, ldS, nq_block) || !S) return hipErrorInvalidValue;
+    const unsigned chunks = (unsigned)((p.a.n_docs + WIN_CHUNK - 1) / WIN_CHUNK);
+    hipLaunchKernelGGL(window_rescore_kernel, dim3(chunks, (unsigned)nq_block), dim3(256), 0, s, p, S, ldS);
+    return hipGetLastError();
+}
+
+hipError_t launch_window_select(const WindowSearchArgs& p, const float* S, size_t ldS, int nq_block, hipStream_t s) {
+    if (!window_args_ok(p, ldS, nq_block) || !S) return hipErrorInvalidValue;
+    int n_sort = 64;                                                       // the power of two that holds k keys
+    while (n_sort < p.a.k) n_sort <<= 1;
+    hipLaunchKernelGGL(window_select_kernel, dim3((unsigned)nq_block), dim3(256), 0, s, p, S, ldS, n_sort);
+    return hipGetLastError();
+}
+
+}  // namespace vr

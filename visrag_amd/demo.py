@@ -98,7 +98,7 @@ def load_knowledge_base(knowledge_base_path: str, device: Optional[int] = None):
 
 @torch.no_grad()
 def retrieve(knowledge_base_path: str, query: str, topk: int, model, tokenizer, index=None, names=None,
-             return_scores: bool = False, documents=None, diverse=None, pool=None):
+             return_scores: bool = False, documents=None, diverse=None, pool=None, offset: int = 0):
     """answer.py:14-40: paths of the `topk` most similar page images (None if the base does not exist).
     Pass `index, names = load_knowledge_base(path)` to keep the index resident between questions.
     `documents`: an iterable of document names (the `doc_of_page` of the page names) — only their pages are ranked
@@ -107,9 +107,18 @@ def retrieve(knowledge_base_path: str, query: str, topk: int, model, tokenizer, 
     one; `query` may then also be the query's embedding ([dim] or [1, dim]).
     `diverse`: a lambda in [0, 1] — the pages are picked by maximal marginal relevance from the `pool` best ones
     (HipIndex.search_diverse; `pool=None`: its default) and come in PICK order with their relevance scores, so near-duplicate
-    pages do not fill the generator's context; with `documents` the pool holds only their pages.  `query` may be an embedding."""
+    pages do not fill the generator's context; with `documents` the pool holds only their pages.  `query` may be an embedding.
+    `offset`: the "next page" of a result list — the pages at ranks offset .. offset + topk - 1 of the same ranking
+    (HipIndex.search_window: exact however deep, page 101 costs what page 2 costs), also among the pages of `documents`;
+    fewer than `topk` paths where the ranking ends.  Not together with `diverse`: ValueError."""
     if not os.path.exists(knowledge_base_path):
         return None
+    if offset < 0:
+        raise ValueError("offset must be >= 0")
+    if offset > 0:
+        if diverse is not None:
+            raise ValueError("offset and diverse exclude each other: MMR picks have no ranks to page through")
+        return _retrieve_window(knowledge_base_path, query, topk, model, tokenizer, index, names, return_scores, documents, int(offset))
     if diverse is not None:
         return _retrieve_diverse(knowledge_base_path, query, topk, model, tokenizer, index, names, return_scores, documents,
                                  float(diverse), pool)
@@ -147,6 +156,33 @@ def _retrieve_filtered(knowledge_base_path, query, topk, model, tokenizer, index
         keep = [int(i) for i in ids[0] if i >= 0]
         paths = [os.path.join(knowledge_base_path, names[i]) for i in keep]
         scores = [float(s) for s in sc[0][: len(keep)]]
+    if own:
+        index.close()
+    return (paths, scores) if return_scores else paths
+
+
+def _retrieve_window(knowledge_base_path, query, topk, model, tokenizer, index, names, return_scores, documents, offset):
+    """retrieve() at ranks [offset, offset + topk); `documents` given: among their pages, through one filter set for this question"""
+    own = index is None
+    if own:
+        index, names = load_knowledge_base(knowledge_base_path, model.encoder.device if model is not None else None)
+    n = len(index)
+    if isinstance(query, str):
+        q = encode(model, tokenizer, [QUERY_INSTRUCTION + query])
+    else:
+        q = np.asarray(query.detach().cpu() if isinstance(query, torch.Tensor) else query, dtype=np.float32).reshape(1, -1)
+    mask = None if documents is None else label_filters([doc_of_page(nm) for nm in names[:n]], [documents])
+    rows = n if mask is None else int(mask.sum())
+    paths, scores = [], []
+    if topk > 0 and offset < rows:
+        if mask is not None:
+            index.set_filters(mask)
+        for o in range(offset, min(offset + topk, rows), 1000):           # a list longer than one window: paged
+            sc, ids = index.search_window(q, o, min(1000, offset + topk - o, rows - o), None if mask is None else 0)
+            sc, ids = (x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in (sc, ids))
+            keep = [int(i) for i in ids[0] if i >= 0]
+            paths += [os.path.join(knowledge_base_path, names[i]) for i in keep]
+            scores += [float(s) for s in sc[0][: len(keep)]]
     if own:
         index.close()
     return (paths, scores) if return_scores else paths

@@ -17,6 +17,9 @@ library does to the filters it keeps.
 The rank search (HipIndex.rank_rows) returns the rank of every qrel positive, in CSR form (query q's positives are entries
 lims[q] .. lims[q + 1] - 1): `reciprocal_ranks` / `mrr_from_ranks` and `recall_at` turn them into the metrics a run of fixed
 depth cannot give — MRR without a cut-off, recall at any k.
+
+The windowed search (HipIndex.search_window) returns the rows at ranks [offset, offset + k): `window_negatives` takes such a
+window and a query's positives and leaves the hard negatives a trainer wants ("ranks 30-200 minus the positives").
 Pure numpy: nothing here touches the GPU.
 """
 from __future__ import annotations
@@ -215,3 +218,25 @@ def recall_at(ranks, lims, ks) -> np.ndarray:
             n += 1
             out += (r[None, :] < ks[:, None]).sum(1) / len(r)
     return out / n if n else out
+
+
+def window_negatives(ids, positives_of_query, count: int) -> np.ndarray:
+    """int64 [nq][count]: for every query the first `count` ids of its window `ids[q]` (HipIndex.search_window: rows in ranking
+    order, -1 where the ranking has ended) that are not among `positives_of_query[q]` (a sequence of row ids per query, or a
+    callable q -> row ids) — the window's order kept, padded with -1."""
+    ids = np.asarray(ids, dtype=np.int64)
+    if ids.ndim != 2:
+        raise ValueError("ids must be [nq][k]")
+    count = int(count)
+    if count < 0:
+        raise ValueError("count must be >= 0")
+    get = positives_of_query if callable(positives_of_query) else (lambda q: positives_of_query[q])
+    if not callable(positives_of_query) and len(positives_of_query) != len(ids):
+        raise ValueError(f"{len(positives_of_query)} positive lists for {len(ids)} queries")
+    out = np.full((len(ids), count), -1, dtype=np.int64)
+    for q in range(len(ids)):
+        pos = np.asarray(list(get(q)), dtype=np.int64).reshape(-1)
+        row = ids[q]
+        keep = row[(row >= 0) & ~np.isin(row, pos)][:count]
+        out[q, :len(keep)] = keep
+    return out

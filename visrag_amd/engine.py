@@ -608,6 +608,37 @@ class HipIndex:
         _lib.check(self.lib.vr_index_rank_search_stats(self._h, out, 1 if reset else 0))
         return {"pairs": int(out[0]), "candidates": int(out[1]), "counted": int(out[2])}
 
+    # ---- windowed search (include/visrag_hip.h: vr_index_search_window) ----
+    def search_window(self, queries, offset, k: int, filter_of_query=None):
+        """The rows at ranks [offset, offset + k) of every query's fp32 ranking (include/visrag_hip.h: vr_index_search_window)
+        -> (scores [nq,k] f32, ids [nq,k] i64): entry j is the row of rank offset + j — score descending, then lower id first,
+        among the rows the query's filter allows — so `search_window(q, o, k)` is `search(q, o + k)[..., o:]` wherever `search`
+        reaches, and `rank_rows` of the ids returned is `offset + arange(k)`.  `offset`: an int (every query's) or one per query
+        (any int sequence or tensor), each >= 0, however deep; slots at or past the number of allowed rows are (-inf, -1).
+        1 <= k <= 1000: page for more.  `filter_of_query` as in `search_filtered`, None = no filter (none need to be set).
+        cuda in -> cuda out, numpy / cpu in -> numpy out."""
+        nq = int(queries.shape[0])
+        off = self._row_ids(offset)
+        if off.size == 1 and nq != 1:
+            off = np.full(nq, off[0], dtype=np.int64)
+        if len(off) != nq:
+            raise ValueError(f"{len(off)} offsets for {nq} queries")
+        if (off < 0).any():
+            raise ValueError("offsets must be >= 0")
+        keep, fptr = (None, C.c_void_p(None)) if filter_of_query is None else self._filter_of_query(queries, filter_of_query)
+
+        def fn(h, q, n, kk, out_scores, out_ids, on_device, stream):
+            return self.lib.vr_index_search_window(h, q, n, C.c_void_p(off.ctypes.data), kk, fptr, out_scores, out_ids, on_device, stream)
+
+        return self._search(fn, "vr_index_search_window", queries, k, 1)
+
+    def window_search_stats(self, reset: bool = False) -> Dict[str, int]:
+        """Windowed searches since the last reset: queries, rows of the bands re-scored in fp32, rows certainly ahead of their
+        query's window (decided by the bf16 score alone)."""
+        out = (C.c_int64 * 3)()
+        _lib.check(self.lib.vr_index_window_search_stats(self._h, out, 1 if reset else 0))
+        return {"queries": int(out[0]), "candidates": int(out[1]), "ahead": int(out[2])}
+
     def search_keys(self, queries: torch.Tensor, k: int, id_offset: int = 0) -> torch.Tensor:
         """The same search with each result packed into ONE 64-bit word (include/visrag_hip.h:
         vr_index_search_keys): orderable(score) << 32 | ~(row + id_offset); 0 = empty slot.  -> int64 [nq, k]

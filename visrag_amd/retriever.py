@@ -326,6 +326,132 @@ def rank_rows(args, targets_of_query, index_factory: Optional[Callable] = None) 
             for qi, q in enumerate(qids)}
 
 
+WINDOW_PAGE = 1000          # rows per HipIndex.search_window call (its k limit)
+
+
+def _shard_pages(ix, queries, first: int, count: int, page: int = WINDOW_PAGE) -> Tuple[np.ndarray, np.ndarray]:
+    """ranks [first, first + count) of every query over one index, paged in windows of <= `page` -> (scores [nq][count] f32,
+    rows [nq][count] i64), tails (-inf, -1)"""
+    if count <= 0:
+        return np.zeros((len(queries), 0), dtype=np.float32), np.zeros((len(queries), 0), dtype=np.int64)
+    sc, rows = [], []
+    for o in range(first, first + count, page):
+        s, r = ix.search_window(queries, o, min(page, first + count - o))
+        sc.append(np.asarray(s, dtype=np.float32)); rows.append(np.asarray(r, dtype=np.int64))
+    return np.concatenate(sc, axis=1), np.concatenate(rows, axis=1)
+
+
+def merge_pages_host(scores: List[np.ndarray], positions: List[np.ndarray], depth: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Per-shard lists (scores [nq][d_s] f32, GLOBAL positions [nq][d_s] i64 with -1 for an empty slot) -> the best `depth`
+    entries per query (scores [nq][depth], positions [nq][depth]), by score descending, then global position ascending; tails
+    (-inf, -1).  The global top `depth` is contained in the union of the shards' top `depth`."""
+    sc = np.concatenate([np.asarray(s, dtype=np.float32) for s in scores], axis=1)
+    pos = np.concatenate([np.asarray(p, dtype=np.int64) for p in positions], axis=1)
+    nq = sc.shape[0]
+    out_s = np.full((nq, depth), -np.inf, dtype=np.float32)
+    out_p = np.full((nq, depth), -1, dtype=np.int64)
+    for q in range(nq):
+        live = np.flatnonzero(pos[q] >= 0)
+        order = live[np.lexsort((pos[q][live], -sc[q][live].astype(np.float64)))][:depth]
+        out_s[q, :len(order)], out_p[q, :len(order)] = sc[q][order], pos[q][order]
+    return out_s, out_p
+
+
+def retrieve_deep(args, depth: int, index_factory: Optional[Callable] = None) -> Dict[str, Dict[str, float]]:
+    """A run of any depth over the same pickle shards: this rank's query shard(s) against ALL corpus shards, the `depth` best
+    rows of the WHOLE corpus per query — score descending, then shard and row order — with `depth` beyond the 1 000 rows one
+    `search` returns.  -> {qid: {docid: score}}, a query's entries best first; it goes to `save_as_trec` as it is, and at
+    depth <= 1000 it is the run of `distributed_parallel_retrieve(args, depth, global_topk=True)`.  The corpus is taken shard
+    by shard and the index never holds more than one shard: every shard is paged in windows of <= 1 000 rows down to `depth`
+    (HipIndex.search_window: exact at every offset), the per-shard lists are merged on the host.
+
+    Replicated form only, like retrieve_documents: every rank sees the whole corpus."""
+    make_index = index_factory or HipIndex
+    queries, qids, _ = _load_queries(args)
+    corpus_parts = list_shards(args.output_dir, "corpus")
+    if len(corpus_parts) == 0:
+        raise ValueError("No pre-computed document embeddings found")
+    depth = int(depth)
+    result: Dict[str, Dict[str, float]] = {q: {} for q in qids}
+    if depth <= 0:
+        return result
+    dev = _device_index(args)
+    all_ids: List[str] = []
+    lists_s, lists_p = [], []
+    for p in corpus_parts:
+        reps, ids = read_shard(p)
+        if len(ids) == 0:
+            continue
+        ix = make_index(queries.shape[1], len(ids), dev)
+        ix.add(np.asarray(reps, dtype=np.float32))
+        sc, rows = _shard_pages(ix, queries, 0, min(depth, len(ids)))
+        ix.close()
+        lists_s.append(sc)
+        lists_p.append(np.where(rows >= 0, rows + len(all_ids), -1))
+        all_ids.extend(ids)
+    if not lists_s:
+        return result
+    sc, pos = merge_pages_host(lists_s, lists_p, depth)
+    for qi, q in enumerate(qids):
+        for s, j in zip(sc[qi], pos[qi]):
+            if j >= 0:
+                result[q][all_ids[int(j)]] = float(s)
+    return result
+
+
+def mine_negatives(args, positives_of_query, start: int, count: int, index_factory: Optional[Callable] = None
+                   ) -> Dict[str, List[str]]:
+    """Hard negatives for a trainer that takes one positive and a list of negatives per query (the reference's train_dataset):
+    for every query the first `count` docids of the rank window that starts at rank `start` (skipping the top: "ranks 30-200
+    minus the positives") which are not among its positives.  `positives_of_query`: {qid: [docid, ...]} or a callable qid ->
+    docids.  The window taken is [start, start + count + the largest number of positives of a query), so that `count`
+    negatives are left wherever the corpus has that many rows (a window wider than 1 000 rows is paged); -> {qid: [docid,
+    ...]} in ranking order, fewer than `count` where the ranking ends.  Ranks are those of the whole corpus (retrieve_deep's
+    order), over a single shard or several: the rows of ranks below start + count + positives of every shard are merged.
+
+    Replicated form only, like retrieve_documents: every rank sees the whole corpus."""
+    from .documents import window_negatives
+    make_index = index_factory or HipIndex
+    queries, qids, _ = _load_queries(args)
+    corpus_parts = list_shards(args.output_dir, "corpus")
+    if len(corpus_parts) == 0:
+        raise ValueError("No pre-computed document embeddings found")
+    start, count = int(start), int(count)
+    if start < 0 or count < 0:
+        raise ValueError("start and count must be >= 0")
+    get = positives_of_query if callable(positives_of_query) else (lambda q: positives_of_query.get(q, ()))
+    positives = [list(dict.fromkeys(get(q))) for q in qids]
+    width = count + max((len(p) for p in positives), default=0)
+    dev = _device_index(args)
+    shards = [(p, *read_shard(p)) for p in corpus_parts]
+    shards = [s for s in shards if len(s[2])]
+    all_ids: List[str] = []
+    lists_s, lists_p = [], []
+    for _, reps, ids in shards:
+        ix = make_index(queries.shape[1], len(ids), dev)
+        ix.add(np.asarray(reps, dtype=np.float32))
+        if len(shards) == 1:                      # the window itself
+            sc, rows = _shard_pages(ix, queries, start, width)
+        else:                                     # every row that can stand above the window's end
+            sc, rows = _shard_pages(ix, queries, 0, min(start + width, len(ids)))
+        ix.close()
+        lists_s.append(sc)
+        lists_p.append(np.where(rows >= 0, rows + len(all_ids), -1))
+        all_ids.extend(ids)
+    if not lists_s or width == 0:
+        return {q: [] for q in qids}
+    if len(shards) == 1:
+        pos = lists_p[0]
+    else:
+        pos = merge_pages_host(lists_s, lists_p, start + width)[1][:, start:]
+    row_of: Dict[str, int] = {}
+    for r, d in enumerate(all_ids):
+        row_of.setdefault(d, r)
+    pos_rows = [[row_of[d] for d in p if d in row_of] for p in positives]
+    neg = window_negatives(pos, pos_rows, count)
+    return {q: [all_ids[int(j)] for j in neg[qi] if j >= 0] for qi, q in enumerate(qids)}
+
+
 def _retrieve_corpus_sharded(args, topk: int, global_topk: bool, make_index: Callable, merge_keys: Optional[Callable]
                              ) -> Dict[str, Dict[str, float]]:
     """The corpus-sharded form (module docstring).  Row ids are global: files in sorted order (the order the
