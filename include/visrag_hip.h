@@ -792,6 +792,62 @@ int vr_op_chat_select(int device_id, int32_t mode, const float* logits, int32_t 
 int vr_op_chat_prompt_scatter(int device_id, const void* qkv, int32_t ld, int32_t E, int32_t B, const int32_t* seq_offsets,
                               const int32_t* slots, int32_t n_slots, int32_t max_len, void* kplane, void* vplane, void* stream);
 
+/* ---- the EVisRAG generator's small kernels (csrc/gen_kernels.hip; the model calls them through vg_*, include/visrag_gen.h) ----
+ * Thin forwards to the launchers gen.hip / gen_vision.hip call.  The entries check NULL pointers and counts (VR_ERR_INVALID); a
+ * shape a launcher cannot run is refused THERE, before its kernel is launched, and comes back as VR_ERR_HIP.  Buffers are the
+ * caller's, on the device, unless stated otherwise.
+ *
+ *   entry                    launcher(s)
+ *   vr_op_gen_mrope_cache    launch_mrope_cache
+ *   vr_op_gen_rope2d         launch_rope2d_table + launch_rope2d_inplace
+ *   vr_op_gen_sample         launch_sample
+ *   vr_op_gen_mark_seen      launch_mark_seen
+ *   vr_op_gen_decode_begin   launch_decode_begin
+ *   vr_op_gen_rows           launch_scatter_rows / launch_gather_rows_bf16 / launch_patch_rows_u8
+ *
+ * `state` below is the decode state that lives on the device, 42 i32 words:
+ *   0 token | 1..3 temporal / height / width position | 4 len (KV-cache rows in use before the step) | 5 step (index of the next
+ *   sampled token: selects the sampling noise) | 6 splits | 7 unused | 8..24 cu_q[17] | 25..41 cu_kv[17] */
+/* Multimodal RoPE + KV-cache append, head_dim 128: T rows of H query, KV key and KV value heads ((H + 2 KV) * 128 columns).
+ * Source: parts NULL: bf16 rows src_bf16 [T][ld]; else fp32 planes parts [n_parts][plane_stride] of rows [T][ld], summed in
+ * float32 in the order bias (f32 [(H + 2 KV) * 128] or NULL: 0) + plane 0 + plane 1 + ...  Pair p of a head is columns
+ * (p, p + 64), its angle float(pos3[c][t]) * inv_freq[p] (f32 [64]) with c = 0 for p < sec_t, 1 for p < sec_t + sec_h, else 2;
+ * pos3 i32 [3][pos_stride].  Rotated q -> q_out bf16 [T][ldq]; rotated k and the unrotated v -> row r(t) of k_cache / v_cache
+ * bf16 [rows][ld_cache], r(t) = cache_rows[t] (i32 [T] on the device) if given, else row0 + t with row0 = *row0_dev (i32 on the
+ * device) if given, else cache_row0.  cu_kv (i32 [2] on the device, or NULL) receives {0, row0 + T}.  Nothing else is written. */
+int vr_op_gen_mrope_cache(int device_id, const void* src_bf16, const float* parts, int32_t n_parts, int64_t plane_stride,
+                          const float* bias, int32_t ld, int32_t T, int32_t H, int32_t KV, const int32_t* pos3, int32_t pos_stride,
+                          int32_t sec_t, int32_t sec_h, const float* inv_freq, void* q_out, int32_t ldq, void* k_cache, void* v_cache,
+                          int32_t ld_cache, int32_t cache_row0, const int32_t* row0_dev, const int32_t* cache_rows, int32_t* cu_kv,
+                          void* stream);
+/* The vision tower's 2-D rotary embedding, in place: head slot j < n_slots of row t is columns [2 hh j, 2 hh (j + 1)) of qkv bf16
+ * [T][ld], its pair p < hh the columns (p, p + hh), the pair's angle float(p < sec_h ? pos_h[t] : pos_w[t]) * freq[p]; pos_h,
+ * pos_w i32 [T], freq f32 [64].  Columns from 2 hh n_slots on (v, padding) are not touched.  hh <= 64.  Synchronises the stream. */
+int vr_op_gen_rope2d(int device_id, void* qkv, int32_t ld, int32_t T, int32_t n_slots, int32_t hh, const int32_t* pos_h,
+                     const int32_t* pos_w, int32_t sec_h, const float* freq, void* stream);
+/* Next token of one row of logits f32 [vocab]: repetition penalty on the ids of the bit set seen u32 [ceil(vocab / 32)] (logit > 0:
+ * / penalty, else * penalty), then temperature 0: the argmax, ties to the lowest id; temperature > 0: the argmax of
+ * logit / temperature + Gumbel noise of (seed, step, id).  The pick's bit is set in `seen` and it is copied to *out_token (host).
+ * state (or NULL): word 0 receives the pick; step_from_state: the noise index is word 5, not `step`; advance: words 1..5 grow by
+ * one.  The 64 partial keys are the entry's own scratch.  Synchronises the stream. */
+int vr_op_gen_sample(int device_id, const float* logits, int32_t vocab, uint32_t* seen, float repetition_penalty, float temperature,
+                     uint64_t seed, int32_t step, int32_t* state, int32_t step_from_state, int32_t advance, int32_t* out_token,
+                     void* stream);
+/* seen[id / 32] |= 1 << (id % 32) for the n ids (i32, device); ids outside [0, vocab) are ignored. */
+int vr_op_gen_mark_seen(int device_id, const int32_t* ids, int32_t n, uint32_t* seen, int32_t vocab, void* stream);
+/* The KV ranges of a decode step's attention from word 4 of `state`: L = len + 1 cache rows in at most 16 ranges of `chunk` rows, a
+ * multiple of 64; splits = the ranges that hold a row, cu_kv[i] = min(L, i chunk), cu_q[i] = i q_rows, i = 0..16. */
+int vr_op_gen_decode_begin(int device_id, int32_t* state, int32_t q_rows, void* stream);
+/* The row movers.  kind 0: dst f32 [.][ld], dst[row_idx[i]][0..dim) = src[i][0..dim), src f32 [n][dim].
+ *   kind 1: dst bf16 [n][ld], dst[i] = bf16(src[row_idx[i]][0..dim)), columns [dim, ld) zero; src rows are dense ([.][dim]).
+ *   kind 2: dst bf16 [n][ld], dst[i] = patch (ph[i], pw[i]) of page img[i], P x P pixels, element (c, t, y, x) =
+ *           (u8 / 255 - mean3[c]) / std3[c] in float32, the same for each of the tp temporal copies, columns [3 tp P^2, ld) zero.
+ *           pages: HOST array of n_pages device pointers to u8 HWC pages, page_w their widths (host), both uploaded by the entry;
+ *           img, ph, pw i32 [n] on the device; mean3, std3 on the host.  Synchronises the stream. */
+int vr_op_gen_rows(int device_id, int32_t kind, const float* src, const int32_t* row_idx, int32_t n, int32_t dim, void* dst,
+                   int32_t ld, const void* const* pages, const int32_t* page_w, int32_t n_pages, const int32_t* img, const int32_t* ph,
+                   const int32_t* pw, int32_t P, int32_t tp, const float* mean3, const float* std3, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -249,3 +249,60 @@ def op_patch_embed(imgs, H, W, patch, weight, D, K, bias, pos, ld_pos, out, ldo)
                                      None), "vr_op_patch_embed")
     torch.cuda.synchronize()
     return out
+
+
+# ---- the EVisRAG generator's small kernels (tests/test_gpu_gen_ops.py).  Outputs are the caller's, prefilled with a sentinel.
+def op_gen_mrope_cache(T, H, KV, pos3, pos_stride, sections, inv_freq, q_out, ldq, k_cache, v_cache, ld_cache, ld, src=None, parts=None,
+                       n_parts=0, plane_stride=0, bias=None, cache_row0=0, row0_dev=None, cache_rows=None, cu_kv=None):
+    lib = _lib.load()
+    _lib.check(lib.vr_op_gen_mrope_cache(k_cache.device.index or 0 if k_cache is not None else 0, P(src), P(parts), n_parts, int(plane_stride), P(bias), ld, T, H, KV, P(pos3),
+                                         pos_stride, sections[0], sections[1], P(inv_freq), P(q_out), ldq, P(k_cache), P(v_cache), ld_cache,
+                                         cache_row0, P(row0_dev), P(cache_rows), P(cu_kv), None), "vr_op_gen_mrope_cache")
+    torch.cuda.synchronize()
+
+
+def op_gen_rope2d(qkv, ld, T, n_slots, hh, pos_h, pos_w, sec_h, freq):
+    lib = _lib.load()
+    dev = freq.device.index or 0 if freq is not None else 0
+    _lib.check(lib.vr_op_gen_rope2d(dev, P(qkv), ld, T, n_slots, hh, P(pos_h), P(pos_w), sec_h, P(freq), None), "vr_op_gen_rope2d")
+    torch.cuda.synchronize()
+    return qkv
+
+
+def op_gen_sample(logits, vocab, seen, penalty=1.0, temperature=0.0, seed=0, step=0, state=None, step_from_state=False, advance=False):
+    """logits f32 [>= vocab], seen int32 words, state int32 [42] or None (all cuda) -> the pick (also marked in `seen`)"""
+    lib = _lib.load()
+    tok = C.c_int32(-7)
+    dev = seen.device.index or 0 if seen is not None else 0
+    _lib.check(lib.vr_op_gen_sample(dev, P(logits), vocab, P(seen), float(penalty), float(temperature), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                    int(step), P(state), int(step_from_state), int(advance), C.byref(tok), None), "vr_op_gen_sample")
+    return int(tok.value)
+
+
+def op_gen_mark_seen(ids, n, seen, vocab):
+    lib = _lib.load()
+    dev = seen.device.index or 0 if seen is not None else 0
+    _lib.check(lib.vr_op_gen_mark_seen(dev, P(ids), n, P(seen), vocab, None), "vr_op_gen_mark_seen")
+    torch.cuda.synchronize()
+    return seen
+
+
+def op_gen_decode_begin(state, q_rows):
+    lib = _lib.load()
+    _lib.check(lib.vr_op_gen_decode_begin(state.device.index or 0 if state is not None else 0, P(state), q_rows, None), "vr_op_gen_decode_begin")
+    torch.cuda.synchronize()
+    return state
+
+
+def op_gen_rows(kind, n, dst, ld, src=None, row_idx=None, dim=0, pages=None, page_w=None, img=None, ph=None, pw=None, patch=0, tp=0,
+                mean=None, std=None):
+    """kind 0 scatter f32 rows, 1 gather to bf16 + zero pad, 2 u8 patch rows (pages: a list of u8 HWC device tensors)"""
+    lib = _lib.load()
+    ptrs = (C.c_void_p * len(pages))(*[t.data_ptr() if t is not None else None for t in pages]) if pages is not None else None
+    f3 = lambda v: (C.c_float * 3)(*[float(x) for x in v]) if v is not None else None  # noqa: E731
+    dev = dst.device.index or 0 if dst is not None else 0
+    _lib.check(lib.vr_op_gen_rows(dev, kind, P(src), P(row_idx), n, dim, P(dst), ld, ptrs, _i32(page_w) if page_w is not None else None,
+                                  len(pages) if pages is not None else 0, P(img), P(ph), P(pw), patch, tp, f3(mean), f3(std), None),
+               "vr_op_gen_rows")
+    torch.cuda.synchronize()
+    return dst

@@ -11,6 +11,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from tests import chat_ref as R  # noqa: E402
+from tests import gen_ops_ref as G  # noqa: E402
 from tests.decode_bars import ACCUM_FP32_TERM, ATTN_FP32_TERM, SWIGLU_FP32_TERM  # noqa: E402
 from tests.gpu_util import from_bf16_bits, op_chat_attention, op_chat_select, op_gemm_skinny, op_plane_sum  # noqa: E402
 
@@ -238,6 +239,23 @@ def _sampler_loop(c, T, seed):
     seen = torch.zeros((1, (V + 31) // 32), dtype=torch.int32, device=DEV)
     torch.cuda.synchronize()
     return lambda step: op_chat_select(R.SAMPLE, lg, seen, V, [0, 1], c["K"], 1, temperature=T, seed=seed, step=step)
+
+
+@pytest.mark.parametrize("seed,step,idx", G.defective_triples())
+def test_chat_sampler_defective_draw(seed, step, idx):
+    """The chat twin of tests/test_gpu_gen_ops.py::test_sampler_defective_draw: (seed, step, idx) hashes to the draw 0xFFFFFF,
+    whose noise the parent's map made infinite.  K = 64 candidates: D at logit 30, token idx and 62 others at 0, everything else
+    at -20; T = 1.  The finite noise lies in [-2.86, 16.64], so the draw is D."""
+    V = 4096
+    D = (idx + 1500) % V
+    x = np.full((1, V), -20.0, np.float32)
+    others = [t for t in range(7, V, 61) if t not in (idx, D)][:62]
+    x[0, others] = 0.0
+    x[0, idx] = 0.0
+    x[0, D] = 30.0
+    c = dict(mode=R.SAMPLE, V=V, sizes=[1], logits=x, seen=np.zeros((1, V), bool), K=64, kout=1, pen=1.0, bscore=None)
+    sc, tk, pa = _select(c, temperature=1.0, seed=seed, step=step)
+    assert int(tk[0, 0]) == D and pa[0, 0] == 0 and sc[0, 0] == 30.0
 
 
 def test_chat_sampler_top64_membership():

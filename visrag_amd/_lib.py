@@ -153,6 +153,14 @@ SIGNATURES = {
     "vr_op_chat_select": (C.c_int, [C.c_int, _i32, _vp, _i32, _i32, _vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_f32), _i32, _i32,
                                     _f32, _f32, C.c_uint64, _i32, C.POINTER(_f32), C.POINTER(_i32), C.POINTER(_i32), _vp]),
     "vr_op_chat_prompt_scatter": (C.c_int, [C.c_int, _vp, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _vp, _vp, _vp]),
+    "vr_op_gen_mrope_cache": (C.c_int, [C.c_int, _vp, _vp, _i32, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32,
+                                        _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "vr_op_gen_rope2d": (C.c_int, [C.c_int, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "vr_op_gen_sample": (C.c_int, [C.c_int, _vp, _i32, _vp, _f32, _f32, C.c_uint64, _i32, _vp, _i32, _i32, C.POINTER(_i32), _vp]),
+    "vr_op_gen_mark_seen": (C.c_int, [C.c_int, _vp, _i32, _vp, _i32, _vp]),
+    "vr_op_gen_decode_begin": (C.c_int, [C.c_int, _vp, _i32, _vp]),
+    "vr_op_gen_rows": (C.c_int, [C.c_int, _i32, _vp, _vp, _i32, _i32, _vp, _i32, C.POINTER(_vp), C.POINTER(_i32), _i32, _vp, _vp, _vp,
+                                 _i32, _i32, C.POINTER(_f32), C.POINTER(_f32), _vp]),
     "vr_chat_create": (C.c_int, [_vp, C.POINTER(VRChatConfig), C.POINTER(_vp)]),
     "vr_chat_destroy": (C.c_int, [_vp]),
     "vr_chat_load_head": (C.c_int, [_vp, _vp, C.POINTER(_i64), _i32, _i32, _i32]),

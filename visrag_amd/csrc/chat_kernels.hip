@@ -25,16 +25,6 @@ __device__ __forceinline__ unsigned f2ord(float f) {
 }
 __device__ __forceinline__ float ord2f(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o); }
 
-// 64-bit counter hash -> standard Gumbel noise (the style of gen_kernels.hip's sampling noise)
-__device__ __forceinline__ float chat_gumbel(unsigned long long seed, unsigned step, unsigned idx) {
-    unsigned long long x = seed + 0x9E3779B97F4A7C15ull * ((unsigned long long)step << 32 | idx);
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    const float u = ((float)(x >> 40) + 0.5f) * (1.0f / 16777216.0f);
-    return -__logf(-__logf(u));
-}
-
 __device__ __forceinline__ unsigned long long key_max(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
 
 // max of a 64-bit key over the block (blockDim.x = 256); every thread gets the result
@@ -374,7 +364,7 @@ __global__ __launch_bounds__(256) void chat_topk_final_kernel(const unsigned lon
     int tok = -1, par = -1;
     if (tid < K) {
         decode(top[tid], s, tok, par);
-        if (tok >= 0) v = s * inv_t + chat_gumbel(seed, step, (unsigned)tok);
+        if (tok >= 0) v = s * inv_t + gumbel_noise(seed, step, (unsigned)tok);
     }
     // argmax over the lanes (ties: the lower lane = the better-ranked candidate)
     unsigned long long key = tok >= 0 ? ((unsigned long long)f2ord(v) << 32) | (unsigned)(~(unsigned)tid) : 0ull;

@@ -9,20 +9,6 @@
 
 namespace vr {
 
-namespace {
-
-// 64-bit counter hash -> uniform in (0, 1): the sampling noise of token `idx` at decode step `step`
-__device__ __forceinline__ float gumbel_noise(unsigned long long seed, unsigned step, unsigned idx) {
-    unsigned long long x = seed + 0x9E3779B97F4A7C15ull * ((unsigned long long)step << 32 | idx);
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    const float u = ((float)(x >> 40) + 0.5f) * (1.0f / 16777216.0f);
-    return -__logf(-__logf(u));
-}
-
-}  // namespace
-
 // One wave per (token, head slot): slots [0, H) rotate the query heads in place, [H, H + KV) rotate the key
 // heads into the K cache, [H + KV, H + 2 KV) copy the value heads into the V cache.  head_dim 128: lane p holds
 // the rotate-half pair (p, p + 64).  Multimodal RoPE (modeling_qwen2_5_vl.py:486-538, 557-599): the pair's angle is

@@ -21,6 +21,19 @@ __device__ __forceinline__ float sumsq4(f32x4 v) {
     return __builtin_fmaf(v[3], v[3], __builtin_fmaf(v[2], v[2], __builtin_fmaf(v[1], v[1], v[0] * v[0])));
 }
 
+// The samplers' noise (gen_kernels.hip, chat_kernels.hip): 64-bit counter hash of (seed, step, token id) -> a 24-bit draw ->
+// u = (draw + 0.5) 2^-24 -> standard Gumbel noise -log(-log(u)).  draw + 0.5 is rounded to float32 (from 2^23 on it is a tie, to
+// even), and for the draw 0xFFFFFF that rounding gives 2^24, i.e. u = 1 and infinite noise — the token was then drawn whatever
+// its logit, once in 2^24 (token, step) pairs.  That one draw is held at the largest float below 1; every other draw keeps its bits.
+__device__ __forceinline__ float gumbel_noise(unsigned long long seed, unsigned step, unsigned idx) {
+    unsigned long long x = seed + 0x9E3779B97F4A7C15ull * ((unsigned long long)step << 32 | idx);
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    const float u = fminf(((float)(x >> 40) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
+    return -__logf(-__logf(u));
+}
+
 // one KV range's contribution to the merge of partial attention rows: weight e = 2^(lse - max)
 __device__ __forceinline__ void merge_range(float& num, float& den, float e, float pv) {
 #pragma clang fp contract(off)

@@ -164,7 +164,8 @@ hipError_t launch_chat_select(const ChatSel& sel, int mode, const float* logits,
 // ---- EVisRAG generator (gen_kernels.hip) ---------------------------------------------------
 constexpr int GEN_ATT_SPLITS = 16;  // most KV ranges one decode step's attention is cut into
 // What a decode step needs beyond the caches, resident on the device so that consecutive steps need no host round trip
-// (gen.hip: host-driven steps upload the first five words; free-running steps advance them on the device).
+// (gen.hip: host-driven steps upload the first five words; free-running steps advance them on the device).  The op-level
+// entries take it as 42 i32 words: the layout is tabled in include/visrag_hip.h and asserted next to vr_op_gen_sample (ops.hip).
 struct GenState {
     int token;                      // the token this step appends
     int pos[3];                     // its temporal / height / width position

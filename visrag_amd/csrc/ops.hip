@@ -501,3 +501,103 @@ extern "C" int vr_op_patch_embed(int device_id, const void* const* imgs, int32_t
     if (e != hipSuccess) return fail(VR_ERR_HIP, "launch_patch_embed(...) failed: %s", hipGetErrorString(e));
     return VR_OK;
 }
+
+// ---- the EVisRAG generator's small kernels (gen_kernels.hip) ---
+// Thin forwards like the block above: NULL pointers and counts are checked here, what a kernel cannot do is the launcher's to
+// refuse (VR_ERR_HIP).  Entries that own a temporary drain the stream before they return.
+extern "C" int vr_op_gen_mrope_cache(int device_id, const void* src_bf16, const float* parts, int32_t n_parts, int64_t plane_stride,
+                                     const float* bias, int32_t ld, int32_t T, int32_t H, int32_t KV, const int32_t* pos3,
+                                     int32_t pos_stride, int32_t sec_t, int32_t sec_h, const float* inv_freq, void* q_out, int32_t ldq,
+                                     void* k_cache, void* v_cache, int32_t ld_cache, int32_t cache_row0, const int32_t* row0_dev,
+                                     const int32_t* cache_rows, int32_t* cu_kv, void* stream) {
+    if ((!src_bf16 && !parts) || !pos3 || !inv_freq || !q_out || !k_cache || !v_cache) return fail(VR_ERR_INVALID, "NULL argument");
+    if (T < 1 || H < 1 || KV < 1 || (parts && n_parts < 1)) return fail(VR_ERR_INVALID, "need T, H, KV >= 1 (and n_parts >= 1 with planes)");
+    VRCHK(set_dev(device_id));
+    HIPCHK(launch_mrope_cache(parts ? nullptr : src_bf16, parts, n_parts, (size_t)plane_stride, bias, ld, T, H, KV, pos3, pos_stride,
+                              sec_t, sec_h, inv_freq, q_out, ldq, k_cache, v_cache, ld_cache, cache_row0, cu_kv, (hipStream_t)stream,
+                              row0_dev, cache_rows));
+    return VR_OK;
+}
+
+extern "C" int vr_op_gen_rope2d(int device_id, void* qkv, int32_t ld, int32_t T, int32_t n_slots, int32_t hh, const int32_t* pos_h,
+                                const int32_t* pos_w, int32_t sec_h, const float* freq, void* stream) {
+    if (!qkv || !pos_h || !pos_w || !freq) return fail(VR_ERR_INVALID, "NULL argument");
+    if (T < 1 || n_slots < 1) return fail(VR_ERR_INVALID, "need T, n_slots >= 1");
+    VRCHK(set_dev(device_id));
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf cs;                                              // f32 [T][64][2] (freed on return: the stream is drained first)
+    VRCHK(cs.alloc((size_t)T * 64 * 8));
+    hipError_t e = launch_rope2d_table(pos_h, pos_w, T, sec_h, freq, cs.p, s);
+    if (e == hipSuccess) e = launch_rope2d_inplace(qkv, ld, T, n_slots, hh, cs.p, s);
+    HIPCHK(hipStreamSynchronize(s));
+    if (e != hipSuccess) return fail(VR_ERR_HIP, "launch_rope2d_table / launch_rope2d_inplace(...) failed: %s", hipGetErrorString(e));
+    return VR_OK;
+}
+
+// the words of `state` (include/visrag_hip.h) are GenState's
+static_assert(sizeof(GenState) == 42 * 4 && GEN_ATT_SPLITS == 16, "vr_op_gen_sample / vr_op_gen_decode_begin document 42 words");
+static std::map<int, DevBuf> g_gen_op_scratch;              // 64 partial keys + the token, per device
+
+extern "C" int vr_op_gen_sample(int device_id, const float* logits, int32_t vocab, uint32_t* seen, float repetition_penalty,
+                                float temperature, uint64_t seed, int32_t step, int32_t* state, int32_t step_from_state,
+                                int32_t advance, int32_t* out_token, void* stream) {
+    if (!logits || !seen || !out_token || ((step_from_state || advance) && !state)) return fail(VR_ERR_INVALID, "NULL argument");
+    if (vocab < 1) return fail(VR_ERR_INVALID, "vocab must be positive");
+    VRCHK(set_dev(device_id));
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf& sc = g_gen_op_scratch[device_id];
+    if (sc.bytes < 64 * 8 + 16) { HIPCHK(hipStreamSynchronize(s)); VRCHK(sc.reserve(64 * 8 + 16)); }
+    int* tok = (int*)((char*)sc.p + 64 * 8);
+    HIPCHK(launch_sample(logits, vocab, (unsigned*)seen, repetition_penalty, temperature, (unsigned long long)seed, (unsigned)step, tok,
+                         sc.as<unsigned long long>(), s, (GenState*)state, step_from_state, advance));
+    HIPCHK(hipMemcpyAsync(out_token, tok, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
+}
+
+extern "C" int vr_op_gen_mark_seen(int device_id, const int32_t* ids, int32_t n, uint32_t* seen, int32_t vocab, void* stream) {
+    if (!ids || !seen) return fail(VR_ERR_INVALID, "NULL argument");
+    if (n < 1 || vocab < 1) return fail(VR_ERR_INVALID, "need n, vocab >= 1");
+    VRCHK(set_dev(device_id));
+    HIPCHK(launch_mark_seen(ids, n, (unsigned*)seen, vocab, (hipStream_t)stream));
+    return VR_OK;
+}
+
+extern "C" int vr_op_gen_decode_begin(int device_id, int32_t* state, int32_t q_rows, void* stream) {
+    if (!state) return fail(VR_ERR_INVALID, "NULL argument");
+    if (q_rows < 1) return fail(VR_ERR_INVALID, "q_rows must be positive");
+    VRCHK(set_dev(device_id));
+    HIPCHK(launch_decode_begin((GenState*)state, q_rows, (hipStream_t)stream));
+    return VR_OK;
+}
+
+extern "C" int vr_op_gen_rows(int device_id, int32_t kind, const float* src, const int32_t* row_idx, int32_t n, int32_t dim, void* dst,
+                              int32_t ld, const void* const* pages, const int32_t* page_w, int32_t n_pages, const int32_t* img,
+                              const int32_t* ph, const int32_t* pw, int32_t P, int32_t tp, const float* mean3, const float* std3,
+                              void* stream) {
+    if (kind < 0 || kind > 2) return fail(VR_ERR_INVALID, "kind %d: 0 scatter f32 rows, 1 gather to bf16 + zero pad, 2 u8 patch rows", kind);
+    if (!dst || n < 1) return fail(VR_ERR_INVALID, "NULL argument or n < 1");
+    hipStream_t s = (hipStream_t)stream;
+    if (kind < 2) {
+        if (!src || !row_idx) return fail(VR_ERR_INVALID, "NULL argument");
+        if (dim < 1) return fail(VR_ERR_INVALID, "dim must be positive");
+        VRCHK(set_dev(device_id));
+        if (kind == 0) HIPCHK(launch_scatter_rows(src, row_idx, n, dim, (float*)dst, ld, s));
+        else HIPCHK(launch_gather_rows_bf16(src, row_idx, n, dim, dst, ld, s));
+        return VR_OK;
+    }
+    if (!pages || !page_w || !img || !ph || !pw || !mean3 || !std3) return fail(VR_ERR_INVALID, "NULL argument");
+    if (n_pages < 1 || P < 1 || tp < 1) return fail(VR_ERR_INVALID, "need n_pages, P, tp >= 1");
+    for (int i = 0; i < n_pages; ++i)
+        if (!pages[i]) return fail(VR_ERR_INVALID, "NULL argument");
+    VRCHK(set_dev(device_id));
+    DevBuf tab;                                             // the page pointers, then their widths (freed on return: the stream is drained first)
+    VRCHK(tab.alloc((size_t)n_pages * 12));
+    HIPCHK(hipMemcpyAsync(tab.p, pages, (size_t)n_pages * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync((char*)tab.p + (size_t)n_pages * 8, page_w, (size_t)n_pages * 4, hipMemcpyHostToDevice, s));
+    const hipError_t e = launch_patch_rows_u8((const uint8_t* const*)tab.p, (const int*)((const char*)tab.p + (size_t)n_pages * 8), img, ph, pw,
+                                              n, P, tp, mean3, std3, dst, ld, s);
+    HIPCHK(hipStreamSynchronize(s));
+    if (e != hipSuccess) return fail(VR_ERR_HIP, "launch_patch_rows_u8(...) failed: %s", hipGetErrorString(e));
+    return VR_OK;
+}
