@@ -511,6 +511,43 @@ int vr_index_search_window(vr_index_t ix, const float* queries, int32_t nq,
 /* Windowed searches since the last reset: out3 = {queries, band candidates re-scored in fp32, rows certainly ahead of their
  * window} — 64-bit counters in device memory. */
 int vr_index_window_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
+/* ---- fused search: the top-k rows by max or min over a group of sub-queries ---- */
+/* vr_index_search_multi: one question, several vectors (reformulations, the last turns of a chat, the sub-questions of a
+ * multi-hop question).  The sub-queries are a flat [n_sub][dim] float32 array; group g holds sub-queries lims[g] ..
+ * lims[g + 1] - 1 (CSR).  For group g, its sub-queries j and row i the FUSED score is
+ *     E_g(i) = max_j e_j(i)   (fuse = 0, "any-of": a row scores as its best sub-query does)
+ *     E_g(i) = min_j e_j(i)   (fuse = 1, "all-of": a row scores as its worst sub-query does)
+ * with e_j(i) the library's one fp32 dot product (the bits vr_index_search returns for that pair); max and min are taken in the
+ * ranking's own order of floats, in which -0.0 < +0.0.  The result of group g is the k rows of largest E_g among the rows the
+ * group's filter allows (filter_of_group NULL or an entry of -1: all rows), score descending, then lower id first; slots past
+ * the allowed rows hold (-inf, -1, -1).  out_which names, for every returned row, the lowest in-group index j (0-based inside
+ * the group) whose e_j(i) has exactly the fused score's bits.  A group of one equals vr_index_search / _search_filtered bit for
+ * bit, with which == 0.
+ *   Layout: lims [n_groups + 1] int64 is always a HOST array (as the offsets of vr_index_search_window are); queries, filter_of_group
+ * [n_groups] int32 and the outputs [n_groups][k] are all host or all device per `on_device`.
+ *   Exactness: with |b_j - e_j| <= eps_j for the bf16 MFMA scores b_j, the fused bf16 value B_g = max_j b_j (or min) lies within
+ * eps_g = max_j eps_j of E_g for every row, because max and min over a fixed set are 1-Lipschitz in the sup norm.  From there it
+ * is the windowed search's argument at offset 0: a row whose B_g lies more than 2 eps_g below the min(k, allowed)-th largest B_g
+ * is certainly behind the whole result; every other row is re-scored in fp32 against every sub-query of the group and ranked by
+ * key.  No candidate margin, no widening, no flagged group; the result is exact in every setting of vr_index_set_search_eps
+ * (with certification off the default error model defines the band).
+ *   Checks, all before any launch and with the outputs untouched: NULL pointers with n_groups > 0, n_groups < 0, n_sub < 0,
+ * k outside 1..1000, fuse outside {0, 1}, an unsupported dim (as vr_index_search_window), lims[0] != 0, a decreasing lims, an
+ * empty group, a group of more than 256 sub-queries, lims[n_groups] != n_sub: VR_ERR_INVALID; the filter checks are those of
+ * vr_index_search_window (on the device an out-of-range filter index gives a row of tails).  n_groups == 0 (then n_sub == 0):
+ * VR_OK, nothing is launched.  An empty index: tails, nothing is launched.  Nothing is stored between calls.  A host caller's
+ * call synchronises the stream.  Not offered: weighted-sum fusion (linear: sum the queries into one), reciprocal-rank fusion,
+ * a window offset, groups of documents, MMR over a fused pool, corpus-sharded ranks, groups of more than 256 sub-queries. */
+int vr_index_search_multi(vr_index_t ix, const float* queries, int32_t n_sub,
+                          const int64_t* lims,              /* host [n_groups + 1] */
+                          int32_t n_groups, int32_t k,
+                          int32_t fuse,                     /* 0: max, 1: min */
+                          const int32_t* filter_of_group,   /* NULL: no filter for any group */
+                          float* out_scores, int64_t* out_ids, int32_t* out_which,   /* [n_groups][k] */
+                          int32_t on_device, void* stream);
+/* Fused searches since the last reset: out3 = {groups, band columns re-scored in fp32, fp32 row dot products (columns x group
+ * size)} — 64-bit counters in device memory. */
+int vr_index_multi_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
 /* ---- editing in place: remove rows, overwrite rows, read rows back ---- */
 /* After any of the calls below every search behaves exactly — score bits, ids, groups, lims — as on an index freshly built
  * (vr_index_create, vr_index_add, vr_index_set_filters / vr_index_set_groups) from the rows that remain.  Ids are positions, as

@@ -50,6 +50,10 @@ struct vr_index_s {
     // windowed search (vr_index_search_window, search_window.hip): scratch and counters of its own, no stored result
     DevBuf woff, wedge, wstate;       // int64 offsets of the call's queries | f32 band edges {lo, hi} of a block's queries | u64 words:
                                       // [0..2] the counters of vr_index_window_search_stats, [4..] never written (as rstate's)
+    // fused search (vr_index_search_multi, search_multi.hip): scratch and counters of its own, no stored result
+    DevBuf mlims, mfsub, medge, mwhich, mstate;   // int lims of the call's groups | int filter of every sub-query | f32 band edge of a
+                                      // block's groups | staged out_which | u64 words: [0..2] the counters of vr_index_multi_search_stats,
+                                      // [4..] never written (as rstate's)
     // editing in place (vr_index_remove / vr_index_update / vr_index_get_rows, index_edit.hip)
     DevBuf eids, erows, fbits2;       // int row ids of the call | rows of a host caller, staged (<= EDIT_SCRATCH bytes for get_rows) |
                                       // the filters compacted out of place: swapped with fbits
@@ -86,6 +90,7 @@ extern "C" int vr_index_destroy(vr_index_t ix) {
                       &ix->sbuf, &ix->cert, &ix->flags, &ix->flagq, &ix->goff, &ix->gB, &ix->og, &ix->gstate,
                       &ix->fbits, &ix->fcount, &ix->ffq, &ix->fstate, &ix->dps, &ix->dpi, &ix->rs, &ix->ri, &ix->rthr, &ix->rlims,
                       &ix->rcnt, &ix->roff, &ix->rstate, &ix->kq, &ix->kv, &ix->kbar, &ix->keps, &ix->kstate, &ix->woff, &ix->wedge, &ix->wstate,
+                      &ix->mlims, &ix->mfsub, &ix->medge, &ix->mwhich, &ix->mstate,
                       &ix->eids, &ix->erows, &ix->fbits2})
         b->free();
     if (ix->range_host) (void)hipHostFree(ix->range_host);
@@ -1019,6 +1024,144 @@ extern "C" int vr_index_search_window(vr_index_t ix, const float* queries, int32
     }
     VRCHK(return_output(out_scores, os, n_out, on_device, s));
     VRCHK(return_output(out_ids, oi, n_out, on_device, s));
+    if (!on_device) HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
+}
+
+extern "C" int vr_index_multi_search_stats(vr_index_t ix, int64_t* out3, int32_t reset) {
+    if (!ix || !out3) return fail(VR_ERR_INVALID, "NULL argument");
+    out3[0] = out3[1] = out3[2] = 0;
+    if (!ix->mstate.p) return VR_OK;              // no fused search ever ran: nothing counted
+    VRCHK(set_dev(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    unsigned long long w[3];
+    HIPCHK(hipMemcpy(w, ix->mstate.p, sizeof(w), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 3; ++i) out3[i] = (int64_t)w[i];
+    if (reset) HIPCHK(hipMemset(ix->mstate.p, 0, sizeof(w)));
+    return VR_OK;
+}
+
+// The k rows of largest fused score of every group of sub-queries (search_multi.hip): every check first, then whole groups packed
+// greedily into blocks of <= 256 sub-queries, and per block the score rows, the mask, the fusion, the band edges, the rewritten
+// fused rows and the select.  Scratch (query staging, score rows, the staged filter_of_group and outputs) is shared with the
+// other searches; nothing is stored.
+extern "C" int vr_index_search_multi(vr_index_t ix, const float* queries, int32_t n_sub, const int64_t* lims, int32_t n_groups,
+                                     int32_t k, int32_t fuse, const int32_t* filter_of_group, float* out_scores, int64_t* out_ids,
+                                     int32_t* out_which, int32_t on_device, void* stream) {
+    if (!ix || n_groups < 0 || n_sub < 0 || (n_groups > 0 && (!queries || !lims || !out_scores || !out_ids || !out_which)))
+        return fail(VR_ERR_INVALID, "bad arguments");
+    if (k <= 0 || k > search_bigk_max()) return fail(VR_ERR_INVALID, "k=%d unsupported (1..%d)", k, search_bigk_max());
+    if (fuse != 0 && fuse != 1) return fail(VR_ERR_INVALID, "fuse=%d unsupported (0: max, 1: min)", (int)fuse);
+    if (!range_dim_ok(ix->dim)) return fail(VR_ERR_INVALID, "dim %d unsupported", ix->dim);
+    if (n_groups == 0) {
+        if (n_sub != 0) return fail(VR_ERR_INVALID, "%d sub-queries in no group", (int)n_sub);
+        return VR_OK;                             // no group: no launch
+    }
+    if (lims[0] != 0) return fail(VR_ERR_INVALID, "lims[0] = %lld, not 0", (long long)lims[0]);
+    for (int32_t g = 0; g < n_groups; ++g) {
+        const int64_t m = lims[g + 1] - lims[g];
+        if (m < 0) return fail(VR_ERR_INVALID, "lims[%d] = %lld decreases", (int)g + 1, (long long)lims[g + 1]);
+        if (m == 0) return fail(VR_ERR_INVALID, "group %d is empty", (int)g);
+        if (m > 256) return fail(VR_ERR_INVALID, "group %d holds %lld sub-queries (1..256)", (int)g, (long long)m);
+    }
+    if (lims[n_groups] != n_sub)
+        return fail(VR_ERR_INVALID, "lims[%d] = %lld, not the %d sub-queries", (int)n_groups, (long long)lims[n_groups], (int)n_sub);
+    if (filter_of_group) {
+        if (ix->n_filters <= 0 || ix->n <= 0) return fail(VR_ERR_STATE, "no filters set for the rows of the index (vr_index_set_filters)");
+        if (!on_device)
+            for (int32_t g = 0; g < n_groups; ++g)
+                if (filter_of_group[g] < -1 || filter_of_group[g] >= ix->n_filters)
+                    return fail(VR_ERR_INVALID, "filter_of_group[%d] = %d outside [-1, %lld)", (int)g, (int)filter_of_group[g], (long long)ix->n_filters);
+    }
+    VRCHK(set_dev(ix->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n_out = (size_t)n_groups * k;
+    if (ix->n == 0) {                             // no row: tails, no launch
+        if (on_device) {
+            HIPCHK(hipMemsetD32Async((hipDeviceptr_t)out_scores, (int)0xFF800000u, n_out, s));     // -inf
+            HIPCHK(hipMemsetAsync(out_ids, 0xFF, n_out * 8, s));                                   // -1
+            HIPCHK(hipMemsetAsync(out_which, 0xFF, n_out * 4, s));
+        } else {
+            std::fill(out_scores, out_scores + n_out, -INFINITY);
+            std::fill(out_ids, out_ids + n_out, (int64_t)-1);
+            std::fill(out_which, out_which + n_out, (int32_t)-1);
+        }
+        return VR_OK;
+    }
+    if (!ix->mstate.p) VRCHK(ix->mstate.alloc(WIN_WORDS * 8));
+    const int dim = ix->dim;
+    const int64_t ldS = pad256l(ix->n);
+    const int64_t qblk = 256;                     // one fp32 score row per sub-query, as on the deep path
+    const float* q32 = nullptr;
+    VRCHK(stage_queries(ix, queries, n_sub, pad256l(std::min<int64_t>(n_sub, qblk)), on_device, s, &q32));
+    std::vector<int> lims32((size_t)n_groups + 1);
+    for (int32_t g = 0; g <= n_groups; ++g) lims32[g] = (int)lims[g];
+    VRCHK(ix->mlims.reserve(lims32.size() * 4));
+    VRCHK(ix->medge.reserve((size_t)qblk * 4));
+    HIPCHK(hipMemcpyAsync(ix->mlims.p, lims32.data(), lims32.size() * 4, hipMemcpyHostToDevice, s));
+    const int* fog = filter_of_group;
+    if (fog) {                                    // the group's filter for every one of its score rows: what the mask reads
+        if (!on_device) {
+            VRCHK(ix->ffq.reserve((size_t)n_groups * 4));
+            HIPCHK(hipMemcpyAsync(ix->ffq.p, filter_of_group, (size_t)n_groups * 4, hipMemcpyHostToDevice, s));
+            fog = ix->ffq.as<int>();
+        }
+        VRCHK(ix->mfsub.reserve((size_t)n_sub * 4));
+        HIPCHK(launch_multi_expand(ix->mlims.as<int>(), fog, n_groups, ix->mfsub.as<int>(), s));
+    }
+    HIPCHK(hipStreamSynchronize(s));              // (the host arrays are free from here on)
+    float* os = nullptr; int64_t* oi = nullptr; int32_t* ow = nullptr;
+    VRCHK(stage_output(ix->os, out_scores, n_out, on_device, &os));
+    VRCHK(stage_output(ix->oi, out_ids, n_out, on_device, &oi));
+    VRCHK(stage_output(ix->mwhich, out_which, n_out, on_device, &ow));
+    VRCHK(ix->sbuf.reserve((size_t)qblk * ldS * 4));
+    unsigned long long* words = ix->mstate.as<unsigned long long>();
+    const bool certify = ix->eps_rel == -2.f || ix->eps_rel >= 0.f;
+    for (int32_t g0 = 0; g0 < n_groups;) {
+        int32_t g1 = g0 + 1;                      // whole groups while the block holds <= 256 sub-queries
+        while (g1 < n_groups && lims[g1 + 1] - lims[g0] <= qblk) ++g1;
+        const int64_t s0 = lims[g0];
+        const int nb = (int)(lims[g1] - s0), ng = g1 - g0;
+        const int64_t nbp = pad256l(nb);
+        HIPCHK(launch_f32_to_bf16_pad(q32 + (size_t)s0 * dim, ix->qbf.p, (size_t)nb * dim, (size_t)nbp * dim, s));   // rows >= nb: zeros
+        MultiSearchArgs p{};
+        SearchArgs& a = p.a;
+        a.index_bf16 = ix->bf16.p; a.index_f32 = ix->f32.as<float>(); a.n_docs = ix->n; a.dim = dim;
+        a.q_bf16 = ix->qbf.p; a.q_f32 = q32 + (size_t)s0 * dim; a.nq = nb; a.k = k;
+        // the band is defined by the error model: with certification off, the default one defines it
+        fill_error_model(ix, a);
+        if (!certify) { a.eps_data = 1; a.eps_rel = 0.f; }
+        a.out_scores = os + (size_t)g0 * k; a.out_ids = oi + (size_t)g0 * k;
+        p.out_which = ow + (size_t)g0 * k;
+        p.lims = ix->mlims.as<int>() + g0;
+        p.sub_base = (int)s0;
+        p.fuse = fuse;
+        p.filter_of_group = fog ? fog + g0 : nullptr;
+        p.n_filters = (int)ix->n_filters;
+        p.allowed = fog ? ix->fcount.as<int>() : nullptr;
+        p.edges = ix->medge.as<float>();
+        p.stats = words;
+        // S[sub-query][row] = sub-queries x index^T on the bf16 MFMA GEMM, the deep path's launch; disallowed columns -> -inf
+        VRCHK(score_rows(ix, ix->qbf.p, nb, nullptr, 0, GEMM_VARIANT_AUTO, ldS, s));
+        if (fog) {
+            FilterSearchArgs f{};                 // the mask reads bits, words, n_filters and filter_of_query; the rest passes its argument check
+            f.a = a;
+            f.a.flag_count = reinterpret_cast<int*>(words + WIN_SPARE); f.a.flag_list = f.a.flag_count + 2;
+            f.bits = ix->fbits.as<uint32_t>(); f.words = (size_t)((ix->n + 31) / 32); f.n_filters = (int)ix->n_filters;
+            f.allowed = ix->fcount.as<int>();
+            f.filter_of_query = ix->mfsub.as<int>() + s0;
+            f.stats = reinterpret_cast<unsigned*>(words + WIN_SPARE) + 4;
+            HIPCHK(launch_filter_mask(f, ix->sbuf.as<float>(), (size_t)ldS, nb, nullptr, 0, s));
+        }
+        HIPCHK(launch_multi_fuse(p, ix->sbuf.as<float>(), (size_t)ldS, ng, s));
+        HIPCHK(launch_multi_edges(p, ix->sbuf.as<float>(), (size_t)ldS, ng, s));
+        HIPCHK(launch_multi_rescore(p, ix->sbuf.as<float>(), (size_t)ldS, ng, s));
+        HIPCHK(launch_multi_select(p, ix->sbuf.as<float>(), (size_t)ldS, ng, s));
+        g0 = g1;
+    }
+    VRCHK(return_output(out_scores, os, n_out, on_device, s));
+    VRCHK(return_output(out_ids, oi, n_out, on_device, s));
+    VRCHK(return_output(out_which, ow, n_out, on_device, s));
     if (!on_device) HIPCHK(hipStreamSynchronize(s));
     return VR_OK;
 }

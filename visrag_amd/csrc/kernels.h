@@ -462,6 +462,30 @@ hipError_t launch_window_edges(const WindowSearchArgs& p, const float* S, size_t
 hipError_t launch_window_rescore(const WindowSearchArgs& p, float* S, size_t ldS, int nq_block, hipStream_t s);
 // ranks [offset, offset + k) of the rewritten rows -> a.out_scores / a.out_ids, (-inf, -1) past the allowed rows
 hipError_t launch_window_select(const WindowSearchArgs& p, const float* S, size_t ldS, int nq_block, hipStream_t s);
+// ---- fused search (search_multi.hip): the k rows of largest max (or min) fp32 score over a group of sub-queries
+struct MultiSearchArgs {
+    SearchArgs a;                    // the block's view, as WindowSearchArgs': q_f32 and nq are the block's SUB-QUERIES (whole groups, <= 256),
+                                     // k, out_scores / out_ids [groups][k]: the block's part of the result (no out_keys), a valid error model
+    const int* lims;                 // [groups + 1] device: the block's entries of the call's lims; group g = sub-queries lims[g] .. lims[g + 1] - 1
+    int sub_base;                    // the call's index of the block's first sub-query (= lims[0]): score row of sub-query s is s - sub_base
+    int fuse;                        // 0: max over the group, 1: min
+    const int* filter_of_group;      // [groups] device or null, as WindowSearchArgs' filter_of_query: the score rows have been masked
+    int n_filters;                   //   with the group's filter in every sub-row; an entry outside [-1, n_filters): a row of tails
+    const int* allowed;              // [n_filters] device (filter_of_group set): the rows every filter allows
+    float* edges;                    // [groups] scratch: the band's lower edge lo of fused bf16 scores (NaN: nothing allowed)
+    int* out_which;                  // [groups][k] the block's part: the in-group sub-query that decided every row (-1: a tail)
+    unsigned long long* stats;       // [0] groups [1] band columns re-scored in fp32 [2] fp32 row dots (columns x group size)
+};
+// filter_of_sub[s] = filter_of_group[g] for lims[g] <= s < lims[g + 1]: the mask's filter of every score row
+hipError_t launch_multi_expand(const int* lims, const int* filter_of_group, int n_groups, int* filter_of_sub, hipStream_t s);
+// the group's first score row becomes the column-wise max / min over its rows (masked bf16-MFMA scores)
+hipError_t launch_multi_fuse(const MultiSearchArgs& p, float* S, size_t ldS, int n_groups, hipStream_t s);
+// edges[g] from a radix select over group g's fused row; S is only read
+hipError_t launch_multi_edges(const MultiSearchArgs& p, const float* S, size_t ldS, int n_groups, hipStream_t s);
+// the fused rows rewritten in place: -inf certainly behind or masked, the fp32 fused score at or above the edge
+hipError_t launch_multi_rescore(const MultiSearchArgs& p, float* S, size_t ldS, int n_groups, hipStream_t s);
+// the k best of the rewritten fused rows -> a.out_scores / a.out_ids / out_which, (-inf, -1, -1) past the allowed rows
+hipError_t launch_multi_select(const MultiSearchArgs& p, const float* S, size_t ldS, int n_groups, hipStream_t s);
 // ---- diversified search (search_diverse.hip): k rows per query picked by maximal marginal relevance from a pool of its best rows
 struct MmrArgs {
     const float* index_f32;          // [n_docs][dim] f32

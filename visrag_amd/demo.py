@@ -6,6 +6,9 @@
   * `retrieve(knowledge_base_path, query, topk, ...)` -> paths of the top-k page images
                                                                answer.py:14-40
     (`documents=[...]`: only the pages of those documents are ranked — HipIndex.search_filtered)
+  * `retrieve_any(knowledge_base_path, questions, topk, ...)` -> the top-k pages for a question asked in several ways, by the
+                                                               best ("any-of") or the worst ("all-of") of their scores
+                                                               (HipIndex.search_multi; no reference counterpart)
   * `retrieve_documents(knowledge_base_path, query, topk, ...)` -> the best page of each of the top-k DOCUMENTS
                                                                (no reference counterpart: its top-k is pages)
   * `retrieve_above(knowledge_base_path, query, min_score, ...)` -> EVERY page at or above a score, best first
@@ -186,6 +189,44 @@ def _retrieve_window(knowledge_base_path, query, topk, model, tokenizer, index, 
     if own:
         index.close()
     return (paths, scores) if return_scores else paths
+
+
+@torch.no_grad()
+def retrieve_any(knowledge_base_path: str, questions, topk: int, model, tokenizer, index=None, names=None, fuse: str = "max",
+                 documents=None, return_scores: bool = False):
+    """Paths of the `topk` pages that serve a question asked in SEVERAL ways (None if the base does not exist): `questions` is
+    a list of strings — reformulations, the last turns of a chat, the sub-questions of a multi-hop question — or their
+    embeddings [m, dim].  `fuse="max"` ("any-of") scores a page as its best question does, `fuse="min"` ("all-of") as its worst
+    does, so a page has to serve every part (HipIndex.search_multi: the exact top-k of the fused score, no duplicates to
+    collapse, never fewer than `topk` pages while the base has them).  `documents`: only the pages of those documents, as in
+    `retrieve` (one filter, set for this question).  With `return_scores` -> (paths, scores, deciding): `deciding[i]` is the
+    index into `questions` of the question whose score is page i's fused score.  Pass `index, names = load_knowledge_base(path)`
+    to keep the index resident."""
+    if not os.path.exists(knowledge_base_path):
+        return None
+    own = index is None
+    if own:
+        index, names = load_knowledge_base(knowledge_base_path, model.encoder.device if model is not None else None)
+    n = len(index)
+    if isinstance(questions, (list, tuple)) and all(isinstance(x, str) for x in questions):
+        q = encode(model, tokenizer, [QUERY_INSTRUCTION + x for x in questions])
+    else:
+        q = np.asarray(questions.detach().cpu() if isinstance(questions, torch.Tensor) else questions, dtype=np.float32)
+    q = np.ascontiguousarray(np.asarray(q, dtype=np.float32).reshape(-1, index.dim))
+    mask = None if documents is None else label_filters([doc_of_page(nm) for nm in names[:n]], [documents])
+    k = min(topk, n if mask is None else int(mask.sum()), 1000)
+    paths, scores, deciding = [], [], []
+    if k > 0 and len(q) > 0:
+        if mask is not None:
+            index.set_filters(mask)
+        sc, ids, which = index.search_multi(q, [0, len(q)], k, fuse, None if mask is None else 0)
+        keep = [int(i) for i in ids[0] if i >= 0]
+        paths = [os.path.join(knowledge_base_path, names[i]) for i in keep]
+        scores = [float(s) for s in sc[0][: len(keep)]]
+        deciding = [int(w) for w in which[0][: len(keep)]]
+    if own:
+        index.close()
+    return (paths, scores, deciding) if return_scores else paths
 
 
 def _retrieve_diverse(knowledge_base_path, query, topk, model, tokenizer, index, names, return_scores, documents, lam, pool):

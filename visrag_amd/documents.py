@@ -20,6 +20,10 @@ depth cannot give — MRR without a cut-off, recall at any k.
 
 The windowed search (HipIndex.search_window) returns the rows at ranks [offset, offset + k): `window_negatives` takes such a
 window and a query's positives and leaves the hard negatives a trainer wants ("ranks 30-200 minus the positives").
+
+The fused search (HipIndex.search_multi) ranks rows by the max or the min of their scores over a group of sub-queries:
+`group_rows` of the sub-queries' labels gives its `lims`, and `fuse_runs` states what per-sub-query top-k lists can and cannot
+say about that ranking — the workaround the fused search replaces.
 Pure numpy: nothing here touches the GPU.
 """
 from __future__ import annotations
@@ -36,7 +40,11 @@ def group_rows(labels: Sequence[Hashable]) -> Tuple[np.ndarray, np.ndarray, List
     j of the grouped layout; groups come in the order their label first appears and rows keep their order inside a group, so
     labels that are contiguous already give the identity.  `offsets` (int64 [n_groups + 1]) are the groups' first rows in the
     grouped layout — what `HipIndex.set_groups` takes — and `names[g]` is the label of group g.  A row id `i` returned by a
-    search over the grouped layout is row `order[i]` of the input."""
+    search over the grouped layout is row `order[i]` of the input.
+
+    The same call groups SUB-QUERIES for `HipIndex.search_multi`: with `labels[s]` the question sub-query s belongs to,
+    `queries[order]` is the flat layout it takes, `offsets` its `lims` and `names[g]` the question of group g; `which` of a
+    result counts inside the group, so the deciding sub-query of the input is `order[offsets[g] + which]`."""
     first: dict = {}
     gid = np.empty(len(labels), dtype=np.int64)
     names: List[Hashable] = []
@@ -240,3 +248,56 @@ def window_negatives(ids, positives_of_query, count: int) -> np.ndarray:
         keep = row[(row >= 0) & ~np.isin(row, pos)][:count]
         out[q, :len(keep)] = keep
     return out
+
+
+def fuse_runs(scores, ids, lims, k: int, fuse: str = "max") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """What per-sub-query top lists say about the fused ranking of `HipIndex.search_multi` -> (scores f32 [n_groups][k], ids i64
+    [n_groups][k], determined bool [n_groups]).  `scores` / `ids` [n_sub][depth] are the lists of `search(depth)` for every
+    sub-query (best first, tails (-inf, -1)); group g holds sub-queries lims[g] .. lims[g + 1] - 1.  The result is ranked score
+    descending, then lower id first, padded with (-inf, -1).
+
+    fuse="max" ("any-of"): a listed row scores as the best of its listed scores.  A row of the true top-k stands in the top-k
+    of the sub-query that decides it, so with depth >= k (or lists that ended: every row is listed) the answer is the true
+    one: determined.  fuse="min" ("all-of"): only a row that appears in EVERY list of its group has a known score, and a row
+    missing from a full list j may still score up to that list's last entry.  The rows returned are those of every list;
+    `determined[g]` says whether k of them (or, when every list ended, all of them) lie strictly above that bound — otherwise
+    a row at rank 5 000 for one part and rank 3 for the other may belong in front, and no top-k list shows it."""
+    if fuse not in ("max", "min"):
+        raise ValueError("fuse must be 'max' or 'min'")
+    scores, ids = np.asarray(scores, dtype=np.float32), np.asarray(ids, dtype=np.int64)
+    lims = np.asarray(lims, dtype=np.int64).reshape(-1)
+    k = int(k)
+    if scores.ndim != 2 or scores.shape != ids.shape:
+        raise ValueError("scores and ids must both be [n_sub][depth]")
+    if len(lims) < 1 or lims[0] != 0 or (np.diff(lims) < 1).any() or lims[-1] != len(ids):
+        raise ValueError("lims must start at 0, increase and end at the number of sub-queries")
+    if k < 1:
+        raise ValueError("k must be >= 1")
+    ng, depth = len(lims) - 1, scores.shape[1]
+    out_s = np.full((ng, k), -np.inf, dtype=np.float32)
+    out_i = np.full((ng, k), -1, dtype=np.int64)
+    determined = np.zeros(ng, dtype=bool)
+    for g in range(ng):
+        rows: dict = {}                                # row -> [fused score so far, lists it appears in]
+        ended, bound = True, -np.inf                   # every list ended | the largest last entry of a full list
+        m = int(lims[g + 1] - lims[g])
+        for s in range(int(lims[g]), int(lims[g + 1])):
+            live = ids[s] >= 0
+            if live.all() and depth > 0:
+                ended, bound = False, max(bound, float(scores[s, -1]))
+            for i, v in zip(ids[s][live].tolist(), scores[s][live].tolist()):
+                e = rows.get(i)
+                if e is None:
+                    rows[i] = [v, 1]
+                else:
+                    e[0], e[1] = (max(e[0], v) if fuse == "max" else min(e[0], v)), e[1] + 1
+        known = [(v, i) for i, (v, c) in rows.items() if fuse == "max" or c == m]
+        known.sort(key=lambda t: (-t[0], t[1]))
+        top = known[:k]
+        out_s[g, :len(top)] = [v for v, _ in top]
+        out_i[g, :len(top)] = [i for _, i in top]
+        if fuse == "max" or m == 1:                    # (a group of one: the list itself, under either fusion)
+            determined[g] = ended or depth >= k
+        else:
+            determined[g] = ended or (len(top) == k and top[-1][0] > bound)
+    return out_s, out_i, determined

@@ -639,6 +639,60 @@ class HipIndex:
         _lib.check(self.lib.vr_index_window_search_stats(self._h, out, 1 if reset else 0))
         return {"queries": int(out[0]), "candidates": int(out[1]), "ahead": int(out[2])}
 
+    # ---- fused search (include/visrag_hip.h: vr_index_search_multi) ----
+    def search_multi(self, queries, lims, k: int, fuse: str = "max", filter_of_group=None):
+        """The k rows of largest fused score per group of sub-queries (include/visrag_hip.h: vr_index_search_multi) -> (scores
+        [n_groups,k] f32, ids [n_groups,k] i64, which [n_groups,k] i32).  A row's fused score is the max (`fuse="max"`, "any-of")
+        or the min (`fuse="min"`, "all-of") of its fp32 scores — the bits `search` returns — over the group's sub-queries; rows
+        come score descending, then lower id first, among the rows the group's filter allows, slots past them are (-inf, -1, -1);
+        `which` is the lowest in-group index of a sub-query whose score IS the fused score.  `queries`: flat [n_sub][dim] with
+        `lims` [n_groups + 1] (group g = sub-queries lims[g] .. lims[g + 1] - 1; documents.group_rows makes it from labels), or
+        [n_groups][m][dim] with `lims=None`.  Groups hold 1..256 sub-queries, 1 <= k <= 1000.  `filter_of_group` as
+        `filter_of_query` in `search_filtered`, one entry per group; None = no filter (none need to be set).  cuda in -> cuda
+        out, numpy / cpu in -> numpy out."""
+        if fuse not in ("max", "min"):
+            raise ValueError("fuse must be 'max' or 'min'")
+        cuda = isinstance(queries, torch.Tensor) and queries.is_cuda
+        if cuda:
+            q = queries.to(torch.float32).contiguous()
+        else:
+            q = np.ascontiguousarray(queries.numpy() if isinstance(queries, torch.Tensor) else queries, dtype=np.float32)
+        if lims is None:
+            if q.ndim != 3 or q.shape[2] != self.dim:
+                raise ValueError(f"queries must be [n_groups][m][{self.dim}] when lims is None")
+            lim = np.arange(q.shape[0] + 1, dtype=np.int64) * q.shape[1]
+            q = q.reshape(-1, self.dim)
+        else:
+            if q.ndim != 2 or q.shape[1] != self.dim:
+                raise ValueError(f"queries must be [n_sub][{self.dim}] with lims")
+            lim = np.ascontiguousarray(self._row_ids(lims), dtype=np.int64)
+            if len(lim) < 1:
+                raise ValueError("lims must hold n_groups + 1 entries")
+        ng, n_sub = len(lim) - 1, int(q.shape[0])
+        if filter_of_group is None:
+            keep, fptr = None, C.c_void_p(None)
+        else:
+            keep, fptr = self._filter_of_query(torch.empty((ng, 0), device=q.device) if cuda else np.empty((ng, 0)), filter_of_group)
+        if cuda:
+            outs = [torch.empty((ng, k), dtype=d, device=q.device) for d in (torch.float32, torch.int64, torch.int32)]
+            ptrs = [x.data_ptr() for x in [q] + outs]
+        else:
+            outs = [np.empty((ng, max(k, 0)), dtype=d) for d in (np.float32, np.int64, np.int32)]
+            ptrs = [x.ctypes.data for x in [q] + outs]
+        _lib.check(self.lib.vr_index_search_multi(self._h, C.c_void_p(ptrs[0]), n_sub, C.c_void_p(lim.ctypes.data), ng, k,
+                                                  0 if fuse == "max" else 1, fptr, C.c_void_p(ptrs[1]), C.c_void_p(ptrs[2]),
+                                                  C.c_void_p(ptrs[3]), 1 if cuda else 0, C.c_void_p(_stream_ptr(self.device))),
+                   "vr_index_search_multi")
+        del keep
+        return tuple(outs)
+
+    def multi_search_stats(self, reset: bool = False) -> Dict[str, int]:
+        """Fused searches since the last reset: groups, columns of the bands re-scored in fp32, fp32 row dot products (every
+        band column against every sub-query of its group)."""
+        out = (C.c_int64 * 3)()
+        _lib.check(self.lib.vr_index_multi_search_stats(self._h, out, 1 if reset else 0))
+        return {"groups": int(out[0]), "candidates": int(out[1]), "dots": int(out[2])}
+
     def search_keys(self, queries: torch.Tensor, k: int, id_offset: int = 0) -> torch.Tensor:
         """The same search with each result packed into ONE 64-bit word (include/visrag_hip.h:
         vr_index_search_keys): orderable(score) << 32 | ~(row + id_offset); 0 = empty slot.  -> int64 [nq, k]

@@ -27,7 +27,7 @@ from __future__ import annotations
 import logging
 import os
 import warnings
-from typing import Callable, Dict, List, Optional, Tuple
+from typing import Callable, Dict, Hashable, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -396,6 +396,54 @@ def retrieve_deep(args, depth: int, index_factory: Optional[Callable] = None) ->
         for s, j in zip(sc[qi], pos[qi]):
             if j >= 0:
                 result[q][all_ids[int(j)]] = float(s)
+    return result
+
+
+def retrieve_fused(args, group_of_query: Callable, topk: int, fuse: str = "max", index_factory: Optional[Callable] = None
+                   ) -> Dict[Hashable, Dict[str, float]]:
+    """One run per QUESTION over the same pickle shards, where a question is several queries (reformulations, the turns of a
+    chat, sub-questions): the queries are grouped by `group_of_query(qid)` and every group gets the `topk` rows of the whole
+    corpus of largest fused score — the max (`fuse="max"`, "any-of") or the min (`fuse="min"`, "all-of") of a row's scores
+    over the group's queries (HipIndex.search_multi: exact).  -> {group: {docid: score}}, groups in the order their first
+    query appears, a group's entries best first — score descending, then shard and row order; it goes to `save_as_trec` as it
+    is.  A row's fused score depends on that row only, so the global top-k lies in the union of the shards' top-k: the corpus
+    is taken shard by shard and the per-shard lists are merged on the host (merge_pages_host).  1 <= topk <= 1000, groups of
+    at most 256 queries.
+
+    Replicated form only, like retrieve_deep: every rank sees the whole corpus."""
+    make_index = index_factory or HipIndex
+    queries, qids, _ = _load_queries(args)
+    corpus_parts = list_shards(args.output_dir, "corpus")
+    if len(corpus_parts) == 0:
+        raise ValueError("No pre-computed document embeddings found")
+    topk = int(topk)
+    order, lims, groups = group_rows([group_of_query(q) for q in qids])
+    result: Dict[Hashable, Dict[str, float]] = {g: {} for g in groups}
+    if len(groups) == 0 or topk <= 0:
+        return result
+    grouped = np.ascontiguousarray(np.asarray(queries, dtype=np.float32)[order])
+    dev = _device_index(args)
+    all_ids: List[str] = []
+    lists_s, lists_p = [], []
+    for p in corpus_parts:
+        reps, ids = read_shard(p)
+        if len(ids) == 0:
+            continue
+        ix = make_index(queries.shape[1], len(ids), dev)
+        ix.add(np.asarray(reps, dtype=np.float32))
+        sc, rows, _ = ix.search_multi(grouped, lims, topk, fuse)
+        ix.close()
+        rows = np.asarray(rows, dtype=np.int64)
+        lists_s.append(np.asarray(sc, dtype=np.float32))
+        lists_p.append(np.where(rows >= 0, rows + len(all_ids), -1))
+        all_ids.extend(ids)
+    if not lists_s:
+        return result
+    sc, pos = merge_pages_host(lists_s, lists_p, topk)
+    for gi, g in enumerate(groups):
+        for s, j in zip(sc[gi], pos[gi]):
+            if j >= 0:
+                result[g][all_ids[int(j)]] = float(s)
     return result
 
 
