@@ -1,4 +1,4 @@
-"""-m gpu: the index edited in place (vr_index_remove / vr_index_update / vr_index_get_rows, csrc/index_edit.hip and index.hip)
+"""-m gpu: the index edited in place (vr_index_remove / vr_index_update / vr_index_get_rows, csrc/index_edit.hip and index_rows.hip)
 against the numpy model tests/index_edit_ref.py.
 
 One bar, no tolerance: the edited index E and a FRESH index F — a new HipIndex, `add` of the model's rows, the model's compacted

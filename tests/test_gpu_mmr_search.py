@@ -196,6 +196,29 @@ def test_few_rows_and_filters():
         ix.close()
 
 
+def test_two_query_blocks_under_filters_and_the_empty_index():
+    """600 rows (three 256-row tiles, the last partial), 257 queries (a second block of one query), a half-density and an empty
+    filter, pool 20 (the plain pool is the fused sweep's, the filtered one the deep path's): query 256 is on filter 0.  After
+    reset() the pool is empty: k tails for a host and a device caller, and a filter is a state error."""
+    C, Q = R.unit(600, 64, 1), R.unit(257, 64, 2)
+    masks = np.concatenate([F.random_filters(600, (0.5,), seed=11), np.zeros((1, 600), dtype=bool)])
+    foq = np.arange(257) % 3 - 1                                         # -1 (no filter), 0, 1 (allows nothing), ...
+    assert foq[256] == 0
+    ref = M.mmr_ref(Q, C, 5, 20, 0.5, masks, foq)
+    assert (ref[1][foq == 1] == -1).all() and (ref[1][foq != 1] >= 0).all()
+    plain_ref = M.mmr_ref(Q, C, 5, 20, 0.5)
+    ix = _index(C, masks)
+    for q_in in (Q, torch.tensor(Q).cuda()):
+        _check(ix.search_diverse(q_in, 5, 20, 0.5, foq), Q, C, 5, 20, 0.5, ref, masks, foq)
+        _check(ix.search_diverse(q_in, 5, 20, 0.5), Q, C, 5, 20, 0.5, plain_ref)
+    ix.reset()
+    for q_in in (Q, torch.tensor(Q).cuda()):
+        sc, ids = _np(*ix.search_diverse(q_in, 5, 20, 0.5))
+        assert sc.shape == ids.shape == (257, 5) and (ids == -1).all() and np.isneginf(sc).all()
+    assert _raw(ix, Q, 5, 20, 0.5, foq.astype(np.int32)) == (VR_ERR_STATE, True)
+    ix.close()
+
+
 def _raw(ix, Q, k, pool, lam, foq=None):
     """vr_index_search_diverse itself on host arrays whose outputs hold a sentinel -> (status, outputs untouched?)"""
     sc, ids = np.full((len(Q), max(k, 1)), 7.5, np.float32), np.full((len(Q), max(k, 1)), 77, np.int64)

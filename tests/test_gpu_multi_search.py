@@ -243,6 +243,25 @@ def test_tails_and_filters():
     ix.close()
 
 
+def test_two_blocks_of_sub_queries_under_filters():
+    """600 rows (three 256-row tiles, the last partial), 257 sub-queries in groups of 1, 2 and 3 (the last group alone in a second
+    block), a half-density and an empty filter: the block's lims, filters of sub-queries and outputs start at its first group"""
+    C, Q = R.unit(600, 64, 1), R.unit(257, 64, 2)
+    masks = np.concatenate([F.random_filters(600, (0.5,), seed=11), np.zeros((1, 600), dtype=bool)])
+    lims = M.layout(257, (1, 2, 3))
+    ng = len(lims) - 1
+    fog = ((ng - np.arange(ng)) % 3 - 1).astype(np.int64)                # -1 (no filter), 0, 1 (allows nothing); the last group on filter 0
+    assert lims[-2] <= 256 < lims[-1] and fog[-1] == 0 and set(fog.tolist()) == {-1, 0, 1}
+    ix = _index(C, masks)
+    E = _matrix(ix, Q)
+    for fuse in FUSES:
+        want = _expect(E, lims, 5, fuse, [None if f < 0 else masks[f] for f in fog])
+        assert (want[1][fog == 1] == -1).all() and (want[1][fog != 1] >= 0).all()
+        for q_in, l_in, f_in in _both(Q, lims, fog):
+            _same(ix.search_multi(q_in, l_in, 5, fuse, f_in), want)
+    ix.close()
+
+
 # ------------------------------------------------------------------------------------------------ 5. tie tier ---
 def test_tie_tier():
     C, Q, _ = R.tie_tier()

@@ -250,6 +250,19 @@ def test_filters():
     ix.close()
 
 
+def test_two_query_blocks_under_filters():
+    """600 rows (three 256-row tiles, the last partial), 257 queries (a second block of one query), a half-density and an empty
+    filter: the block's thresholds, filters and lims start at its first query.  Query 256 is on filter 0."""
+    C, Q, t, S = X.random_case(600, 257, 64, CYCLE_B)
+    M = np.concatenate([F.random_filters(600, (0.5,), seed=11), np.zeros((1, 600), dtype=bool)])
+    foq = (np.arange(257) % 3 - 1).astype(np.int64)                      # -1 (no filter), 0, 1 (allows nothing), ...
+    ref_lims = X.range_ref(Q, C, t, M, foq)[0]
+    assert foq[256] == 0 and ref_lims[257] > ref_lims[256] and (np.diff(ref_lims)[foq == 1] == 0).all()
+    ix = _index(C, M)
+    _four_ways(ix, Q, S, t, "two blocks, filters", masks=M, foq=foq)
+    ix.close()
+
+
 # --------------------------------------------------------------------------- 6. a segment does not depend on its batch ---
 def test_a_query_alone_equals_its_segment_in_the_batch():
     C, Q, t, S = X.random_case(3001, 300, 128, CYCLE_B)

@@ -147,6 +147,34 @@ def test_ranks_under_a_filter():
     ix.close()
 
 
+def test_two_query_blocks_under_filters():
+    """600 rows (three 256-row tiles, the last partial), 257 queries (a second block of one query), a half-density and an empty
+    filter: the block's pairs and filters start at its first query.  Ranks against the fp64 reference inside the interval bar
+    of the module docstring, counts equal to the range search's segments; query 256 is on filter 0."""
+    C, Q, t, S = X.random_case(600, 257, 64, CYCLE_B)
+    M = np.concatenate([F.random_filters(600, (0.5,), seed=11), np.zeros((1, 600), dtype=bool)])
+    foq = (np.arange(257) % 3 - 1).astype(np.int64)                      # -1 (no filter), 0, 1 (allows nothing), ...
+    assert foq[256] == 0
+    T = np.tile(np.arange(0, 600, 120, dtype=np.int64), (257, 1))        # five targets per query
+    ix = _index(C, M)
+    first = None
+    for q_in, f_in in ((Q, foq), (torch.tensor(Q).cuda(), torch.tensor(foq).cuda())):
+        sc, rk = _np(*ix.rank_rows(q_in, T, filter_of_query=f_in))
+        np.testing.assert_allclose(sc, np.take_along_axis(S, T, 1), atol=ATOL, rtol=0)
+        for q in range(257):
+            Sq = S[q] if foq[q] < 0 else S[q][M[foq[q]]]
+            for i, r in zip(T[q], rk[q]):
+                lo, hi = K.interval(Sq, S[q, i])
+                hi += 0 if foq[q] < 0 or M[foq[q]][i] else 1             # (a forbidden target is not among the rows counted)
+                assert lo <= r <= hi, (q, i, r, lo, hi)
+        assert (rk[foq == 1] == 0).all()
+        first = first or (_u32(sc).tolist(), rk.tolist())
+        assert (_u32(sc).tolist(), rk.tolist()) == first                 # host and device callers: the same bits
+    want = _counts_equal_range(ix, Q, t, foq)
+    assert want[256] > 0 and (want[foq == 1] == 0).all()
+    ix.close()
+
+
 # ------------------------------------------------------------------------------------------------ 4. tie tier ---
 def test_tie_tier():
     C, Q, _ = R.tie_tier()

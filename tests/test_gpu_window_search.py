@@ -200,6 +200,32 @@ def test_windows_under_filters():
     ix.close()
 
 
+def test_two_query_blocks_under_filters():
+    """600 rows (three 256-row tiles, the last partial), 257 queries (a second block of one query), a half-density and an empty
+    filter, per-query offsets: the block's offsets, filters and outputs start at its first query.  Against the fp64 reference
+    (the interval bar of the module docstring) and, bit for bit, the range search's ranking; query 256 is on filter 0."""
+    C, Q = R.unit(600, 64, 1), R.unit(257, 64, 2)
+    M = np.concatenate([F.random_filters(600, (0.5,), seed=11), np.zeros((1, 600), dtype=bool)])
+    foq = (np.arange(257) % 3 - 1).astype(np.int64)                      # -1 (no filter), 0, 1 (allows nothing), ...
+    off = (np.arange(257) * 7 % 40).astype(np.int64)
+    assert foq[256] == 0 and off[256] > 0
+    k, S64 = 5, R.scores64(Q, C)
+    ix = _index(C, M)
+    want_s, want_i = _slices(*_padded_ranking(ix, Q, 50, foq), off, k)
+    assert (want_i[foq == 1] == -1).all() and (want_i[foq != 1] >= 0).all()
+    for q_in, f_in in ((Q, foq), (torch.tensor(Q).cuda(), torch.tensor(foq).cuda())):
+        got = ix.search_window(q_in, off, k, f_in)
+        _same(got, want_s, want_i)
+        sc, ids = _np(*got)
+        for q in np.flatnonzero(foq != 1):
+            rows = np.arange(600) if foq[q] < 0 else np.flatnonzero(M[foq[q]])
+            pos = {int(r): j for j, r in enumerate(rows)}
+            n_q, _, bad = W.check_window(S64[q][rows], np.asarray([pos[int(i)] for i in ids[q]]), int(off[q]))
+            assert n_q == k and bad is None, (q, bad)
+            np.testing.assert_allclose(sc[q], S64[q][ids[q]], atol=ATOL, rtol=0)
+    ix.close()
+
+
 # ------------------------------------------------------------------------------------------------ 4. tie tier ---
 def test_tie_tier():
     C, Q, _ = R.tie_tier()

@@ -1,4 +1,4 @@
-// Host-side helpers shared by the engines of libvisrag_hip.so (model.hip / encode.hip / index.hip / ops.hip / chat.hip: the
+// Host-side helpers shared by the engines of libvisrag_hip.so (model.hip / encode.hip / index*.hip / ops.hip / chat.hip: the
 // VisRAG-Ret encoder, its index and its chat; gen.hip: the EVisRAG generator's language model): error reporting, owning device buffers, packed weights and their loaders.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,0 +1,211 @@
+// The search index's handle and the host helpers its three files share: index.hip (life cycle, vr_index_search*), index_searches.hip
+// (the score-row searches: groups, filtered, range, rank, window, fused, diverse) and index_rows.hip (editing in place).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "engine_common.h"
+
+constexpr int CERT_WORDS = 32, CERT_FLAG = 2, CERT_FLAG2 = 3, CERT_STATS = 4, CERT_NSTATS = 6;   // (the two flag counters are consecutive: cleared together)
+constexpr int GRP_STATS = 2, GRP_LIST = 8, GRP_WORDS = GRP_LIST + 256;
+constexpr int FLT_STATS = 2, FLT_LIST = 8, FLT_WORDS = FLT_LIST + 256;
+constexpr int RNG_TOTAL = 3, RNG_WORDS = RNG_TOTAL + 1, RNK_WORDS = 3, WIN_WORDS = 3, MUL_WORDS = 3;   // (u64 words; 0..2 the counters)
+
+struct vr_index_s {
+    int device = 0, dim = 0;
+    int64_t cap = 0, n = 0;
+    DevBuf f32, bf16;                 // [cap_pad][dim]
+    DevBuf q32, qbf, cs, ci, ck, os, oi, ok, thr, sbuf;  // query staging / candidates / outputs / thresholds / score rows
+    int64_t qcap = 0, ccap = 0, kcap = 0;
+    // certification state (search_common.h), 32 words: f32 [0] largest row norm, [1] largest bf16 rounding residual of a row;
+    // int [2] flag count, [3] second-level flag count (exact fp32 pass); u32 [4..9] query counters {certified at once, after
+    // extended re-scoring, flagged, uncertified mode, candidates gathered a second time, of the flagged: exact fp32 pass}
+    DevBuf cert, flags, flagq;        // flags: int flag_list[fcap] | int flag2_list[fcap] | f32 flag_tau[fcap]; flagq: bf16 [fcap][dim]
+    int64_t fcap = 0;
+    int* huge_seen = nullptr;         // pinned host word: a streaming search met a band beyond search_band_max() rows (SearchArgs::huge_seen)
+    float eps_rel = -2.f;             // -2: the rigorous data-dependent default; >= 0: the caller's eps_rel |q| max|d|; else off
+    // Every search below has state of its own in a member of its own: no other search reads any of it (the filters excepted:
+    // range, rank, windowed, fused and diversified search read flt.bits / flt.count and stage their filter ids in flt.ids).
+    struct {                          // grouped search (vr_index_search_groups, search_group.hip)
+        int64_t n_groups = 0;         // 0: no grouping set (vr_index_add / vr_index_reset drop it)
+        DevBuf off, B, out, state;    // int first rows [n_groups + 1] | group maxima [256][ldB] | staged out_groups | int words: [0] flag
+                                      // count, [1] unused (cleared with it), u32 [2..4] the three counters of vr_index_group_search_stats,
+                                      // [GRP_LIST..] flag list of a block of <= 256 queries
+    } grp;
+    struct {                          // filtered search (vr_index_search_filtered, search_filter.hip), independent of the grouping
+        int64_t n_filters = 0;        // 0: no filters set (vr_index_add / vr_index_reset drop them)
+        DevBuf bits, count, ids, state;   // u32 [n_filters][ceil(n / 32)] the library's copy | int allowed rows [n_filters] | staged
+                                      // filter_of_query (filter_of_group) of a host caller | int words laid out as grp.state's: [0] flag count,
+                                      // [1] unused, u32 [2..4] the counters of vr_index_filter_search_stats, [FLT_LIST..] flag list of a block
+    } flt;
+    // diversified search (vr_index_search_diverse, search_diverse.hip): its pool — the result of the plain or the filtered search for
+    // k = pool — in buffers of its own, because that very search overwrites the shared scratch
+    struct { DevBuf scores, ids; } div;   // f32 pool scores [nq][pool] | int64 pool ids [nq][pool]
+    struct {                          // range search (vr_index_search_range, search_range.hip): its result and state
+        DevBuf scores, ids;           // the result: f32 scores [cap] | int64 row ids [cap], valid entries [0, total)
+        int64_t cap = 0, total = -1;  // -1: no result (none yet, vr_index_reset, or the last range search failed)
+        DevBuf thr, lims, cnt, off, state;   // staged thresholds / lims of a host caller | int rows kept [256][slots] | int their exclusive
+                                      // scan per query | u64 words: [0..2] the counters of vr_index_range_search_stats, [3] a block's total
+        int64_t* host_total = nullptr;    // pinned host word: the block total as the host reads it
+    } rng;
+    struct {                          // rank search (vr_index_rank_rows / vr_index_count_range, search_rank.hip): no stored result
+        DevBuf q, v, bar, eps, state; // int query of every pair | int target rows or f32 thresholds | u64 bars | f32 eps per pair | u64
+                                      // words: [0..2] the counters of vr_index_rank_search_stats
+    } rnk;
+    struct {                          // windowed search (vr_index_search_window, search_window.hip): no stored result
+        DevBuf off, edge, state;      // int64 offsets of the call's queries | f32 band edges {lo, hi} of a block's queries | u64 words:
+                                      // [0..2] the counters of vr_index_window_search_stats
+    } win;
+    struct {                          // fused search (vr_index_search_multi, search_multi.hip): no stored result
+        DevBuf lims, fsub, edge, which, state;   // int lims of the call's groups | int filter of every sub-query | f32 band edge of a
+                                      // block's groups | staged out_which | u64 words: [0..2] the counters of vr_index_multi_search_stats
+    } mul;
+    struct {                          // editing in place (vr_index_remove / vr_index_update / vr_index_get_rows, index_edit.hip)
+        DevBuf ids, rows, bits2;      // int row ids of the call | rows of a host caller, staged (<= EDIT_SCRATCH bytes for get_rows) |
+                                      // the filters compacted out of place: swapped with flt.bits
+    } edit;
+    // per-stage HIP events (vr_index_set_search_profile): convert | thresholds | sweep | merge | exact pass
+    bool prof_on = false;
+    hipEvent_t prof_ev[SEARCH_PROF_EVENTS] = {};
+    double prof_ms[SEARCH_PROF_EVENTS - 1] = {};
+    int64_t prof_calls = 0;
+};
+
+// queries [nq][dim] -> top k per query, as (scores, ids) or as packed keys with `id_offset` added to the row ids (index.hip)
+int search_impl(vr_index_t ix, const float* queries, int32_t nq, int32_t k, float* out_scores, int64_t* out_ids,
+                unsigned long long* out_keys, int64_t id_offset, int32_t on_device, void* stream);
+
+// ---- staging: what a host caller's arrays go through -------------------------------------------------------------------------
+// Query staging for passes of up to `nqp` (padded) queries: capacity of the bf16 rows and thresholds, host queries to the
+// device.  *q32: the fp32 queries on the device.
+static inline int stage_queries(vr_index_t ix, const float* queries, int32_t nq, int64_t nqp, int32_t on_device, hipStream_t s,
+                                const float** q32) {
+    if (ix->qcap < nqp) {
+        VRCHK(ix->qbf.alloc((size_t)nqp * ix->dim * 2));
+        VRCHK(ix->thr.alloc((size_t)nqp * 8));            // thresholds | what the lists are complete down to (thr_cert)
+        ix->qcap = nqp;
+    }
+    *q32 = queries;
+    if (!on_device) {
+        VRCHK(ix->q32.reserve((size_t)nq * ix->dim * 4));
+        HIPCHK(hipMemcpyAsync(ix->q32.p, queries, (size_t)nq * ix->dim * 4, hipMemcpyHostToDevice, s));
+        *q32 = ix->q32.as<float>();
+    }
+    return VR_OK;
+}
+
+// One input array of n elements: the kernels read *dev — the caller's own array, or a host array's copy in `buf` (the copy is
+// asynchronous: a caller whose source dies before the call's last synchronisation synchronises itself)
+template <typename T>
+static inline int stage_input(DevBuf& buf, const T* in, size_t n, int32_t on_device, hipStream_t s, const T** dev) {
+    *dev = in;
+    if (!on_device) {
+        VRCHK(buf.reserve(n * sizeof(T)));
+        HIPCHK(hipMemcpyAsync(buf.p, in, n * sizeof(T), hipMemcpyHostToDevice, s));
+        *dev = buf.as<T>();
+    }
+    return VR_OK;
+}
+
+// One output array of n elements: the kernels write *dev — the caller's own array, or for a host caller the staging buffer
+// that return_output copies back (the caller synchronises the stream after the last one)
+template <typename T>
+static inline int stage_output(DevBuf& buf, T* out, size_t n, int32_t on_device, T** dev) {
+    *dev = out;
+    if (!on_device) { VRCHK(buf.reserve(n * sizeof(T))); *dev = buf.as<T>(); }
+    return VR_OK;
+}
+template <typename T>
+static inline int return_output(T* out, const T* dev, size_t n, int32_t on_device, hipStream_t s) {
+    if (!on_device) HIPCHK(hipMemcpyAsync(out, dev, n * sizeof(T), hipMemcpyDeviceToHost, s));
+    return VR_OK;
+}
+
+// n result slots of a search over no row: (-inf, -1) and, for the fused search, which = -1
+static inline int fill_tails(float* out_scores, int64_t* out_ids, int32_t* out_which, size_t n, int32_t on_device, hipStream_t s) {
+    if (on_device) {
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)out_scores, (int)0xFF800000u, n, s));     // -inf
+        HIPCHK(hipMemsetAsync(out_ids, 0xFF, n * 8, s));                                   // -1
+        if (out_which) HIPCHK(hipMemsetAsync(out_which, 0xFF, n * 4, s));
+    } else {
+        std::fill(out_scores, out_scores + n, -INFINITY);
+        std::fill(out_ids, out_ids + n, (int64_t)-1);
+        if (out_which) std::fill(out_which, out_which + n, (int32_t)-1);
+    }
+    return VR_OK;
+}
+
+// ---- a block of <= 256 queries on the score-row route: S[q][row] in ix->sbuf, one fp32 row per query ---------------------------
+static inline bool certifies(vr_index_t ix) { return ix->eps_rel == -2.f || ix->eps_rel >= 0.f; }
+
+// The block's view for the kernels: index, queries [q0, q0 + nb), k and the error model of the certification (search_common.h:
+// query_eps) as vr_index_set_search_eps left it.  always_model: the model also defines what is re-scored (a band, the rows of
+// a group) — with certification off, the default one does that.
+static inline SearchArgs block_view(vr_index_t ix, const float* q32, int64_t q0, int nb, int k, bool always_model) {
+    SearchArgs a{};
+    a.index_bf16 = ix->bf16.p; a.index_f32 = ix->f32.as<float>(); a.n_docs = ix->n; a.dim = ix->dim;
+    a.q_bf16 = ix->qbf.p; a.q_f32 = q32 + (size_t)q0 * ix->dim; a.nq = nb; a.k = k;
+    a.eps_data = (ix->eps_rel == -2.f || (always_model && !certifies(ix))) ? 1 : 0;
+    a.eps_rel = a.eps_data ? 0.f : ix->eps_rel;
+    a.acc_rel = search_acc_rel(ix->dim);
+    a.dmax = ix->cert.as<float>();
+    return a;
+}
+
+// S[r][row] = bf16 rows A[0, M) x index^T on the bf16 MFMA GEMM, fp32 out (m_dev set: the row count is read on the device)
+static inline int score_rows(vr_index_t ix, const void* A_bf16, int M, const int* m_dev, int m_sub, int variant, int64_t ldS, hipStream_t s) {
+    GemmArgs g{};
+    g.A = A_bf16; g.lda = ix->dim;
+    g.W = ix->bf16.p; g.ldw = ix->dim; g.M = M; g.N = (int)pad128l(ix->n); g.K = ix->dim;
+    g.out = ix->sbuf.p; g.ldo = (int)ldS; g.alpha = 1.0f;
+    g.m_dev = m_dev; g.m_sub = m_sub;
+    HIPCHK(launch_gemm(g, EPI_F32, variant, s));
+    return VR_OK;
+}
+
+// The block's queries to bf16 (rows >= nb of the padded tile: zeros; clear_words set: those two ints cleared along, a search's
+// flag counter), then their score rows: the deep path's GEMM launch
+static inline int score_block(vr_index_t ix, const float* q32, int64_t q0, int nb, int64_t ldS, int* clear_words, hipStream_t s) {
+    HIPCHK(launch_f32_to_bf16_pad(q32 + (size_t)q0 * ix->dim, ix->qbf.p, (size_t)nb * ix->dim, (size_t)pad256l(nb) * ix->dim, s, clear_words));
+    return score_rows(ix, ix->qbf.p, nb, nullptr, 0, GEMM_VARIANT_AUTO, ldS, s);
+}
+
+// ---- filters as the searches other than the filtered one use them ---------------------------------------------------------------
+// filter ids (`what`: the argument's name) before any launch: filters must be set; a host array is range-checked (a device
+// array cannot be read here: an entry outside [-1, n_filters) allows nothing)
+static inline int check_filter_ids(vr_index_t ix, const int32_t* ids, int32_t n, int32_t on_device, const char* what) {
+    if (ix->flt.n_filters <= 0 || ix->n <= 0) return fail(VR_ERR_STATE, "no filters set for the rows of the index (vr_index_set_filters)");
+    if (!on_device)
+        for (int32_t i = 0; i < n; ++i)
+            if (ids[i] < -1 || ids[i] >= ix->flt.n_filters)
+                return fail(VR_ERR_INVALID, "%s[%d] = %d outside [-1, %lld)", what, (int)i, (int)ids[i], (long long)ix->flt.n_filters);
+    return VR_OK;
+}
+
+// disallowed columns of the block's score rows -> -inf: row i is masked by filter foq_block[i] (slot_count set: the first
+// *slot_count - sub rows only, row i by the filter of query flag_list[sub + i])
+static inline int mask_block(vr_index_t ix, const int* foq_block, int nb, int64_t ldS, const int* flag_list, const int* slot_count, int sub,
+                             hipStream_t s) {
+    const MaskArgs m{ix->flt.bits.as<uint32_t>(), (size_t)((ix->n + 31) / 32), (int)ix->flt.n_filters, foq_block, ix->n};
+    HIPCHK(launch_filter_mask(m, ix->sbuf.as<float>(), (size_t)ldS, nb, flag_list, slot_count, sub, s));
+    return VR_OK;
+}
+
+// ---- counters ---------------------------------------------------------------------------------------------------------------------
+// out[0, N) = words [first_word, first_word + N) of a search's state buffer (W: their width), then cleared with `reset`; a
+// buffer that was never allocated counted nothing: zeros, no device call
+template <typename W, int N>
+static inline int read_counters(vr_index_t ix, const DevBuf& state, int first_word, int64_t* out, int32_t reset) {
+    std::fill(out, out + N, (int64_t)0);
+    if (!state.p) return VR_OK;
+    VRCHK(set_dev(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    W w[N];
+    HIPCHK(hipMemcpy(w, state.as<W>() + first_word, sizeof(w), hipMemcpyDeviceToHost));
+    for (int i = 0; i < N; ++i) out[i] = (int64_t)w[i];
+    if (reset) HIPCHK(hipMemset(state.as<W>() + first_word, 0, sizeof(w)));
+    return VR_OK;
+}

@@ -1,4 +1,4 @@
-// Editing the index in place (vr_index_remove / vr_index_update / vr_index_get_rows, index.hip): whole rows moved by whole waves,
+// Editing the index in place (vr_index_remove / vr_index_update / vr_index_get_rows, index_rows.hip): whole rows moved by whole waves,
 // 16 bytes per lane and access.  A row of the fp32 store is dim * 4 bytes (a multiple of 256), a row of the bf16 store dim * 2
 // (a multiple of 128): both are counted here in 16-byte units, and one kernel serves both stores.
 //
@@ -7,7 +7,7 @@
 // — monotone, src(j) >= j, found by a binary search over nr ints.  In place this is a hazard: new row j is also the source of
 // some earlier new row (remove row 0 alone: src(j) = j + 1 everywhere), and the workgroups of one launch run in no order.  No
 // kernel here looks at another workgroup: every LAUNCH reads a set of rows and writes a set of rows that are disjoint by
-// construction, and stream order between launches is the only ordering (index.hip: compact_store picks the launches).
+// construction, and stream order between launches is the only ordering (index_rows.hip: compact_store picks the launches).
 #include "common.h"
 #include "kernels.h"
 

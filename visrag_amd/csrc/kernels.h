@@ -398,10 +398,18 @@ struct FilterSearchArgs {
 };
 // the library's copy of the filters as the caller's words arrived: spare bits of the last word cleared, allowed[f] = popcount
 hipError_t launch_filter_prepare(uint32_t* bits, size_t words, int n_filters, int64_t n_rows, int* allowed, hipStream_t s);
+// what the mask reads: the first three as FilterSearchArgs', filter_of_query [nq] device, the rows of the index
+struct MaskArgs {
+    const uint32_t* bits;
+    size_t words;
+    int n_filters;
+    const int* filter_of_query;
+    int64_t n_docs;
+};
 // disallowed columns of score rows [0, n_slots) of S -> -inf (row i = query i of the block; slot_count set: the first
-// *slot_count - sub rows only, row i = query p.a.flag_list[sub + i])
-hipError_t launch_filter_mask(const FilterSearchArgs& p, float* S, size_t ldS, int n_slots, const int* slot_count, int sub,
-                              hipStream_t s);
+// *slot_count - sub rows only, row i = query flag_list[sub + i])
+hipError_t launch_filter_mask(const MaskArgs& m, float* S, size_t ldS, int n_slots, const int* flag_list, const int* slot_count,
+                              int sub, hipStream_t s);
 hipError_t launch_filter_select(const FilterSearchArgs& p, const float* S, size_t ldS, int nq_block, hipStream_t s);
 // the flagged queries from masked EXACT score rows (slot i = query flag_list[sub + i]): overwrites their outputs
 hipError_t launch_filter_select_exact(const FilterSearchArgs& p, const float* S, size_t ldS, int sub, int max_slots, hipStream_t s);

@@ -64,22 +64,10 @@ __device__ __forceinline__ void band_rescore(const SearchArgs& p, const f32x4 (&
     constexpr int NW = NT / 64;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nv = p.dim >> 2;
     auto load_row = [&](f32x4 (&dv)[MERGE_MAXV], int cidx) {
-        if (cidx >= n_band) return;
-        const f32x4* dr = reinterpret_cast<const f32x4*>(p.index_f32 + (size_t)L.cand[cidx] * p.dim);
-#pragma unroll
-        for (int i = 0; i < MERGE_MAXV; ++i) {
-            const int cc = lane + i * 64;
-            dv[i] = (cc < nv) ? dr[cc] : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
+        if (cidx < n_band) load_row_regs(dv, p.index_f32 + (size_t)L.cand[cidx] * p.dim, nv, lane);
     };
     auto score_row = [&](const f32x4 (&dv)[MERGE_MAXV], int cidx) {
-        float a = 0.f;
-#pragma unroll
-        for (int i = 0; i < MERGE_MAXV; ++i) {
-            const int cc = lane + i * 64;
-            if (cc < nv) a = dot_chunk(qv[i], dv[i], a);                  // the chain of dot_lane(q, row)
-        }
-        a = wave_sum(a);
+        const float a = wave_sum(dot_regs(qv, dv, nv, lane));
         if (lane == 0) L.keys[cidx] = make_key(a, L.cand[cidx]);
     };
     f32x4 dr_[BAND_NR][MERGE_MAXV];

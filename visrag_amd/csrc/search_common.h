@@ -88,6 +88,39 @@ __device__ __forceinline__ float dot_lane(const f32x4 (&qv)[MERGE_MAXV], const f
     }
     return a;
 }
+// The same chain with the row in registers: a kernel that wants every load of a row out before the first fma waits for one
+// loads it with load_row_regs and runs dot_regs over it (search_rank.hip, search_window.hip, search_band.h).  search_multi.hip's
+// multi_fused_score holds the row in registers and reads its queries from memory: dot_regs does not fit it, its chain is this one.
+__device__ __forceinline__ void load_row_regs(f32x4 (&dv)[MERGE_MAXV], const float* row, int nv, int lane) {
+    load_query_regs(dv, row, nv, lane);
+}
+__device__ __forceinline__ float dot_regs(const f32x4 (&qv)[MERGE_MAXV], const f32x4 (&dv)[MERGE_MAXV], int nv, int lane) {
+    float a = 0.f;
+#pragma unroll
+    for (int i = 0; i < MERGE_MAXV; ++i) {
+        const int cc = lane + i * 64;
+        if (cc < nv) a = dot_chunk(qv[i], dv[i], a);
+    }
+    return a;
+}
+
+// rows a query on filter f may see: all of them (-1), the filter's count, or none (an entry outside [-1, n_filters)); a caller
+// without a filter array passes -1
+__device__ __forceinline__ int rows_allowed(int64_t n_docs, int n_filters, const int* allowed, int f) {
+    return f == -1 ? (int)n_docs : ((unsigned)f < (unsigned)n_filters ? allowed[f] : 0);
+}
+
+// Column `col` of every lane with `in` set goes on the LDS candidate list cand[0, *n_cand), in no particular order: one atomic
+// per wave, the lanes' slots from the ballot.  Called by whole waves; the list has a slot for every column a workgroup offers.
+__device__ __forceinline__ void band_append(bool in, int col, int* cand, int* n_cand) {
+    const unsigned long long m = __ballot(in);
+    if (m == 0ull) return;                                                 // (wave-uniform; most waves hold no candidate)
+    const int lane = threadIdx.x & 63;
+    int base = 0;
+    if (lane == 0) base = atomicAdd(n_cand, __popcll(m));
+    base = __shfl(base, 0, 64);
+    if (in) cand[base + __popcll(m & ((1ull << lane) - 1ull))] = col;
+}
 
 __device__ __forceinline__ float key_score(uint64_t key) { return orderable_f32((uint32_t)(key >> 32)); }
 

@@ -1,6 +1,6 @@
 // vr_index_search_diverse: k rows per query picked from a POOL of its best rows by maximal marginal relevance (MMR), so that
 // near-duplicate rows do not fill the result.  The pool is what vr_index_search / vr_index_search_filtered return for k = pool
-// (index.hip calls them as they stand: certified, fp32 scores r_c, (-inf, -1) tail where fewer rows exist); this file holds the
+// (index_searches.hip calls them as they stand: certified, fp32 scores r_c, (-inf, -1) tail where fewer rows exist); this file holds the
 // selection over it.
 //
 // mmr_select_kernel, one workgroup of 256 threads per query:

@@ -8,7 +8,7 @@
 // query_eps — the index-wide max |d| and max |d - bf16(d)| bound those of any subset of the rows, so the eps of the whole
 // index holds for the sub-index, only looser), the certification of the deep path (search_bigk.hip) applies verbatim with
 // na = the number of allowed rows in the place of n_docs:
-//   1. score rows S[q][row] of a block of <= 256 queries on the bf16 MFMA GEMM (the deep path's launch, index.hip);
+//   1. score rows S[q][row] of a block of <= 256 queries on the bf16 MFMA GEMM (the deep path's launch, index.h: score_block);
 //   2. filter_mask_kernel: the disallowed columns of S become -inf in place (S is scratch), the filter words read once per 32
 //      columns — from here on a disallowed row cannot be selected, gathered or re-scored, and search_select.h stays as it is;
 //      the select never looks past column n_docs, so the zero scores of the index's padded columns never win either;
@@ -31,11 +31,6 @@
 namespace vr {
 
 constexpr int FILT_COLS = 4;                // columns per thread of the mask kernel (one 16-byte store)
-
-// rows a query may see: all of them (-1), its filter's count, or none (an entry outside [-1, n_filters))
-__device__ __forceinline__ int filter_allowed(const FilterSearchArgs& p, int f) {
-    return f == -1 ? (int)p.a.n_docs : ((unsigned)f < (unsigned)p.n_filters ? p.allowed[f] : 0);
-}
 
 // The library's copy of filter blockIdx.x: bits at or beyond n_rows cleared, allowed[f] = its population count.
 __global__ __launch_bounds__(256) void filter_prepare_kernel(uint32_t* __restrict__ bits, size_t words, int64_t n_rows,
@@ -94,7 +89,7 @@ __global__ __launch_bounds__(256) void filter_select_kernel(FilterSearchArgs p, 
     const int q = exact ? a.flag_list[sub + slot] : slot;
     const float* row = S + (size_t)slot * ldS;
     const int n_docs = (int)a.n_docs, k = a.k, dim = a.dim;
-    const int na = filter_allowed(p, p.filter_of_query[q]);             // (workgroup-uniform)
+    const int na = rows_allowed(a.n_docs, p.n_filters, p.allowed, p.filter_of_query[q]);    // (workgroup-uniform)
     int kp = min(na, kp_want);
     __syncthreads();                                                    // (LDS of the previous slot is free)
     if (na == 0) {                                                      // nothing allowed: k empty slots, certified
@@ -162,14 +157,16 @@ hipError_t launch_filter_prepare(uint32_t* bits, size_t words, int n_filters, in
     return hipGetLastError();
 }
 
-// score rows [0, n_slots) of S (slot_count set: only the first *slot_count - sub of them, slot i = query p.a.flag_list[sub + i])
-hipError_t launch_filter_mask(const FilterSearchArgs& p, float* S, size_t ldS, int n_slots, const int* slot_count, int sub,
-                              hipStream_t s) {
+// score rows [0, n_slots) of S (slot_count set: only the first *slot_count - sub of them, slot i = query flag_list[sub + i])
+hipError_t launch_filter_mask(const MaskArgs& m, float* S, size_t ldS, int n_slots, const int* flag_list, const int* slot_count,
+                              int sub, hipStream_t s) {
     if (n_slots <= 0) return hipSuccess;
-    if (!filter_args_ok(p) || !S || n_slots > 65535 || p.words * 32 > ldS || ldS % FILT_COLS) return hipErrorInvalidValue;
+    if (!m.bits || !m.filter_of_query || m.n_filters < 1 || m.n_docs < 1 || m.words != (size_t)((m.n_docs + 31) / 32) ||
+        (slot_count && !flag_list) || !S || n_slots > 65535 || m.words * 32 > ldS || ldS % FILT_COLS)
+        return hipErrorInvalidValue;
     const size_t per_wg = 256 * FILT_COLS / 32;                            // filter words per workgroup
-    hipLaunchKernelGGL(filter_mask_kernel, dim3((unsigned)((p.words + per_wg - 1) / per_wg), (unsigned)n_slots), dim3(256), 0, s, S,
-                       ldS, p.bits, p.words, p.n_filters, p.filter_of_query, slot_count ? p.a.flag_list : nullptr, slot_count, sub);
+    hipLaunchKernelGGL(filter_mask_kernel, dim3((unsigned)((m.words + per_wg - 1) / per_wg), (unsigned)n_slots), dim3(256), 0, s, S,
+                       ldS, m.bits, m.words, m.n_filters, m.filter_of_query, slot_count ? flag_list : nullptr, slot_count, sub);
     return hipGetLastError();
 }
 

@@ -4,7 +4,7 @@
 // With b_i the bf16-MFMA score of row i, e_i its fp32 score and |b_i - e_i| <= eps (search_common.h: query_eps), the group
 // maxima B_g = max b_i and E_g = max e_i obey |B_g - E_g| <= eps too (max is 1-Lipschitz), so the certification of the deep
 // path (search_bigk.hip) carries over with groups in the place of rows:
-//   1. score rows S[q][row] of a block of <= 256 queries on the bf16 MFMA GEMM (the deep path's launch, index.hip);
+//   1. score rows S[q][row] of a block of <= 256 queries on the bf16 MFMA GEMM (the deep path's launch, index.h: score_block);
 //   2. group_max_kernel: B[q][g] = max of S[q] over the group's rows (columns < n_docs only: the padding never wins);
 //   3. group_select_kernel, one workgroup per query: the K' = k + 24 largest B_g in group order (search_select.h: the deep
 //      path's radix select and ordered gather, over B in the place of S); inside every candidate group

@@ -12,7 +12,7 @@
 //      lies above the band's upper edge: only the lower edge lo = one_ulp_down(v_z - 2 eps_g) is ever tested, one radix select
 //      finds it, and exactly the rows with B >= lo are re-scored in fp32;
 //   4. no candidate margin, no widening, no flagged groups; with certification off the default error model defines the band.
-// The host (index.hip) packs whole groups greedily into blocks of <= 256 sub-queries.  Per block:
+// The host (index_searches.hip) packs whole groups greedily into blocks of <= 256 sub-queries.  Per block:
 //   1. score rows S[sub-query][row] on the bf16 MFMA GEMM (the deep path's launch); under filters launch_filter_mask runs with the
 //      group's filter expanded to its sub-queries (multi_expand_kernel), so a masked column is -inf in every sub-row and stays
 //      -inf under either fusion;
@@ -54,10 +54,9 @@ __device__ __forceinline__ float multi_pick(float a, float b, int fuse) {
     return (b_larger != (fuse != 0)) ? b : a;
 }
 
-// rows group g may see: all of them, its filter's count, or none (an entry outside [-1, n_filters))
-__device__ __forceinline__ int multi_allowed(const MultiSearchArgs& p, int g) {
-    const int f = p.filter_of_group ? p.filter_of_group[g] : -1;
-    return f == -1 ? (int)p.a.n_docs : ((unsigned)f < (unsigned)p.n_filters ? p.allowed[f] : 0);
+// rows group g may see (search_common.h: rows_allowed); no filter array: every group is on -1
+__device__ __forceinline__ int group_rows(const MultiSearchArgs& p, int g) {
+    return rows_allowed(p.a.n_docs, p.n_filters, p.allowed, p.filter_of_group ? p.filter_of_group[g] : -1);
 }
 
 // filter_of_sub[s] = filter_of_group[g] for the sub-queries s of group g: what launch_filter_mask reads, one entry per score row
@@ -94,7 +93,7 @@ __global__ __launch_bounds__(256) void multi_edge_kernel(MultiSearchArgs p, cons
     const SearchArgs& a = p.a;
     const int g = blockIdx.x, n_docs = (int)a.n_docs, nv = a.dim >> 2;
     if (g == 0 && tid == 0) atomicAdd(&p.stats[0], (unsigned long long)gridDim.x);
-    const int na = multi_allowed(p, g);
+    const int na = group_rows(p, g);
     if (na <= 0) {                                                         // (workgroup-uniform) nothing allowed: a row of tails
         if (tid == 0) p.edges[g] = __builtin_nanf("");
         return;
@@ -163,12 +162,7 @@ __global__ __launch_bounds__(256) void multi_rescore_kernel(MultiSearchArgs p, f
         for (int e = 0; e < 4; ++e) {
             const bool in = i0 + e < c1 && b[e] >= lo;
             any_band |= in;
-            const unsigned long long mk = __ballot(in);
-            if (mk == 0ull) continue;                                      // (wave-uniform)
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&L.n_cand, __popcll(mk));
-            base = __shfl(base, 0, 64);
-            if (in) L.cand[base + __popcll(mk & ((1ull << lane) - 1ull))] = i0 + e;    // (< MULTI_CHUNK: one slot per column)
+            band_append(in, i0 + e, L.cand, &L.n_cand);                    // (< MULTI_CHUNK: one slot per column)
         }
         // a band column is written by the wave that re-scores it, a column at or past n_docs by nobody
         if (i0 + 4 <= c1 && !any_band) {
@@ -206,7 +200,7 @@ __global__ __launch_bounds__(256) void multi_select_kernel(MultiSearchArgs p, co
         return;
     }
     const int s0 = p.lims[g] - p.sub_base, m = p.lims[g + 1] - p.lims[g];
-    const int kz = min(k, multi_allowed(p, g));                            // >= 1: at least kz columns hold a finite fp32 score
+    const int kz = min(k, group_rows(p, g));                               // >= 1: at least kz columns hold a finite fp32 score
     const float* row = S + (size_t)s0 * ldS;
     const KthKey kth = select_kth(row, n_docs, kz, L);
     gather_ordered(row, n_docs, kth.T, kz - kth.need_eq, kth.need_eq, SEL_CAND, L);

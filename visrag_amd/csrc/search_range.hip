@@ -2,7 +2,7 @@
 // form (lims, scores, ids), ascending row id inside a query.  With b_i the bf16-MFMA score of row i, e_i its fp32 score and
 // |b_i - e_i| <= eps (search_common.h: query_eps), every row with e_i >= t has b_i >= t - eps: re-scoring exactly the rows of
 // that band in fp32 and keeping those with e_i >= t IS the fp32 answer.  No candidate margin, no widening, no flagged queries;
-// a query costs what its band holds.  Per block of <= 256 queries (index.hip):
+// a query costs what its band holds.  Per block of <= 256 queries (index_searches.hip):
 //   1. score rows S[q][row] on the bf16 MFMA GEMM (the deep path's launch); with filters launch_filter_mask turns the columns a
 //      query may not see into -inf in place, so that they can never be candidates;
 //   2. range_rescore_kernel, grid (column chunk of 4096, query): the columns with b >= one_ulp_down(t - eps) are compacted into
@@ -71,15 +71,7 @@ __global__ __launch_bounds__(256) void range_rescore_kernel(RangeSearchArgs p, f
     for (int i0 = c0 + tid * 4; i0 < c1; i0 += 256 * 4) {                  // (c0 and ldS are multiples of 4: aligned; < ldS)
         const f32x4 b = *reinterpret_cast<const f32x4*>(row + i0);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const bool in = i0 + e < c1 && b[e] >= bound;
-            const unsigned long long m = __ballot(in);
-            if (m == 0ull) continue;                                       // (wave-uniform; most waves hold no candidate)
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&L.n_cand, __popcll(m));
-            base = __shfl(base, 0, 64);
-            if (in) L.cand[base + __popcll(m & ((1ull << lane) - 1ull))] = i0 + e;     // (< RANGE_CHUNK: one slot per column)
-        }
+        for (int e = 0; e < 4; ++e) band_append(i0 + e < c1 && b[e] >= bound, i0 + e, L.cand, &L.n_cand);   // (< RANGE_CHUNK: one slot per column)
     }
     __syncthreads();
     // ---- fp32 re-scoring, one candidate per wave

@@ -4,7 +4,7 @@
 // is the threshold t.  With b_j the bf16-MFMA score of row j, e_j its fp32 score and |b_j - e_j| <= eps (search_common.h:
 // query_eps), a row with b_j > t + eps lies certainly ahead of the bar and one with b_j < t - eps certainly behind it (t = e for
 // a rank): only the rows of the band between need their fp32 dot product.  No candidate margin, no widening, no flagged queries;
-// exact under the conditions of the range search (search_range.hip).  Per block of <= 256 queries (index.hip):
+// exact under the conditions of the range search (search_range.hip).  Per block of <= 256 queries (index_searches.hip):
 //   1. score rows S[q][row] on the bf16 MFMA GEMM (the deep path's launch); with filters launch_filter_mask turns the columns a
 //      query may not see into -inf: below every finite bar, never counted;
 //   2. rank_bar_kernel, one wave per pair: eps of the pair's query; for a rank the target's fp32 score from the fp32 store ->
@@ -92,13 +92,7 @@ __global__ __launch_bounds__(256) void rank_count_kernel(RankSearchArgs p, const
         for (int e = 0; e < 4; ++e) {
             const bool valid = i0 + e < c1;
             mine += (unsigned)__popcll(__ballot(valid && b[e] > hi));
-            const bool in = valid && b[e] >= lo && b[e] <= hi;
-            const unsigned long long m = __ballot(in);
-            if (m == 0ull) continue;                                       // (wave-uniform)
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&L.n_cand, __popcll(m));
-            base = __shfl(base, 0, 64);
-            if (in) L.cand[base + __popcll(m & ((1ull << lane) - 1ull))] = i0 + e;     // (< RANK_CHUNK: one slot per column)
+            band_append(valid && b[e] >= lo && b[e] <= hi, i0 + e, L.cand, &L.n_cand);  // (< RANK_CHUNK: one slot per column)
         }
     }
     __syncthreads();
@@ -109,20 +103,9 @@ __global__ __launch_bounds__(256) void rank_count_kernel(RankSearchArgs p, const
         load_query_regs(qv, a.q_f32 + (size_t)q * a.dim, nv, lane);
         for (int c = wave; c < m; c += 4) {
             const int id = L.cand[c];
-            const f32x4* dr = reinterpret_cast<const f32x4*>(a.index_f32 + (size_t)id * a.dim);
             f32x4 dv[MERGE_MAXV];
-#pragma unroll
-            for (int i = 0; i < MERGE_MAXV; ++i) {
-                const int cc = lane + i * 64;
-                dv[i] = (cc < nv) ? dr[cc] : f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-            float s = 0.f;
-#pragma unroll
-            for (int i = 0; i < MERGE_MAXV; ++i) {
-                const int cc = lane + i * 64;
-                if (cc < nv) s = dot_chunk(qv[i], dv[i], s);               // the chain of dot_lane(query, row)
-            }
-            s = wave_sum(s);
+            load_row_regs(dv, a.index_f32 + (size_t)id * a.dim, nv, lane);
+            const float s = wave_sum(dot_regs(qv, dv, nv, lane));
             const bool ahead = by_key ? make_key(s, (uint32_t)id) > bar : (p.strict ? s > t : s >= t);
             mine += ahead ? 1u : 0u;                                       // (every lane holds the same s)
         }

@@ -10,7 +10,7 @@
 // With A the rows certainly ahead (A <= o always: fewer than o + 1 rows have b > b_(o + 1)), the window is positions
 // o - A .. o - A + k - 1 of the band rows sorted by make_key(e, id).  Both bounds are rounded outward by one ulp (the rounded
 // subtraction / addition cannot have narrowed the band).  No candidate margin, no widening, no flagged queries; with
-// certification off the default error model defines the band.  Per block of <= 256 queries (index.hip):
+// certification off the default error model defines the band.  Per block of <= 256 queries (index_searches.hip):
 //   1. score rows S[q][row] on the bf16 MFMA GEMM (the deep path's launch); with filters launch_filter_mask turns the columns a
 //      query may not see into -inf;
 //   2. window_edge_kernel, one workgroup per query: eps, na; o >= na (or a filter index outside [-1, n_filters), which a device
@@ -53,19 +53,13 @@ __device__ __forceinline__ float one_ulp_up(float x) {
     return o != 0xFFFFFFFFu ? orderable_f32(o + 1u) : x;
 }
 
-// rows query q may see: all of them, its filter's count, or none (an entry outside [-1, n_filters))
-__device__ __forceinline__ int window_allowed(const WindowSearchArgs& p, int q) {
-    const int f = p.filter_of_query ? p.filter_of_query[q] : -1;
-    return f == -1 ? (int)p.a.n_docs : ((unsigned)f < (unsigned)p.n_filters ? p.allowed[f] : 0);
-}
-
 __global__ __launch_bounds__(256) void window_edge_kernel(WindowSearchArgs p, const float* __restrict__ S, size_t ldS) {
     __shared__ SelectLds L;
     const int tid = threadIdx.x, lane = tid & 63;
     const SearchArgs& a = p.a;
     const int q = blockIdx.x, n_docs = (int)a.n_docs, nv = a.dim >> 2;
     if (q == 0 && tid == 0) atomicAdd(&p.stats[0], (unsigned long long)gridDim.x);
-    const int na = window_allowed(p, q);
+    const int na = rows_allowed(a.n_docs, p.n_filters, p.allowed, p.filter_of_query ? p.filter_of_query[q] : -1);
     const int64_t o = p.offsets[q];
     if (o >= (int64_t)na) {                                                // (workgroup-uniform) an empty window: a row of tails
         if (tid == 0) { p.edges[2 * q] = __builtin_nanf(""); p.edges[2 * q + 1] = __builtin_nanf(""); }
@@ -111,12 +105,7 @@ __global__ __launch_bounds__(256) void window_rescore_kernel(WindowSearchArgs p,
             w[e] = up ? INFINITY : -INFINITY;
             any_band |= in;
             mine += (unsigned)__popcll(__ballot(up));
-            const unsigned long long m = __ballot(in);
-            if (m == 0ull) continue;                                       // (wave-uniform)
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&L.n_cand, __popcll(m));
-            base = __shfl(base, 0, 64);
-            if (in) L.cand[base + __popcll(m & ((1ull << lane) - 1ull))] = i0 + e;     // (< WIN_CHUNK: one slot per column)
+            band_append(in, i0 + e, L.cand, &L.n_cand);                    // (< WIN_CHUNK: one slot per column)
         }
         // a band column is written by the wave that re-scores it, a column at or past n_docs by nobody
         if (i0 + 4 <= c1 && !any_band) {
@@ -136,20 +125,9 @@ __global__ __launch_bounds__(256) void window_rescore_kernel(WindowSearchArgs p,
         load_query_regs(qv, a.q_f32 + (size_t)q * a.dim, nv, lane);
         for (int c = wave; c < m; c += 4) {
             const int id = L.cand[c];
-            const f32x4* dr = reinterpret_cast<const f32x4*>(a.index_f32 + (size_t)id * a.dim);
             f32x4 dv[MERGE_MAXV];
-#pragma unroll
-            for (int i = 0; i < MERGE_MAXV; ++i) {
-                const int cc = lane + i * 64;
-                dv[i] = (cc < nv) ? dr[cc] : f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-            float s = 0.f;
-#pragma unroll
-            for (int i = 0; i < MERGE_MAXV; ++i) {
-                const int cc = lane + i * 64;
-                if (cc < nv) s = dot_chunk(qv[i], dv[i], s);               // the chain of dot_lane(query, row)
-            }
-            s = wave_sum(s);
+            load_row_regs(dv, a.index_f32 + (size_t)id * a.dim, nv, lane);
+            const float s = wave_sum(dot_regs(qv, dv, nv, lane));
             if (lane == 0) row[id] = s;
         }
     }
@@ -215,7 +193,7 @@ __global__ __launch_bounds__(256) void window_select_kernel(WindowSearchArgs p, 
         for (int c = tid; c < k; c += 256) emit_slot(a, q, c, KEY_NONE);
         return;
     }
-    const int na = window_allowed(p, q);
+    const int na = rows_allowed(a.n_docs, p.n_filters, p.allowed, p.filter_of_query ? p.filter_of_query[q] : -1);
     const int o = (int)p.offsets[q];                                       // (< na: the edge kernel saw it)
     const int kz = (int)min((int64_t)o + k, (int64_t)na);
     const float* row = S + (size_t)q * ldS;

@@ -334,6 +334,24 @@ class HipIndex:
                                               1 if device else 0, C.c_void_p(_stream_ptr(self.device))), "vr_index_get_rows")
         return out
 
+    def _queries(self, queries, ndim: int = 2, shape: Optional[str] = None):
+        """`queries` as contiguous float32 where they live -> (q, cuda): a cuda tensor stays one, a cpu tensor or anything else
+        becomes numpy.  They have `ndim` axes, `dim` the last (`shape`: how the ValueError names that)."""
+        cuda = isinstance(queries, torch.Tensor) and queries.is_cuda
+        if cuda:
+            q = queries.to(torch.float32).contiguous()
+        else:
+            q = np.ascontiguousarray(queries.numpy() if isinstance(queries, torch.Tensor) else queries, dtype=np.float32)
+        if q.ndim != ndim or q.shape[-1] != self.dim:
+            raise ValueError(f"queries must be {shape or f'[nq][{self.dim}]'}")
+        return q, cuda
+
+    def _stats3(self, fn, names, reset: bool) -> Dict[str, int]:
+        """the three counters of one search's `*_search_stats` under `names`, cleared with `reset`"""
+        out = (C.c_int64 * 3)()
+        _lib.check(fn(self._h, out, 1 if reset else 0))
+        return {name: int(v) for name, v in zip(names, out)}
+
     def _search(self, fn, what: str, queries, k: int, n_int_out: int):
         """One call of a library search that writes scores [nq,k] f32 and `n_int_out` arrays [nq,k] i64: torch cuda tensors in ->
         cuda tensors out, numpy / cpu in -> numpy out (sized with max(k, 0): a negative k reaches the library's own error)."""
@@ -371,9 +389,7 @@ class HipIndex:
     def group_search_stats(self, reset: bool = False) -> Dict[str, int]:
         """Grouped-search queries since the last reset by outcome: certified from the first candidate set / after widening it /
         redone from exact fp32 scores of every row."""
-        out = (C.c_int64 * 3)()
-        _lib.check(self.lib.vr_index_group_search_stats(self._h, out, 1 if reset else 0))
-        return {"certified": int(out[0]), "certified_widened": int(out[1]), "exact": int(out[2])}
+        return self._stats3(self.lib.vr_index_group_search_stats, ("certified", "certified_widened", "exact"), reset)
 
     def set_filters(self, masks) -> None:
         """Row filters for `search_filtered` over the rows present: `masks` is bool [n_filters][len(self)] (True = the row is
@@ -460,9 +476,7 @@ class HipIndex:
     def filter_search_stats(self, reset: bool = False) -> Dict[str, int]:
         """Filtered-search queries since the last reset by outcome: certified from the first candidate set (or no row allowed) /
         after widening it / redone from exact fp32 scores of every row."""
-        out = (C.c_int64 * 3)()
-        _lib.check(self.lib.vr_index_filter_search_stats(self._h, out, 1 if reset else 0))
-        return {"certified": int(out[0]), "certified_widened": int(out[1]), "exact": int(out[2])}
+        return self._stats3(self.lib.vr_index_filter_search_stats, ("certified", "certified_widened", "exact"), reset)
 
     def search_range(self, queries, threshold, filter_of_query=None, max_total: Optional[int] = None, sort: bool = True):
         """Every row whose fp32 score is >= the query's threshold (include/visrag_hip.h: vr_index_search_range) -> (lims int64
@@ -471,13 +485,7 @@ class HipIndex:
         no filter (none need to be set).  `max_total=None`: min(nq * rows, 2 ** 26) entries; a larger result raises
         (VR_ERR_CAPACITY).  `sort=True`: every segment by score descending, then id ascending — the library's ranking order;
         `sort=False`: the ABI's ascending-id order."""
-        cuda = isinstance(queries, torch.Tensor) and queries.is_cuda
-        if cuda:
-            q = queries.to(torch.float32).contiguous()
-        else:
-            q = np.ascontiguousarray(queries.numpy() if isinstance(queries, torch.Tensor) else queries, dtype=np.float32)
-        if q.ndim != 2 or q.shape[1] != self.dim:
-            raise ValueError(f"queries must be [nq][{self.dim}]")
+        q, cuda = self._queries(queries)
         nq = int(q.shape[0])
         if isinstance(threshold, torch.Tensor):
             threshold = threshold.detach().cpu().numpy()
@@ -524,9 +532,7 @@ class HipIndex:
     def range_search_stats(self, reset: bool = False) -> Dict[str, int]:
         """Range searches since the last reset: queries, candidate rows re-scored in fp32 (the rows inside the error band below
         the thresholds and everything above), rows returned."""
-        out = (C.c_int64 * 3)()
-        _lib.check(self.lib.vr_index_range_search_stats(self._h, out, 1 if reset else 0))
-        return {"queries": int(out[0]), "candidates": int(out[1]), "returned": int(out[2])}
+        return self._stats3(self.lib.vr_index_range_search_stats, ("queries", "candidates", "returned"), reset)
 
     # ---- rank search (include/visrag_hip.h: vr_index_rank_rows / vr_index_count_range) ----
     @staticmethod
@@ -555,13 +561,7 @@ class HipIndex:
 
     def _rank_call(self, queries, flat, lims, shape, filter_of_query, strict):
         """vr_index_rank_rows (int64 targets) or vr_index_count_range (float32 thresholds) -> (scores or None, counts)"""
-        cuda = isinstance(queries, torch.Tensor) and queries.is_cuda
-        if cuda:
-            q = queries.to(torch.float32).contiguous()
-        else:
-            q = np.ascontiguousarray(queries.numpy() if isinstance(queries, torch.Tensor) else queries, dtype=np.float32)
-        if q.ndim != 2 or q.shape[1] != self.dim:
-            raise ValueError(f"queries must be [nq][{self.dim}]")
+        q, cuda = self._queries(queries)
         nq, n = int(q.shape[0]), len(flat)
         ranks = flat.dtype == np.int64
         keep, fptr = (None, C.c_void_p(None)) if filter_of_query is None else self._filter_of_query(q, filter_of_query)
@@ -604,9 +604,7 @@ class HipIndex:
 
     def rank_search_stats(self, reset: bool = False) -> Dict[str, int]:
         """Rank searches and counts since the last reset: (query, bar) pairs, rows of the error bands re-scored in fp32, rows counted."""
-        out = (C.c_int64 * 3)()
-        _lib.check(self.lib.vr_index_rank_search_stats(self._h, out, 1 if reset else 0))
-        return {"pairs": int(out[0]), "candidates": int(out[1]), "counted": int(out[2])}
+        return self._stats3(self.lib.vr_index_rank_search_stats, ("pairs", "candidates", "counted"), reset)
 
     # ---- windowed search (include/visrag_hip.h: vr_index_search_window) ----
     def search_window(self, queries, offset, k: int, filter_of_query=None):
@@ -635,9 +633,7 @@ class HipIndex:
     def window_search_stats(self, reset: bool = False) -> Dict[str, int]:
         """Windowed searches since the last reset: queries, rows of the bands re-scored in fp32, rows certainly ahead of their
         query's window (decided by the bf16 score alone)."""
-        out = (C.c_int64 * 3)()
-        _lib.check(self.lib.vr_index_window_search_stats(self._h, out, 1 if reset else 0))
-        return {"queries": int(out[0]), "candidates": int(out[1]), "ahead": int(out[2])}
+        return self._stats3(self.lib.vr_index_window_search_stats, ("queries", "candidates", "ahead"), reset)
 
     # ---- fused search (include/visrag_hip.h: vr_index_search_multi) ----
     def search_multi(self, queries, lims, k: int, fuse: str = "max", filter_of_group=None):
@@ -652,19 +648,12 @@ class HipIndex:
         out, numpy / cpu in -> numpy out."""
         if fuse not in ("max", "min"):
             raise ValueError("fuse must be 'max' or 'min'")
-        cuda = isinstance(queries, torch.Tensor) and queries.is_cuda
-        if cuda:
-            q = queries.to(torch.float32).contiguous()
-        else:
-            q = np.ascontiguousarray(queries.numpy() if isinstance(queries, torch.Tensor) else queries, dtype=np.float32)
         if lims is None:
-            if q.ndim != 3 or q.shape[2] != self.dim:
-                raise ValueError(f"queries must be [n_groups][m][{self.dim}] when lims is None")
+            q, cuda = self._queries(queries, 3, f"[n_groups][m][{self.dim}] when lims is None")
             lim = np.arange(q.shape[0] + 1, dtype=np.int64) * q.shape[1]
             q = q.reshape(-1, self.dim)
         else:
-            if q.ndim != 2 or q.shape[1] != self.dim:
-                raise ValueError(f"queries must be [n_sub][{self.dim}] with lims")
+            q, cuda = self._queries(queries, 2, f"[n_sub][{self.dim}] with lims")
             lim = np.ascontiguousarray(self._row_ids(lims), dtype=np.int64)
             if len(lim) < 1:
                 raise ValueError("lims must hold n_groups + 1 entries")
@@ -689,9 +678,7 @@ class HipIndex:
     def multi_search_stats(self, reset: bool = False) -> Dict[str, int]:
         """Fused searches since the last reset: groups, columns of the bands re-scored in fp32, fp32 row dot products (every
         band column against every sub-query of its group)."""
-        out = (C.c_int64 * 3)()
-        _lib.check(self.lib.vr_index_multi_search_stats(self._h, out, 1 if reset else 0))
-        return {"groups": int(out[0]), "candidates": int(out[1]), "dots": int(out[2])}
+        return self._stats3(self.lib.vr_index_multi_search_stats, ("groups", "candidates", "dots"), reset)
 
     def search_keys(self, queries: torch.Tensor, k: int, id_offset: int = 0) -> torch.Tensor:
         """The same search with each result packed into ONE 64-bit word (include/visrag_hip.h:
