@@ -501,7 +501,8 @@ int vr_index_rank_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
  * vr_index_search_range (on the device an out-of-range filter index gives a row of tails).  nq == 0: VR_OK, nothing is
  * launched.  An empty index: tails, nothing is launched.  Nothing is stored: a later vr_index_remove / update / add has nothing
  * to invalidate.  A host caller's call synchronises the stream.  Not offered: corpus-sharded ranks inside the library (merge
- * per-shard pages on the host), windows of groups, windows under MMR, k > 1000 in one call, a k per query. */
+ * per-shard pages on the host), windows under MMR, k > 1000 in one call, a k per query.  Windows of groups:
+ * vr_index_search_groups_window below. */
 int vr_index_search_window(vr_index_t ix, const float* queries, int32_t nq,
                            const int64_t* offsets,           /* host [nq] */
                            int32_t k,
@@ -511,6 +512,44 @@ int vr_index_search_window(vr_index_t ix, const float* queries, int32_t nq,
 /* Windowed searches since the last reset: out3 = {queries, band candidates re-scored in fp32, rows certainly ahead of their
  * window} — 64-bit counters in device memory. */
 int vr_index_window_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
+/* ---- document window search: the groups at ranks [offset, offset + k) of a query's document ranking, under filters ---- */
+/* vr_index_search_groups_window: the document-level search with a filter and a window.  For query q with filter f
+ * (filter_of_query NULL or an entry of -1: every row) a group g (vr_index_set_groups) is PRESENT if f allows at least one of
+ * its rows; its score is E_g = the largest e_i over its ALLOWED rows — e_i the library's one fp32 dot product, the bits
+ * vr_index_search returns for that pair — and its best row the lowest allowed row id that attains E_g.  Present groups rank by
+ * E_g descending, then lower best row first (groups are runs of adjacent rows: lower group first).  Entry j of query q is the
+ * group at rank offsets[q] + j:
+ *   out_scores [nq][k] float32 = E_g;  out_ids [nq][k] int64 = best row;  out_groups [nq][k] int64 = g.
+ * Slots at or past the number of present groups are (-inf, -1, -1); an offset at or past that number gives a row of them.
+ * With offset 0 and no filter the result equals vr_index_search_groups bit for bit; with
+ * groups of one row it equals vr_index_search_window with out_groups == out_ids.
+ *   Layout: offsets [nq] int64 is always a HOST array, each >= 0, with no upper limit; 1 <= k <= 1000 (page for more); queries
+ * [nq][dim] float32, filter_of_query [nq] int32 and the outputs [nq][k] are all host or all device per `on_device`.
+ *   Exactness: the windowed search's argument composed with the grouped search's.  With |b_i - e_i| <= eps over the allowed
+ * rows, the masked group maximum B_g lies within eps of E_g (max is 1-Lipschitz) and the r-th largest B within eps of the r-th
+ * largest E (so are order statistics); groups whose B lies more than 2 eps above the B at rank offset + 1 are certainly ahead of
+ * the window, groups more than 2 eps below the B at rank offset + k certainly behind it; inside a group of the band between,
+ * exactly the rows with b_i >= B_g - 2 eps — only such a row can attain E_g — are re-scored in fp32, and the groups are ranked
+ * by key.  Every edge is rounded outward by one ulp.  No candidate margin, no widening, no flagged query; a query costs what
+ * its band holds; with certification off the default error model defines the band, so the result is exact in every setting of
+ * vr_index_set_search_eps.
+ *   Checks, all before any launch and with the outputs untouched: NULL pointers with nq > 0, nq < 0, k outside 1..1000, a
+ * negative offset, an unsupported dim (as vr_index_search_range), a HOST filter_of_query entry outside [-1, n_filters):
+ * VR_ERR_INVALID; no grouping set for the rows present, or filter_of_query given while no filters are set for them:
+ * VR_ERR_STATE.  On the device an out-of-range filter index allows nothing: a row of tails.  nq == 0: VR_OK, nothing is
+ * launched.  Nothing is stored between calls.  A host caller's call synchronises the stream.  The call counts in no other
+ * search's statistics and leaves every state the other searches read alone; vr_index_search_groups is untouched by it.
+ * Not offered: ranks of named documents, a thresholded (range) document search, documents under the fused search or MMR,
+ * corpus-sharded ranks (merge per-shard pages on the host), k > 1000 in one call, a k per query. */
+int vr_index_search_groups_window(vr_index_t ix, const float* queries, int32_t nq,
+                                  const int64_t* offsets,           /* host [nq] */
+                                  int32_t k,
+                                  const int32_t* filter_of_query,   /* NULL: no filter for any query */
+                                  float* out_scores, int64_t* out_ids, int64_t* out_groups,   /* [nq][k] */
+                                  int32_t on_device, void* stream);
+/* Document window searches since the last reset: out3 = {queries, band groups re-scored, fp32 row dot products} — 64-bit
+ * counters in device memory. */
+int vr_index_group_window_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
 /* ---- fused search: the top-k rows by max or min over a group of sub-queries ---- */
 /* vr_index_search_multi: one question, several vectors (reformulations, the last turns of a chat, the sub-questions of a
  * multi-hop question).  The sub-queries are a flat [n_sub][dim] float32 array; group g holds sub-queries lims[g] ..

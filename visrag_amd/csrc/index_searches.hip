@@ -1,5 +1,5 @@
 // The searches of the index that work on score rows (vr_index_search_groups / _filtered / _range / _rank_rows / _count_range /
-// _window / _multi / _diverse of include/visrag_hip.h, with what sets them up and their counters).  Each of them: every argument
+// _window / _groups_window / _multi / _diverse of include/visrag_hip.h, with what sets them up and their counters).  Each of them: every argument
 // check first, then per block of <= 256 queries the block's score rows S[q][row] (index.h: score_block, the deep path's bf16
 // MFMA GEMM), with filters the mask (mask_block: disallowed columns -> -inf), then the search's own kernels.  Scratch (query
 // staging, score rows, staged outputs, the staged filter ids) is shared between the searches; what a search keeps is its member
@@ -430,6 +430,79 @@ extern "C" int vr_index_search_window(vr_index_t ix, const float* queries, int32
     }
     VRCHK(return_output(out_scores, os, n_out, on_device, s));
     VRCHK(return_output(out_ids, oi, n_out, on_device, s));
+    if (!on_device) HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
+}
+
+// ---- document window search (search_group_window.hip) -------------------------------------------------------------------------
+extern "C" int vr_index_group_window_search_stats(vr_index_t ix, int64_t* out3, int32_t reset) {
+    if (!ix || !out3) return fail(VR_ERR_INVALID, "NULL argument");
+    return read_counters<unsigned long long, 3>(ix, ix->gwin.state, 0, out3, reset);
+}
+
+// The groups at ranks [offsets[q], offsets[q] + k) of every query's document ranking under its filter: per block the (masked)
+// score rows, their group maxima, the band edges, the rewritten maxima and the select.  Group maxima, best rows and counters are
+// the search's own; the grouping and the filters are read.  Nothing is stored.
+extern "C" int vr_index_search_groups_window(vr_index_t ix, const float* queries, int32_t nq, const int64_t* offsets, int32_t k,
+                                             const int32_t* filter_of_query, float* out_scores, int64_t* out_ids,
+                                             int64_t* out_groups, int32_t on_device, void* stream) {
+    if (!ix || nq < 0 || (nq > 0 && (!queries || !offsets || !out_scores || !out_ids || !out_groups)))
+        return fail(VR_ERR_INVALID, "bad arguments");
+    if (k <= 0 || k > search_bigk_max()) return fail(VR_ERR_INVALID, "k=%d unsupported (1..%d)", k, search_bigk_max());
+    if (!range_dim_ok(ix->dim)) return fail(VR_ERR_INVALID, "dim %d unsupported", ix->dim);
+    for (int32_t q = 0; q < nq; ++q)
+        if (offsets[q] < 0) return fail(VR_ERR_INVALID, "offsets[%d] = %lld is negative", (int)q, (long long)offsets[q]);
+    if (ix->grp.n_groups <= 0 || ix->n <= 0) return fail(VR_ERR_STATE, "no grouping set for the rows of the index (vr_index_set_groups)");
+    if (filter_of_query) VRCHK(check_filter_ids(ix, filter_of_query, nq, on_device, "filter_of_query"));
+    if (nq == 0) return VR_OK;                    // no query: no launch
+    VRCHK(set_dev(ix->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n_out = (size_t)nq * k;
+    if (!ix->gwin.state.p) VRCHK(ix->gwin.state.alloc(GWIN_WORDS * 8));
+    const int ng = (int)ix->grp.n_groups;
+    const int64_t ldS = pad256l(ix->n), ldB = (ix->grp.n_groups + 63) / 64 * 64;
+    const int64_t qblk = 256;                     // one fp32 score row per query, as on the deep path
+    const float* q32 = nullptr;
+    VRCHK(stage_queries(ix, queries, nq, pad256l(std::min<int64_t>(nq, qblk)), on_device, s, &q32));
+    const int* foq = nullptr;
+    if (filter_of_query) VRCHK(stage_input(ix->flt.ids, filter_of_query, (size_t)nq, on_device, s, &foq));
+    const int64_t* off = nullptr;                 // (a host array whoever calls)
+    VRCHK(stage_input(ix->gwin.off, offsets, (size_t)nq, 0, s, &off));
+    VRCHK(ix->gwin.edge.reserve((size_t)qblk * 12));
+    HIPCHK(hipStreamSynchronize(s));              // (the host array is free from here on)
+    float* os = nullptr; int64_t* oi = nullptr; int64_t* og = nullptr;
+    VRCHK(stage_output(ix->os, out_scores, n_out, on_device, &os));
+    VRCHK(stage_output(ix->oi, out_ids, n_out, on_device, &oi));
+    VRCHK(stage_output(ix->gwin.out, out_groups, n_out, on_device, &og));
+    VRCHK(ix->sbuf.reserve((size_t)qblk * ldS * 4));
+    VRCHK(ix->gwin.B.reserve((size_t)qblk * ldB * 4));
+    VRCHK(ix->gwin.R.reserve((size_t)qblk * ldB * 4));
+    float* S = ix->sbuf.as<float>();
+    for (int64_t q0 = 0; q0 < nq; q0 += qblk) {
+        const int nb = (int)std::min<int64_t>(qblk, nq - q0);
+        GroupWindowArgs p{};
+        p.a = block_view(ix, q32, q0, nb, k, true);                        // (the band is defined by the error model)
+        p.a.out_scores = os + (size_t)q0 * k; p.a.out_ids = oi + (size_t)q0 * k;
+        p.out_groups = og + (size_t)q0 * k;
+        p.goff = ix->grp.off.as<int>(); p.n_groups = ng;
+        p.B = ix->gwin.B.as<float>(); p.ldB = (size_t)ldB;
+        p.R = ix->gwin.R.as<int>();
+        p.offsets = off + q0;
+        p.filter_of_query = foq ? foq + q0 : nullptr;
+        p.n_filters = (int)ix->flt.n_filters;
+        p.edges = ix->gwin.edge.as<float>();
+        p.present = ix->gwin.edge.as<int>() + 2 * qblk;
+        p.stats = ix->gwin.state.as<unsigned long long>();
+        VRCHK(score_block(ix, q32, q0, nb, ldS, nullptr, s));
+        if (foq) VRCHK(mask_block(ix, foq + q0, nb, ldS, nullptr, nullptr, 0, s));
+        HIPCHK(launch_group_max(S, (size_t)ldS, p.goff, ng, p.B, p.ldB, nb, nullptr, 0, s));
+        HIPCHK(launch_group_window_edges(p, nb, s));
+        HIPCHK(launch_group_window_rescore(p, S, (size_t)ldS, nb, s));
+        HIPCHK(launch_group_window_select(p, nb, s));
+    }
+    VRCHK(return_output(out_scores, os, n_out, on_device, s));
+    VRCHK(return_output(out_ids, oi, n_out, on_device, s));
+    VRCHK(return_output(out_groups, og, n_out, on_device, s));
     if (!on_device) HIPCHK(hipStreamSynchronize(s));
     return VR_OK;
 }

@@ -470,6 +470,29 @@ hipError_t launch_window_edges(const WindowSearchArgs& p, const float* S, size_t
 hipError_t launch_window_rescore(const WindowSearchArgs& p, float* S, size_t ldS, int nq_block, hipStream_t s);
 // ranks [offset, offset + k) of the rewritten rows -> a.out_scores / a.out_ids, (-inf, -1) past the allowed rows
 hipError_t launch_window_select(const WindowSearchArgs& p, const float* S, size_t ldS, int nq_block, hipStream_t s);
+// ---- document window search (search_group_window.hip): the groups at ranks [offset, offset + k) of a query's document ranking
+struct GroupWindowArgs {
+    SearchArgs a;                    // the block's view, as WindowSearchArgs': index_f32, n_docs, dim, q_f32, nq and a valid error model;
+                                     // k, out_scores / out_ids [nq][k]: the block's part of the result (no out_keys)
+    const int* goff;                 // [n_groups + 1] first row of every group; goff[n_groups] = n_docs
+    int n_groups;
+    float* B; size_t ldB;            // [nq][ldB] group maxima of the (masked) score rows: launch_group_max; rewritten in place
+    int* R;                          // [nq][ldB] scratch: the best row of every band group
+    const int64_t* offsets;          // [nq] device: the first rank of every query's window, >= 0
+    const int* filter_of_query;      // [nq] device or null, as WindowSearchArgs': the score rows have been masked; an entry outside
+    int n_filters;                   //   [-1, n_filters): a row of tails
+    float* edges;                    // [nq][2] scratch: the band {lo, hi} of group maxima the window's groups lie in (NaN: an empty window)
+    int* present;                    // [nq] scratch: groups with an allowed row
+    int64_t* out_groups;             // [nq][k] the block's part: the group of every result (-1: a tail)
+    unsigned long long* stats;       // [0] queries [1] band groups re-scored [2] fp32 row dots
+};
+// edges[q] / present[q] from p.B row q (group maxima of masked bf16-MFMA scores); B is only read
+hipError_t launch_group_window_edges(const GroupWindowArgs& p, int nq_block, hipStream_t s);
+// B rows [0, nq_block) rewritten in place: +inf certainly ahead, -inf certainly behind or absent, E_g inside the band (R: its best
+// row); S (the masked score rows the maxima came from) is only read
+hipError_t launch_group_window_rescore(const GroupWindowArgs& p, const float* S, size_t ldS, int nq_block, hipStream_t s);
+// ranks [offset, offset + k) of the rewritten rows -> a.out_scores / a.out_ids / out_groups, (-inf, -1, -1) past the present groups
+hipError_t launch_group_window_select(const GroupWindowArgs& p, int nq_block, hipStream_t s);
 // ---- fused search (search_multi.hip): the k rows of largest max (or min) fp32 score over a group of sub-queries
 struct MultiSearchArgs {
     SearchArgs a;                    // the block's view, as WindowSearchArgs': q_f32 and nq are the block's SUB-QUERIES (whole groups, <= 256),

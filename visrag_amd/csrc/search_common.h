@@ -23,6 +23,11 @@ __device__ __forceinline__ float one_ulp_down(float x) {
     const uint32_t o = f32_orderable(x);
     return o ? orderable_f32(o - 1u) : x;
 }
+// the next float above x: the same for an upper bound computed by one rounded addition
+__device__ __forceinline__ float one_ulp_up(float x) {
+    const uint32_t o = f32_orderable(x);
+    return o != 0xFFFFFFFFu ? orderable_f32(o + 1u) : x;
+}
 // sort key: larger key = better candidate (higher score, then LOWER id)
 __device__ __forceinline__ uint64_t make_key(float score, uint32_t id) {
     return ((uint64_t)f32_orderable(score) << 32) | (uint32_t)(~id);

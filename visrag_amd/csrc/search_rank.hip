@@ -33,11 +33,6 @@ struct RankLds {
     unsigned ahead;                         // rows of this chunk ahead of the bar
 };
 
-__device__ __forceinline__ float one_ulp_up(float x) {
-    const uint32_t o = f32_orderable(x);
-    return o != 0xFFFFFFFFu ? orderable_f32(o + 1u) : x;
-}
-
 __global__ __launch_bounds__(256) void rank_bar_kernel(RankSearchArgs p, int n_pairs) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const SearchArgs& a = p.a;

@@ -3,7 +3,9 @@
 //   select_kth      3-pass radix select (11 + 11 + 10 bits of the order-preserving key, histograms in LDS) of the key of
 //                   the kp-th largest value, and how many of its ties belong to the kp best;
 //   gather_ordered  the positions of the candidates in ascending order: every key above a threshold, then the LOWEST positions
-//                   among the keys equal to it — the one place where "lowest ids first at the threshold" is decided.
+//                   among the keys equal to it — the one place where "lowest ids first at the threshold" is decided;
+//   gather_window   the positions at ranks [o, kz) between two such keys, the same tie rule at both edges (search_window.hip:
+//                   values = a rewritten score row; search_group_window.hip: values = rewritten group maxima).
 // What is done with the candidates (re-scoring, certification, output) is the kernels' own.
 // Also here: flag_slots, the part of a flag list that one launch of a fallback kernel walks.
 #pragma once
@@ -109,6 +111,56 @@ __device__ __forceinline__ int gather_ordered(const float* __restrict__ vals, in
         __syncthreads();
     }
     return L.run[0];
+}
+
+struct WindowSelectLds {
+    SelectLds s;
+    int wc[4][3], run[3];                   // gather_window: per-wave and running counts {== T_a, == T_z, selected}
+};
+
+// Positions i of vals[0, n) that are NOT among the first o of the ranking (value descending, then lower position) and ARE among
+// its first kz, into L.s.cand in ascending order; returns how many (kz - o when both keys come from select_kth over vals).
+//   first o:  key > a.T, or key == a.T at equal-position < a.need_eq      (skip_a == false: o == 0, nothing is excluded)
+//   first kz: key > z.T, or key == z.T at equal-position < z.need_eq
+// Nothing is written at or beyond slot SEL_CAND.  Called by the whole workgroup; the LDS must be free (barrier).
+__device__ __forceinline__ int gather_window(const float* __restrict__ vals, int n, KthKey a, bool skip_a, KthKey z, WindowSelectLds& L) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid < 3) L.run[tid] = 0;
+    __syncthreads();
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int i0 = 0; i0 < n; i0 += 256) {
+        const int i = i0 + tid;
+        const unsigned key = i < n ? f32_orderable(vals[i]) : 0u;
+        const bool eqa = i < n && skip_a && key == a.T, eqz = i < n && key == z.T;
+        const bool span = i < n && key >= z.T && (!skip_a || key <= a.T);  // every selected position, and every tie of an edge
+        if (!__syncthreads_or(span)) continue;                             // (barrier; most blocks hold none)
+        const unsigned long long ba = __ballot(eqa), bz = __ballot(eqz);
+        if (lane == 0) { L.wc[wave][0] = __popcll(ba); L.wc[wave][1] = __popcll(bz); }
+        __syncthreads();
+        int pa = L.run[0] + __popcll(ba & below), pz = L.run[1] + __popcll(bz & below), ta = 0, tz = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            if (w < wave) { pa += L.wc[w][0]; pz += L.wc[w][1]; }
+            ta += L.wc[w][0]; tz += L.wc[w][1];
+        }
+        const bool past_o = !skip_a || key < a.T || (eqa && pa >= a.need_eq);
+        const bool in_kz = key > z.T || (eqz && pz < z.need_eq);
+        const bool sel = span && past_o && in_kz;
+        const unsigned long long bs = __ballot(sel);
+        if (lane == 0) L.wc[wave][2] = __popcll(bs);
+        __syncthreads();
+        int ps = L.run[2] + __popcll(bs & below), ts = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            if (w < wave) ps += L.wc[w][2];
+            ts += L.wc[w][2];
+        }
+        if (sel && ps < SEL_CAND) L.s.cand[ps] = i;
+        __syncthreads();
+        if (tid == 0) { L.run[0] += ta; L.run[1] += tz; L.run[2] += ts; }
+        __syncthreads();
+    }
+    return L.run[2];
 }
 
 }  // namespace vr

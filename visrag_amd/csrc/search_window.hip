@@ -43,16 +43,6 @@ struct WindowLds {
     unsigned ahead;                         // rows of this chunk certainly ahead of the window
 };
 
-struct WindowSelectLds {
-    SelectLds s;
-    int wc[4][3], run[3];                   // gather_window: per-wave and running counts {== T_a, == T_z, selected}
-};
-
-__device__ __forceinline__ float one_ulp_up(float x) {
-    const uint32_t o = f32_orderable(x);
-    return o != 0xFFFFFFFFu ? orderable_f32(o + 1u) : x;
-}
-
 __global__ __launch_bounds__(256) void window_edge_kernel(WindowSearchArgs p, const float* __restrict__ S, size_t ldS) {
     __shared__ SelectLds L;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -136,51 +126,6 @@ __global__ __launch_bounds__(256) void window_rescore_kernel(WindowSearchArgs p,
         const unsigned n = L.ahead;
         if (n > 0) atomicAdd(&p.stats[2], (unsigned long long)n);
     }
-}
-
-// Positions i of vals[0, n) that are NOT among the first o of the ranking (value descending, then lower position) and ARE among
-// its first kz, into L.s.cand in ascending order; returns how many (kz - o when both keys come from select_kth over vals).
-//   first o:  key > a.T, or key == a.T at equal-position < a.need_eq      (skip_a == false: o == 0, nothing is excluded)
-//   first kz: key > z.T, or key == z.T at equal-position < z.need_eq
-// Nothing is written at or beyond slot SEL_CAND.  Called by the whole workgroup; the LDS must be free (barrier).
-__device__ __forceinline__ int gather_window(const float* __restrict__ vals, int n, KthKey a, bool skip_a, KthKey z, WindowSelectLds& L) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid < 3) L.run[tid] = 0;
-    __syncthreads();
-    const unsigned long long below = (1ull << lane) - 1ull;
-    for (int i0 = 0; i0 < n; i0 += 256) {
-        const int i = i0 + tid;
-        const unsigned key = i < n ? f32_orderable(vals[i]) : 0u;
-        const bool eqa = i < n && skip_a && key == a.T, eqz = i < n && key == z.T;
-        const bool span = i < n && key >= z.T && (!skip_a || key <= a.T);  // every selected position, and every tie of an edge
-        if (!__syncthreads_or(span)) continue;                             // (barrier; most blocks hold none)
-        const unsigned long long ba = __ballot(eqa), bz = __ballot(eqz);
-        if (lane == 0) { L.wc[wave][0] = __popcll(ba); L.wc[wave][1] = __popcll(bz); }
-        __syncthreads();
-        int pa = L.run[0] + __popcll(ba & below), pz = L.run[1] + __popcll(bz & below), ta = 0, tz = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            if (w < wave) { pa += L.wc[w][0]; pz += L.wc[w][1]; }
-            ta += L.wc[w][0]; tz += L.wc[w][1];
-        }
-        const bool past_o = !skip_a || key < a.T || (eqa && pa >= a.need_eq);
-        const bool in_kz = key > z.T || (eqz && pz < z.need_eq);
-        const bool sel = span && past_o && in_kz;
-        const unsigned long long bs = __ballot(sel);
-        if (lane == 0) L.wc[wave][2] = __popcll(bs);
-        __syncthreads();
-        int ps = L.run[2] + __popcll(bs & below), ts = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            if (w < wave) ps += L.wc[w][2];
-            ts += L.wc[w][2];
-        }
-        if (sel && ps < SEL_CAND) L.s.cand[ps] = i;
-        __syncthreads();
-        if (tid == 0) { L.run[0] += ta; L.run[1] += tz; L.run[2] += ts; }
-        __syncthreads();
-    }
-    return L.run[2];
 }
 
 __global__ __launch_bounds__(256) void window_select_kernel(WindowSearchArgs p, const float* __restrict__ S, size_t ldS, int n_sort) {

@@ -11,6 +11,7 @@
                                                                (HipIndex.search_multi; no reference counterpart)
   * `retrieve_documents(knowledge_base_path, query, topk, ...)` -> the best page of each of the top-k DOCUMENTS
                                                                (no reference counterpart: its top-k is pages)
+    (`documents=[...]`: only those documents are ranked; `offset=n`: the next page of documents — HipIndex.search_groups_window)
   * `retrieve_above(knowledge_base_path, query, min_score, ...)` -> EVERY page at or above a score, best first
   * `duplicate_pages(knowledge_base_path, threshold, ...)` -> groups of near-duplicate pages
                                                                (HipIndex.search_range; no reference counterpart either)
@@ -278,14 +279,20 @@ def load_document_base(knowledge_base_path: str, device: Optional[int] = None):
 
 @torch.no_grad()
 def retrieve_documents(knowledge_base_path: str, query, topk: int, model, tokenizer, index=None, names=None,
-                       return_scores: bool = False):
+                       return_scores: bool = False, documents=None, offset: int = 0):
     """Paths of the best page of each of the `topk` most similar DOCUMENTS, best document first (None if the base does not
     exist): a document scores as its best page does, so ten results are ten documents, not ten pages of one.  Documents are
     the `doc_of_page` of the page names.  Pass `index, names = load_document_base(path)` to keep the index resident between
     questions; an index of your own must hold every document's pages adjacently, `names` in its row order.  `query` is the
-    question, or its embedding ([dim] or [1, dim]) if it has been encoded already."""
+    question, or its embedding ([dim] or [1, dim]) if it has been encoded already.
+    `documents`: an iterable of document names — only those documents are ranked, each by its best page (one filter, set for this
+    question as in `retrieve`; HipIndex.search_groups_window); a name no page carries raises ValueError.  `offset`: the "next
+    page" of the document list — the documents at ranks offset .. offset + topk - 1 of the same ranking, exact however deep;
+    fewer than `topk` paths where the ranking ends.  With both at their defaults the call is HipIndex.search_groups."""
     if not os.path.exists(knowledge_base_path):
         return None
+    if offset < 0:
+        raise ValueError("offset must be >= 0")
     own = index is None
     if own:
         index, names = load_document_base(knowledge_base_path, model.encoder.device if model is not None else None)
@@ -298,7 +305,9 @@ def retrieve_documents(knowledge_base_path: str, query, topk: int, model, tokeni
         q = encode(model, tokenizer, [QUERY_INSTRUCTION + query])
     else:
         q = np.asarray(query.detach().cpu() if isinstance(query, torch.Tensor) else query, dtype=np.float32).reshape(1, -1)
-    if len(index) == 0:
+    if documents is not None or offset > 0:
+        paths, scores = _document_window(knowledge_base_path, q, topk, index, names, documents, int(offset))
+    elif len(index) == 0:
         paths, scores = [], []
     else:
         sc, ids, _ = index.search_groups(q, max(1, min(topk, index.n_groups)))
@@ -308,6 +317,31 @@ def retrieve_documents(knowledge_base_path: str, query, topk: int, model, tokeni
     if own:
         index.close()
     return (paths, scores) if return_scores else paths
+
+
+def _document_window(knowledge_base_path, q, topk, index, names, documents, offset):
+    """retrieve_documents() at ranks [offset, offset + topk); `documents` given: among them, through one filter set for this question"""
+    n = len(index)
+    mask, present = None, int(index.n_groups) if n else 0
+    if documents is not None:
+        docs = [doc_of_page(nm) for nm in names[:n]]
+        wanted = set(documents)
+        unknown = sorted(wanted - set(docs))
+        if unknown:
+            raise ValueError(f"no page of the base belongs to {unknown[0]!r}" + (f" (and {len(unknown) - 1} more)" if len(unknown) > 1 else ""))
+        mask = label_filters(docs, [wanted])
+        present = len(wanted)
+    paths, scores = [], []
+    if topk > 0 and offset < present:
+        if mask is not None:
+            index.set_filters(mask)
+        for o in range(offset, min(offset + topk, present), 1000):        # a list longer than one window: paged
+            sc, ids, _ = index.search_groups_window(q, o, min(1000, offset + topk - o, present - o), None if mask is None else 0)
+            sc, ids = (x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in (sc, ids))
+            keep = [int(i) for i in ids[0] if i >= 0]
+            paths += [os.path.join(knowledge_base_path, names[i]) for i in keep]
+            scores += [float(v) for v in sc[0][: len(keep)]]
+    return paths, scores
 
 
 @torch.no_grad()

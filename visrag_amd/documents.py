@@ -21,6 +21,9 @@ depth cannot give — MRR without a cut-off, recall at any k.
 The windowed search (HipIndex.search_window) returns the rows at ranks [offset, offset + k): `window_negatives` takes such a
 window and a query's positives and leaves the hard negatives a trainer wants ("ranks 30-200 minus the positives").
 
+The document window search (HipIndex.search_groups_window) ranks documents under a row filter: `collection_filters` builds such
+filters from a label per DOCUMENT ("the ten best documents of this collection").
+
 The fused search (HipIndex.search_multi) ranks rows by the max or the min of their scores over a group of sub-queries:
 `group_rows` of the sub-queries' labels gives its `lims`, and `fuse_runs` states what per-sub-query top-k lists can and cannot
 say about that ranking — the workaround the fused search replaces.
@@ -100,6 +103,24 @@ def label_filters(labels: Sequence[Hashable], wanted_sets: Sequence[Optional[Ite
             continue
         w = set(wanted)
         out[j] = [lab in w for lab in labels]
+    return out
+
+
+def collection_filters(offsets, collection_of_group: Sequence[Hashable],
+                       wanted_sets: Sequence[Optional[Iterable[Hashable]]]) -> np.ndarray:
+    """bool [len(wanted_sets)][rows]: filter j allows every row of the groups of `offsets` whose label `collection_of_group[g]` is in
+    wanted_sets[j] (None: every row) — `label_filters` with a label per document, not per row; what `HipIndex.set_filters` takes
+    for `search_groups_window`.  A wanted label that no group carries allows nothing."""
+    off = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    if len(collection_of_group) != len(off) - 1:
+        raise ValueError(f"{len(collection_of_group)} labels for {len(off) - 1} groups")
+    out = np.zeros((len(wanted_sets), int(off[-1])), dtype=bool)
+    for j, wanted in enumerate(wanted_sets):
+        if wanted is None:
+            out[j] = True
+            continue
+        w = set(wanted)
+        out[j] = group_filter(off, [g for g, lab in enumerate(collection_of_group) if lab in w])
     return out
 
 

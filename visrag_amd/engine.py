@@ -635,6 +635,36 @@ class HipIndex:
         query's window (decided by the bf16 score alone)."""
         return self._stats3(self.lib.vr_index_window_search_stats, ("queries", "candidates", "ahead"), reset)
 
+    # ---- document window search (include/visrag_hip.h: vr_index_search_groups_window) ----
+    def search_groups_window(self, queries, offset, k: int, filter_of_query=None):
+        """The documents at ranks [offset, offset + k) of every query's document ranking, under its filter (include/visrag_hip.h:
+        vr_index_search_groups_window) -> (scores [nq,k] f32, best row ids [nq,k] i64, groups [nq,k] i64).  A group (`set_groups`)
+        is present if the query's filter allows one of its rows; it scores as its best ALLOWED row does, that row — the lowest
+        among equals — is its best row, and present groups rank score descending, then lower group first.  Entry j is the group
+        of rank offset + j; slots at or past the number of present groups are (-inf, -1, -1).  `search_groups_window(q, 0, k)` is
+        `search_groups(q, k)` bit for bit.  `offset`: an int (every query's) or one per query (any int sequence or tensor), each
+        >= 0, however deep.  1 <= k <= 1000: page for more.  `filter_of_query` as in `search_filtered`, None = no filter (none
+        need to be set).  cuda in -> cuda out, numpy / cpu in -> numpy out."""
+        nq = int(queries.shape[0])
+        off = self._row_ids(offset)
+        if off.size == 1 and nq != 1:
+            off = np.full(nq, off[0], dtype=np.int64)
+        if len(off) != nq:
+            raise ValueError(f"{len(off)} offsets for {nq} queries")
+        if (off < 0).any():
+            raise ValueError("offsets must be >= 0")
+        keep, fptr = (None, C.c_void_p(None)) if filter_of_query is None else self._filter_of_query(queries, filter_of_query)
+
+        def fn(h, q, n, kk, out_scores, out_ids, out_groups, on_device, stream):
+            return self.lib.vr_index_search_groups_window(h, q, n, C.c_void_p(off.ctypes.data), kk, fptr, out_scores, out_ids,
+                                                          out_groups, on_device, stream)
+
+        return self._search(fn, "vr_index_search_groups_window", queries, k, 2)
+
+    def group_window_search_stats(self, reset: bool = False) -> Dict[str, int]:
+        """Document window searches since the last reset: queries, documents of the bands re-scored, fp32 page dot products."""
+        return self._stats3(self.lib.vr_index_group_window_search_stats, ("queries", "documents", "page_dots"), reset)
+
     # ---- fused search (include/visrag_hip.h: vr_index_search_multi) ----
     def search_multi(self, queries, lims, k: int, fuse: str = "max", filter_of_group=None):
         """The k rows of largest fused score per group of sub-queries (include/visrag_hip.h: vr_index_search_multi) -> (scores

@@ -32,7 +32,7 @@ from typing import Callable, Dict, Hashable, List, Optional, Tuple
 import numpy as np
 import torch
 
-from .documents import group_rows, label_filters
+from .documents import collection_filters, group_rows, label_filters
 from .engine import HipIndex, topk_merge_keys
 from .utils import list_shards, read_shard, shard_rank
 
@@ -226,6 +226,61 @@ def retrieve_filtered(args, topk: int, label_of: Callable[[str], object], labels
             if r >= 0:
                 result[q][doc_ids[int(r)]] = float(s)
     return result
+
+
+def retrieve_documents_filtered(args, topk: int, doc_of: Callable[[str], str], label_of_doc: Callable[[str], object],
+                                labels_of_query: Callable[[str], Optional[set]], offset: int = 0,
+                                index_factory: Optional[Callable] = None
+                                ) -> Tuple[Dict[str, Dict[str, float]], Dict[str, Dict[str, str]]]:
+    """Document-level retrieval inside a subset of the documents, over the same pickle shards: retrieve_documents plus
+    retrieve_filtered.  The corpus rows are PAGES, `doc_of(page_id)` the document of a page, `label_of_doc(doc)` the collection of
+    a document; query `qid` ranks only the documents whose label is in `labels_of_query(qid)` (None = every document).
+    -> ({qid: {doc: score}}, {qid: {doc: best_page_id}}): the documents at ranks offset .. offset + topk - 1 of that ranking, a
+    document scoring as its best page does (HipIndex.search_groups_window: the fp32 ranking, exact however deep the offset, fewer
+    entries where the ranking ends); the first dict goes to `save_as_trec` as it is.  One filter is built per distinct label set.
+
+    Replicated form only, like retrieve_documents: every rank holds the whole corpus."""
+    if offset < 0:
+        raise ValueError("offset must be >= 0")
+    make_index = index_factory or HipIndex
+    queries, qids, _ = _load_queries(args)
+    corpus_parts = list_shards(args.output_dir, "corpus")
+    if len(corpus_parts) == 0:
+        raise ValueError("No pre-computed document embeddings found")
+    reps, page_ids = [], []
+    for p in corpus_parts:
+        r, i = read_shard(p)
+        if len(i):
+            reps.append(np.asarray(r, dtype=np.float32))
+            page_ids.extend(i)
+    scores: Dict[str, Dict[str, float]] = {q: {} for q in qids}
+    pages: Dict[str, Dict[str, str]] = {q: {} for q in qids}
+    if not page_ids or topk <= 0:
+        return scores, pages
+    order, offsets, docs = group_rows([doc_of(i) for i in page_ids])
+    sets: List[Optional[frozenset]] = []
+    which: Dict[Optional[frozenset], int] = {}
+    filter_of_query = np.empty(len(qids), dtype=np.int32)
+    for qi, q in enumerate(qids):
+        wanted = labels_of_query(q)
+        key = None if wanted is None else frozenset(wanted)
+        if key not in which:
+            which[key] = len(sets)
+            sets.append(key)
+        filter_of_query[qi] = which[key]
+    ix = make_index(queries.shape[1], len(page_ids), _device_index(args))
+    ix.add(np.concatenate(reps)[order])
+    ix.set_groups(offsets)
+    ix.set_filters(collection_filters(offsets, [label_of_doc(d) for d in docs], sets))
+    for o in range(int(offset), min(int(offset) + topk, len(docs)), WINDOW_PAGE):     # a list longer than one window: paged
+        sc, rows, groups = ix.search_groups_window(queries, o, min(WINDOW_PAGE, int(offset) + topk - o, len(docs) - o), filter_of_query)
+        for qi, q in enumerate(qids):
+            for s_, r, g in zip(sc[qi], rows[qi], groups[qi]):
+                if r >= 0:
+                    scores[q][docs[int(g)]] = float(s_)
+                    pages[q][docs[int(g)]] = page_ids[int(order[int(r)])]
+    ix.close()
+    return scores, pages
 
 
 def retrieve_range(args, threshold: float, max_per_query: Optional[int] = None, index_factory: Optional[Callable] = None
