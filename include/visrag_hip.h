@@ -463,7 +463,7 @@ int vr_index_range_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
  * pairs: VR_OK, nothing is launched.  An empty index: vr_index_count_range writes zeros, vr_index_rank_rows with pairs is
  * VR_ERR_INVALID (no id is in range).  Nothing is stored: a later vr_index_remove / update / add has nothing to invalidate.
  * A host caller's call synchronises the stream.  Not offered: corpus-sharded ranks inside the library (add per-shard counts),
- * ranks of groups, ranks under MMR. */
+ * ranks under MMR.  Ranks of groups: vr_index_rank_groups below. */
 int vr_index_rank_rows(vr_index_t ix, const float* queries, int32_t nq,
                        const int64_t* lims,              /* host [nq + 1] */
                        const int64_t* ids,               /* host [lims[nq]] */
@@ -539,7 +539,7 @@ int vr_index_window_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
  * VR_ERR_STATE.  On the device an out-of-range filter index allows nothing: a row of tails.  nq == 0: VR_OK, nothing is
  * launched.  Nothing is stored between calls.  A host caller's call synchronises the stream.  The call counts in no other
  * search's statistics and leaves every state the other searches read alone; vr_index_search_groups is untouched by it.
- * Not offered: ranks of named documents, a thresholded (range) document search, documents under the fused search or MMR,
+ * Ranks of named documents: vr_index_rank_groups below.  Not offered: a thresholded (range) document search, documents under the fused search or MMR,
  * corpus-sharded ranks (merge per-shard pages on the host), k > 1000 in one call, a k per query. */
 int vr_index_search_groups_window(vr_index_t ix, const float* queries, int32_t nq,
                                   const int64_t* offsets,           /* host [nq] */
@@ -550,6 +550,55 @@ int vr_index_search_groups_window(vr_index_t ix, const float* queries, int32_t n
 /* Document window searches since the last reset: out3 = {queries, band groups re-scored, fp32 row dot products} — 64-bit
  * counters in device memory. */
 int vr_index_group_window_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
+/* ---- document rank search: the exact rank of named groups, exact counts of groups against thresholds, under filters ---- */
+/* vr_index_rank_groups: WHERE a named document stands.  The semantics are those of vr_index_search_groups_window: for query q
+ * with filter f (filter_of_query NULL or an entry of -1: every row) a group g (vr_index_set_groups) is PRESENT if f allows at
+ * least one of its rows; its score is E_g = the largest e_i over its ALLOWED rows — e_i the library's one fp32 dot product, the
+ * bits vr_index_search returns for that pair — its best row the lowest allowed row id that attains E_g; present groups rank by
+ * E_g descending, then lower group first.  For a present target g
+ *   out_scores = E_g;  out_rows = best row;  out_ranks = the number of present groups h whose key (E_h, h) is greater.
+ * A group of rank r is therefore entry r - o of vr_index_search_groups_window for every offset o <= r < o + k, with the same
+ * score bits and the same best row; groups with identical bits get consecutive ranks in group order; duplicate targets are
+ * allowed.  A target the filter leaves no row of is NOT in the ranking: it gets (-inf, -1, -1).  This differs from
+ * vr_index_rank_rows, where a forbidden row gets the position it WOULD take: a row has a score whether or not it is allowed, a
+ * group's score is defined over its allowed rows, and an absent group has none.
+ *   vr_index_count_groups_range: for query q and threshold t the number of present groups with E_g >= t, or with E_g > t when
+ * strict.  -0.0 counts as +0.0, as in vr_index_count_range.
+ *   Layout: targets / thresholds in CSR form: query q's are entries lims[q] .. lims[q + 1] - 1.  lims [nq + 1] int64, groups
+ * int64 and thresholds float32 are always HOST arrays (as the ids of vr_index_rank_rows are); queries [nq][dim] float32,
+ * filter_of_query [nq] int32 and the outputs (lims[nq] entries each) are all host or all device per `on_device`.
+ *   Exactness: the rank search's argument composed with the grouped search's.  With |b_i - e_i| <= eps over the allowed rows
+ * the masked group maximum B_h lies within eps of E_h (max is 1-Lipschitz): a group with B_h > t + eps is certainly ahead of a
+ * bar t (t = E_g for a rank), one with B_h < t - eps certainly behind it or absent; inside a group of the band between exactly
+ * the rows with b_i >= B_h - 2 eps — only such a row can attain E_h — are re-scored in fp32, and the group is compared by key
+ * for a rank, by the fp32 compare for a count.  The target is found the same way and never counts itself.  Every edge is rounded
+ * outward by one ulp.  No candidate margin, no widening, no flagged query; a pair costs what its band holds; with certification
+ * off the default error model defines the band, so the result is exact in every setting of vr_index_set_search_eps.
+ *   Checks, all before any launch and with the outputs untouched: NULL pointers, nq < 0, lims[0] != 0 or decreasing lims,
+ * 2^31 pairs or more, an unsupported dim (as vr_index_search_range): VR_ERR_INVALID; no grouping set for the rows present
+ * (vr_index_add / vr_index_remove drop it): VR_ERR_STATE; a group outside [0, n_groups), a threshold that is NaN or +-inf, a
+ * HOST filter_of_query entry outside [-1, n_filters): VR_ERR_INVALID; filter_of_query given while no filters are set:
+ * VR_ERR_STATE.  On the device an out-of-range filter index allows nothing: ranks (-inf, -1, -1), counts 0.  Zero pairs: VR_OK,
+ * nothing is launched; a block of 256 queries without pairs is skipped.  Nothing is stored between calls.  A host caller's call
+ * synchronises the stream.  The calls count in no other search's statistics and leave every state the other searches read
+ * alone.  Not offered: a thresholded (range) list of documents, document ranks under the fused search or MMR, corpus-sharded
+ * ranks inside the library (add per-shard counts), several bars of one query per read of its group maxima. */
+int vr_index_rank_groups(vr_index_t ix, const float* queries, int32_t nq,
+                         const int64_t* lims,              /* host [nq + 1] */
+                         const int64_t* groups,            /* host [lims[nq]] */
+                         const int32_t* filter_of_query,   /* NULL: no filter for any query */
+                         float* out_scores, int64_t* out_rows, int64_t* out_ranks,   /* [lims[nq]] */
+                         int32_t on_device, void* stream);
+int vr_index_count_groups_range(vr_index_t ix, const float* queries, int32_t nq,
+                                const int64_t* lims,            /* host [nq + 1] */
+                                const float* thresholds,        /* host [lims[nq]] */
+                                int32_t strict,                 /* 0: E >= t, 1: E > t */
+                                const int32_t* filter_of_query, /* NULL: no filter for any query */
+                                int64_t* out_counts,            /* [lims[nq]] */
+                                int32_t on_device, void* stream);
+/* Document rank searches and counts since the last reset: out3 = {pairs, band groups re-scored (a rank's own target among
+ * them), fp32 row dot products} — 64-bit counters in device memory. */
+int vr_index_group_rank_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
 /* ---- fused search: the top-k rows by max or min over a group of sub-queries ---- */
 /* vr_index_search_multi: one question, several vectors (reformulations, the last turns of a chat, the sub-questions of a
  * multi-hop question).  The sub-queries are a flat [n_sub][dim] float32 array; group g holds sub-queries lims[g] ..

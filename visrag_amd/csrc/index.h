@@ -1,5 +1,5 @@
 // The search index's handle and the host helpers its three files share: index.hip (life cycle, vr_index_search*), index_searches.hip
-// (the score-row searches: groups, filtered, range, rank, window, document window, fused, diverse) and index_rows.hip (editing in place).
+// (the score-row searches: groups, filtered, range, rank, window, document window, document rank, fused, diverse) and index_rows.hip (editing in place).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,7 +12,7 @@
 constexpr int CERT_WORDS = 32, CERT_FLAG = 2, CERT_FLAG2 = 3, CERT_STATS = 4, CERT_NSTATS = 6;   // (the two flag counters are consecutive: cleared together)
 constexpr int GRP_STATS = 2, GRP_LIST = 8, GRP_WORDS = GRP_LIST + 256;
 constexpr int FLT_STATS = 2, FLT_LIST = 8, FLT_WORDS = FLT_LIST + 256;
-constexpr int RNG_TOTAL = 3, RNG_WORDS = RNG_TOTAL + 1, RNK_WORDS = 3, WIN_WORDS = 3, MUL_WORDS = 3, GWIN_WORDS = 3;   // (u64 words; 0..2 the counters)
+constexpr int RNG_TOTAL = 3, RNG_WORDS = RNG_TOTAL + 1, RNK_WORDS = 3, WIN_WORDS = 3, MUL_WORDS = 3, GWIN_WORDS = 3, GRNK_WORDS = 3;   // (u64 words; 0..2 the counters)
 
 struct vr_index_s {
     int device = 0, dim = 0;
@@ -29,7 +29,7 @@ struct vr_index_s {
     float eps_rel = -2.f;             // -2: the rigorous data-dependent default; >= 0: the caller's eps_rel |q| max|d|; else off
     // Every search below has state of its own in a member of its own: no other search reads any of it (the filters excepted:
     // range, rank, windowed, fused and diversified search read flt.bits / flt.count and stage their filter ids in flt.ids; the
-    // document window search does too, and reads grp.off / grp.n_groups: the grouping is the index's, not a search's).
+    // document window and document rank searches do too, and read grp.off / grp.n_groups: the grouping is the index's, not a search's).
     struct {                          // grouped search (vr_index_search_groups, search_group.hip)
         int64_t n_groups = 0;         // 0: no grouping set (vr_index_add / vr_index_reset drop it)
         DevBuf off, B, out, state;    // int first rows [n_groups + 1] | group maxima [256][ldB] | staged out_groups | int words: [0] flag
@@ -66,6 +66,12 @@ struct vr_index_s {
                                       // rows [256][ldB] | staged out_groups | u64 words: [0..2] the counters of
                                       // vr_index_group_window_search_stats
     } gwin;
+    struct {                          // document rank search (vr_index_rank_groups / vr_index_count_groups_range, search_group_rank.hip):
+                                      // no stored result
+        DevBuf q, v, bar, eps, B, out, state;   // int query of every pair | int target groups or f32 thresholds | u64 bars | f32 eps per
+                                      // pair | group maxima [256][ldB], only read | staged out_ranks | u64 words: [0..2] the counters
+                                      // of vr_index_group_rank_search_stats
+    } grnk;
     struct {                          // fused search (vr_index_search_multi, search_multi.hip): no stored result
         DevBuf lims, fsub, edge, which, state;   // int lims of the call's groups | int filter of every sub-query | f32 band edge of a
                                       // block's groups | staged out_which | u64 words: [0..2] the counters of vr_index_multi_search_stats

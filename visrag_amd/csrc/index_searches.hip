@@ -1,5 +1,5 @@
 // The searches of the index that work on score rows (vr_index_search_groups / _filtered / _range / _rank_rows / _count_range /
-// _window / _groups_window / _multi / _diverse of include/visrag_hip.h, with what sets them up and their counters).  Each of them: every argument
+// _window / _groups_window / _rank_groups / _count_groups_range / _multi / _diverse of include/visrag_hip.h, with what sets them up and their counters).  Each of them: every argument
 // check first, then per block of <= 256 queries the block's score rows S[q][row] (index.h: score_block, the deep path's bf16
 // MFMA GEMM), with filters the mask (mask_block: disallowed columns -> -inf), then the search's own kernels.  Scratch (query
 // staging, score rows, staged outputs, the staged filter ids) is shared between the searches; what a search keeps is its member
@@ -371,6 +371,116 @@ extern "C" int vr_index_count_range(vr_index_t ix, const float* queries, int32_t
                                     int32_t strict, const int32_t* filter_of_query, int64_t* out_counts, int32_t on_device, void* stream) {
     return rank_impl(ix, false, queries, nq, lims, nullptr, thresholds, strict, filter_of_query, nullptr, out_counts,
                      on_device, stream);
+}
+
+// ---- document rank search (search_group_rank.hip) -----------------------------------------------------------------------------
+extern "C" int vr_index_group_rank_search_stats(vr_index_t ix, int64_t* out3, int32_t reset) {
+    if (!ix || !out3) return fail(VR_ERR_INVALID, "NULL argument");
+    return read_counters<unsigned long long, 3>(ix, ix->grnk.state, 0, out3, reset);
+}
+
+// What vr_index_rank_groups (groups set) and vr_index_count_groups_range (thresholds set) share: per block with pairs the
+// (masked) score rows, their group maxima, the bars of the block's pairs and their counts.  Pairs, bars, group maxima and
+// counters are the search's own; the grouping and the filters are read.  Nothing is stored.
+static int group_rank_impl(vr_index_t ix, bool ranks, const float* queries, int32_t nq, const int64_t* lims, const int64_t* groups,
+                           const float* thresholds, int32_t strict, const int32_t* filter_of_query, float* out_scores,
+                           int64_t* out_rows, int64_t* out_counts, int32_t on_device, void* stream) {
+    if (!ix || !lims || nq < 0 || (nq > 0 && !queries)) return fail(VR_ERR_INVALID, "bad arguments");
+    if (!range_dim_ok(ix->dim)) return fail(VR_ERR_INVALID, "dim %d unsupported", ix->dim);
+    if (lims[0] != 0) return fail(VR_ERR_INVALID, "lims[0] = %lld must be 0", (long long)lims[0]);
+    for (int32_t q = 0; q < nq; ++q)
+        if (lims[q + 1] < lims[q]) return fail(VR_ERR_INVALID, "lims[%d] = %lld decreases", (int)q + 1, (long long)lims[q + 1]);
+    const int64_t np = lims[nq];
+    if (np >= ((int64_t)1 << 31)) return fail(VR_ERR_INVALID, "%lld pairs: too many for one call", (long long)np);
+    if (np > 0 && (!out_counts || (ranks ? !groups || !out_scores || !out_rows : !thresholds))) return fail(VR_ERR_INVALID, "bad arguments");
+    if (ix->grp.n_groups <= 0 || ix->n <= 0) return fail(VR_ERR_STATE, "no grouping set for the rows of the index (vr_index_set_groups)");
+    if (ranks) {
+        for (int64_t i = 0; i < np; ++i)
+            if (groups[i] < 0 || groups[i] >= ix->grp.n_groups)
+                return fail(VR_ERR_INVALID, "groups[%lld] = %lld outside [0, %lld)", (long long)i, (long long)groups[i], (long long)ix->grp.n_groups);
+    } else {
+        for (int64_t i = 0; i < np; ++i)
+            if (!std::isfinite(thresholds[i])) return fail(VR_ERR_INVALID, "thresholds[%lld] = %g is not finite", (long long)i, (double)thresholds[i]);
+    }
+    if (filter_of_query) VRCHK(check_filter_ids(ix, filter_of_query, nq, on_device, "filter_of_query"));
+    if (np == 0) return VR_OK;                    // no pair: no launch
+    VRCHK(set_dev(ix->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (!ix->grnk.state.p) VRCHK(ix->grnk.state.alloc(GRNK_WORDS * 8));
+    const int ng = (int)ix->grp.n_groups;
+    const int64_t ldS = pad256l(ix->n), ldB = (ix->grp.n_groups + 63) / 64 * 64;
+    const int64_t qblk = 256;                     // one fp32 score row per query, as on the deep path
+    const float* q32 = nullptr;
+    VRCHK(stage_queries(ix, queries, nq, pad256l(std::min<int64_t>(nq, qblk)), on_device, s, &q32));
+    const int* foq = nullptr;
+    if (filter_of_query) VRCHK(stage_input(ix->flt.ids, filter_of_query, (size_t)nq, on_device, s, &foq));
+    // the pairs: their query inside its block and their target group or threshold, 4 bytes each
+    std::vector<int> pq((size_t)np), pv(ranks ? (size_t)np : 0);
+    for (int32_t q = 0; q < nq; ++q)
+        for (int64_t i = lims[q]; i < lims[q + 1]; ++i) pq[(size_t)i] = (int)(q % qblk);
+    if (ranks) for (int64_t i = 0; i < np; ++i) pv[(size_t)i] = (int)groups[i];
+    VRCHK(ix->grnk.q.reserve((size_t)np * 4));
+    VRCHK(ix->grnk.v.reserve((size_t)np * 4));
+    VRCHK(ix->grnk.bar.reserve((size_t)np * 8));
+    VRCHK(ix->grnk.eps.reserve((size_t)np * 4));
+    HIPCHK(hipMemcpyAsync(ix->grnk.q.p, pq.data(), (size_t)np * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ix->grnk.v.p, ranks ? (const void*)pv.data() : (const void*)thresholds, (size_t)np * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));              // (the host arrays are free from here on)
+    float* os = nullptr; int64_t* orow = nullptr; int64_t* oc = nullptr;
+    if (ranks) {
+        VRCHK(stage_output(ix->os, out_scores, (size_t)np, on_device, &os));
+        VRCHK(stage_output(ix->oi, out_rows, (size_t)np, on_device, &orow));
+    }
+    VRCHK(stage_output(ix->grnk.out, out_counts, (size_t)np, on_device, &oc));
+    VRCHK(ix->sbuf.reserve((size_t)qblk * ldS * 4));
+    VRCHK(ix->grnk.B.reserve((size_t)qblk * ldB * 4));
+    float* S = ix->sbuf.as<float>();
+    for (int64_t q0 = 0; q0 < nq; q0 += qblk) {
+        const int nb = (int)std::min<int64_t>(qblk, nq - q0);
+        const int64_t p0 = lims[q0], pn = lims[q0 + nb] - p0;
+        if (pn == 0) continue;                    // a block without pairs: no launch
+        GroupRankArgs p{};
+        p.a = block_view(ix, q32, q0, nb, 1, true);                        // (the band is defined by the error model)
+        p.goff = ix->grp.off.as<int>(); p.n_groups = ng;
+        p.B = ix->grnk.B.as<float>(); p.ldB = (size_t)ldB;
+        p.pair_query = ix->grnk.q.as<int>() + p0;
+        p.pair_group = ranks ? ix->grnk.v.as<int>() + p0 : nullptr;
+        p.pair_thr = ranks ? nullptr : ix->grnk.v.as<float>() + p0;
+        p.strict = strict ? 1 : 0;
+        p.filter_of_query = foq ? foq + q0 : nullptr;
+        p.n_filters = (int)ix->flt.n_filters;
+        p.bars = ix->grnk.bar.as<unsigned long long>() + p0;
+        p.bar_eps = ix->grnk.eps.as<float>() + p0;
+        p.out_scores = ranks ? os + p0 : nullptr;
+        p.out_rows = ranks ? reinterpret_cast<long long*>(orow) + p0 : nullptr;
+        p.out_counts = reinterpret_cast<unsigned long long*>(oc) + p0;
+        p.stats = ix->grnk.state.as<unsigned long long>();
+        VRCHK(score_block(ix, q32, q0, nb, ldS, nullptr, s));
+        if (foq) VRCHK(mask_block(ix, foq + q0, nb, ldS, nullptr, nullptr, 0, s));
+        HIPCHK(launch_group_max(S, (size_t)ldS, p.goff, ng, ix->grnk.B.as<float>(), p.ldB, nb, nullptr, 0, s));
+        HIPCHK(launch_group_rank_bars(p, S, (size_t)ldS, nb, pn, s));
+        HIPCHK(launch_group_rank_count(p, S, (size_t)ldS, nb, pn, s));
+    }
+    if (ranks) {
+        VRCHK(return_output(out_scores, os, (size_t)np, on_device, s));
+        VRCHK(return_output(out_rows, orow, (size_t)np, on_device, s));
+    }
+    VRCHK(return_output(out_counts, oc, (size_t)np, on_device, s));
+    if (!on_device) HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
+}
+
+extern "C" int vr_index_rank_groups(vr_index_t ix, const float* queries, int32_t nq, const int64_t* lims, const int64_t* groups,
+                                    const int32_t* filter_of_query, float* out_scores, int64_t* out_rows, int64_t* out_ranks,
+                                    int32_t on_device, void* stream) {
+    return group_rank_impl(ix, true, queries, nq, lims, groups, nullptr, 0, filter_of_query, out_scores, out_rows, out_ranks, on_device, stream);
+}
+
+extern "C" int vr_index_count_groups_range(vr_index_t ix, const float* queries, int32_t nq, const int64_t* lims,
+                                           const float* thresholds, int32_t strict, const int32_t* filter_of_query,
+                                           int64_t* out_counts, int32_t on_device, void* stream) {
+    return group_rank_impl(ix, false, queries, nq, lims, nullptr, thresholds, strict, filter_of_query, nullptr, nullptr, out_counts, on_device,
+                           stream);
 }
 
 // ---- windowed search (search_window.hip) --------------------------------------------------------------------------------------

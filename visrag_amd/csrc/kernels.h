@@ -493,6 +493,31 @@ hipError_t launch_group_window_edges(const GroupWindowArgs& p, int nq_block, hip
 hipError_t launch_group_window_rescore(const GroupWindowArgs& p, const float* S, size_t ldS, int nq_block, hipStream_t s);
 // ranks [offset, offset + k) of the rewritten rows -> a.out_scores / a.out_ids / out_groups, (-inf, -1, -1) past the present groups
 hipError_t launch_group_window_select(const GroupWindowArgs& p, int nq_block, hipStream_t s);
+// ---- document rank search (search_group_rank.hip): the exact rank, score and best row of named groups, exact counts of groups
+// against thresholds, under filters; a pair = (query, bar)
+struct GroupRankArgs {
+    SearchArgs a;                    // the block's view, as RankSearchArgs': index_f32, n_docs, dim, q_f32, nq and a valid error model
+    const int* goff;                 // [n_groups + 1] first row of every group; goff[n_groups] = n_docs
+    int n_groups;
+    const float* B; size_t ldB;      // [nq][ldB] group maxima of the (masked) score rows: launch_group_max; only read
+    const int* pair_query;           // [pairs] device: the pair's query inside the block, 0 .. nq - 1
+    const int* pair_group;           // [pairs] device: the target group of a rank, in [0, n_groups) ... (exactly one of the two is set)
+    const float* pair_thr;           // [pairs] device: ... or the threshold of a count, finite
+    int strict;                      // counts: 0 = groups with E >= t, 1 = groups with E > t
+    const int* filter_of_query;      // [nq] device or null, as RankSearchArgs': the score rows have been masked; an entry outside
+    int n_filters;                   //   [-1, n_filters): a rank's tail triple, a count of 0
+    unsigned long long* bars;        // [pairs] scratch: make_key(target's E_g, g), or the threshold's bits
+    float* bar_eps;                  // [pairs] scratch: query_eps of the pair's query (NaN: a dead pair, its outputs are final)
+    float* out_scores;               // [pairs] ranks: E_g of the target (-inf: absent); counts: unused
+    long long* out_rows;             // [pairs] ranks: the target's best row (-1: absent); counts: unused
+    unsigned long long* out_counts;  // [pairs] groups ahead of the bar (a rank's absent target: -1)
+    unsigned long long* stats;       // [0] pairs [1] band groups re-scored (a rank's target among them) [2] fp32 row dots
+};
+// the bars (and score / best row of the targets) of the block's pairs from p.B and S; their counts start at 0, or stay at -1
+hipError_t launch_group_rank_bars(const GroupRankArgs& p, const float* S, size_t ldS, int nq_block, int64_t n_pairs, hipStream_t s);
+// out_counts[pair] += groups of B row pair_query[pair] ahead of the pair's bar, the band around it decided by fp32 re-scoring of
+// the band groups' rows; B and S are only read
+hipError_t launch_group_rank_count(const GroupRankArgs& p, const float* S, size_t ldS, int nq_block, int64_t n_pairs, hipStream_t s);
 // ---- fused search (search_multi.hip): the k rows of largest max (or min) fp32 score over a group of sub-queries
 struct MultiSearchArgs {
     SearchArgs a;                    // the block's view, as WindowSearchArgs': q_f32 and nq are the block's SUB-QUERIES (whole groups, <= 256),

@@ -418,6 +418,54 @@ def explain(knowledge_base_path: str, query, pages, documents=None, index=None, 
             index.close()
 
 
+@torch.no_grad()
+def explain_documents(knowledge_base_path: str, query, wanted, documents=None, index=None, names=None, model=None, tokenizer=None):
+    """Where named DOCUMENTS stand for a question: -> [(score, best page name, rank)] for the document names `wanted` (one name:
+    one triple; None if the base does not exist).  The ranking is `retrieve_documents`': a document scores as its best page
+    does, `rank` is its position among the documents (0 = the best; HipIndex.rank_groups: exact, however deep) —
+    `retrieve_documents(topk)` returns the document iff rank < topk, through the same page.  With `documents=[...]` the rank is
+    among those documents, as `retrieve_documents(documents=...)` ranks them (one filter, set for this question); a wanted
+    document outside them is not in that ranking and gives (-inf, None, -1).  A name no page belongs to raises ValueError.
+    `query` is the question (`model`, `tokenizer` encode it) or its embedding ([dim] or [1, dim]).  Pass `index, names =
+    load_document_base(path)` to keep the index resident; an index of your own must hold every document's pages adjacently."""
+    if not os.path.exists(knowledge_base_path):
+        return None
+    own = index is None
+    if own:
+        index, names = load_document_base(knowledge_base_path, model.encoder.device if model is not None else None)
+    try:
+        n = len(index)
+        one = isinstance(wanted, str)
+        want = [wanted] if one else list(wanted)
+        docs = [doc_of_page(nm) for nm in names[:n]]
+        order, offsets, doc_names = group_rows(docs)
+        if not np.array_equal(order, np.arange(len(order))):
+            raise ValueError("the pages of a document are not adjacent in this index: load it with load_document_base()")
+        group_of = {d: g for g, d in enumerate(doc_names)}
+        unknown = [d for d in list(want) + list(documents or ()) if d not in group_of]
+        if unknown:
+            raise ValueError(f"no page of the base belongs to {unknown[0]!r}")
+        if not index.n_groups and n:
+            index.set_groups(offsets)
+        if isinstance(query, str):
+            q = encode(model, tokenizer, [QUERY_INSTRUCTION + query])
+        else:
+            q = np.asarray(query.detach().cpu() if isinstance(query, torch.Tensor) else query, dtype=np.float32).reshape(1, -1)
+        if not want:
+            return []
+        foq = None
+        if documents is not None:
+            index.set_filters(label_filters(docs, [set(documents)]))
+            foq = 0
+        sc, rows, rk = index.rank_groups(q, np.asarray([[group_of[d] for d in want]], dtype=np.int64), filter_of_query=foq)
+        sc, rows, rk = (x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in (sc, rows, rk))
+        out = [(float(s), names[int(r)] if r >= 0 else None, int(k)) for s, r, k in zip(sc[0], rows[0], rk[0])]
+        return out[0] if one else out
+    finally:
+        if own:
+            index.close()
+
+
 def duplicate_pages(knowledge_base_path: str, threshold: float, index=None, names=None, batch: int = 256) -> Optional[List[List[str]]]:
     """Groups of page names whose embeddings are chained by a dot product >= `threshold` (None if the base does not exist): the
     near-duplicate pages of a knowledge base, found before they reach the generator.  The base's own rows are the queries of a

@@ -24,6 +24,9 @@ window and a query's positives and leaves the hard negatives a trainer wants ("r
 The document window search (HipIndex.search_groups_window) ranks documents under a row filter: `collection_filters` builds such
 filters from a label per DOCUMENT ("the ten best documents of this collection").
 
+The document rank search (HipIndex.rank_groups) returns the rank of named documents, -1 for one the filter leaves no page of:
+`never_retrieved` turns that into a rank the three metrics above count as a miss.
+
 The fused search (HipIndex.search_multi) ranks rows by the max or the min of their scores over a group of sub-queries:
 `group_rows` of the sub-queries' labels gives its `lims`, and `fuse_runs` states what per-sub-query top-k lists can and cannot
 say about that ranking — the workaround the fused search replaces.
@@ -247,6 +250,20 @@ def recall_at(ranks, lims, ks) -> np.ndarray:
             n += 1
             out += (r[None, :] < ks[:, None]).sum(1) / len(r)
     return out / n if n else out
+
+
+NEVER_RETRIEVED = 1 << 62       # a rank no cut-off reaches
+
+
+def never_retrieved(ranks) -> np.ndarray:
+    """int64, shaped as `ranks`: the ranks of HipIndex.rank_groups with every -1 — a document the query's filter leaves no page
+    of, which is not in the ranking — replaced by NEVER_RETRIEVED (2^62).  `reciprocal_ranks` / `mrr_from_ranks` / `recall_at`
+    refuse negative ranks; with this they treat an absent positive as not retrieved: it misses every recall@k, falls outside
+    every `cutoff`, and without a cut-off adds a reciprocal rank below 1e-18."""
+    r = np.array(ranks, dtype=np.int64)
+    if r.size and r.min() < -1:
+        raise ValueError("ranks are positions, or -1 for a document that is not in the ranking")
+    return np.where(r < 0, np.int64(NEVER_RETRIEVED), r)
 
 
 def window_negatives(ids, positives_of_query, count: int) -> np.ndarray:

@@ -665,6 +665,58 @@ class HipIndex:
         """Document window searches since the last reset: queries, documents of the bands re-scored, fp32 page dot products."""
         return self._stats3(self.lib.vr_index_group_window_search_stats, ("queries", "documents", "page_dots"), reset)
 
+    # ---- document rank search (include/visrag_hip.h: vr_index_rank_groups / vr_index_count_groups_range) ----
+    def _group_rank_call(self, queries, flat, lims, shape, filter_of_query, strict):
+        """vr_index_rank_groups (int64 targets) -> (scores, best rows, ranks), or vr_index_count_groups_range (float32 thresholds)
+        -> counts"""
+        q, cuda = self._queries(queries)
+        nq, n = int(q.shape[0]), len(flat)
+        ranks = flat.dtype == np.int64
+        keep, fptr = (None, C.c_void_p(None)) if filter_of_query is None else self._filter_of_query(q, filter_of_query)
+        if cuda:
+            outs = [torch.empty(n, dtype=d, device=q.device) for d in (torch.float32, torch.int64, torch.int64)]
+            ptrs = [C.c_void_p(x.data_ptr()) for x in [q] + outs]
+        else:
+            outs = [np.empty(n, dtype=d) for d in (np.float32, np.int64, np.int64)]
+            ptrs = [C.c_void_p(x.ctypes.data) for x in [q] + outs]
+        stream = C.c_void_p(_stream_ptr(self.device))
+        if ranks:
+            _lib.check(self.lib.vr_index_rank_groups(self._h, ptrs[0], nq, C.c_void_p(lims.ctypes.data), C.c_void_p(flat.ctypes.data),
+                                                     fptr, ptrs[1], ptrs[2], ptrs[3], 1 if cuda else 0, stream), "vr_index_rank_groups")
+        else:
+            _lib.check(self.lib.vr_index_count_groups_range(self._h, ptrs[0], nq, C.c_void_p(lims.ctypes.data),
+                                                            C.c_void_p(flat.ctypes.data), 1 if strict else 0, fptr, ptrs[3],
+                                                            1 if cuda else 0, stream), "vr_index_count_groups_range")
+        del keep
+        return tuple(x.reshape(shape) for x in outs) if ranks else outs[2].reshape(shape)
+
+    def rank_groups(self, queries, groups, lims=None, filter_of_query=None):
+        """Where the named documents stand (include/visrag_hip.h: vr_index_rank_groups) -> (scores f32, best rows i64, ranks i64)
+        shaped as `groups`.  The ranking is `search_groups_window`'s: a group (`set_groups`) is present if the query's filter
+        allows one of its rows, it scores as its best ALLOWED row does, that row — the lowest among equals — is its best row, and
+        present groups rank score descending, then lower group first.  The rank is the number of present groups ahead, so a group
+        of rank r is entry r - o of `search_groups_window(q, o, k, f)` for every o <= r < o + k, with the same score bits and the
+        same best row.  A target the filter leaves no row of is NOT in the ranking: it gets (-inf, -1, -1) — unlike `rank_rows`,
+        where a forbidden row gets the position it would take: a group's score is defined over its allowed rows, an absent group
+        has none (`documents.never_retrieved` turns the -1 into a rank no cut-off reaches).  `groups`: host ints, [nq] (one
+        target per query), [nq][T], or flat with `lims` [nq + 1]; duplicates allowed.  `filter_of_query` as in `search_filtered`,
+        None = no filter.  cuda queries -> cuda tensors, numpy / cpu -> numpy."""
+        flat, lims, shape = self._pairs(groups, lims, int(queries.shape[0]), np.int64, "groups")
+        return self._group_rank_call(queries, flat, lims, shape, filter_of_query, False)
+
+    def count_groups_range(self, queries, thresholds, lims=None, filter_of_query=None, strict: bool = False):
+        """How many documents reach a threshold (include/visrag_hip.h: vr_index_count_groups_range) -> counts i64 shaped as
+        `thresholds` (a scalar: [nq]): present groups whose score — that of their best allowed row — is >= t, with `strict` > t.
+        `thresholds`: a scalar, [nq], [nq][T], or flat with `lims`; finite; -0.0 counts as +0.0.  `filter_of_query` as in
+        `search_filtered`.  cuda queries -> a cuda tensor, numpy / cpu -> numpy."""
+        flat, lims, shape = self._pairs(thresholds, lims, int(queries.shape[0]), np.float32, "thresholds")
+        return self._group_rank_call(queries, flat, lims, shape, filter_of_query, strict)
+
+    def group_rank_search_stats(self, reset: bool = False) -> Dict[str, int]:
+        """Document rank searches and counts since the last reset: (query, bar) pairs, documents of the error bands re-scored (a
+        rank's own target among them), fp32 page dot products."""
+        return self._stats3(self.lib.vr_index_group_rank_search_stats, ("pairs", "documents", "page_dots"), reset)
+
     # ---- fused search (include/visrag_hip.h: vr_index_search_multi) ----
     def search_multi(self, queries, lims, k: int, fuse: str = "max", filter_of_group=None):
         """The k rows of largest fused score per group of sub-queries (include/visrag_hip.h: vr_index_search_multi) -> (scores

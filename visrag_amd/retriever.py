@@ -283,6 +283,67 @@ def retrieve_documents_filtered(args, topk: int, doc_of: Callable[[str], str], l
     return scores, pages
 
 
+def rank_documents(args, docs_of_query, doc_of: Callable[[str], str], label_of_doc: Optional[Callable[[str], object]] = None,
+                   labels_of_query: Optional[Callable[[str], Optional[set]]] = None, index_factory: Optional[Callable] = None
+                   ) -> Dict[str, Dict[str, Tuple[float, Optional[str], int]]]:
+    """Where named DOCUMENTS stand, over the same pickle shards: `docs_of_query` is {qid: [doc, ...]} (qrels that name a PDF, not a
+    page) or a callable qid -> docs; -> {qid: {doc: (score, best_page_id, rank)}}.  The corpus rows are PAGES, `doc_of(page_id)`
+    the document of a page; a document scores as its best page does and `rank` is its position (0 = the best) in the ranking of
+    ALL documents, however deep it lies (HipIndex.rank_groups: exact counts, no run of fixed depth) — the ranking
+    `retrieve_documents` / `retrieve_documents_filtered` cut at a k.  With `label_of_doc` and `labels_of_query` given, query `qid`
+    ranks only the documents whose label is in `labels_of_query(qid)` (None = every document), one filter per distinct label
+    set; a named document outside them is not in that ranking: (-inf, None, -1) — `documents.never_retrieved` turns such ranks
+    into what `mrr_from_ranks` / `recall_at` count as a miss.  Without labels there is no filter.  A document no page belongs to
+    raises ValueError; a query without documents gets {}.
+
+    Replicated form only, like retrieve_documents: every rank holds the whole corpus, all shards in ONE index."""
+    if (label_of_doc is None) != (labels_of_query is None):
+        raise ValueError("label_of_doc and labels_of_query go together")
+    make_index = index_factory or HipIndex
+    queries, qids, _ = _load_queries(args)
+    corpus_parts = list_shards(args.output_dir, "corpus")
+    if len(corpus_parts) == 0:
+        raise ValueError("No pre-computed document embeddings found")
+    reps, page_ids = [], []
+    for p in corpus_parts:
+        r, i = read_shard(p)
+        if len(i):
+            reps.append(np.asarray(r, dtype=np.float32))
+            page_ids.extend(i)
+    get = docs_of_query if callable(docs_of_query) else (lambda q: docs_of_query.get(q, ()))
+    wanted = [list(dict.fromkeys(get(q))) for q in qids]                  # a document named twice counts once
+    lims = np.concatenate([np.zeros(1, np.int64), np.cumsum([len(w) for w in wanted])]).astype(np.int64)
+    flat = [d for w in wanted for d in w]
+    if not flat:
+        return {q: {} for q in qids}
+    order, offsets, docs = group_rows([doc_of(i) for i in page_ids])
+    group_of = {d: g for g, d in enumerate(docs)}
+    missing = [d for d in flat if d not in group_of]
+    if missing:
+        raise ValueError(f"no such document in the corpus shards: {missing[0]}")
+    ix = make_index(queries.shape[1], len(page_ids), _device_index(args))
+    ix.add(np.concatenate(reps)[order])
+    ix.set_groups(offsets)
+    filter_of_query = None
+    if labels_of_query is not None:
+        sets: List[Optional[frozenset]] = []
+        which: Dict[Optional[frozenset], int] = {}
+        filter_of_query = np.empty(len(qids), dtype=np.int32)
+        for qi, q in enumerate(qids):
+            labels = labels_of_query(q)
+            key = None if labels is None else frozenset(labels)
+            if key not in which:
+                which[key] = len(sets)
+                sets.append(key)
+            filter_of_query[qi] = which[key]
+        ix.set_filters(collection_filters(offsets, [label_of_doc(d) for d in docs], sets))
+    sc, rows, rk = ix.rank_groups(queries, np.asarray([group_of[d] for d in flat], dtype=np.int64), lims, filter_of_query)
+    ix.close()
+    return {q: {d: (float(sc[j]), page_ids[int(order[int(rows[j])])] if rows[j] >= 0 else None, int(rk[j]))
+                for j, d in zip(range(lims[qi], lims[qi + 1]), wanted[qi])}
+            for qi, q in enumerate(qids)}
+
+
 def retrieve_range(args, threshold: float, max_per_query: Optional[int] = None, index_factory: Optional[Callable] = None
                    ) -> Dict[str, Dict[str, float]]:
     """A run of variable depth over the same pickle shards: this rank's query shard(s) against ALL corpus shards, every row
