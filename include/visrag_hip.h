@@ -425,9 +425,9 @@ int vr_index_search_diverse(vr_index_t ix, const float* queries, int32_t nq, int
  * else of the index changes but the range search's own counters, which have counted the blocks that ran.
  *   The call synchronises the stream, because the sizes of its result are host values: once per block of 256 queries and
  * once at the end.  It leaves every state the other searches read alone and counts in none of their statistics.
- * Not offered: sorted output (sort a segment by score on the caller's side: the Python wrapper does), groups (a thresholded
- * document search is vr_index_search_groups plus a cut), corpus-sharded ranks (a range result over shards is the union of the
- * shards' results).  An exact count without the rows: vr_index_count_range below. */
+ * Not offered: sorted output (sort a segment by score on the caller's side: the Python wrapper does), corpus-sharded ranks
+ * (a range result over shards is the union of the shards' results).  An exact count without the rows: vr_index_count_range
+ * below; documents in the place of rows: vr_index_search_groups_range. */
 int vr_index_search_range(vr_index_t ix, const float* queries, int32_t nq,
                           const float* thresholds,          /* [nq] */
                           const int32_t* filter_of_query,   /* NULL: no filter for any query */
@@ -539,8 +539,8 @@ int vr_index_window_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
  * VR_ERR_STATE.  On the device an out-of-range filter index allows nothing: a row of tails.  nq == 0: VR_OK, nothing is
  * launched.  Nothing is stored between calls.  A host caller's call synchronises the stream.  The call counts in no other
  * search's statistics and leaves every state the other searches read alone; vr_index_search_groups is untouched by it.
- * Ranks of named documents: vr_index_rank_groups below.  Not offered: a thresholded (range) document search, documents under the fused search or MMR,
- * corpus-sharded ranks (merge per-shard pages on the host), k > 1000 in one call, a k per query. */
+ * Ranks of named documents: vr_index_rank_groups below; every document above a threshold: vr_index_search_groups_range.
+ * Not offered: documents under the fused search or MMR, corpus-sharded ranks (merge per-shard pages on the host), k > 1000 in one call, a k per query. */
 int vr_index_search_groups_window(vr_index_t ix, const float* queries, int32_t nq,
                                   const int64_t* offsets,           /* host [nq] */
                                   int32_t k,
@@ -581,7 +581,7 @@ int vr_index_group_window_search_stats(vr_index_t ix, int64_t* out3, int32_t res
  * VR_ERR_STATE.  On the device an out-of-range filter index allows nothing: ranks (-inf, -1, -1), counts 0.  Zero pairs: VR_OK,
  * nothing is launched; a block of 256 queries without pairs is skipped.  Nothing is stored between calls.  A host caller's call
  * synchronises the stream.  The calls count in no other search's statistics and leave every state the other searches read
- * alone.  Not offered: a thresholded (range) list of documents, document ranks under the fused search or MMR, corpus-sharded
+ * alone.  Not offered: document ranks under the fused search or MMR, corpus-sharded
  * ranks inside the library (add per-shard counts), several bars of one query per read of its group maxima. */
 int vr_index_rank_groups(vr_index_t ix, const float* queries, int32_t nq,
                          const int64_t* lims,              /* host [nq + 1] */
@@ -599,6 +599,54 @@ int vr_index_count_groups_range(vr_index_t ix, const float* queries, int32_t nq,
 /* Document rank searches and counts since the last reset: out3 = {pairs, band groups re-scored (a rank's own target among
  * them), fp32 row dot products} — 64-bit counters in device memory. */
 int vr_index_group_rank_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
+/* ---- document range search: every group at or above a score threshold, under filters, exact ---- */
+/* vr_index_search_groups_range: WHICH documents reach a threshold.  The semantics are those of vr_index_search_groups_window and
+ * vr_index_count_groups_range: for query q with filter f (filter_of_query NULL or an entry of -1: every row) a group g
+ * (vr_index_set_groups) is PRESENT if f allows at least one of its rows; its score is E_g = the largest e_i over its ALLOWED rows
+ * — e_i the library's one fp32 dot product, the bits vr_index_search returns for that pair — its best row the lowest allowed row
+ * id that attains E_g.  The result of query q is the SET of present groups with E_g >= thresholds[q], an fp32 compare: -0.0 counts
+ * as +0.0.  Its size is exactly vr_index_count_groups_range's non-strict count for the same threshold and filter, its entries
+ * carry the score bits and best rows of vr_index_search_groups_window / vr_index_rank_groups.  Nothing is cut at a k.
+ *   Layout: CSR, as vr_index_search_range's.  out_lims [nq + 1] int64: entries out_lims[q] .. out_lims[q + 1] - 1 are query q's,
+ * out_lims[0] = 0, out_lims[nq] = *total; inside a query the entries are in ASCENDING GROUP (deterministic, no sort).  queries
+ * [nq][dim] float32, thresholds [nq] float32, filter_of_query [nq] int32 and out_lims are all host or all device per `on_device`;
+ * `total` is always a host pointer.
+ *   Ownership: scores, best rows and groups are written to device buffers the library owns — the document range search's own,
+ * not vr_index_search_range's: either result survives the other search.  They stay valid until the next document range search,
+ * vr_index_reset, vr_index_add, vr_index_set_groups, vr_index_remove, vr_index_update or vr_index_destroy.
+ * vr_index_group_range_results copies the first n entries (n <= the last total) to the caller's arrays (out_scores [n] float32,
+ * out_rows [n] int64, out_groups [n] int64, host or device per `on_device`); n larger than the last total, or no stored result:
+ * VR_ERR_STATE.
+ *   Exactness: with |b_i - e_i| <= eps over the allowed rows (the error model of vr_index_set_search_eps) the masked group
+ * maximum B_g of the bf16 MFMA scores lies within eps of E_g, because max is 1-Lipschitz: E_g >= t implies B_g >= t - eps.  Inside
+ * such a group only a row with b_i >= B_g - 2 eps can attain E_g.  Exactly those rows of exactly those groups are re-scored in
+ * fp32 and the groups with E_g >= t kept; every edge is rounded outward by one ulp.  No candidate margin, no widening, no flagged
+ * query; a query costs what its band holds; with certification off the default error model defines the band, so the result is
+ * exact in every setting of vr_index_set_search_eps.
+ *   Checks, all before any launch, the outputs and the previous result untouched: NULL pointers, nq < 1, max_total < 1, an
+ * unsupported dim (as vr_index_search_range), a HOST threshold that is NaN or +-inf, a HOST filter_of_query entry outside
+ * [-1, n_filters): VR_ERR_INVALID; no grouping set for the rows present (vr_index_add / vr_index_remove drop it), or
+ * filter_of_query given while no filters are set: VR_ERR_STATE.  On the device a non-finite threshold or an out-of-range filter
+ * index yields an empty segment, and nothing is read for that query.  An empty index: all-zero lims and total 0 without a launch.
+ *   Capacity: if the running total would exceed max_total the call returns VR_ERR_CAPACITY (the text names the first block of
+ * 256 queries that overran); the previous result is gone and nothing else of the index changes but this search's own counters,
+ * which have counted the blocks that ran.
+ *   The call synchronises the stream, because the sizes of its result are host values: once per block of 256 queries and once
+ * at the end.  It counts in no other search's statistics and leaves every state the other searches read alone.
+ * Not offered: sorted output (the Python wrapper sorts a segment by score, then group), corpus-sharded ranks (a result over
+ * shards of whole documents is the union of the shards' results), documents under the fused search or MMR. */
+int vr_index_search_groups_range(vr_index_t ix, const float* queries, int32_t nq,
+                                 const float* thresholds,          /* [nq] */
+                                 const int32_t* filter_of_query,   /* NULL: no filter for any query */
+                                 int64_t max_total,
+                                 int64_t* out_lims,                /* [nq + 1] */
+                                 int64_t* total,                   /* host */
+                                 int32_t on_device, void* stream);
+int vr_index_group_range_results(vr_index_t ix, float* out_scores, int64_t* out_rows, int64_t* out_groups, int64_t n,
+                                 int32_t on_device, void* stream);
+/* Document range searches since the last reset: out3 = {queries, band groups re-scored, fp32 row dot products} — 64-bit counters
+ * in device memory. */
+int vr_index_group_range_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
 /* ---- fused search: the top-k rows by max or min over a group of sub-queries ---- */
 /* vr_index_search_multi: one question, several vectors (reformulations, the last turns of a chat, the sub-questions of a
  * multi-hop question).  The sub-queries are a flat [n_sub][dim] float32 array; group g holds sub-queries lims[g] ..

@@ -122,6 +122,9 @@ SIGNATURES = {
     "vr_index_rank_groups": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "vr_index_count_groups_range": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp]),
     "vr_index_group_rank_search_stats": (C.c_int, [_vp, C.POINTER(_i64), _i32]),
+    "vr_index_search_groups_range": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i64, _vp, C.POINTER(_i64), _i32, _vp]),
+    "vr_index_group_range_results": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "vr_index_group_range_search_stats": (C.c_int, [_vp, C.POINTER(_i64), _i32]),
     "vr_index_search_multi": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
     "vr_index_multi_search_stats": (C.c_int, [_vp, C.POINTER(_i64), _i32]),
     "vr_index_search_diverse": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _i32, _vp]),

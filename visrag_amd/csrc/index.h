@@ -1,5 +1,5 @@
 // The search index's handle and the host helpers its three files share: index.hip (life cycle, vr_index_search*), index_searches.hip
-// (the score-row searches: groups, filtered, range, rank, window, document window, document rank, fused, diverse) and index_rows.hip (editing in place).
+// (the score-row searches: groups, filtered, range, rank, window, document window, document rank, document range, fused, diverse) and index_rows.hip (editing in place).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,7 +12,7 @@
 constexpr int CERT_WORDS = 32, CERT_FLAG = 2, CERT_FLAG2 = 3, CERT_STATS = 4, CERT_NSTATS = 6;   // (the two flag counters are consecutive: cleared together)
 constexpr int GRP_STATS = 2, GRP_LIST = 8, GRP_WORDS = GRP_LIST + 256;
 constexpr int FLT_STATS = 2, FLT_LIST = 8, FLT_WORDS = FLT_LIST + 256;
-constexpr int RNG_TOTAL = 3, RNG_WORDS = RNG_TOTAL + 1, RNK_WORDS = 3, WIN_WORDS = 3, MUL_WORDS = 3, GWIN_WORDS = 3, GRNK_WORDS = 3;   // (u64 words; 0..2 the counters)
+constexpr int RNG_TOTAL = 3, RNG_WORDS = RNG_TOTAL + 1, RNK_WORDS = 3, WIN_WORDS = 3, MUL_WORDS = 3, GWIN_WORDS = 3, GRNK_WORDS = 3, GRNG_TOTAL = 3, GRNG_WORDS = GRNG_TOTAL + 1;   // (u64 words; 0..2 the counters)
 
 struct vr_index_s {
     int device = 0, dim = 0;
@@ -29,7 +29,7 @@ struct vr_index_s {
     float eps_rel = -2.f;             // -2: the rigorous data-dependent default; >= 0: the caller's eps_rel |q| max|d|; else off
     // Every search below has state of its own in a member of its own: no other search reads any of it (the filters excepted:
     // range, rank, windowed, fused and diversified search read flt.bits / flt.count and stage their filter ids in flt.ids; the
-    // document window and document rank searches do too, and read grp.off / grp.n_groups: the grouping is the index's, not a search's).
+    // document window, document rank and document range searches do too, and read grp.off / grp.n_groups: the grouping is the index's, not a search's).
     struct {                          // grouped search (vr_index_search_groups, search_group.hip)
         int64_t n_groups = 0;         // 0: no grouping set (vr_index_add / vr_index_reset drop it)
         DevBuf off, B, out, state;    // int first rows [n_groups + 1] | group maxima [256][ldB] | staged out_groups | int words: [0] flag
@@ -52,6 +52,16 @@ struct vr_index_s {
                                       // scan per query | u64 words: [0..2] the counters of vr_index_range_search_stats, [3] a block's total
         int64_t* host_total = nullptr;    // pinned host word: the block total as the host reads it
     } rng;
+    struct {                          // document range search (vr_index_search_groups_range, search_group_range.hip): its result and
+                                      // state, laid out like rng
+        DevBuf scores, rows, groups;  // the result: f32 scores [cap] | int64 best rows [cap] | int64 groups [cap], valid entries [0, total)
+        int64_t cap = 0, total = -1;  // -1: no result (none yet, vr_index_reset / _add / _set_groups / _remove / _update, or the last
+                                      // document range search failed)
+        DevBuf thr, lims, cnt, off, B, R, state;   // staged thresholds / lims of a host caller | int groups kept [256][slots] | int their
+                                      // exclusive scan per query | group maxima [256][ldB], rewritten in place | int best rows [256][ldB]
+                                      // | u64 words: [0..2] the counters of vr_index_group_range_search_stats, [3] a block's total
+        int64_t* host_total = nullptr;    // pinned host word: the block total as the host reads it
+    } grng;
     struct {                          // rank search (vr_index_rank_rows / vr_index_count_range, search_rank.hip): no stored result
         DevBuf q, v, bar, eps, state; // int query of every pair | int target rows or f32 thresholds | u64 bars | f32 eps per pair | u64
                                       // words: [0..2] the counters of vr_index_rank_search_stats

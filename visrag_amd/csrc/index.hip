@@ -26,6 +26,7 @@ extern "C" int vr_index_destroy(vr_index_t ix) {
     (void)hipSetDevice(ix->device);
     (void)hipDeviceSynchronize();
     if (ix->rng.host_total) (void)hipHostFree(ix->rng.host_total);
+    if (ix->grng.host_total) (void)hipHostFree(ix->grng.host_total);
     for (hipEvent_t e : ix->prof_ev) if (e) (void)hipEventDestroy(e);
     if (ix->huge_seen) (void)hipHostFree(ix->huge_seen);
     delete ix;                                    // every DevBuf frees what it owns
@@ -41,6 +42,7 @@ extern "C" int vr_index_reset(vr_index_t ix) {
     ix->grp.n_groups = 0;
     ix->flt.n_filters = 0;
     ix->rng.total = -1;
+    ix->grng.total = -1;
     if (ix->huge_seen) *ix->huge_seen = 0;
     return VR_OK;
 }
@@ -65,6 +67,7 @@ extern "C" int vr_index_add(vr_index_t ix, const float* reps, int64_t n, int32_t
     ix->n += n;
     ix->grp.n_groups = 0;             // the grouping described the rows that were there
     ix->flt.n_filters = 0;            // ... and so did the filters
+    ix->grng.total = -1;              // ... and the document range result names groups of that grouping
     return VR_OK;
 }
 

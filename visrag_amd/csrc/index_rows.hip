@@ -105,6 +105,7 @@ extern "C" int vr_index_remove(vr_index_t ix, const int64_t* ids, int64_t n, int
     ix->n = new_n;
     ix->grp.n_groups = 0;             // a removal can empty a group: the caller sets the offsets of the rows that remain
     ix->rng.total = -1;               // its ids name rows as they were
+    ix->grng.total = -1;              // ... and so do the document range result's
     if (ix->huge_seen) *ix->huge_seen = 0;
     VRCHK(recompute_error_model(ix, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -131,6 +132,7 @@ extern "C" int vr_index_update(vr_index_t ix, const int64_t* ids, const float* r
     HIPCHK(launch_rows_update(src, ix->edit.ids.as<int>(), n, ix->dim, ix->f32.as<float>(), ix->bf16.p, s));
     VRCHK(recompute_error_model(ix, s));          // (an overwritten row may have been the largest)
     ix->rng.total = -1;
+    ix->grng.total = -1;
     if (ix->huge_seen) *ix->huge_seen = 0;
     HIPCHK(hipStreamSynchronize(s));
     return VR_OK;

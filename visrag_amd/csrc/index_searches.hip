@@ -1,5 +1,5 @@
 // The searches of the index that work on score rows (vr_index_search_groups / _filtered / _range / _rank_rows / _count_range /
-// _window / _groups_window / _rank_groups / _count_groups_range / _multi / _diverse of include/visrag_hip.h, with what sets them up and their counters).  Each of them: every argument
+// _window / _groups_window / _rank_groups / _count_groups_range / _groups_range / _multi / _diverse of include/visrag_hip.h, with what sets them up and their counters).  Each of them: every argument
 // check first, then per block of <= 256 queries the block's score rows S[q][row] (index.h: score_block, the deep path's bf16
 // MFMA GEMM), with filters the mask (mask_block: disallowed columns -> -inf), then the search's own kernels.  Scratch (query
 // staging, score rows, staged outputs, the staged filter ids) is shared between the searches; what a search keeps is its member
@@ -18,6 +18,7 @@ extern "C" int vr_index_set_groups(vr_index_t ix, const int64_t* group_offsets, 
     VRCHK(set_dev(ix->device));
     HIPCHK(hipDeviceSynchronize());               // (a grouped search in flight reads the offsets)
     ix->grp.n_groups = 0;
+    ix->grng.total = -1;              // the document range result names groups of the grouping that was
     std::vector<int> off((size_t)n_groups + 1);   // rows are 32-bit (vr_index_create)
     for (int64_t g = 0; g <= n_groups; ++g) off[(size_t)g] = (int)group_offsets[g];
     VRCHK(ix->grp.off.reserve(off.size() * 4));
@@ -481,6 +482,140 @@ extern "C" int vr_index_count_groups_range(vr_index_t ix, const float* queries, 
                                            int64_t* out_counts, int32_t on_device, void* stream) {
     return group_rank_impl(ix, false, queries, nq, lims, nullptr, thresholds, strict, filter_of_query, nullptr, nullptr, out_counts, on_device,
                            stream);
+}
+
+// ---- document range search (search_group_range.hip) ---------------------------------------------------------------------------
+extern "C" int vr_index_group_range_search_stats(vr_index_t ix, int64_t* out3, int32_t reset) {
+    if (!ix || !out3) return fail(VR_ERR_INVALID, "NULL argument");
+    return read_counters<unsigned long long, 3>(ix, ix->grng.state, 0, out3, reset);
+}
+
+// room for `need` entries of the document range result, the first `keep` of which are kept (what earlier blocks of the call packed)
+static int group_range_reserve(vr_index_t ix, int64_t need, int64_t keep, int64_t max_total, hipStream_t s) {
+    if (need <= ix->grng.cap && ix->grng.scores.p && ix->grng.rows.p && ix->grng.groups.p) return VR_OK;
+    const int64_t cap = std::max<int64_t>(std::min(max_total, std::max(need, 2 * ix->grng.cap)), std::max<int64_t>(need, 1));
+    DevBuf ns, nr, ng;
+    VRCHK(ns.reserve((size_t)cap * 4));
+    VRCHK(nr.reserve((size_t)cap * 8));
+    VRCHK(ng.reserve((size_t)cap * 8));
+    if (keep > 0) {
+        HIPCHK(hipMemcpyAsync(ns.p, ix->grng.scores.p, (size_t)keep * 4, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(nr.p, ix->grng.rows.p, (size_t)keep * 8, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(ng.p, ix->grng.groups.p, (size_t)keep * 8, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    ix->grng.scores = std::move(ns);
+    ix->grng.rows = std::move(nr);
+    ix->grng.groups = std::move(ng);
+    ix->grng.cap = cap;
+    return VR_OK;
+}
+
+// Every document at or above a query's threshold, under its filter: result, group maxima, best rows, counts, offsets and counters
+// are the document range search's own; the grouping and the filters are read.
+extern "C" int vr_index_search_groups_range(vr_index_t ix, const float* queries, int32_t nq, const float* thresholds,
+                                            const int32_t* filter_of_query, int64_t max_total, int64_t* out_lims, int64_t* total,
+                                            int32_t on_device, void* stream) {
+    if (!ix || !queries || !thresholds || !out_lims || !total || nq < 1) return fail(VR_ERR_INVALID, "bad arguments");
+    if (max_total < 1) return fail(VR_ERR_INVALID, "max_total=%lld must be at least 1", (long long)max_total);
+    if (!range_dim_ok(ix->dim)) return fail(VR_ERR_INVALID, "dim %d unsupported", ix->dim);
+    if (!on_device)
+        for (int32_t q = 0; q < nq; ++q)
+            if (!std::isfinite(thresholds[q])) return fail(VR_ERR_INVALID, "thresholds[%d] = %g is not finite", (int)q, (double)thresholds[q]);
+    if (ix->n > 0 && ix->grp.n_groups <= 0) return fail(VR_ERR_STATE, "no grouping set for the rows of the index (vr_index_set_groups)");
+    if (filter_of_query) VRCHK(check_filter_ids(ix, filter_of_query, nq, on_device, "filter_of_query"));
+    VRCHK(set_dev(ix->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (ix->n == 0) {                             // no row, no document: no launch
+        if (on_device) {
+            HIPCHK(hipMemsetAsync(out_lims, 0, ((size_t)nq + 1) * 8, s));
+            HIPCHK(hipStreamSynchronize(s));
+        } else {
+            std::fill(out_lims, out_lims + nq + 1, (int64_t)0);
+        }
+        *total = 0;
+        ix->grng.total = 0;
+        return VR_OK;
+    }
+    if (!ix->grng.state.p) VRCHK(ix->grng.state.alloc(GRNG_WORDS * 8));
+    if (!ix->grng.host_total && hipHostMalloc((void**)&ix->grng.host_total, 64, hipHostMallocDefault) != hipSuccess) {
+        ix->grng.host_total = nullptr;
+        return fail(VR_ERR_HIP, "hipHostMalloc");
+    }
+    ix->grng.total = -1;                          // from here on the previous result is gone
+    const int ng = (int)ix->grp.n_groups;
+    const int64_t ldS = pad256l(ix->n), ldB = (ix->grp.n_groups + 63) / 64 * 64, slots = range_scan_slots(ix->grp.n_groups);
+    const int64_t qblk = 256;                     // one fp32 score row per query, as on the deep path
+    const float* q32 = nullptr;
+    VRCHK(stage_queries(ix, queries, nq, pad256l(std::min<int64_t>(nq, qblk)), on_device, s, &q32));
+    const float* thr = nullptr;
+    const int* foq = nullptr;
+    int64_t* lims = nullptr;
+    VRCHK(stage_input(ix->grng.thr, thresholds, (size_t)nq, on_device, s, &thr));
+    if (filter_of_query) VRCHK(stage_input(ix->flt.ids, filter_of_query, (size_t)nq, on_device, s, &foq));
+    VRCHK(stage_output(ix->grng.lims, out_lims, (size_t)nq + 1, on_device, &lims));
+    VRCHK(ix->sbuf.reserve((size_t)qblk * ldS * 4));
+    VRCHK(ix->grng.B.reserve((size_t)qblk * ldB * 4));
+    VRCHK(ix->grng.R.reserve((size_t)qblk * ldB * 4));
+    VRCHK(ix->grng.cnt.reserve((size_t)qblk * slots * 4));
+    VRCHK(ix->grng.off.reserve((size_t)qblk * slots * 4));
+    VRCHK(group_range_reserve(ix, std::min<int64_t>(max_total, 65536), 0, max_total, s));
+    float* S = ix->sbuf.as<float>();
+    int64_t* block_total = ix->grng.state.as<int64_t>() + GRNG_TOTAL;
+    int64_t base = 0;
+    for (int64_t q0 = 0; q0 < nq; q0 += qblk) {
+        const int nb = (int)std::min<int64_t>(qblk, nq - q0);
+        GroupRangeArgs p{};
+        p.a = block_view(ix, q32, q0, nb, 1, true);                        // (the band is defined by the error model)
+        p.goff = ix->grp.off.as<int>(); p.n_groups = ng;
+        p.B = ix->grng.B.as<float>(); p.ldB = (size_t)ldB;
+        p.R = ix->grng.R.as<int>();
+        p.thresholds = thr + q0;
+        p.filter_of_query = foq ? foq + q0 : nullptr;
+        p.n_filters = (int)ix->flt.n_filters;
+        p.stats = ix->grng.state.as<unsigned long long>();
+        VRCHK(score_block(ix, q32, q0, nb, ldS, nullptr, s));
+        if (foq) VRCHK(mask_block(ix, foq + q0, nb, ldS, nullptr, nullptr, 0, s));
+        HIPCHK(launch_group_max(S, (size_t)ldS, p.goff, ng, p.B, p.ldB, nb, nullptr, 0, s));
+        HIPCHK(launch_group_range_rescore(p, S, (size_t)ldS, nb, ix->grng.cnt.as<int>(), s));
+        HIPCHK(launch_range_scan(ix->grng.cnt.as<int>(), ix->grng.off.as<int>(), ix->grp.n_groups, nb, base, q0 == 0 ? 1 : 0, lims + q0,
+                                 block_total, s));
+        // the size of the block's result is a host value: capacity check, growth of the result arrays
+        HIPCHK(hipMemcpyAsync(ix->grng.host_total, block_total, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        const int64_t bt = *ix->grng.host_total;
+        if (bt < 0 || base + bt > max_total)
+            return fail(VR_ERR_CAPACITY,
+                        "document range result exceeds max_total=%lld in query block %lld (queries %lld..%lld): %lld entries by then",
+                        (long long)max_total, (long long)(q0 / qblk), (long long)q0, (long long)(q0 + nb - 1), (long long)(base + bt));
+        VRCHK(group_range_reserve(ix, base + bt, base, max_total, s));
+        p.out_scores = ix->grng.scores.as<float>(); p.out_rows = ix->grng.rows.as<int64_t>(); p.out_groups = ix->grng.groups.as<int64_t>();
+        if (bt > 0)
+            HIPCHK(launch_group_range_pack(p, nb, ix->grng.cnt.as<int>(), ix->grng.off.as<int>(), lims + q0, s));
+        base += bt;
+    }
+    VRCHK(return_output(out_lims, lims, (size_t)nq + 1, on_device, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *total = base;
+    ix->grng.total = base;
+    return VR_OK;
+}
+
+extern "C" int vr_index_group_range_results(vr_index_t ix, float* out_scores, int64_t* out_rows, int64_t* out_groups, int64_t n,
+                                            int32_t on_device, void* stream) {
+    if (!ix || n < 0 || (n > 0 && (!out_scores || !out_rows || !out_groups))) return fail(VR_ERR_INVALID, "bad arguments");
+    if (ix->grng.total < 0) return fail(VR_ERR_STATE, "no document range result (vr_index_search_groups_range)");
+    if (n > ix->grng.total)
+        return fail(VR_ERR_STATE, "%lld entries asked for, the last document range search found %lld", (long long)n, (long long)ix->grng.total);
+    if (n == 0) return VR_OK;
+    VRCHK(set_dev(ix->device));
+    hipStream_t s = (hipStream_t)stream;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    HIPCHK(hipMemcpyAsync(out_scores, ix->grng.scores.p, (size_t)n * 4, kind, s));
+    HIPCHK(hipMemcpyAsync(out_rows, ix->grng.rows.p, (size_t)n * 8, kind, s));
+    HIPCHK(hipMemcpyAsync(out_groups, ix->grng.groups.p, (size_t)n * 8, kind, s));
+    if (!on_device) HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
 }
 
 // ---- windowed search (search_window.hip) --------------------------------------------------------------------------------------

@@ -518,6 +518,28 @@ hipError_t launch_group_rank_bars(const GroupRankArgs& p, const float* S, size_t
 // out_counts[pair] += groups of B row pair_query[pair] ahead of the pair's bar, the band around it decided by fp32 re-scoring of
 // the band groups' rows; B and S are only read
 hipError_t launch_group_rank_count(const GroupRankArgs& p, const float* S, size_t ldS, int nq_block, int64_t n_pairs, hipStream_t s);
+// ---- document range search (search_group_range.hip): every group whose score reaches the query's threshold, under filters, CSR,
+// ascending group
+struct GroupRangeArgs {
+    SearchArgs a;                    // the block's view, as RangeSearchArgs': index_f32, n_docs, dim, q_f32, nq and a valid error model
+    const int* goff;                 // [n_groups + 1] first row of every group; goff[n_groups] = n_docs
+    int n_groups;
+    float* B; size_t ldB;            // [nq][ldB] group maxima of the (masked) score rows: launch_group_max; rewritten in place
+    int* R;                          // [nq][ldB] scratch: the best row of every band group
+    const float* thresholds;         // [nq] device: the threshold of every query of the block; not finite: an empty segment
+    const int* filter_of_query;      // [nq] device or null, as RangeSearchArgs': the score rows have been masked; an entry outside
+    int n_filters;                   //   [-1, n_filters): an empty segment
+    float* out_scores; int64_t* out_rows; int64_t* out_groups;   // the result arrays of the whole call (the pack writes at lims[q] +
+                                     // scanned offset)
+    unsigned long long* stats;       // [0] queries [1] band groups re-scored [2] fp32 row dots
+};
+// B rows [0, nq_block): the band B >= t - eps re-scored in place (E_g where E_g >= t, else -inf; R: its best row); counts
+// [nq_block][range_scan_slots(n_groups)] = groups kept per 1024; S (the masked score rows the maxima came from) is only read.
+// The scan between the two launches is launch_range_scan with n_groups in the place of n_docs
+hipError_t launch_group_range_rescore(const GroupRangeArgs& p, const float* S, size_t ldS, int nq_block, int* counts, hipStream_t s);
+// (B[g], R[g], g) of every group with B >= t -> p.out_scores / p.out_rows / p.out_groups [lims[q] + offs ...], in group order
+hipError_t launch_group_range_pack(const GroupRangeArgs& p, int nq_block, const int* counts, const int* offs, const int64_t* lims,
+                                   hipStream_t s);
 // ---- fused search (search_multi.hip): the k rows of largest max (or min) fp32 score over a group of sub-queries
 struct MultiSearchArgs {
     SearchArgs a;                    // the block's view, as WindowSearchArgs': q_f32 and nq are the block's SUB-QUERIES (whole groups, <= 256),

@@ -13,6 +13,8 @@
                                                                (no reference counterpart: its top-k is pages)
     (`documents=[...]`: only those documents are ranked; `offset=n`: the next page of documents — HipIndex.search_groups_window)
   * `retrieve_above(knowledge_base_path, query, min_score, ...)` -> EVERY page at or above a score, best first
+  * `retrieve_documents_above(knowledge_base_path, query, min_score, ...)` -> the best page of EVERY document at or above a
+                                                               score, best document first (HipIndex.search_groups_range)
   * `duplicate_pages(knowledge_base_path, threshold, ...)` -> groups of near-duplicate pages
                                                                (HipIndex.search_range; no reference counterpart either)
   * `explain(knowledge_base_path, query, pages, ...)` -> the score and the rank of named pages for a question: "why was my page
@@ -372,6 +374,55 @@ def retrieve_above(knowledge_base_path: str, query, min_score: float, model, tok
         if max_pages is not None:
             sc, ids = sc[:max_pages], ids[:max_pages]
         paths = [os.path.join(knowledge_base_path, names[int(i)]) for i in ids]
+        scores = [float(s) for s in sc]
+    if own:
+        index.close()
+    return (paths, scores) if return_scores else paths
+
+
+@torch.no_grad()
+def retrieve_documents_above(knowledge_base_path: str, query, min_score: float, model, tokenizer, index=None, names=None,
+                             documents=None, max_documents: Optional[int] = None, return_scores: bool = False):
+    """Paths of the best page of EVERY document whose score is at least `min_score`, best document first (None if the base does
+    not exist): `retrieve_above` one level up — a document scores as its best page does, so a relevant 300-page report is one
+    entry, and an irrelevant one is none (HipIndex.search_groups_range: the exact fp32 answer, no cap at a k).  Documents are the
+    `doc_of_page` of the page names; pass `index, names = load_document_base(path)` to keep the index resident, as in
+    `retrieve_documents`.  `documents`: only those documents, each by its best page (one filter, set for this question); a name
+    no page carries raises ValueError.  `max_documents`, if given, cuts the sorted result.  `query` is the question, or its
+    embedding ([dim] or [1, dim])."""
+    if not os.path.exists(knowledge_base_path):
+        return None
+    own = index is None
+    if own:
+        index, names = load_document_base(knowledge_base_path, model.encoder.device if model is not None else None)
+    elif not index.n_groups and len(index):
+        order, offsets, _ = group_rows([doc_of_page(n) for n in names])
+        if not np.array_equal(order, np.arange(len(order))):
+            raise ValueError("the pages of a document are not adjacent in this index: load it with load_document_base()")
+        index.set_groups(offsets)
+    n = len(index)
+    if isinstance(query, str):
+        q = encode(model, tokenizer, [QUERY_INSTRUCTION + query])
+    else:
+        q = np.asarray(query.detach().cpu() if isinstance(query, torch.Tensor) else query, dtype=np.float32).reshape(1, -1)
+    mask = None
+    if documents is not None:
+        docs = [doc_of_page(nm) for nm in names[:n]]
+        wanted = set(documents)
+        unknown = sorted(wanted - set(docs))
+        if unknown:
+            raise ValueError(f"no page of the base belongs to {unknown[0]!r}" + (f" (and {len(unknown) - 1} more)" if len(unknown) > 1 else ""))
+        mask = label_filters(docs, [wanted])
+    if n == 0 or (mask is not None and not mask.any()) or (max_documents is not None and max_documents <= 0):
+        paths, scores = [], []
+    else:
+        if mask is not None:
+            index.set_filters(mask)
+        _, sc, rows, _ = index.search_groups_range(q, float(min_score), None if mask is None else 0)
+        sc, rows = (x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in (sc, rows))
+        if max_documents is not None:
+            sc, rows = sc[:max_documents], rows[:max_documents]
+        paths = [os.path.join(knowledge_base_path, names[int(i)]) for i in rows]
         scores = [float(s) for s in sc]
     if own:
         index.close()

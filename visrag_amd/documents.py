@@ -27,6 +27,9 @@ filters from a label per DOCUMENT ("the ten best documents of this collection").
 The document rank search (HipIndex.rank_groups) returns the rank of named documents, -1 for one the filter leaves no page of:
 `never_retrieved` turns that into a rank the three metrics above count as a miss.
 
+The document range search (HipIndex.search_groups_range) returns every document at or above a threshold as a CSR result (lims,
+scores, best rows, groups): `split_document_ranges` cuts it into per-query triples.
+
 The fused search (HipIndex.search_multi) ranks rows by the max or the min of their scores over a group of sub-queries:
 `group_rows` of the sub-queries' labels gives its `lims`, and `fuse_runs` states what per-sub-query top-k lists can and cannot
 say about that ranking — the workaround the fused search replaces.
@@ -134,6 +137,16 @@ def split_ranges(lims, scores, ids) -> List[Tuple[np.ndarray, np.ndarray]]:
     if len(lims) < 1 or lims[0] != 0 or (np.diff(lims) < 0).any() or lims[-1] != len(ids) or len(scores) != len(ids):
         raise ValueError("lims must start at 0, be non-decreasing and end at the number of entries")
     return [(scores[lims[q]:lims[q + 1]], ids[lims[q]:lims[q + 1]]) for q in range(len(lims) - 1)]
+
+
+def split_document_ranges(lims, scores, rows, groups) -> List[Tuple[np.ndarray, np.ndarray, np.ndarray]]:
+    """A document range result (HipIndex.search_groups_range) -> [(scores, best rows, groups)] per query: views of entries
+    lims[q] .. lims[q + 1] - 1."""
+    lims = np.asarray(lims, dtype=np.int64).reshape(-1)
+    scores, rows, groups = np.asarray(scores), np.asarray(rows), np.asarray(groups)
+    if len(lims) < 1 or lims[0] != 0 or (np.diff(lims) < 0).any() or lims[-1] != len(groups) or len(scores) != len(groups) or len(rows) != len(groups):
+        raise ValueError("lims must start at 0, be non-decreasing and end at the number of entries")
+    return [(scores[lims[q]:lims[q + 1]], rows[lims[q]:lims[q + 1]], groups[lims[q]:lims[q + 1]]) for q in range(len(lims) - 1)]
 
 
 def duplicate_groups(lims, ids, n_rows: int) -> List[List[int]]:

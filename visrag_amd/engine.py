@@ -717,6 +717,74 @@ class HipIndex:
         rank's own target among them), fp32 page dot products."""
         return self._stats3(self.lib.vr_index_group_rank_search_stats, ("pairs", "documents", "page_dots"), reset)
 
+    # ---- document range search (include/visrag_hip.h: vr_index_search_groups_range) ----
+    def search_groups_range(self, queries, threshold, filter_of_query=None, max_total: Optional[int] = None, sort: bool = True):
+        """Every document whose score reaches the query's threshold, under its filter (include/visrag_hip.h:
+        vr_index_search_groups_range) -> (lims int64 [nq + 1], scores f32 [total], best rows i64 [total], groups i64 [total]):
+        entries lims[q] .. lims[q + 1] - 1 are query q's; cuda in -> cuda out, numpy / cpu in -> numpy out.  The semantics are
+        `search_groups_window`'s and `count_groups_range`'s: a group (`set_groups`) is present if the query's filter allows one of
+        its rows, it scores as its best ALLOWED row does, that row — the lowest among equals — is its best row; the result is every
+        present group with score >= t (-0.0 counts as +0.0), so `np.diff(lims)` is `count_groups_range(queries, t, ...)`.
+        `threshold`: a scalar or one per query.  `filter_of_query` as in `search_filtered`, None = no filter (none need to be
+        set).  `max_total=None`: min(nq * groups, 2 ** 26) entries, at least 1; a larger result raises (VR_ERR_CAPACITY).
+        `sort=True`: every segment in `search_groups_window`'s order, score descending, then lower group first; `sort=False`: the
+        ABI's ascending-group order."""
+        q, cuda = self._queries(queries)
+        nq = int(q.shape[0])
+        if isinstance(threshold, torch.Tensor):
+            threshold = threshold.detach().cpu().numpy()
+        thr = np.array(threshold, dtype=np.float32).reshape(-1)          # (a copy: the caller's array may be read-only)
+        thr = np.full(nq, thr[0], dtype=np.float32) if thr.size == 1 else np.ascontiguousarray(thr)
+        if len(thr) != nq:
+            raise ValueError(f"{len(thr)} thresholds for {nq} queries")
+        keep, fptr = (None, C.c_void_p(None)) if filter_of_query is None else self._filter_of_query(q, filter_of_query)
+        if max_total is None:
+            max_total = max(1, min(nq * self.n_groups, 2 ** 26))
+        total = C.c_int64(0)
+        stream = C.c_void_p(_stream_ptr(self.device))
+        if cuda:
+            thr_d = torch.from_numpy(thr).to(q.device)
+            lims = torch.empty(nq + 1, dtype=torch.int64, device=q.device)
+            ptrs = (q.data_ptr(), thr_d.data_ptr(), lims.data_ptr())
+        else:
+            lims = np.empty(nq + 1, dtype=np.int64)
+            ptrs = (q.ctypes.data, thr.ctypes.data, lims.ctypes.data)
+        _lib.check(self.lib.vr_index_search_groups_range(self._h, C.c_void_p(ptrs[0]), nq, C.c_void_p(ptrs[1]), fptr, int(max_total),
+                                                         C.c_void_p(ptrs[2]), C.byref(total), 1 if cuda else 0, stream),
+                   "vr_index_search_groups_range")
+        n = int(total.value)
+        if cuda:
+            scores = torch.empty(n, dtype=torch.float32, device=q.device)
+            rows = torch.empty(n, dtype=torch.int64, device=q.device)
+            groups = torch.empty(n, dtype=torch.int64, device=q.device)
+            optrs = (scores.data_ptr(), rows.data_ptr(), groups.data_ptr())
+        else:
+            scores, rows, groups = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int64)
+            optrs = (scores.ctypes.data, rows.ctypes.data, groups.ctypes.data)
+        _lib.check(self.lib.vr_index_group_range_results(self._h, C.c_void_p(optrs[0]), C.c_void_p(optrs[1]), C.c_void_p(optrs[2]), n,
+                                                         1 if cuda else 0, stream), "vr_index_group_range_results")
+        del keep
+        if sort and n > 1:
+            # the ranking's order of floats is that of the keys' orderable bits (-0.0 < +0.0); groups ascend already
+            if cuda:
+                bits = scores.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+                key = torch.where(bits >= 0x80000000, 0xFFFFFFFF - bits, bits + 0x80000000)
+                seg = torch.repeat_interleave(torch.arange(nq, device=q.device), lims[1:] - lims[:-1])
+                o1 = torch.sort(key, descending=True, stable=True)[1]
+                order = o1[torch.sort(seg[o1], stable=True)[1]]
+            else:
+                bits = scores.view(np.uint32).astype(np.int64)
+                key = np.where(bits >= 0x80000000, 0xFFFFFFFF - bits, bits + 0x80000000)
+                seg = np.repeat(np.arange(nq), np.diff(lims))
+                order = np.lexsort((groups, -key, seg))
+            scores, rows, groups = scores[order], rows[order], groups[order]
+        return lims, scores, rows, groups
+
+    def group_range_search_stats(self, reset: bool = False) -> Dict[str, int]:
+        """Document range searches since the last reset: queries, documents of the error bands re-scored (everything that can
+        reach its threshold), fp32 page dot products."""
+        return self._stats3(self.lib.vr_index_group_range_search_stats, ("queries", "documents", "page_dots"), reset)
+
     # ---- fused search (include/visrag_hip.h: vr_index_search_multi) ----
     def search_multi(self, queries, lims, k: int, fuse: str = "max", filter_of_group=None):
         """The k rows of largest fused score per group of sub-queries (include/visrag_hip.h: vr_index_search_multi) -> (scores

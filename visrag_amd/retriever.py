@@ -344,6 +344,67 @@ def rank_documents(args, docs_of_query, doc_of: Callable[[str], str], label_of_d
             for qi, q in enumerate(qids)}
 
 
+def retrieve_documents_range(args, threshold: float, doc_of: Callable[[str], str], label_of_doc: Optional[Callable[[str], object]] = None,
+                             labels_of_query: Optional[Callable[[str], Optional[set]]] = None, max_per_query: Optional[int] = None,
+                             index_factory: Optional[Callable] = None
+                             ) -> Tuple[Dict[str, Dict[str, float]], Dict[str, Dict[str, str]]]:
+    """A run of variable depth over DOCUMENTS, over the same pickle shards: retrieve_range one level up.  The corpus rows are
+    PAGES, `doc_of(page_id)` the document of a page; a document scores as its best page does, and query `qid` gets every document
+    whose score is at least `threshold` (HipIndex.search_groups_range: the exact fp32 answer, not cut at a k).
+    -> ({qid: {doc: score}}, {qid: {doc: best_page_id}}), a query's entries best first (score descending, then the order the
+    documents first appear in the shards); the first dict goes to `save_as_trec` as it is.  With `label_of_doc` and
+    `labels_of_query` given, query `qid` sees only the documents whose label is in `labels_of_query(qid)` (None = every document),
+    one filter per distinct label set, as in retrieve_documents_filtered; without them there is no filter.  `max_per_query`, if
+    given, keeps a query's best entries only.
+
+    Replicated form only, like retrieve_documents: every rank holds the whole corpus, all shards in ONE index — a document's
+    pages may straddle the shards."""
+    if (label_of_doc is None) != (labels_of_query is None):
+        raise ValueError("label_of_doc and labels_of_query go together")
+    make_index = index_factory or HipIndex
+    queries, qids, _ = _load_queries(args)
+    corpus_parts = list_shards(args.output_dir, "corpus")
+    if len(corpus_parts) == 0:
+        raise ValueError("No pre-computed document embeddings found")
+    reps, page_ids = [], []
+    for p in corpus_parts:
+        r, i = read_shard(p)
+        if len(i):
+            reps.append(np.asarray(r, dtype=np.float32))
+            page_ids.extend(i)
+    scores: Dict[str, Dict[str, float]] = {q: {} for q in qids}
+    pages: Dict[str, Dict[str, str]] = {q: {} for q in qids}
+    if not page_ids or (max_per_query is not None and max_per_query <= 0):
+        return scores, pages
+    order, offsets, docs = group_rows([doc_of(i) for i in page_ids])
+    ix = make_index(queries.shape[1], len(page_ids), _device_index(args))
+    ix.add(np.concatenate(reps)[order])
+    ix.set_groups(offsets)
+    filter_of_query = None
+    if labels_of_query is not None:
+        sets: List[Optional[frozenset]] = []
+        which: Dict[Optional[frozenset], int] = {}
+        filter_of_query = np.empty(len(qids), dtype=np.int32)
+        for qi, q in enumerate(qids):
+            wanted = labels_of_query(q)
+            key = None if wanted is None else frozenset(wanted)
+            if key not in which:
+                which[key] = len(sets)
+                sets.append(key)
+            filter_of_query[qi] = which[key]
+        ix.set_filters(collection_filters(offsets, [label_of_doc(d) for d in docs], sets))
+    lims, sc, rows, groups = ix.search_groups_range(queries, float(threshold), filter_of_query)
+    ix.close()
+    for qi, q in enumerate(qids):
+        a, b = int(lims[qi]), int(lims[qi + 1])
+        if max_per_query is not None:
+            b = min(b, a + int(max_per_query))
+        for s_, r, g in zip(sc[a:b], rows[a:b], groups[a:b]):
+            scores[q][docs[int(g)]] = float(s_)
+            pages[q][docs[int(g)]] = page_ids[int(order[int(r)])]
+    return scores, pages
+
+
 def retrieve_range(args, threshold: float, max_per_query: Optional[int] = None, index_factory: Optional[Callable] = None
                    ) -> Dict[str, Dict[str, float]]:
     """A run of variable depth over the same pickle shards: this rank's query shard(s) against ALL corpus shards, every row
