@@ -267,7 +267,15 @@ int vr_index_size(vr_index_t ix, int64_t* n);
  *   queries [nq][dim] float32;  out_scores [nq][k] float32;  out_ids [nq][k] int64
  * (all host or all device per `on_device`).  If the index holds fewer than k rows the
  * tail is filled with score -inf, id -1.  k = 1..1000: up to 26 on the fused sweep (the
- * throughput path; --retrieve_depth 10 in eval.sh), deeper runs on GEMM + radix select. */
+ * throughput path; --retrieve_depth 10 in eval.sh), deeper runs on GEMM + radix select.
+ * NaN, the same on every route (sweeps, merges, deep path, band pass, exact pass): a row whose
+ * fp32 score against a query is NaN never ranks for that query — a row with a NaN component is
+ * returned for no query, the other rows rank as if it were not there.  A query with a NaN
+ * component gets (-inf, -1) in every slot, and key 0 in every slot from vr_index_search_keys;
+ * the other queries of the batch are unaffected.  Both are counted by vr_index_search_stats
+ * like any other query.  Infinite components, and finite ones whose fp32 or bf16 products or
+ * sums overflow, are outside this contract: their scores may be inf or NaN on one route and
+ * not on another. */
 int vr_index_search(vr_index_t ix, const float* queries, int32_t nq, int32_t k,
                     float* out_scores, int64_t* out_ids, int32_t on_device, void* stream);
 /* The error model of the certification.  Default (NaN restores it): the rigorous bound for the

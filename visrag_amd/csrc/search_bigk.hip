@@ -40,9 +40,9 @@ __global__ __launch_bounds__(256) void bigk_select_kernel(SearchArgs p, const fl
     __syncthreads();                                                    // (LDS of the previous slot is free)
 
     // ---- 2. the kp best bf16 scores' rows in row order (search_select.h)
-    const KthKey kth = select_kth(row, n_docs, kp, L);
+    const KthKey kth = select_kth<true>(row, n_docs, kp, L);       // (a NaN score sorts last: never a candidate before a number)
     const unsigned T = kth.T;
-    gather_ordered(row, n_docs, T, kp - kth.need_eq, kth.need_eq, SEL_CAND, L);
+    gather_ordered<true>(row, n_docs, T, kp - kth.need_eq, kth.need_eq, SEL_CAND, L);
     // ---- 3. exact fp32 re-scoring, sort
     const int nv = dim >> 2;
     f32x4 qv[MERGE_MAXV];
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void bigk_select_kernel(SearchArgs p, const fl
         for (int c = wave; c < m; c += 4) {
             const int id = L.cand[c];
             const float a = wave_sum(dot_lane(qv, p.index_f32 + (size_t)id * dim, nv, lane));
-            if (lane == 0) L.keys[c] = make_key(a, (uint32_t)id);
+            if (lane == 0) L.keys[c] = make_key_ranked(a, (uint32_t)id);
         }
         __syncthreads();
         block_bitonic_desc(L.keys, n2, tid, 256);
@@ -64,14 +64,16 @@ __global__ __launch_bounds__(256) void bigk_select_kernel(SearchArgs p, const fl
     if (!exact && (p.eps_data || p.eps_rel >= 0.f)) {
         int what = 0;
         float tau = -INFINITY;
-        if (kp < n_docs) {
+        // (fewer than k numbers among the re-scored kp: NaN scores sort last, so the candidates hold EVERY row that ranks — a NaN
+        // query, or an index with fewer than k rows free of NaN — and the result stands as it is)
+        if (kp < n_docs && L.keys[k - 1] != KEY_NONE) {
             const float eps = query_eps(p, qv);
             tau = key_score(L.keys[k - 1]) - eps;                       // kp >= k here (kp < n_docs => kp = k + margin)
             if (!(orderable_f32(T) < tau)) {
                 // every row whose bf16 score is >= tau (strictly above the key just below tau's)
                 __syncthreads();
                 const unsigned tk = f32_orderable(tau);
-                const int m = gather_ordered(row, n_docs, tk ? tk - 1u : 0u, 0, 0, SEL_CAND, L);
+                const int m = gather_ordered<true>(row, n_docs, tk ? tk - 1u : 0u, 0, 0, SEL_CAND, L);
                 __syncthreads();
                 if (m <= SEL_CAND && m >= kp) { rescore_sort(m); kp = m; what = 1; }
                 else what = 2;

@@ -33,6 +33,11 @@ __device__ __forceinline__ uint64_t make_key(float score, uint32_t id) {
     return ((uint64_t)f32_orderable(score) << 32) | (uint32_t)(~id);
 }
 constexpr uint64_t KEY_NONE = 0;    // below every real key (score -inf, id 0xffffffff -> ~ = 0 ...)
+// the key of a row RE-SCORED from a score row that may hold NaN (the deep path, the exact pass): a NaN fp32 score never ranks
+// (include/visrag_hip.h: vr_index_search) — without this a positive NaN is the largest key there is
+__device__ __forceinline__ uint64_t make_key_ranked(float score, uint32_t id) {
+    return score == score ? make_key(score, id) : KEY_NONE;
+}
 
 __device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
     const uint32_t lo = __shfl_xor((uint32_t)v, m, 64);

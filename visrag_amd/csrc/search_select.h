@@ -31,12 +31,20 @@ __device__ __forceinline__ int flag_slots(const int* count, int sub, int max_slo
     return count ? min(max(count[0] - sub, 0), max_slots) : max_slots;
 }
 
+// the order-preserving key of a value to select by.  NAN_LOW (the plain search, search_bigk.hip): a NaN sorts below every
+// number, -inf included — key 0, which no number has — so that the kp best are numbers as long as there are kp of them
+template <bool NAN_LOW>
+__device__ __forceinline__ unsigned select_key(float v) {
+    return NAN_LOW && !(v == v) ? 0u : f32_orderable(v);
+}
+
 struct KthKey {
     unsigned T;                             // key of the kp-th largest value
     int need_eq;                            // how many keys == T belong to the kp best (lowest positions first); kp - need_eq keys are > T
 };
 
 // Called by the whole workgroup, 1 <= kp <= n; the LDS must be free (barrier) when it is entered.
+template <bool NAN_LOW = false>
 __device__ __forceinline__ KthKey select_kth(const float* __restrict__ vals, int n, int kp, SelectLds& L) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid == 0) { L.prefix = 0u; L.rank = kp; }
@@ -48,7 +56,7 @@ __device__ __forceinline__ KthKey select_kth(const float* __restrict__ vals, int
         const int top = shift + (pass < 2 ? 11 : 10);                // the pass's digit: key bits [shift, top)
         const unsigned prefix = L.prefix, mask = top < 32 ? ~0u << top : 0u;    // ... the bits above it: fixed by the passes before
         for (int i = tid; i < n; i += 256) {
-            const unsigned key = f32_orderable(vals[i]);
+            const unsigned key = select_key<NAN_LOW>(vals[i]);
             if ((key & mask) == prefix) atomicAdd(&L.hist[(key >> shift) & (nb - 1)], 1u);
         }
         __syncthreads();
@@ -84,6 +92,7 @@ __device__ __forceinline__ KthKey select_kth(const float* __restrict__ vals, int
 // Positions i of vals[0, n) in ascending order into L.cand: those with key > hi_T from slot 0, then the first `eq_take` with
 // key == hi_T from slot n_gt (n_gt = how many are above); nothing is written at or beyond slot `cap`.  Returns the number of
 // keys > hi_T (may exceed cap).  Called by the whole workgroup.
+template <bool NAN_LOW = false>
 __device__ __forceinline__ int gather_ordered(const float* __restrict__ vals, int n, unsigned hi_T, int n_gt, int eq_take, int cap,
                                               SelectLds& L) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -91,7 +100,7 @@ __device__ __forceinline__ int gather_ordered(const float* __restrict__ vals, in
     __syncthreads();
     for (int i0 = 0; i0 < n; i0 += 256) {
         const int i = i0 + tid;
-        const unsigned key = i < n ? f32_orderable(vals[i]) : 0u;
+        const unsigned key = i < n ? select_key<NAN_LOW>(vals[i]) : 0u;
         const bool gt = i < n && key > hi_T, eq = i < n && key == hi_T && eq_take > 0;
         const unsigned long long bg = __ballot(gt), be = __ballot(eq);
         if (!__syncthreads_or(gt || eq)) continue;                   // (barrier; most blocks hold no candidate)
