@@ -680,8 +680,9 @@ int vr_index_group_range_search_stats(vr_index_t ix, int64_t* out3, int32_t rese
  * empty group, a group of more than 256 sub-queries, lims[n_groups] != n_sub: VR_ERR_INVALID; the filter checks are those of
  * vr_index_search_window (on the device an out-of-range filter index gives a row of tails).  n_groups == 0 (then n_sub == 0):
  * VR_OK, nothing is launched.  An empty index: tails, nothing is launched.  Nothing is stored between calls.  A host caller's
- * call synchronises the stream.  Not offered: weighted-sum fusion (linear: sum the queries into one), reciprocal-rank fusion,
- * a window offset, groups of documents, MMR over a fused pool, corpus-sharded ranks, groups of more than 256 sub-queries. */
+ * call synchronises the stream.  Not offered: weighted-sum fusion (linear: sum the queries into one), a window offset, groups of
+ * documents, MMR over a fused pool, corpus-sharded ranks, groups of more than 256 sub-queries.  Reciprocal-rank fusion, which
+ * fuses positions and not scores, is vr_index_search_rrf below. */
 int vr_index_search_multi(vr_index_t ix, const float* queries, int32_t n_sub,
                           const int64_t* lims,              /* host [n_groups + 1] */
                           int32_t n_groups, int32_t k,
@@ -692,6 +693,58 @@ int vr_index_search_multi(vr_index_t ix, const float* queries, int32_t n_sub,
 /* Fused searches since the last reset: out3 = {groups, band columns re-scored in fp32, fp32 row dot products (columns x group
  * size)} — 64-bit counters in device memory. */
 int vr_index_multi_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
+/* ---- rank-fusion search: the top-k of reciprocal-rank fusion (RRF) over the lists of a group's sub-queries ---- */
+/* RRF fuses POSITIONS, not scores: it needs no comparable score scales, so a paraphrase with a flat score profile and one with a
+ * peaked profile count the same, and lists under different filters, of pages and of documents, or from different indexes can be
+ * fused.  Definition (normative; a numpy statement of it reproduces every bit): group g has lists L_0 .. L_{m-1} of `depth`
+ * slots each; slot r of list j holds an id >= 0, or -1 for an empty slot.  For an id i
+ *     F(i)    = fp32( sum over the entries (j, r) with L_j[r] == i of  (double)w_j / ((double)c + (double)(r + 1)) )
+ *     hits(i) = the number of such entries
+ * — an fp64 sum that starts at 0.0 and runs in ascending (j, r), every term that ONE division, rounded to fp32 once; c a float32
+ * (60 is customary), w_j a float32 weight per list (weights NULL: every weight 1).  A duplicate id inside one list counts at
+ * both positions.  The result is the k ids of largest F in the ranking's own order of floats, then lower id first;
+ * slots past the distinct ids hold (-inf, -1, 0).  A row below position `depth` of a list contributes nothing.
+ *   vr_rrf_fuse fuses lists from anywhere: ids [n_lists][depth] int64 and the three outputs [n_groups][k] are all host or all
+ * device per `on_device`; lims [n_groups + 1] int64 (group g = lists lims[g] .. lims[g + 1] - 1) and weights [n_lists] are always
+ * HOST arrays.  Host ids must lie in [-1, 2^31 - 2]; a device id outside [0, 2^31 - 2] is an empty slot, as -1 is.  The call
+ * synchronises the stream.
+ *   vr_index_search_rrf runs the lists itself: list j is what vr_index_search(k = depth) returns for sub-query j; with
+ * filter_of_group (one entry per group, expanded to its sub-queries as by vr_index_search_multi; -1: no filter) what
+ * vr_index_search_filtered(k = depth) returns; with by_groups != 0 the GROUPS vr_index_search_groups_window(offset 0,
+ * k = depth) returns under the same filters, and the ids are then documents.  The lists are produced by those code paths as they
+ * stand, into buffers the library owns (as the pool of vr_index_search_diverse is), and are therefore exact in every setting
+ * of vr_index_set_search_eps; they count in that search's own statistics.  queries [n_sub][dim], filter_of_group
+ * [n_groups] int32 and the outputs are all host or all device per `on_device`; lims and weights [n_sub] are HOST arrays.
+ *   One launch of one kernel (one workgroup per group, none waits for another) holds the whole definition for both calls.
+ *   Checks, all before any launch and with the outputs untouched: NULL pointers with n_groups > 0, negative counts, k outside
+ * 1..1000, depth outside 1..1000, lims[0] != 0, a decreasing lims, an empty group, a group of more than 256 lists, a group with
+ * m * depth above the value of vr_rrf_max_entries (16384), lims[n_groups] != the number of lists, c not finite or negative, a
+ * weight not finite, a host id out of range: VR_ERR_INVALID; by_groups without a grouping, or filter_of_group while no
+ * filters are set for the rows present: VR_ERR_STATE; a HOST filter_of_group entry outside [-1, n_filters): VR_ERR_INVALID.
+ * n_groups == 0 (then no lists): VR_OK, nothing is launched.  An empty index: tails, nothing is launched.  Nothing is stored
+ * between calls, and no other search's state or counters change beyond the statistics of the search that made the lists.
+ * Not offered: RRF over full rankings, a window offset or MMR over a fused list, corpus-sharded ranks (merge every
+ * sub-query's per-shard lists into its global list first: retriever.retrieve_rrf does), groups of more than 256 lists, the
+ * best rows of fused documents. */
+int vr_rrf_fuse(int device_id, const int64_t* ids, int32_t n_lists, int32_t depth,
+                const int64_t* lims,                /* host [n_groups + 1] */
+                int32_t n_groups, int32_t k, float c,
+                const float* weights,               /* host [n_lists], NULL: every weight 1 */
+                float* out_scores, int64_t* out_ids, int32_t* out_hits,      /* [n_groups][k] */
+                int32_t on_device, void* stream);
+/* The largest m * depth of one group. */
+int vr_rrf_max_entries(void);
+int vr_index_search_rrf(vr_index_t ix, const float* queries, int32_t n_sub,
+                        const int64_t* lims,              /* host [n_groups + 1] */
+                        int32_t n_groups, int32_t k, int32_t depth, float c,
+                        const float* weights,             /* host [n_sub], NULL: every weight 1 */
+                        const int32_t* filter_of_group,   /* NULL: no filter for any group */
+                        int32_t by_groups,                /* != 0: fuse documents (vr_index_set_groups) */
+                        float* out_scores, int64_t* out_ids, int32_t* out_hits,    /* [n_groups][k] */
+                        int32_t on_device, void* stream);
+/* Rank-fusion searches since the last reset: out3 = {groups, non-empty list entries, distinct ids} — 64-bit counters in device
+ * memory. */
+int vr_index_rrf_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
 /* ---- editing in place: remove rows, overwrite rows, read rows back ---- */
 /* After any of the calls below every search behaves exactly — score bits, ids, groups, lims — as on an index freshly built
  * (vr_index_create, vr_index_add, vr_index_set_filters / vr_index_set_groups) from the rows that remain.  Ids are positions, as

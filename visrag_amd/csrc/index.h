@@ -1,5 +1,5 @@
 // The search index's handle and the host helpers its three files share: index.hip (life cycle, vr_index_search*), index_searches.hip
-// (the score-row searches: groups, filtered, range, rank, window, document window, document rank, document range, fused, diverse) and index_rows.hip (editing in place).
+// (the score-row searches: groups, filtered, range, rank, window, document window, document rank, document range, fused, diverse, rank fusion) and index_rows.hip (editing in place).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -86,6 +86,12 @@ struct vr_index_s {
         DevBuf lims, fsub, edge, which, state;   // int lims of the call's groups | int filter of every sub-query | f32 band edge of a
                                       // block's groups | staged out_which | u64 words: [0..2] the counters of vr_index_multi_search_stats
     } mul;
+    struct {                          // rank-fusion search (vr_index_search_rrf, search_rrf.hip): no stored result
+        DevBuf scores, ids, groups;   // the pool — the plain, the filtered or the document window search's result for k = depth, by
+                                      // that search as it stands — f32 [n_sub][depth] | int64 rows | int64 groups (by_groups: the lists)
+        DevBuf lims, fsub, w, hits, state;   // int lims of the call's groups | int filter of every sub-query | f32 weights | staged
+                                      // out_hits | u64 words: [0..2] the counters of vr_index_rrf_search_stats
+    } rrf;
     struct {                          // editing in place (vr_index_remove / vr_index_update / vr_index_get_rows, index_edit.hip)
         DevBuf ids, rows, bits2;      // int row ids of the call | rows of a host caller, staged (<= EDIT_SCRATCH bytes for get_rows) |
                                       // the filters compacted out of place: swapped with flt.bits
@@ -158,6 +164,42 @@ static inline int fill_tails(float* out_scores, int64_t* out_ids, int32_t* out_w
         std::fill(out_ids, out_ids + n, (int64_t)-1);
         if (out_which) std::fill(out_which, out_which + n, (int32_t)-1);
     }
+    return VR_OK;
+}
+
+// ---- rank fusion: what vr_rrf_fuse and vr_index_search_rrf check of n_groups >= 1 groups of lists before anything else --------
+// *max_entries = the largest m * depth of a group
+static inline int rrf_check(const int64_t* lims, int32_t n_lists, int32_t n_groups, int32_t k, int32_t depth, float c,
+                            const float* weights, int* max_entries) {
+    if (k <= 0 || k > search_bigk_max()) return fail(VR_ERR_INVALID, "k=%d unsupported (1..%d)", k, search_bigk_max());
+    if (depth <= 0 || depth > search_bigk_max()) return fail(VR_ERR_INVALID, "depth=%d unsupported (1..%d)", depth, search_bigk_max());
+    if (!std::isfinite(c) || c < 0.f) return fail(VR_ERR_INVALID, "c=%g must be finite and >= 0", (double)c);
+    if (lims[0] != 0) return fail(VR_ERR_INVALID, "lims[0] = %lld, not 0", (long long)lims[0]);
+    int64_t most = 0;
+    for (int32_t g = 0; g < n_groups; ++g) {
+        const int64_t m = lims[g + 1] - lims[g];
+        if (m < 0) return fail(VR_ERR_INVALID, "lims[%d] = %lld decreases", (int)g + 1, (long long)lims[g + 1]);
+        if (m == 0) return fail(VR_ERR_INVALID, "group %d is empty", (int)g);
+        if (m > 256) return fail(VR_ERR_INVALID, "group %d holds %lld lists (1..256)", (int)g, (long long)m);
+        if (m * depth > rrf_max_entries())
+            return fail(VR_ERR_INVALID, "group %d holds %lld lists x depth %d = %lld entries (at most %d)", (int)g, (long long)m, (int)depth,
+                        (long long)(m * depth), rrf_max_entries());
+        most = std::max(most, m * depth);
+    }
+    if (lims[n_groups] != n_lists)
+        return fail(VR_ERR_INVALID, "lims[%d] = %lld, not the %d lists", (int)n_groups, (long long)lims[n_groups], (int)n_lists);
+    if (weights)
+        for (int32_t j = 0; j < n_lists; ++j)
+            if (!std::isfinite(weights[j])) return fail(VR_ERR_INVALID, "weights[%d] = %g is not finite", (int)j, (double)weights[j]);
+    *max_entries = (int)most;
+    return VR_OK;
+}
+
+// n result slots of a rank fusion over no list entry: (-inf, -1, 0)
+static inline int rrf_fill_tails(float* out_scores, int64_t* out_ids, int32_t* out_hits, size_t n, int32_t on_device, hipStream_t s) {
+    VRCHK(fill_tails(out_scores, out_ids, nullptr, n, on_device, s));
+    if (on_device) HIPCHK(hipMemsetAsync(out_hits, 0, n * 4, s));
+    else std::fill(out_hits, out_hits + n, (int32_t)0);
     return VR_OK;
 }
 

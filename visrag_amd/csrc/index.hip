@@ -1,4 +1,4 @@
-// The search index of libvisrag_hip.so (vr_index_* / vr_topk_merge* of include/visrag_hip.h): fp32 + bf16 row store, its life
+// The search index of libvisrag_hip.so (vr_index_* / vr_topk_merge* / vr_rrf_* of include/visrag_hip.h): fp32 + bf16 row store, its life
 // cycle, and the certified top-k search over it with its fallback passes (search*.hip).  The searches over score rows are in
 // index_searches.hip, editing in place in index_rows.hip, the handle and what the three share in index.h.
 #include "index.h"
@@ -298,6 +298,48 @@ extern "C" int vr_topk_merge(int device_id, const float* scores, const int64_t* 
     if (!scores || !ids || !out_scores || !out_ids || n_parts <= 0 || nq <= 0) return fail(VR_ERR_INVALID, "bad arguments");
     VRCHK(set_dev(device_id));
     HIPCHK(launch_topk_merge(scores, ids, n_parts, nq, k, out_scores, out_ids, (hipStream_t)stream));
+    return VR_OK;
+}
+
+// ---- rank fusion of lists from anywhere (search_rrf.hip); the index's own is vr_index_search_rrf (index_searches.hip) ----------
+extern "C" int vr_rrf_max_entries(void) { return rrf_max_entries(); }
+
+extern "C" int vr_rrf_fuse(int device_id, const int64_t* ids, int32_t n_lists, int32_t depth, const int64_t* lims, int32_t n_groups,
+                           int32_t k, float c, const float* weights, float* out_scores, int64_t* out_ids, int32_t* out_hits,
+                           int32_t on_device, void* stream) {
+    if (n_groups < 0 || n_lists < 0 || (n_groups > 0 && (!ids || !lims || !out_scores || !out_ids || !out_hits)))
+        return fail(VR_ERR_INVALID, "bad arguments");
+    if (n_groups == 0) {
+        if (n_lists != 0) return fail(VR_ERR_INVALID, "%d lists in no group", (int)n_lists);
+        return VR_OK;                             // no group: no launch
+    }
+    int max_entries = 0;
+    VRCHK(rrf_check(lims, n_lists, n_groups, k, depth, c, weights, &max_entries));
+    const size_t n_in = (size_t)n_lists * depth, n_out = (size_t)n_groups * k;
+    if (!on_device)
+        for (size_t e = 0; e < n_in; ++e)
+            if (ids[e] < -1 || ids[e] > ((int64_t)1 << 31) - 2)
+                return fail(VR_ERR_INVALID, "ids[%lld] = %lld outside [-1, 2^31 - 2]", (long long)e, (long long)ids[e]);
+    VRCHK(set_dev(device_id));
+    hipStream_t s = (hipStream_t)stream;
+    // no handle to keep scratch in: the call's own buffers, released when it returns (the stream is synchronised first)
+    DevBuf b_ids, b_lims, b_w, b_os, b_oi, b_oh;
+    std::vector<int> lims32((size_t)n_groups + 1);
+    for (int32_t g = 0; g <= n_groups; ++g) lims32[(size_t)g] = (int)lims[g];
+    RrfArgs p{};
+    const int* glims = nullptr;
+    VRCHK(stage_input(b_ids, ids, n_in, on_device, s, &p.ids));
+    VRCHK(stage_input(b_lims, (const int*)lims32.data(), lims32.size(), 0, s, &glims));
+    if (weights) VRCHK(stage_input(b_w, weights, (size_t)n_lists, 0, s, &p.weights));
+    VRCHK(stage_output(b_os, out_scores, n_out, on_device, &p.out_scores));
+    VRCHK(stage_output(b_oi, out_ids, n_out, on_device, &p.out_ids));
+    VRCHK(stage_output(b_oh, out_hits, n_out, on_device, &p.out_hits));
+    p.lims = glims; p.depth = depth; p.k = k; p.c = c;
+    HIPCHK(launch_rrf_fuse(p, n_groups, max_entries, s));
+    VRCHK(return_output(out_scores, p.out_scores, n_out, on_device, s));
+    VRCHK(return_output(out_ids, p.out_ids, n_out, on_device, s));
+    VRCHK(return_output(out_hits, p.out_hits, n_out, on_device, s));
+    HIPCHK(hipStreamSynchronize(s));              // (lims and weights are the caller's host memory, the scratch is the call's)
     return VR_OK;
 }
 

@@ -1,5 +1,5 @@
 // The searches of the index that work on score rows (vr_index_search_groups / _filtered / _range / _rank_rows / _count_range /
-// _window / _groups_window / _rank_groups / _count_groups_range / _groups_range / _multi / _diverse of include/visrag_hip.h, with what sets them up and their counters).  Each of them: every argument
+// _window / _groups_window / _rank_groups / _count_groups_range / _groups_range / _multi / _diverse / _rrf of include/visrag_hip.h, with what sets them up and their counters).  Each of them: every argument
 // check first, then per block of <= 256 queries the block's score rows S[q][row] (index.h: score_block, the deep path's bf16
 // MFMA GEMM), with filters the mask (mask_block: disallowed columns -> -inf), then the search's own kernels.  Scratch (query
 // staging, score rows, staged outputs, the staged filter ids) is shared between the searches; what a search keeps is its member
@@ -878,6 +878,83 @@ extern "C" int vr_index_search_diverse(vr_index_t ix, const float* queries, int3
     HIPCHK(launch_mmr_select(m, s));
     VRCHK(return_output(out_scores, os, n_out, on_device, s));
     VRCHK(return_output(out_ids, oi, n_out, on_device, s));
+    if (!on_device) HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
+}
+
+// ---- rank-fusion search (search_rrf.hip) --------------------------------------------------------------------------------------
+extern "C" int vr_index_rrf_search_stats(vr_index_t ix, int64_t* out3, int32_t reset) {
+    if (!ix || !out3) return fail(VR_ERR_INVALID, "NULL argument");
+    return read_counters<unsigned long long, 3>(ix, ix->rrf.state, 0, out3, reset);
+}
+
+// The k ids of largest reciprocal-rank-fusion score of every group of sub-queries.  The lists are the plain, the filtered or the
+// document window search's own result for k = depth, produced by that search as it stands on the staged queries into buffers of
+// the rank fusion's own (as the diversified search's pool is); one launch of the fusion kernel writes the (staged) outputs.
+// No state of its own but the pool and three counters.
+extern "C" int vr_index_search_rrf(vr_index_t ix, const float* queries, int32_t n_sub, const int64_t* lims, int32_t n_groups, int32_t k,
+                                   int32_t depth, float c, const float* weights, const int32_t* filter_of_group, int32_t by_groups,
+                                   float* out_scores, int64_t* out_ids, int32_t* out_hits, int32_t on_device, void* stream) {
+    if (!ix || n_groups < 0 || n_sub < 0 || (n_groups > 0 && (!queries || !lims || !out_scores || !out_ids || !out_hits)))
+        return fail(VR_ERR_INVALID, "bad arguments");
+    if (n_groups == 0) {
+        if (n_sub != 0) return fail(VR_ERR_INVALID, "%d sub-queries in no group", (int)n_sub);
+        return VR_OK;                             // no group: no launch
+    }
+    int max_entries = 0;
+    VRCHK(rrf_check(lims, n_sub, n_groups, k, depth, c, weights, &max_entries));
+    if (!range_dim_ok(ix->dim) || !mmr_dim_ok(ix->dim)) return fail(VR_ERR_INVALID, "dim %d unsupported", ix->dim);
+    if (by_groups && (ix->grp.n_groups <= 0 || ix->n <= 0))
+        return fail(VR_ERR_STATE, "no grouping set for the rows of the index (vr_index_set_groups)");
+    if (filter_of_group) VRCHK(check_filter_ids(ix, filter_of_group, n_groups, on_device, "filter_of_group"));
+    VRCHK(set_dev(ix->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n_out = (size_t)n_groups * k;
+    if (ix->n == 0) return rrf_fill_tails(out_scores, out_ids, out_hits, n_out, on_device, s);   // no row: tails, no launch
+    if (!ix->rrf.state.p) VRCHK(ix->rrf.state.alloc(3 * 8));
+    const float* q32 = nullptr;
+    VRCHK(stage_queries(ix, queries, n_sub, pad256l(std::min<int64_t>(n_sub, 256)), on_device, s, &q32));
+    std::vector<int> lims32((size_t)n_groups + 1);
+    for (int32_t g = 0; g <= n_groups; ++g) lims32[(size_t)g] = (int)lims[g];
+    const int* glims = nullptr;
+    const float* w = nullptr;
+    VRCHK(stage_input(ix->rrf.lims, (const int*)lims32.data(), lims32.size(), 0, s, &glims));
+    if (weights) VRCHK(stage_input(ix->rrf.w, weights, (size_t)n_sub, 0, s, &w));
+    const int* fsub = nullptr;
+    if (filter_of_group) {                        // the group's filter for every one of its sub-queries, as the fused search expands it
+        const int* fog = nullptr;
+        VRCHK(stage_input(ix->flt.ids, filter_of_group, (size_t)n_groups, on_device, s, &fog));
+        VRCHK(ix->rrf.fsub.reserve((size_t)n_sub * 4));
+        HIPCHK(launch_multi_expand(glims, fog, n_groups, ix->rrf.fsub.as<int>(), s));
+        fsub = ix->rrf.fsub.as<int>();
+    }
+    HIPCHK(hipStreamSynchronize(s));              // (the host arrays are free from here on)
+    // ---- the pool: the staged queries are device queries to the search, which then stages nothing and writes the pool buffers
+    const size_t n_pool = (size_t)n_sub * depth;
+    VRCHK(ix->rrf.scores.reserve(n_pool * 4));
+    VRCHK(ix->rrf.ids.reserve(n_pool * 8));
+    if (by_groups) {
+        VRCHK(ix->rrf.groups.reserve(n_pool * 8));
+        const std::vector<int64_t> zero((size_t)n_sub, 0);
+        VRCHK(vr_index_search_groups_window(ix, q32, n_sub, zero.data(), depth, fsub, ix->rrf.scores.as<float>(), ix->rrf.ids.as<int64_t>(),
+                                            ix->rrf.groups.as<int64_t>(), 1, stream));      // (synchronises before `zero` dies)
+    } else if (fsub) {
+        VRCHK(vr_index_search_filtered(ix, q32, n_sub, depth, fsub, ix->rrf.scores.as<float>(), ix->rrf.ids.as<int64_t>(), 1, stream));
+    } else {
+        VRCHK(search_impl(ix, q32, n_sub, depth, ix->rrf.scores.as<float>(), ix->rrf.ids.as<int64_t>(), nullptr, 0, 1, stream));
+    }
+    // ---- the fusion
+    RrfArgs p{};
+    p.ids = by_groups ? ix->rrf.groups.as<int64_t>() : ix->rrf.ids.as<int64_t>();
+    p.lims = glims; p.weights = w; p.depth = depth; p.k = k; p.c = c;
+    VRCHK(stage_output(ix->os, out_scores, n_out, on_device, &p.out_scores));
+    VRCHK(stage_output(ix->oi, out_ids, n_out, on_device, &p.out_ids));
+    VRCHK(stage_output(ix->rrf.hits, out_hits, n_out, on_device, &p.out_hits));
+    p.stats = ix->rrf.state.as<unsigned long long>();
+    HIPCHK(launch_rrf_fuse(p, n_groups, max_entries, s));
+    VRCHK(return_output(out_scores, p.out_scores, n_out, on_device, s));
+    VRCHK(return_output(out_ids, p.out_ids, n_out, on_device, s));
+    VRCHK(return_output(out_hits, p.out_hits, n_out, on_device, s));
     if (!on_device) HIPCHK(hipStreamSynchronize(s));
     return VR_OK;
 }

@@ -577,6 +577,19 @@ struct MmrArgs {
 };
 bool mmr_dim_ok(int dim);            // the dim limits of the fp32 re-scoring (search_common.h: dot_lane)
 hipError_t launch_mmr_select(const MmrArgs& p, hipStream_t s);
+// ---- rank fusion (search_rrf.hip): the k ids of largest reciprocal-rank-fusion score over the lists of a group's sub-queries
+struct RrfArgs {
+    const int64_t* ids;              // [n_lists][depth] device: slot r of list j; an id outside [0, 2^31 - 2] is an empty slot
+    const int* lims;                 // [groups + 1] device: group g = lists lims[g] .. lims[g + 1] - 1 (1..256 of them, m * depth <= rrf_max_entries())
+    const float* weights;            // [n_lists] device or null (every weight 1)
+    int depth, k;                    // slots per list; result slots per group
+    float c;                         // the term of entry (j, r) is (double)w_j / ((double)c + (double)(r + 1)); finite, >= 0
+    float* out_scores; int64_t* out_ids; int* out_hits;   // [groups][k]; (-inf, -1, 0) past the distinct ids
+    unsigned long long* stats;       // null, or [0] groups [1] non-empty entries [2] distinct ids
+};
+int rrf_max_entries();               // the largest m * depth of one group
+// max_entries: the largest m * depth among the groups (sizes the dynamic LDS)
+hipError_t launch_rrf_fuse(const RrfArgs& p, int n_groups, int max_entries, hipStream_t s);
 // ---- editing in place (index_edit.hip): whole rows of `row_bytes` (a multiple of 16) moved by whole waves.  rem: the removed rows,
 // sorted and distinct (device, nr ints); src(j) = j + #{i : rem[i] - i <= j} = the old row that becomes row j
 // out rows [0, n_rows) = store rows src(j0) .. src(j0 + n_rows - 1).  `out` may lie inside `store` if the rows written (all below

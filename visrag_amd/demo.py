@@ -232,6 +232,44 @@ def retrieve_any(knowledge_base_path: str, questions, topk: int, model, tokenize
     return (paths, scores, deciding) if return_scores else paths
 
 
+@torch.no_grad()
+def retrieve_rrf(knowledge_base_path: str, questions, topk: int, model, tokenizer, index=None, names=None, depth: int = 100,
+                 c: float = 60.0, weights=None, documents=None, return_scores: bool = False):
+    """Paths of the `topk` pages that serve a question asked in SEVERAL ways, by reciprocal-rank fusion (None if the base does
+    not exist): every question's `depth` best pages form a list, and a page scores the sum of weight / (c + position) over the
+    lists that hold it, positions from 1 (HipIndex.search_rrf) — positions only, so a reformulation with a flat score profile
+    counts as much as one with a peaked profile.  `questions` as in `retrieve_any`: strings or their embeddings [m, dim];
+    `weights`: one float per question, None = 1.  `documents`: only the pages of those documents, as in `retrieve` (one
+    filter, set for this question).  Fewer than `topk` paths where the lists hold fewer distinct pages.  With `return_scores`
+    -> (paths, scores, hits): `hits[i]` is the number of lists page i stands in.  Pass `index, names =
+    load_knowledge_base(path)` to keep the index resident."""
+    if not os.path.exists(knowledge_base_path):
+        return None
+    own = index is None
+    if own:
+        index, names = load_knowledge_base(knowledge_base_path, model.encoder.device if model is not None else None)
+    n = len(index)
+    if isinstance(questions, (list, tuple)) and all(isinstance(x, str) for x in questions):
+        q = encode(model, tokenizer, [QUERY_INSTRUCTION + x for x in questions])
+    else:
+        q = np.asarray(questions.detach().cpu() if isinstance(questions, torch.Tensor) else questions, dtype=np.float32)
+    q = np.ascontiguousarray(np.asarray(q, dtype=np.float32).reshape(-1, index.dim))
+    mask = None if documents is None else label_filters([doc_of_page(nm) for nm in names[:n]], [documents])
+    k = min(topk, n if mask is None else int(mask.sum()), 1000)
+    paths, scores, hits = [], [], []
+    if k > 0 and len(q) > 0:
+        if mask is not None:
+            index.set_filters(mask)
+        sc, ids, h = index.search_rrf(q, [0, len(q)], k, depth, c, weights, None if mask is None else 0)
+        keep = [int(i) for i in ids[0] if i >= 0]
+        paths = [os.path.join(knowledge_base_path, names[i]) for i in keep]
+        scores = [float(s) for s in sc[0][: len(keep)]]
+        hits = [int(x) for x in h[0][: len(keep)]]
+    if own:
+        index.close()
+    return (paths, scores, hits) if return_scores else paths
+
+
 def _retrieve_diverse(knowledge_base_path, query, topk, model, tokenizer, index, names, return_scores, documents, lam, pool):
     """retrieve() with MMR picks; `documents` given: among their pages, through one filter set for this question"""
     own = index is None

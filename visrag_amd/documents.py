@@ -33,6 +33,9 @@ scores, best rows, groups): `split_document_ranges` cuts it into per-query tripl
 The fused search (HipIndex.search_multi) ranks rows by the max or the min of their scores over a group of sub-queries:
 `group_rows` of the sub-queries' labels gives its `lims`, and `fuse_runs` states what per-sub-query top-k lists can and cannot
 say about that ranking — the workaround the fused search replaces.
+
+The rank-fusion search (HipIndex.search_rrf, engine.rrf_fuse) fuses the POSITIONS of the sub-queries' lists by reciprocal-rank
+fusion: `rrf_runs` is its definition in numpy, bit for bit, and the host workaround it replaces.
 Pure numpy: nothing here touches the GPU.
 """
 from __future__ import annotations
@@ -352,3 +355,73 @@ def fuse_runs(scores, ids, lims, k: int, fuse: str = "max") -> Tuple[np.ndarray,
         else:
             determined[g] = ended or (len(top) == k and top[-1][0] > bound)
     return out_s, out_i, determined
+
+
+RRF_ID_MAX = 2 ** 31 - 2        # ids of a rank fusion lie in [0, RRF_ID_MAX]; anything else is an empty slot
+
+
+def _f32_orderable(x: np.ndarray) -> np.ndarray:
+    """the ranking's order of float32 values as uint32 keys (-0.0 < +0.0), as the library's make_key has it"""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    return np.where(u >> 31 != 0, ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def rrf_runs(ids, lims, k: int, c: float = 60.0, weights=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Reciprocal-rank fusion of top lists, the definition of `HipIndex.search_rrf` / `engine.rrf_fuse` (include/visrag_hip.h:
+    vr_rrf_fuse) in vectorised numpy, bit for bit -> (scores f32 [n_groups][k], ids i64 [n_groups][k], hits i32 [n_groups][k]).
+    `ids` [n_lists][depth]: slot r of list j holds an id in [0, 2^31 - 2] (anything else: an empty slot); group g holds lists
+    lims[g] .. lims[g + 1] - 1.  An id scores F = float32(sum of float64(w_j) / (float64(float32(c)) + float64(r + 1)) over
+    its entries (j, r)), the float64 sum started at 0.0 and taken in ascending (j, r); `hits` counts the entries.  The result
+    is ranked F descending (in the ranking's order of floats), then lower id first, and padded with (-inf, -1, 0).  This is
+    also the host workaround the device call replaces: `search(k=depth)` per sub-query, the lists pulled to the host, this."""
+    ids = np.asarray(ids, dtype=np.int64)
+    lims = np.asarray(lims, dtype=np.int64).reshape(-1)
+    k = int(k)
+    if ids.ndim != 2:
+        raise ValueError("ids must be [n_lists][depth]")
+    if len(lims) < 1 or lims[0] != 0 or (np.diff(lims) < 1).any() or lims[-1] != len(ids):
+        raise ValueError("lims must start at 0, increase and end at the number of lists")
+    if k < 1:
+        raise ValueError("k must be >= 1")
+    c32 = np.float32(c)
+    if not np.isfinite(c32) or c32 < 0:
+        raise ValueError("c must be finite and >= 0")
+    n_lists, ng = len(ids), len(lims) - 1
+    w = np.ones(n_lists, dtype=np.float32) if weights is None else np.asarray(weights, dtype=np.float32).reshape(-1)
+    if len(w) != n_lists or not np.isfinite(w).all():
+        raise ValueError("weights must be one finite value per list")
+    out_s = np.full((ng, k), -np.inf, dtype=np.float32)
+    out_i = np.full((ng, k), -1, dtype=np.int64)
+    out_h = np.zeros((ng, k), dtype=np.int32)
+    jj, rr = np.nonzero((ids >= 0) & (ids <= RRF_ID_MAX))             # row-major: ascending (j, r)
+    if len(jj) == 0:
+        return out_s, out_i, out_h
+    e_id = ids[jj, rr]
+    e_g = np.repeat(np.arange(ng, dtype=np.int64), np.diff(lims))[jj]
+    term = w[jj].astype(np.float64) / (np.float64(c32) + (rr + 1).astype(np.float64))
+    order = np.lexsort((e_id, e_g))                                   # stable: (j, r) stays ascending inside an (group, id) segment
+    e_id, e_g, term = e_id[order], e_g[order], term[order]
+    head = np.ones(len(e_id), dtype=bool)
+    head[1:] = (e_id[1:] != e_id[:-1]) | (e_g[1:] != e_g[:-1])
+    starts = np.flatnonzero(head)
+    seg = np.cumsum(head) - 1
+    t = np.arange(len(e_id)) - starts[seg]                            # an entry's place inside its segment
+    hits = np.bincount(seg, minlength=len(starts))
+    by_t = np.argsort(t, kind="stable")
+    cut = np.concatenate([[0], np.cumsum(np.bincount(t))])
+    acc = np.zeros(len(starts), dtype=np.float64)
+    for step in range(len(cut) - 1):                                  # the t-th entry of every segment that has one: the sum's order
+        sel = by_t[cut[step]:cut[step + 1]]
+        acc[seg[sel]] += term[sel]                                    # (distinct segments: a plain vector add)
+    with np.errstate(over="ignore"):
+        F = acc.astype(np.float32)
+    sg, sid = e_g[starts], e_id[starts]
+    rank = np.lexsort((sid, -_f32_orderable(F).astype(np.int64), sg))
+    sg, sid, F, hits = sg[rank], sid[rank], F[rank], hits[rank]
+    first = np.concatenate([[0], np.cumsum(np.bincount(sg, minlength=ng))])
+    place = np.arange(len(sg)) - first[sg]
+    keep = place < k
+    out_s[sg[keep], place[keep]] = F[keep]
+    out_i[sg[keep], place[keep]] = sid[keep]
+    out_h[sg[keep], place[keep]] = hits[keep]
+    return out_s, out_i, out_h

@@ -346,6 +346,19 @@ class HipIndex:
             raise ValueError(f"queries must be {shape or f'[nq][{self.dim}]'}")
         return q, cuda
 
+    def _grouped_queries(self, queries, lims):
+        """the sub-queries of search_multi / search_rrf -> (q flat [n_sub][dim] where it lives, cuda, lims int64 host): flat
+        `queries` with `lims` [n_groups + 1], or [n_groups][m][dim] with `lims=None`"""
+        if lims is None:
+            q, cuda = self._queries(queries, 3, f"[n_groups][m][{self.dim}] when lims is None")
+            lim = np.arange(q.shape[0] + 1, dtype=np.int64) * q.shape[1]
+            return q.reshape(-1, self.dim), cuda, lim
+        q, cuda = self._queries(queries, 2, f"[n_sub][{self.dim}] with lims")
+        lim = np.ascontiguousarray(self._row_ids(lims), dtype=np.int64)
+        if len(lim) < 1:
+            raise ValueError("lims must hold n_groups + 1 entries")
+        return q, cuda, lim
+
     def _stats3(self, fn, names, reset: bool) -> Dict[str, int]:
         """the three counters of one search's `*_search_stats` under `names`, cleared with `reset`"""
         out = (C.c_int64 * 3)()
@@ -798,15 +811,7 @@ class HipIndex:
         out, numpy / cpu in -> numpy out."""
         if fuse not in ("max", "min"):
             raise ValueError("fuse must be 'max' or 'min'")
-        if lims is None:
-            q, cuda = self._queries(queries, 3, f"[n_groups][m][{self.dim}] when lims is None")
-            lim = np.arange(q.shape[0] + 1, dtype=np.int64) * q.shape[1]
-            q = q.reshape(-1, self.dim)
-        else:
-            q, cuda = self._queries(queries, 2, f"[n_sub][{self.dim}] with lims")
-            lim = np.ascontiguousarray(self._row_ids(lims), dtype=np.int64)
-            if len(lim) < 1:
-                raise ValueError("lims must hold n_groups + 1 entries")
+        q, cuda, lim = self._grouped_queries(queries, lims)
         ng, n_sub = len(lim) - 1, int(q.shape[0])
         if filter_of_group is None:
             keep, fptr = None, C.c_void_p(None)
@@ -829,6 +834,47 @@ class HipIndex:
         """Fused searches since the last reset: groups, columns of the bands re-scored in fp32, fp32 row dot products (every
         band column against every sub-query of its group)."""
         return self._stats3(self.lib.vr_index_multi_search_stats, ("groups", "candidates", "dots"), reset)
+
+    # ---- rank-fusion search (include/visrag_hip.h: vr_index_search_rrf) ----
+    def search_rrf(self, queries, lims, k: int, depth: int = 100, c: float = 60.0, weights=None, filter_of_group=None,
+                   documents: bool = False):
+        """The k ids of largest reciprocal-rank-fusion score per group of sub-queries (include/visrag_hip.h: vr_index_search_rrf)
+        -> (scores [n_groups,k] f32, ids [n_groups,k] i64, hits [n_groups,k] i32).  Every sub-query's list is what
+        `search(k=depth)` returns for it (under `filter_of_group`: `search_filtered`; with `documents=True`: the groups of
+        `search_groups_window(offset 0, k=depth)`, and the ids are documents); an id scores float32(sum of w_j / (c + 1 + r) over
+        the lists j that hold it at 0-based position r), `hits` is the number of those lists; ids come score descending, then
+        lower id first, slots past the distinct ids are (-inf, -1, 0) (documents.rrf_runs is the definition, bit for bit).
+        `queries` and `lims` as in `search_multi`: flat [n_sub][dim] with `lims` [n_groups + 1], or [n_groups][m][dim] with
+        `lims=None`.  `weights`: one float per sub-query, None = 1.  Groups hold 1..256 sub-queries and at most
+        `rrf_max_entries()` list slots, 1 <= k, depth <= 1000.  `filter_of_group` as in `search_multi`.  cuda in -> cuda out,
+        numpy / cpu in -> numpy out."""
+        q, cuda, lim = self._grouped_queries(queries, lims)
+        ng, n_sub = len(lim) - 1, int(q.shape[0])
+        w, wptr = _rrf_weights(weights, n_sub)
+        if filter_of_group is None:
+            keep, fptr = None, C.c_void_p(None)
+        else:
+            keep, fptr = self._filter_of_query(torch.empty((ng, 0), device=q.device) if cuda else np.empty((ng, 0)), filter_of_group)
+        if cuda:
+            outs = [torch.empty((ng, k), dtype=d, device=q.device) for d in (torch.float32, torch.int64, torch.int32)]
+            ptrs = [x.data_ptr() for x in [q] + outs]
+        else:
+            outs = [np.empty((ng, max(k, 0)), dtype=d) for d in (np.float32, np.int64, np.int32)]
+            ptrs = [x.ctypes.data for x in [q] + outs]
+        _lib.check(self.lib.vr_index_search_rrf(self._h, C.c_void_p(ptrs[0]), n_sub, C.c_void_p(lim.ctypes.data), ng, k, int(depth),
+                                                float(c), wptr, fptr, 1 if documents else 0, C.c_void_p(ptrs[1]),
+                                                C.c_void_p(ptrs[2]), C.c_void_p(ptrs[3]), 1 if cuda else 0,
+                                                C.c_void_p(_stream_ptr(self.device))), "vr_index_search_rrf")
+        del keep, w
+        return tuple(outs)
+
+    def rrf_max_entries(self) -> int:
+        """The most list slots (sub-queries x depth) one group of `search_rrf` / `rrf_fuse` may hold."""
+        return int(self.lib.vr_rrf_max_entries())
+
+    def rrf_search_stats(self, reset: bool = False) -> Dict[str, int]:
+        """Rank-fusion searches since the last reset: groups, non-empty list entries, distinct ids."""
+        return self._stats3(self.lib.vr_index_rrf_search_stats, ("groups", "entries", "distinct"), reset)
 
     def search_keys(self, queries: torch.Tensor, k: int, id_offset: int = 0) -> torch.Tensor:
         """The same search with each result packed into ONE 64-bit word (include/visrag_hip.h:
@@ -886,6 +932,58 @@ class HipIndex:
         out = {name: ms[i] / n for i, name in enumerate(self.SEARCH_STAGES)}
         out["calls"] = int(calls.value)
         return out
+
+
+def _rrf_weights(weights, n_lists: int):
+    """`weights` of a rank fusion as a host float32 [n_lists] -> (keep-alive, pointer); None: no array (every weight 1)"""
+    if weights is None:
+        return None, C.c_void_p(None)
+    if isinstance(weights, torch.Tensor):
+        weights = weights.detach().cpu().numpy()
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
+    if len(w) != n_lists:
+        raise ValueError(f"{len(w)} weights for {n_lists} lists")
+    return w, C.c_void_p(w.ctypes.data)
+
+
+def rrf_fuse(ids, lims, k: int, c: float = 60.0, weights=None, device: int = 0):
+    """Reciprocal-rank fusion of lists from anywhere — two indexes built with different models, pages and documents, lists
+    under different filters (include/visrag_hip.h: vr_rrf_fuse) -> (scores [n_groups,k] f32, ids [n_groups,k] i64, hits
+    [n_groups,k] i32), as `HipIndex.search_rrf` returns them.  `ids` [n_lists][depth] int64: slot r of list j, -1 = an empty slot;
+    group g holds lists lims[g] .. lims[g + 1] - 1 (`lims=None`: [n_groups][m][depth]).  cuda in -> cuda out (on the tensor's
+    device), numpy / cpu in -> numpy out (computed on `device`)."""
+    _require_gpu()
+    lib = _lib.load()
+    cuda = isinstance(ids, torch.Tensor) and ids.is_cuda
+    if cuda:
+        a = ids.to(torch.int64).contiguous()
+        device = a.device.index or 0
+    else:
+        a = np.ascontiguousarray(ids.numpy() if isinstance(ids, torch.Tensor) else ids, dtype=np.int64)
+    if lims is None:
+        if a.ndim != 3:
+            raise ValueError("ids must be [n_groups][m][depth] when lims is None")
+        lim = np.arange(a.shape[0] + 1, dtype=np.int64) * a.shape[1]
+        a = a.reshape(-1, a.shape[2])
+    else:
+        if a.ndim != 2:
+            raise ValueError("ids must be [n_lists][depth] with lims")
+        lim = np.ascontiguousarray(HipIndex._row_ids(lims), dtype=np.int64)
+        if len(lim) < 1:
+            raise ValueError("lims must hold n_groups + 1 entries")
+    ng, n_lists, depth = len(lim) - 1, int(a.shape[0]), int(a.shape[1])
+    w, wptr = _rrf_weights(weights, n_lists)
+    if cuda:
+        outs = [torch.empty((ng, k), dtype=d, device=a.device) for d in (torch.float32, torch.int64, torch.int32)]
+        ptrs = [x.data_ptr() for x in [a] + outs]
+    else:
+        outs = [np.empty((ng, max(k, 0)), dtype=d) for d in (np.float32, np.int64, np.int32)]
+        ptrs = [x.ctypes.data for x in [a] + outs]
+    _lib.check(lib.vr_rrf_fuse(int(device), C.c_void_p(ptrs[0]), n_lists, depth, C.c_void_p(lim.ctypes.data), ng, k, float(c), wptr,
+                               C.c_void_p(ptrs[1]), C.c_void_p(ptrs[2]), C.c_void_p(ptrs[3]), 1 if cuda else 0,
+                               C.c_void_p(_stream_ptr(int(device)))), "vr_rrf_fuse")
+    del w
+    return tuple(outs)
 
 
 def topk_merge_keys(keys: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -624,6 +624,60 @@ def retrieve_fused(args, group_of_query: Callable, topk: int, fuse: str = "max",
     return result
 
 
+def retrieve_rrf(args, group_of_query: Callable, topk: int, depth: int = 100, c: float = 60.0,
+                 weight_of_query: Optional[Callable] = None, index_factory: Optional[Callable] = None,
+                 fuse_lists: Optional[Callable] = None) -> Dict[Hashable, Dict[str, float]]:
+    """One run per QUESTION by reciprocal-rank fusion over the same pickle shards: the queries are grouped by
+    `group_of_query(qid)`, every query's list is its `depth` best rows of the WHOLE corpus, and a group gets the `topk` rows of
+    largest sum of weight / (c + position) over its queries' lists, positions from 1 (HipIndex.search_rrf's definition:
+    documents.rrf_runs).  `weight_of_query(qid)`: a float per query, None = 1.  -> {group: {docid: score}}, groups in the order
+    their first query appears, a group's entries best first — score descending, then shard and row order; it goes to
+    `save_as_trec` as it is.  A position is a property of the whole corpus, so per shard only `search(k=depth)` runs; every
+    query's shard lists are merged into its global top `depth` on the host (merge_pages_host) and ONE `rrf_fuse` over those
+    global positions fuses all groups.  1 <= topk, depth <= 1000, groups of at most 256 queries and rrf_max_entries() list slots.
+    `fuse_lists(ids, lims, k, c, weights, device)` defaults to engine.rrf_fuse.
+
+    Replicated form only, like retrieve_deep: every rank sees the whole corpus."""
+    make_index = index_factory or HipIndex
+    if fuse_lists is None:
+        from .engine import rrf_fuse as fuse_lists
+    queries, qids, _ = _load_queries(args)
+    corpus_parts = list_shards(args.output_dir, "corpus")
+    if len(corpus_parts) == 0:
+        raise ValueError("No pre-computed document embeddings found")
+    topk, depth = int(topk), int(depth)
+    order, lims, groups = group_rows([group_of_query(q) for q in qids])
+    result: Dict[Hashable, Dict[str, float]] = {g: {} for g in groups}
+    if len(groups) == 0 or topk <= 0:
+        return result
+    grouped = np.ascontiguousarray(np.asarray(queries, dtype=np.float32)[order])
+    weights = None if weight_of_query is None else np.asarray([weight_of_query(qids[i]) for i in order], dtype=np.float32)
+    dev = _device_index(args)
+    all_ids: List[str] = []
+    lists_s, lists_p = [], []
+    for p in corpus_parts:
+        reps, ids = read_shard(p)
+        if len(ids) == 0:
+            continue
+        ix = make_index(queries.shape[1], len(ids), dev)
+        ix.add(np.asarray(reps, dtype=np.float32))
+        sc, rows = ix.search(grouped, depth)
+        ix.close()
+        rows = np.asarray(rows, dtype=np.int64)
+        lists_s.append(np.asarray(sc, dtype=np.float32))
+        lists_p.append(np.where(rows >= 0, rows + len(all_ids), -1))
+        all_ids.extend(ids)
+    if not lists_s:
+        return result
+    _, pos = merge_pages_host(lists_s, lists_p, depth)                # every query's global list, best first
+    sc, ids, _ = fuse_lists(pos, lims, topk, c, weights, dev)
+    for gi, g in enumerate(groups):
+        for s, j in zip(np.asarray(sc)[gi], np.asarray(ids)[gi]):
+            if j >= 0:
+                result[g][all_ids[int(j)]] = float(s)
+    return result
+
+
 def mine_negatives(args, positives_of_query, start: int, count: int, index_factory: Optional[Callable] = None
                    ) -> Dict[str, List[str]]:
     """Hard negatives for a trainer that takes one positive and a list of negatives per query (the reference's train_dataset):
