@@ -680,9 +680,9 @@ int vr_index_group_range_search_stats(vr_index_t ix, int64_t* out3, int32_t rese
  * empty group, a group of more than 256 sub-queries, lims[n_groups] != n_sub: VR_ERR_INVALID; the filter checks are those of
  * vr_index_search_window (on the device an out-of-range filter index gives a row of tails).  n_groups == 0 (then n_sub == 0):
  * VR_OK, nothing is launched.  An empty index: tails, nothing is launched.  Nothing is stored between calls.  A host caller's
- * call synchronises the stream.  Not offered: weighted-sum fusion (linear: sum the queries into one), a window offset, groups of
- * documents, MMR over a fused pool, corpus-sharded ranks, groups of more than 256 sub-queries.  Reciprocal-rank fusion, which
- * fuses positions and not scores, is vr_index_search_rrf below. */
+ * call synchronises the stream.  Not offered: weighted-sum fusion (linear: sum the queries into one), a window offset, MMR over
+ * a fused pool, corpus-sharded ranks, groups of more than 256 sub-queries; groups of documents are vr_index_search_multi_groups
+ * below.  Reciprocal-rank fusion, which fuses positions and not scores, is vr_index_search_rrf below. */
 int vr_index_search_multi(vr_index_t ix, const float* queries, int32_t n_sub,
                           const int64_t* lims,              /* host [n_groups + 1] */
                           int32_t n_groups, int32_t k,
@@ -693,6 +693,46 @@ int vr_index_search_multi(vr_index_t ix, const float* queries, int32_t n_sub,
 /* Fused searches since the last reset: out3 = {groups, band columns re-scored in fp32, fp32 row dot products (columns x group
  * size)} — 64-bit counters in device memory. */
 int vr_index_multi_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
+/* ---- fused document search: the top-k documents by max or min over a question's sub-queries, with the evidence ---- */
+/* vr_index_search_multi_groups: vr_index_search_multi with DOCUMENTS (the groups of adjacent rows of vr_index_set_groups) in the
+ * place of rows.  A multi-hop question decomposes into sub-questions that different pages of one document answer; the document
+ * wanted is the one whose best page per sub-question is good for every sub-question.  A question is a group of 1..256 sub-queries,
+ * given through lims exactly as vr_index_search_multi takes it.  For question g with filter f (-1 or none: every row),
+ * sub-queries j = 0 .. m - 1 and document D:
+ *     D is PRESENT if f allows at least one of its pages;
+ *     E_j(D)  = max e_j(i) over the ALLOWED pages i of D, row_j(D) the lowest allowed row attaining it;
+ *     F(D)    = max_j E_j(D) (fuse = 0, "any-of")  or  min_j E_j(D) (fuse = 1, "all-of");
+ *     which(D) = the lowest j whose E_j(D) has exactly F(D)'s bits, best_row(D) = row_which(D)
+ * with e_j(i) the library's one fp32 dot product (the bits vr_index_search returns for that pair) and every max and min taken in
+ * the ranking's order of floats (-0.0 < +0.0).  Present documents rank by F descending, then lower document first: out_scores /
+ * out_rows / out_docs / out_which [n_groups][k] hold (F, best_row, D, which), slots at or past the number of present documents
+ * (-inf, -1, -1, -1).  The EVIDENCE (out_ev_scores / out_ev_rows, both NULL or both set; one of each: VR_ERR_INVALID) is what
+ * goes to a generator: flat [n_sub * k] arrays, question g's block starts at k * lims[g] and reads as [k][m_g] — slot-major,
+ * then sub-query — holding (E_j(D), row_j(D)) of the slot's document, (-inf, -1) in a tail slot.
+ *   Layout: lims is a HOST array; queries, filter_of_group [n_groups] int32 and every output are all host or all device per
+ * `on_device`.
+ *   Exactness: |b_j(i) - e_j(i)| <= eps_j for the bf16 MFMA scores; the masked document maximum B_j(D) lies within eps_j of
+ * E_j(D), the fused value BF(D) within eps_g = max_j eps_j of F(D), the r-th largest BF within eps_g of the r-th largest F.  With
+ * v_z the min(k, present)-th largest BF, a document with BF < v_z - 2 eps_g is strictly behind the whole result; every other
+ * document is re-scored: per sub-query every page with b_j(i) >= B_j(D) - 2 eps_j — only such a page can attain E_j(D) — gets
+ * one fp32 dot.  No candidate margin, no widening, no flagged question; exact in every setting of vr_index_set_search_eps (with
+ * certification off the default error model defines eps).
+ *   Checks: every check of vr_index_search_multi, with the same codes, before any launch; no grouping set, or a filter named
+ * while none is set: VR_ERR_STATE.  Errors leave every output untouched.  n_groups == 0 launches nothing; an empty index
+ * returns tails; a device filter id out of range allows nothing.  Nothing is stored, and no other search's state or counters
+ * are touched.  A host caller's call synchronises the stream.  Not offered: a window offset, documents under MMR,
+ * corpus-sharded ranks, questions of more than 256 sub-queries. */
+int vr_index_search_multi_groups(vr_index_t ix, const float* queries, int32_t n_sub,
+                                 const int64_t* lims,              /* host [n_groups + 1] */
+                                 int32_t n_groups, int32_t k,
+                                 int32_t fuse,                     /* 0: max, 1: min */
+                                 const int32_t* filter_of_group,   /* NULL: no filter for any question */
+                                 float* out_scores, int64_t* out_rows, int64_t* out_docs, int32_t* out_which,   /* [n_groups][k] */
+                                 float* out_ev_scores, int64_t* out_ev_rows,   /* NULL, or [n_sub * k] */
+                                 int32_t on_device, void* stream);
+/* Fused document searches since the last reset: out3 = {questions, band documents re-scored, fp32 page dot products} — 64-bit
+ * counters in device memory. */
+int vr_index_multi_group_search_stats(vr_index_t ix, int64_t* out3, int32_t reset);
 /* ---- rank-fusion search: the top-k of reciprocal-rank fusion (RRF) over the lists of a group's sub-queries ---- */
 /* RRF fuses POSITIONS, not scores: it needs no comparable score scales, so a paraphrase with a flat score profile and one with a
  * peaked profile count the same, and lists under different filters, of pages and of documents, or from different indexes can be

@@ -127,6 +127,8 @@ SIGNATURES = {
     "vr_index_group_range_search_stats": (C.c_int, [_vp, C.POINTER(_i64), _i32]),
     "vr_index_search_multi": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
     "vr_index_multi_search_stats": (C.c_int, [_vp, C.POINTER(_i64), _i32]),
+    "vr_index_search_multi_groups": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "vr_index_multi_group_search_stats": (C.c_int, [_vp, C.POINTER(_i64), _i32]),
     "vr_rrf_fuse": (C.c_int, [C.c_int, _vp, _i32, _i32, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _i32, _vp]),
     "vr_rrf_max_entries": (C.c_int, []),
     "vr_index_search_rrf": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp]),

@@ -1,5 +1,5 @@
 // The search index's handle and the host helpers its three files share: index.hip (life cycle, vr_index_search*), index_searches.hip
-// (the score-row searches: groups, filtered, range, rank, window, document window, document rank, document range, fused, diverse, rank fusion) and index_rows.hip (editing in place).
+// (the score-row searches: groups, filtered, range, rank, window, document window, document rank, document range, fused, fused document, diverse, rank fusion) and index_rows.hip (editing in place).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,7 +12,7 @@
 constexpr int CERT_WORDS = 32, CERT_FLAG = 2, CERT_FLAG2 = 3, CERT_STATS = 4, CERT_NSTATS = 6;   // (the two flag counters are consecutive: cleared together)
 constexpr int GRP_STATS = 2, GRP_LIST = 8, GRP_WORDS = GRP_LIST + 256;
 constexpr int FLT_STATS = 2, FLT_LIST = 8, FLT_WORDS = FLT_LIST + 256;
-constexpr int RNG_TOTAL = 3, RNG_WORDS = RNG_TOTAL + 1, RNK_WORDS = 3, WIN_WORDS = 3, MUL_WORDS = 3, GWIN_WORDS = 3, GRNK_WORDS = 3, GRNG_TOTAL = 3, GRNG_WORDS = GRNG_TOTAL + 1;   // (u64 words; 0..2 the counters)
+constexpr int RNG_TOTAL = 3, RNG_WORDS = RNG_TOTAL + 1, RNK_WORDS = 3, WIN_WORDS = 3, MUL_WORDS = 3, GWIN_WORDS = 3, GRNK_WORDS = 3, GRNG_TOTAL = 3, GRNG_WORDS = GRNG_TOTAL + 1, MGRP_WORDS = 3;   // (u64 words; 0..2 the counters)
 
 struct vr_index_s {
     int device = 0, dim = 0;
@@ -86,6 +86,13 @@ struct vr_index_s {
         DevBuf lims, fsub, edge, which, state;   // int lims of the call's groups | int filter of every sub-query | f32 band edge of a
                                       // block's groups | staged out_which | u64 words: [0..2] the counters of vr_index_multi_search_stats
     } mul;
+    struct {                          // fused document search (vr_index_search_multi_groups, search_multi_group.hip): no stored result
+        DevBuf lims, fsub, B, F, eps, edge, docs, which, evs, evr, state;   // int lims of the call's questions | int filter of every
+                                      // sub-query | document maxima [256][ldB], only read | fused rows [256][ldB], rewritten in place |
+                                      // f32 eps of a block's sub-queries | f32 band edge [256], then int present documents [256], of a
+                                      // block's questions | staged out_docs | out_which | out_ev_scores | out_ev_rows | u64 words:
+                                      // [0..2] the counters of vr_index_multi_group_search_stats
+    } mgrp;
     struct {                          // rank-fusion search (vr_index_search_rrf, search_rrf.hip): no stored result
         DevBuf scores, ids, groups;   // the pool — the plain, the filtered or the document window search's result for k = depth, by
                                       // that search as it stands — f32 [n_sub][depth] | int64 rows | int64 groups (by_groups: the lists)

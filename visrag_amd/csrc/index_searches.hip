@@ -841,6 +841,127 @@ extern "C" int vr_index_search_multi(vr_index_t ix, const float* queries, int32_
     return VR_OK;
 }
 
+// ---- fused document search (search_multi_group.hip) ---------------------------------------------------------------------------
+extern "C" int vr_index_multi_group_search_stats(vr_index_t ix, int64_t* out3, int32_t reset) {
+    if (!ix || !out3) return fail(VR_ERR_INVALID, "NULL argument");
+    return read_counters<unsigned long long, 3>(ix, ix->mgrp.state, 0, out3, reset);
+}
+
+// The k documents of largest fused score of every question, with the best page per sub-query: whole questions packed greedily into
+// blocks of <= 256 sub-queries, and per block the (masked) score rows, their document maxima, the fusion, the band edges, the
+// rewritten fused rows and the select.  Maxima, fused rows and counters are the search's own; the grouping and the filters are
+// read.  Nothing is stored.
+extern "C" int vr_index_search_multi_groups(vr_index_t ix, const float* queries, int32_t n_sub, const int64_t* lims, int32_t n_groups,
+                                            int32_t k, int32_t fuse, const int32_t* filter_of_group, float* out_scores,
+                                            int64_t* out_rows, int64_t* out_docs, int32_t* out_which, float* out_ev_scores,
+                                            int64_t* out_ev_rows, int32_t on_device, void* stream) {
+    if (!ix || n_groups < 0 || n_sub < 0 ||
+        (n_groups > 0 && (!queries || !lims || !out_scores || !out_rows || !out_docs || !out_which)))
+        return fail(VR_ERR_INVALID, "bad arguments");
+    if ((out_ev_scores != nullptr) != (out_ev_rows != nullptr))
+        return fail(VR_ERR_INVALID, "the evidence outputs are both NULL or both set");
+    if (k <= 0 || k > search_bigk_max()) return fail(VR_ERR_INVALID, "k=%d unsupported (1..%d)", k, search_bigk_max());
+    if (fuse != 0 && fuse != 1) return fail(VR_ERR_INVALID, "fuse=%d unsupported (0: max, 1: min)", (int)fuse);
+    if (!range_dim_ok(ix->dim)) return fail(VR_ERR_INVALID, "dim %d unsupported", ix->dim);
+    if (n_groups == 0) {
+        if (n_sub != 0) return fail(VR_ERR_INVALID, "%d sub-queries in no question", (int)n_sub);
+        return VR_OK;                             // no question: no launch
+    }
+    if (lims[0] != 0) return fail(VR_ERR_INVALID, "lims[0] = %lld, not 0", (long long)lims[0]);
+    for (int32_t g = 0; g < n_groups; ++g) {
+        const int64_t m = lims[g + 1] - lims[g];
+        if (m < 0) return fail(VR_ERR_INVALID, "lims[%d] = %lld decreases", (int)g + 1, (long long)lims[g + 1]);
+        if (m == 0) return fail(VR_ERR_INVALID, "question %d is empty", (int)g);
+        if (m > 256) return fail(VR_ERR_INVALID, "question %d holds %lld sub-queries (1..256)", (int)g, (long long)m);
+    }
+    if (lims[n_groups] != n_sub)
+        return fail(VR_ERR_INVALID, "lims[%d] = %lld, not the %d sub-queries", (int)n_groups, (long long)lims[n_groups], (int)n_sub);
+    if (filter_of_group) VRCHK(check_filter_ids(ix, filter_of_group, n_groups, on_device, "filter_of_group"));
+    VRCHK(set_dev(ix->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n_out = (size_t)n_groups * k, n_ev = out_ev_scores ? (size_t)n_sub * k : 0;
+    if (ix->n == 0) {                             // no row: tails, no launch
+        VRCHK(fill_tails(out_scores, out_rows, out_which, n_out, on_device, s));
+        VRCHK(fill_tails(out_scores, out_docs, nullptr, n_out, on_device, s));
+        if (n_ev) VRCHK(fill_tails(out_ev_scores, out_ev_rows, nullptr, n_ev, on_device, s));
+        return VR_OK;
+    }
+    if (ix->grp.n_groups <= 0) return fail(VR_ERR_STATE, "no grouping set for the rows of the index (vr_index_set_groups)");
+    if (!ix->mgrp.state.p) VRCHK(ix->mgrp.state.alloc(MGRP_WORDS * 8));
+    const int nd = (int)ix->grp.n_groups;
+    const int64_t ldS = pad256l(ix->n), ldB = (ix->grp.n_groups + 63) / 64 * 64;
+    const int64_t qblk = 256;                     // one fp32 score row per sub-query, as on the deep path
+    const float* q32 = nullptr;
+    VRCHK(stage_queries(ix, queries, n_sub, pad256l(std::min<int64_t>(n_sub, qblk)), on_device, s, &q32));
+    std::vector<int> lims32((size_t)n_groups + 1);
+    for (int32_t g = 0; g <= n_groups; ++g) lims32[g] = (int)lims[g];
+    const int* glims = nullptr;
+    VRCHK(stage_input(ix->mgrp.lims, lims32.data(), lims32.size(), 0, s, &glims));
+    VRCHK(ix->mgrp.edge.reserve((size_t)qblk * 8));
+    VRCHK(ix->mgrp.eps.reserve((size_t)qblk * 4));
+    const int* fog = nullptr;
+    if (filter_of_group) {                        // the question's filter for every one of its score rows: what the mask reads
+        VRCHK(stage_input(ix->flt.ids, filter_of_group, (size_t)n_groups, on_device, s, &fog));
+        VRCHK(ix->mgrp.fsub.reserve((size_t)n_sub * 4));
+        HIPCHK(launch_multi_expand(glims, fog, n_groups, ix->mgrp.fsub.as<int>(), s));
+    }
+    HIPCHK(hipStreamSynchronize(s));              // (the host arrays are free from here on)
+    float* os = nullptr; int64_t* oi = nullptr; int64_t* od = nullptr; int32_t* ow = nullptr; float* es = nullptr; int64_t* er = nullptr;
+    VRCHK(stage_output(ix->os, out_scores, n_out, on_device, &os));
+    VRCHK(stage_output(ix->oi, out_rows, n_out, on_device, &oi));
+    VRCHK(stage_output(ix->mgrp.docs, out_docs, n_out, on_device, &od));
+    VRCHK(stage_output(ix->mgrp.which, out_which, n_out, on_device, &ow));
+    if (n_ev) {
+        VRCHK(stage_output(ix->mgrp.evs, out_ev_scores, n_ev, on_device, &es));
+        VRCHK(stage_output(ix->mgrp.evr, out_ev_rows, n_ev, on_device, &er));
+    }
+    VRCHK(ix->sbuf.reserve((size_t)qblk * ldS * 4));
+    VRCHK(ix->mgrp.B.reserve((size_t)qblk * ldB * 4));
+    VRCHK(ix->mgrp.F.reserve((size_t)qblk * ldB * 4));
+    float* S = ix->sbuf.as<float>();
+    for (int32_t g0 = 0; g0 < n_groups;) {
+        int32_t g1 = g0 + 1;                      // whole questions while the block holds <= 256 sub-queries
+        while (g1 < n_groups && lims[g1 + 1] - lims[g0] <= qblk) ++g1;
+        const int64_t s0 = lims[g0];
+        const int nb = (int)(lims[g1] - s0), nqs = g1 - g0;
+        MultiGroupArgs p{};
+        p.a = block_view(ix, q32, s0, nb, k, true);                        // (the band is defined by the error model)
+        p.a.out_scores = os + (size_t)g0 * k; p.a.out_ids = oi + (size_t)g0 * k;
+        p.out_docs = od + (size_t)g0 * k; p.out_which = ow + (size_t)g0 * k;
+        p.out_ev_scores = es; p.out_ev_rows = er;                          // (the call's arrays: indexed by the call's lims)
+        p.lims = glims + g0;
+        p.sub_base = (int)s0;
+        p.fuse = fuse;
+        p.goff = ix->grp.off.as<int>(); p.n_groups = nd;
+        p.B = ix->mgrp.B.as<float>(); p.ldB = (size_t)ldB;
+        p.F = ix->mgrp.F.as<float>();
+        p.eps_sub = ix->mgrp.eps.as<float>();
+        p.filter_of_group = fog ? fog + g0 : nullptr;
+        p.n_filters = (int)ix->flt.n_filters;
+        p.edges = ix->mgrp.edge.as<float>();
+        p.present = ix->mgrp.edge.as<int>() + qblk;
+        p.stats = ix->mgrp.state.as<unsigned long long>();
+        VRCHK(score_block(ix, q32, s0, nb, ldS, nullptr, s));
+        if (fog) VRCHK(mask_block(ix, ix->mgrp.fsub.as<int>() + s0, nb, ldS, nullptr, nullptr, 0, s));
+        HIPCHK(launch_group_max(S, (size_t)ldS, p.goff, nd, ix->mgrp.B.as<float>(), p.ldB, nb, nullptr, 0, s));
+        HIPCHK(launch_multi_group_fuse(p, nqs, s));
+        HIPCHK(launch_multi_group_edges(p, nqs, s));
+        HIPCHK(launch_multi_group_rescore(p, S, (size_t)ldS, nqs, s));
+        HIPCHK(launch_multi_group_select(p, S, (size_t)ldS, nqs, s));
+        g0 = g1;
+    }
+    VRCHK(return_output(out_scores, os, n_out, on_device, s));
+    VRCHK(return_output(out_rows, oi, n_out, on_device, s));
+    VRCHK(return_output(out_docs, od, n_out, on_device, s));
+    VRCHK(return_output(out_which, ow, n_out, on_device, s));
+    if (n_ev) {
+        VRCHK(return_output(out_ev_scores, es, n_ev, on_device, s));
+        VRCHK(return_output(out_ev_rows, er, n_ev, on_device, s));
+    }
+    if (!on_device) HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
+}
+
 // ---- diversified search (search_diverse.hip) ----------------------------------------------------------------------------------
 // k rows per query picked by maximal marginal relevance from the pool of its `pool` best rows.  The pool is the plain or the
 // filtered search's own result, produced by that search as it stands on the staged queries with device outputs of the diverse

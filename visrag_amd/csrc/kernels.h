@@ -564,6 +564,37 @@ hipError_t launch_multi_edges(const MultiSearchArgs& p, const float* S, size_t l
 hipError_t launch_multi_rescore(const MultiSearchArgs& p, float* S, size_t ldS, int n_groups, hipStream_t s);
 // the k best of the rewritten fused rows -> a.out_scores / a.out_ids / out_which, (-inf, -1, -1) past the allowed rows
 hipError_t launch_multi_select(const MultiSearchArgs& p, const float* S, size_t ldS, int n_groups, hipStream_t s);
+// ---- fused document search (search_multi_group.hip): the k groups of rows (documents) of largest max (or min) over a question's
+// sub-queries of the document's best allowed page, with the best page per sub-query (the evidence)
+struct MultiGroupArgs {
+    SearchArgs a;                    // the block's view, as MultiSearchArgs': q_f32 and nq are the block's SUB-QUERIES (whole questions, <= 256),
+                                     // k, out_scores / out_ids (best rows) [questions][k]: the block's part (no out_keys), a valid error model
+    const int* lims;                 // [questions + 1] device: the block's entries of the call's lims (the call's own numbering)
+    int sub_base;                    // the call's index of the block's first sub-query (= lims[0]): score row of sub-query s is s - sub_base
+    int fuse;                        // 0: max over the question, 1: min
+    const int* goff;                 // [n_groups + 1] first row of every document; goff[n_groups] = n_docs
+    int n_groups;
+    const float* B; size_t ldB;      // [nq][ldB] document maxima of the (masked) score rows: launch_group_max; only read
+    float* F;                        // [questions][ldB] the fused rows: written by the fusion, rewritten in place by the re-scoring
+    float* eps_sub;                  // [nq] scratch: query_eps of every sub-query of a non-empty question
+    const int* filter_of_group;      // [questions] device or null: the score rows have been masked with the question's filter in every
+    int n_filters;                   //   sub-row; an entry outside [-1, n_filters): a row of tails
+    float* edges;                    // [questions] scratch: the band's lower edge lo of fused bf16 values (NaN: no document present)
+    int* present;                    // [questions] scratch: documents with an allowed page
+    int64_t* out_docs;               // [questions][k] the block's part: the document of every result (-1: a tail)
+    int* out_which;                  // [questions][k] the block's part: the in-question sub-query that decided it (-1: a tail)
+    float* out_ev_scores; int64_t* out_ev_rows;   // both null, or the CALL's evidence arrays [n_sub * k]: question g's block starts at
+                                     // k * lims[g] and reads [k][m_g] = (E_j(D), row_j(D)); (-inf, -1) in a tail
+    unsigned long long* stats;       // [0] questions [1] band documents re-scored [2] fp32 page dots
+};
+// F rows [0, n_questions) = column-wise max / min of the questions' B rows
+hipError_t launch_multi_group_fuse(const MultiGroupArgs& p, int n_questions, hipStream_t s);
+// edges / present / eps_sub from the F rows; F is only read
+hipError_t launch_multi_group_edges(const MultiGroupArgs& p, int n_questions, hipStream_t s);
+// the F rows rewritten in place: -inf certainly behind or absent, F(D) at or above the edge; S and B are only read
+hipError_t launch_multi_group_rescore(const MultiGroupArgs& p, const float* S, size_t ldS, int n_questions, hipStream_t s);
+// the k best of the rewritten F rows -> out_scores / out_ids / out_docs / out_which (/ the evidence), tails past the present documents
+hipError_t launch_multi_group_select(const MultiGroupArgs& p, const float* S, size_t ldS, int n_questions, hipStream_t s);
 // ---- diversified search (search_diverse.hip): k rows per query picked by maximal marginal relevance from a pool of its best rows
 struct MmrArgs {
     const float* index_f32;          // [n_docs][dim] f32

@@ -32,6 +32,12 @@ __device__ __forceinline__ float one_ulp_up(float x) {
 __device__ __forceinline__ uint64_t make_key(float score, uint32_t id) {
     return ((uint64_t)f32_orderable(score) << 32) | (uint32_t)(~id);
 }
+// the better of two scores under a fusion (0: max, 1: min), on orderable keys (ties: the same bits either way): search_multi.hip,
+// search_multi_group.hip
+__device__ __forceinline__ float multi_pick(float a, float b, int fuse) {
+    const bool b_larger = f32_orderable(b) > f32_orderable(a);
+    return (b_larger != (fuse != 0)) ? b : a;
+}
 constexpr uint64_t KEY_NONE = 0;    // below every real key (score -inf, id 0xffffffff -> ~ = 0 ...)
 // the key of a row RE-SCORED from a score row that may hold NaN (the deep path, the exact pass): a NaN fp32 score never ranks
 // (include/visrag_hip.h: vr_index_search) — without this a positive NaN is the largest key there is

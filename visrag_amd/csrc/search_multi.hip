@@ -48,12 +48,6 @@ struct MultiEdgeLds {
     float eps[4];                           // the largest query_eps every wave met
 };
 
-// the better of two scores under the fusion, on orderable keys (ties: the same bits either way)
-__device__ __forceinline__ float multi_pick(float a, float b, int fuse) {
-    const bool b_larger = f32_orderable(b) > f32_orderable(a);
-    return (b_larger != (fuse != 0)) ? b : a;
-}
-
 // rows group g may see (search_common.h: rows_allowed); no filter array: every group is on -1
 __device__ __forceinline__ int group_rows(const MultiSearchArgs& p, int g) {
     return rows_allowed(p.a.n_docs, p.n_filters, p.allowed, p.filter_of_group ? p.filter_of_group[g] : -1);

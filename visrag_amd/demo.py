@@ -9,6 +9,10 @@
   * `retrieve_any(knowledge_base_path, questions, topk, ...)` -> the top-k pages for a question asked in several ways, by the
                                                                best ("any-of") or the worst ("all-of") of their scores
                                                                (HipIndex.search_multi; no reference counterpart)
+  * `retrieve_documents_any(knowledge_base_path, questions, topk, ...)` -> the top-k DOCUMENTS for a question asked in several
+                                                               parts, each part answered by the document's best page for it, and
+                                                               with `return_evidence` those pages (HipIndex.search_multi_groups;
+                                                               no reference counterpart)
   * `retrieve_documents(knowledge_base_path, query, topk, ...)` -> the best page of each of the top-k DOCUMENTS
                                                                (no reference counterpart: its top-k is pages)
     (`documents=[...]`: only those documents are ranked; `offset=n`: the next page of documents — HipIndex.search_groups_window)
@@ -357,6 +361,59 @@ def retrieve_documents(knowledge_base_path: str, query, topk: int, model, tokeni
     if own:
         index.close()
     return (paths, scores) if return_scores else paths
+
+
+@torch.no_grad()
+def retrieve_documents_any(knowledge_base_path: str, questions, topk: int, model, tokenizer, index=None, names=None,
+                           fuse: str = "max", documents=None, return_evidence: bool = False):
+    """Paths of the deciding page of each of the `topk` DOCUMENTS that serve a question asked in several parts (None if the base
+    does not exist): `questions` as in `retrieve_any` — strings or their embeddings [m, dim] — form one group.  Per question a
+    document scores as its best page does; `fuse="max"` ("any-of") ranks it by its best question, `fuse="min"` ("all-of") by its
+    worst, so the sub-questions of a multi-hop question may be answered by DIFFERENT pages of the document
+    (HipIndex.search_multi_groups: exact).  The index is a document base (`load_document_base`), as in `retrieve_documents`.
+    `documents`: only those documents are ranked (one filter, set for this question); a name no page carries raises ValueError.
+    With `return_evidence` -> (paths, scores, evidence): `evidence[i]` lists, for document i and every question in order, (path of
+    the document's best page for that question, its score) — the pages to hand to the generator."""
+    if not os.path.exists(knowledge_base_path):
+        return None
+    own = index is None
+    if own:
+        index, names = load_document_base(knowledge_base_path, model.encoder.device if model is not None else None)
+    elif not index.n_groups:
+        order, offsets, _ = group_rows([doc_of_page(n) for n in names])
+        if not np.array_equal(order, np.arange(len(order))):
+            raise ValueError("the pages of a document are not adjacent in this index: load it with load_document_base()")
+        index.set_groups(offsets)
+    n = len(index)
+    if isinstance(questions, (list, tuple)) and all(isinstance(x, str) for x in questions):
+        q = encode(model, tokenizer, [QUERY_INSTRUCTION + x for x in questions])
+    else:
+        q = np.asarray(questions.detach().cpu() if isinstance(questions, torch.Tensor) else questions, dtype=np.float32)
+    q = np.ascontiguousarray(np.asarray(q, dtype=np.float32).reshape(-1, index.dim))
+    mask, present = None, int(index.n_groups) if n else 0
+    if documents is not None:
+        docs = [doc_of_page(nm) for nm in names[:n]]
+        wanted = set(documents)
+        unknown = sorted(wanted - set(docs))
+        if unknown:
+            raise ValueError(f"no page of the base belongs to {unknown[0]!r}" + (f" (and {len(unknown) - 1} more)" if len(unknown) > 1 else ""))
+        mask = label_filters(docs, [wanted])
+        present = len(wanted)
+    k = min(topk, present, 1000)
+    paths, scores, evidence = [], [], []
+    if k > 0 and len(q) > 0:
+        if mask is not None:
+            index.set_filters(mask)
+        sc, rows, _, _, ev_s, ev_r = (x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in
+                                      index.search_multi_groups(q, [0, len(q)], k, fuse, None if mask is None else 0, evidence=True))
+        keep = [int(i) for i in rows[0] if i >= 0]
+        paths = [os.path.join(knowledge_base_path, names[i]) for i in keep]
+        scores = [float(s) for s in sc[0][: len(keep)]]
+        ev_s, ev_r = ev_s.reshape(k, len(q)), ev_r.reshape(k, len(q))
+        evidence = [[(os.path.join(knowledge_base_path, names[int(r)]), float(s)) for r, s in zip(ev_r[i], ev_s[i])] for i in range(len(keep))]
+    if own:
+        index.close()
+    return (paths, scores, evidence) if return_evidence else paths
 
 
 def _document_window(knowledge_base_path, q, topk, index, names, documents, offset):

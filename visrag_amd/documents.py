@@ -357,6 +357,31 @@ def fuse_runs(scores, ids, lims, k: int, fuse: str = "max") -> Tuple[np.ndarray,
     return out_s, out_i, determined
 
 
+def evidence_pages(ev_rows, ev_scores, limit: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """The page list a generator gets from ONE question's evidence of `HipIndex.search_multi_groups(evidence=True)`:
+    `ev_rows` / `ev_scores` [k][m] hold, per returned document (slot) and sub-question, the document's best page and its score.
+    -> (rows i64, scores f32): the DISTINCT evidence rows in (slot, sub-question) order — the best document's pages first —
+    each with the best score seen for it (one page may serve several sub-questions), tail entries (-1) skipped, cut at `limit`
+    pages."""
+    rows = np.asarray(ev_rows, dtype=np.int64)
+    scores = np.asarray(ev_scores, dtype=np.float32)
+    if rows.shape != scores.shape:
+        raise ValueError("ev_rows and ev_scores must have one shape")
+    if limit is not None and limit < 0:
+        raise ValueError("limit must be >= 0")
+    best: dict = {}                                    # row -> best score; dicts keep the order of first appearance
+    for r, v in zip(rows.reshape(-1).tolist(), scores.reshape(-1).tolist()):
+        if r < 0:
+            continue
+        if r not in best:
+            if limit is not None and len(best) >= limit:
+                continue
+            best[r] = v
+        elif v > best[r]:
+            best[r] = v
+    return np.asarray(list(best.keys()), dtype=np.int64), np.asarray(list(best.values()), dtype=np.float32)
+
+
 RRF_ID_MAX = 2 ** 31 - 2        # ids of a rank fusion lie in [0, RRF_ID_MAX]; anything else is an empty slot
 
 

@@ -835,6 +835,55 @@ class HipIndex:
         band column against every sub-query of its group)."""
         return self._stats3(self.lib.vr_index_multi_search_stats, ("groups", "candidates", "dots"), reset)
 
+    # ---- fused document search (include/visrag_hip.h: vr_index_search_multi_groups) ----
+    def search_multi_groups(self, queries, lims, k: int, fuse: str = "max", filter_of_group=None, evidence: bool = False):
+        """The k documents (`set_groups`) of largest fused score per question (include/visrag_hip.h:
+        vr_index_search_multi_groups) -> (scores [n_questions,k] f32, best rows [n_questions,k] i64, docs [n_questions,k] i64,
+        which [n_questions,k] i32).  A document is present if the question's filter allows one of its pages; per sub-query j it
+        scores E_j(D) = its best ALLOWED page's fp32 score — the bits `search` returns — and its fused score is the max
+        (`fuse="max"`, "any-of") or the min (`fuse="min"`, "all-of") of them over the question's sub-queries.  Documents come
+        score descending, then lower document first; slots past the present documents are (-inf, -1, -1, -1).  `which` is the
+        lowest sub-query whose E_j(D) IS the fused score, the best row that sub-query's best page (the lowest among equals).
+        With `evidence=True` two more arrays follow: (ev_scores f32, ev_rows i64), flat [n_sub * k]; question g's block starts at
+        k * lims[g] and reads as [k][m_g] — per returned document the best page of EVERY sub-query and its score, (-inf, -1) in a
+        tail slot (documents.evidence_pages makes a generator's page list of one question's block).  `queries`, `lims` and
+        `filter_of_group` as in `search_multi`; with [n_questions][m][dim] and `lims=None` the evidence comes as
+        [n_questions][k][m].  1 <= k <= 1000.  cuda in -> cuda out, numpy / cpu in -> numpy out."""
+        if fuse not in ("max", "min"):
+            raise ValueError("fuse must be 'max' or 'min'")
+        q, cuda, lim = self._grouped_queries(queries, lims)
+        ng, n_sub = len(lim) - 1, int(q.shape[0])
+        if filter_of_group is None:
+            keep, fptr = None, C.c_void_p(None)
+        else:
+            keep, fptr = self._filter_of_query(torch.empty((ng, 0), device=q.device) if cuda else np.empty((ng, 0)), filter_of_group)
+        kk = max(k, 0)
+        if cuda:
+            outs = [torch.empty((ng, kk), dtype=d, device=q.device) for d in (torch.float32, torch.int64, torch.int64, torch.int32)]
+            if evidence:
+                outs += [torch.empty(n_sub * kk, dtype=d, device=q.device) for d in (torch.float32, torch.int64)]
+            ptrs = [x.data_ptr() for x in [q] + outs]
+        else:
+            outs = [np.empty((ng, kk), dtype=d) for d in (np.float32, np.int64, np.int64, np.int32)]
+            if evidence:
+                outs += [np.empty(n_sub * kk, dtype=d) for d in (np.float32, np.int64)]
+            ptrs = [x.ctypes.data for x in [q] + outs]
+        ev = [C.c_void_p(ptrs[5]), C.c_void_p(ptrs[6])] if evidence else [C.c_void_p(None), C.c_void_p(None)]
+        _lib.check(self.lib.vr_index_search_multi_groups(self._h, C.c_void_p(ptrs[0]), n_sub, C.c_void_p(lim.ctypes.data), ng, k,
+                                                         0 if fuse == "max" else 1, fptr, C.c_void_p(ptrs[1]), C.c_void_p(ptrs[2]),
+                                                         C.c_void_p(ptrs[3]), C.c_void_p(ptrs[4]), *ev, 1 if cuda else 0,
+                                                         C.c_void_p(_stream_ptr(self.device))),
+                   "vr_index_search_multi_groups")
+        del keep
+        if evidence and lims is None:
+            outs[4:] = [x.reshape(ng, kk, n_sub // max(ng, 1)) for x in outs[4:]]
+        return tuple(outs)
+
+    def multi_group_search_stats(self, reset: bool = False) -> Dict[str, int]:
+        """Fused document searches since the last reset: questions, documents of the error bands re-scored, fp32 page dot
+        products."""
+        return self._stats3(self.lib.vr_index_multi_group_search_stats, ("questions", "documents", "page_dots"), reset)
+
     # ---- rank-fusion search (include/visrag_hip.h: vr_index_search_rrf) ----
     def search_rrf(self, queries, lims, k: int, depth: int = 100, c: float = 60.0, weights=None, filter_of_group=None,
                    documents: bool = False):

@@ -624,6 +624,71 @@ def retrieve_fused(args, group_of_query: Callable, topk: int, fuse: str = "max",
     return result
 
 
+def retrieve_documents_fused(args, group_of_query: Callable, topk: int, doc_of: Callable[[str], str], fuse: str = "max",
+                             label_of_doc: Optional[Callable[[str], object]] = None,
+                             labels_of_group: Optional[Callable[[Hashable], Optional[set]]] = None,
+                             index_factory: Optional[Callable] = None
+                             ) -> Tuple[Dict[Hashable, Dict[str, float]], Dict[Hashable, Dict[str, List[str]]]]:
+    """retrieve_fused with DOCUMENTS in the place of rows, over the same pickle shards: the queries are grouped into questions by
+    `group_of_query(qid)`, the corpus rows are pages, `doc_of(page_id)` the document of a page.  Per sub-query a document scores
+    as its best page does, and a question ranks the documents by the max (`fuse="max"`) or the min (`fuse="min"`) of that over its
+    sub-queries — the sub-questions of a multi-hop question may be answered by different pages of one document
+    (HipIndex.search_multi_groups: exact).  With `label_of_doc` and `labels_of_group` question g ranks only the documents whose
+    label is in `labels_of_group(g)` (None = every document), one filter per distinct label set.
+    -> ({group: {doc: score}}, {group: {doc: [page id per sub-query]}}): the `topk` best documents, best first, and for each the
+    evidence — its best page for every sub-query of the question, in the order the question's queries appear; the first dict goes
+    to `save_as_trec` as it is.  1 <= topk <= 1000, questions of at most 256 queries.
+
+    Replicated form only: the shards go into one index reordered so that every document's pages are adjacent, as
+    retrieve_documents_filtered builds it."""
+    make_index = index_factory or HipIndex
+    queries, qids, _ = _load_queries(args)
+    corpus_parts = list_shards(args.output_dir, "corpus")
+    if len(corpus_parts) == 0:
+        raise ValueError("No pre-computed document embeddings found")
+    topk = int(topk)
+    q_order, lims, groups = group_rows([group_of_query(q) for q in qids])
+    scores: Dict[Hashable, Dict[str, float]] = {g: {} for g in groups}
+    pages: Dict[Hashable, Dict[str, List[str]]] = {g: {} for g in groups}
+    reps, page_ids = [], []
+    for p in corpus_parts:
+        r, i = read_shard(p)
+        if len(i):
+            reps.append(np.asarray(r, dtype=np.float32))
+            page_ids.extend(i)
+    if not page_ids or len(groups) == 0 or topk <= 0:
+        return scores, pages
+    grouped = np.ascontiguousarray(np.asarray(queries, dtype=np.float32)[q_order])
+    order, offsets, docs = group_rows([doc_of(i) for i in page_ids])
+    ix = make_index(queries.shape[1], len(page_ids), _device_index(args))
+    ix.add(np.concatenate(reps)[order])
+    ix.set_groups(offsets)
+    filter_of_group = None
+    if label_of_doc is not None and labels_of_group is not None:
+        sets: List[Optional[frozenset]] = []
+        which: Dict[Optional[frozenset], int] = {}
+        filter_of_group = np.empty(len(groups), dtype=np.int32)
+        for gi, g in enumerate(groups):
+            wanted = labels_of_group(g)
+            key = None if wanted is None else frozenset(wanted)
+            if key not in which:
+                which[key] = len(sets)
+                sets.append(key)
+            filter_of_group[gi] = which[key]
+        ix.set_filters(collection_filters(offsets, [label_of_doc(d) for d in docs], sets))
+    k = min(topk, len(docs))
+    sc, _, dd, _, _, ev_r = ix.search_multi_groups(grouped, lims, k, fuse, filter_of_group, evidence=True)
+    ix.close()
+    for gi, g in enumerate(groups):
+        a, b = int(lims[gi]), int(lims[gi + 1])
+        ev = np.asarray(ev_r[k * a:k * b]).reshape(k, b - a)
+        for slot, (s_, d) in enumerate(zip(sc[gi], dd[gi])):
+            if d >= 0:
+                scores[g][docs[int(d)]] = float(s_)
+                pages[g][docs[int(d)]] = [page_ids[int(order[int(r)])] for r in ev[slot]]
+    return scores, pages
+
+
 def retrieve_rrf(args, group_of_query: Callable, topk: int, depth: int = 100, c: float = 60.0,
                  weight_of_query: Optional[Callable] = None, index_factory: Optional[Callable] = None,
                  fuse_lists: Optional[Callable] = None) -> Dict[Hashable, Dict[str, float]]:
