@@ -983,7 +983,29 @@ int vr_op_patch_embed(int device_id, const void* const* imgs, int32_t n, int32_t
                       void* stream);
 /* Flash attention over bf16 q/k/v with row strides ld*, per-batch row ranges cu_q/cu_kv
  * ([B+1], device), head_dim in {64,72,80,128}; causal uses absolute positions within the
- * sequence.  q_batch_stride==0 shares q across the batch (resampler). out bf16 [rows_q][ldo]. */
+ * sequence.  q_batch_stride==0 shares q across the batch (resampler). out bf16 [rows_q][ldo].
+ *
+ * What a launch may touch (every kernel behind it; tests/test_gpu_attention_isolation.py holds them to it on a buffer whose
+ * every other cell is NaN).  Item b has the q / out rows [cu_q[b], cu_q[b+1]) and the key rows [cu_kv[b], cu_kv[b+1]) (or
+ * [cu_kv[b], kv_end[b]), vr_op_attention_ex); H = heads * head_dim (K / V: H / kv_group).
+ *   READ    q: columns [0, H) of the q rows of items that have keys (q_shared: of rows [0, cu_q[b+1] - cu_q[b]) of q itself;
+ *              q_in_rows / q_head_stride: of the rows and head offsets they name), nothing else of q.
+ *           k, v: columns [0, H) of the key rows of items that have q rows, nothing else — not the row behind a range (in a
+ *              cache: stale rows), not the pitch columns [H, ld), not a neighbouring allocation.  The kernels walk keys in
+ *              tiles of 64 that run past a range's last row; what lies there never reaches a result: the loads are bounded by
+ *              the range's last row or their values are replaced (never multiplied by zero) before they are used.
+ *           cu_q, cu_kv [B+1], kv_end / q_in_rows [B].
+ *   WRITTEN out rows [cu_q[b], cu_q[b+1]) x columns [0, H), and the same rows of lse, of items that HAVE keys — every one of
+ *           those cells, and no other: not the row behind an item, not out's pitch columns [H, ldo), nothing of an item
+ *           without keys.  No input is written.
+ *   The ONE exception is a precondition of the head_dim 72 route VR_ATTN_ROUTE_72W (attention_w.hip; the ViT): it stages a
+ *   head's 72 columns as 80, so in every key row of an item it also reads the 8 elements BEHIND a head's 72 of k and of v — the next head's
+ *   first 8 columns or, for the last head, k[row][H .. H+8) and v[row][H .. H+8) — and multiplies them by zero.  Those
+ *   16 bytes must be readable and hold FINITE bf16 values (any finite value: no output bit depends on them; a NaN or an
+ *   infinity there would reach the outputs as 0 * NaN).  The route is only taken when k and v are columns of the same rows
+ *   (v - k inside one row, ldk == ldv), so the cells lie in the caller's own row buffer: in the engine (encode.hip, the only
+ *   caller on this route) the v columns behind k and, behind v, what the qkv GEMM wrote there — the row's pad columns or the
+ *   next row's q columns. */
 int vr_op_attention(int device_id, const void* q, int32_t ldq, const void* k, int32_t ldk,
                     const void* v, int32_t ldv, void* out, int32_t ldo,
                     const int32_t* cu_q, const int32_t* cu_kv, int32_t B, int32_t heads,
@@ -1010,6 +1032,28 @@ int vr_op_attention_ex(int device_id, const void* q, int32_t ldq, const void* k,
                        const int32_t* cu_q, const int32_t* cu_kv, int32_t B, int32_t heads,
                        int32_t head_dim, int32_t max_q, int32_t causal, int32_t q_shared,
                        float scale, const vr_attn_extras_t* extras, void* stream);
+/* The kernel vr_op_attention_ex reaches with the same arguments — the launch dispatches on the very function behind this, so
+ * the answer cannot drift from it.  Host arithmetic only: nothing is launched, no device is selected and no pointer is
+ * dereferenced (pointers and strides are compared with each other, so a test may pass made-up addresses).  Returns
+ *   VR_ATTN_ROUTE_NONE      nothing to do (B <= 0 or max_q <= 0): the launch succeeds without a kernel
+ *   VR_ATTN_ROUTE_REFUSED   the launch fails before anything runs (a NULL pointer, a stride off its alignment, a head_dim
+ *                           nobody implements)
+ *   VR_ATTN_ROUTE_SMALL     attention_small.hip: head_dim 64, max_q <= 80, cu_q and cu_kv the SAME buffer, no extras
+ *   VR_ATTN_ROUTE_72W       attention_w.hip: head_dim 72, non-causal, no extras, k and v columns of the same rows (0 < v - k <
+ *                           one row, heads * 72 elements apart at least, ldk == ldv), max_q >= 192 and at most 1/8 of its 256-row
+ *                           query tiles wasted (which is the stricter of the two: 224..256, 448..512, 672..768, ...)
+ *   VR_ATTN_ROUTE_TILED(head_dim, qf, pipe)   attention.hip's attention_kernel<head_dim, qf, pipe>: 64 qf query rows per
+ *                           workgroup; head_dim 64 / 72 / 80: <1, 0> up to max_q 64, <2, 0> up to 128, <2, 3> beyond; 128: <1, 0> */
+#define VR_ATTN_ROUTE_REFUSED (-1)
+#define VR_ATTN_ROUTE_NONE 0
+#define VR_ATTN_ROUTE_SMALL 1
+#define VR_ATTN_ROUTE_72W 2
+#define VR_ATTN_ROUTE_TILED(head_dim, qf, pipe) (100000 + (head_dim) * 100 + (qf) * 10 + (pipe))
+int vr_op_attention_route(int device_id, const void* q, int32_t ldq, const void* k, int32_t ldk,
+                          const void* v, int32_t ldv, void* out, int32_t ldo,
+                          const int32_t* cu_q, const int32_t* cu_kv, int32_t B, int32_t heads,
+                          int32_t head_dim, int32_t max_q, int32_t causal, int32_t q_shared,
+                          float scale, const vr_attn_extras_t* extras);
 /* Merge of the KV ranges of a decode step's attention (head_dim 128): part bf16 / lse f32 are the out / lse of
  * vr_op_attention_ex run with the `group` query heads of a KV head as rows — the layout is SkinnyCombine's in
  * csrc/kernels.h; row r of n_rows owns the 16 ranges from 16 r on, the first S (or S_dev[r], i32 on the device, when S_dev is

@@ -163,6 +163,35 @@ def op_attention_ex(q, k, v, out, cu_q, cu_kv, heads, hd, max_q, causal, q_share
     return out
 
 
+# the values of vr_op_attention_route (include/visrag_hip.h)
+ROUTE_REFUSED, ROUTE_NONE, ROUTE_SMALL, ROUTE_72W = -1, 0, 1, 2
+
+
+def route_tiled(hd, qf, pipe):
+    return 100000 + hd * 100 + qf * 10 + pipe
+
+
+def op_attention_route(q, ldq, k, ldk, v, ldv, out, ldo, cu_q, cu_kv, B, heads, hd, max_q, causal=False, q_shared=False, scale=1.0,
+                       kv_group=0, kv_end=None, q_in_rows=None, q_head_stride=0, q_prescaled=0, lse=None):
+    """The kernel vr_op_attention_ex reaches with these arguments.  Pointers are plain integers (addresses): the entry compares
+    them and dereferences none, so it runs without a GPU and on made-up values."""
+    lib = _lib.load()
+    ex = _lib.VRAttnExtras(kv_group=kv_group, kv_end=kv_end, q_in_rows=q_in_rows, q_head_stride=q_head_stride,
+                           q_prescaled=int(q_prescaled), lse=lse)
+    return int(lib.vr_op_attention_route(0, q, ldq, k, ldk, v, ldv, out, ldo, cu_q, cu_kv, B, heads, hd, max_q, int(causal),
+                                         int(q_shared), float(scale), C.byref(ex)))
+
+
+def attention_route_of(q, k, v, out, cu_q, cu_kv, heads, hd, max_q, causal, q_shared, scale, B=None, ldq=None, kv_group=0,
+                       kv_end=None, q_in_rows=None, q_head_stride=0, q_prescaled=0, lse=None):
+    """op_attention_route with the arguments of op_attention_ex (tensors)"""
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    return op_attention_route(ptr(q), ldq if ldq is not None else q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(out),
+                              out.stride(0), ptr(cu_q), ptr(cu_kv), B if B is not None else cu_kv.numel() - 1, heads, hd, max_q,
+                              causal, q_shared, scale, kv_group=kv_group, kv_end=ptr(kv_end), q_in_rows=ptr(q_in_rows),
+                              q_head_stride=q_head_stride, q_prescaled=q_prescaled, lse=ptr(lse))
+
+
 def op_attn_combine(part, lse, heads, group, out, S=0, S_dev=None, n_rows=1, ld_out=0, W=None, M=1, N=0, K=0, ksplit=1,
                     planes=1, ldo=0, split_stride=0):
     """part bf16 / lse f32: a decode attention's partial rows (layout: SkinnyCombine, csrc/kernels.h).  W None: `out` bf16

@@ -27,6 +27,12 @@ def test_library_exports_every_declared_symbol():
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in the header but not exported"
     assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
+    # the route query travels with the launch it describes: same arguments, minus the stream
+    assert {"vr_op_attention", "vr_op_attention_ex", "vr_op_attention_route"} <= declared
+    ex_args, route_args = _lib.SIGNATURES["vr_op_attention_ex"][1], _lib.SIGNATURES["vr_op_attention_route"][1]
+    assert route_args == ex_args[:-1] and _lib.SIGNATURES["vr_op_attention_route"][0] is _lib.SIGNATURES["vr_op_attention_ex"][0]
+    proto = lambda name: re.sub(r"\s+", " ", re.search(name + r"\s*\(([^;]*)\)\s*;", hdr).group(1))  # noqa: E731
+    assert proto(r"\bint vr_op_attention_route") + ", void* stream" == proto(r"\bint vr_op_attention_ex")
     # ... and the same for the generator's header
     ghdr = open(os.path.join(ROOT, "include", "visrag_gen.h")).read()
     gdecl = set(re.findall(r"\b(vg_[a-z0-9_]+)\s*\(", ghdr))

@@ -160,6 +160,8 @@ SIGNATURES = {
                                   _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
     "vr_op_attention_ex": (C.c_int, [C.c_int, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32,
                                      _i32, _i32, _i32, _i32, _i32, _f32, C.POINTER(VRAttnExtras), _vp]),
+    "vr_op_attention_route": (C.c_int, [C.c_int, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32,
+                                        _i32, _i32, _i32, _i32, _i32, _f32, C.POINTER(VRAttnExtras)]),
     "vr_op_attn_combine": (C.c_int, [C.c_int, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32,
                                      _i32, _i32, _i64, _vp]),
     "vr_op_gemm_skinny": (C.c_int, [C.c_int, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i64, _vp]),

@@ -63,33 +63,45 @@ hipError_t launch_attention_small(const AttnArgs& a, hipStream_t s);
 bool attention72w_ok(const AttnArgs& a);
 hipError_t launch_attention72w(const AttnArgs& a, hipStream_t s);
 
-hipError_t launch_attention(const AttnArgs& a_in, hipStream_t s) {
-    if (a_in.B <= 0 || a_in.max_q <= 0) return hipSuccess;
-    if ((a_in.ldq | a_in.ldk | a_in.ldv) % 8 || a_in.ldo % 4) return hipErrorInvalidValue;
-    AttnArgs a = a_in;
-    // q rows that already carry scale * log2(e): attention_w.hip takes them as they are, the other kernels multiply the scores by
-    // scale * log2(e) themselves — hand them the scale that makes that factor 1
-    if (a.q_prescaled && !attention72w_ok(a)) a.scale = 1.0f / 1.44269504088896340736f;
+// Which kernel a launch reaches — host arithmetic on the arguments only (pointers and strides are COMPARED, nothing is
+// dereferenced, nothing is launched).  launch_attention dispatches on this, so the two cannot diverge.
+AttnRoute attention_route(const AttnArgs& a) {
+    if (a.B <= 0 || a.max_q <= 0) return {ATTN_ROUTE_NONE, 0, 0, 0};
+    if ((a.ldq | a.ldk | a.ldv) % 8 || a.ldo % 4) return {ATTN_ROUTE_REFUSED, 0, 0, 0};
     // self-attention of short packed sequences (the decoder over a page's 68 tokens): a wave per (sequence, head)
-    if (attention_small_ok(a)) return launch_attention_small(a, s);
-    if (attention72w_ok(a)) return launch_attention72w(a, s);
+    if (attention_small_ok(a)) return {ATTN_ROUTE_SMALL, 64, 0, 0};
+    if (attention72w_ok(a)) return {ATTN_ROUTE_72W, 72, 0, 0};
     // q-fragments per wave: 2 (32 rows) for long sequences; PIPE 0 (single slot, no pipeline prologue) is the
     // fastest form for the one- or two-tile sequences of the decoder (68-token pages: 13.8 vs 15.7 us)
     const bool big = a.max_q > 64;
     const bool tiny = a.max_q <= 128;
     switch (a.head_dim) {
-        case 64:
-            if (tiny) return big ? launch_t<64, 2, 0>(a, s) : launch_t<64, 1, 0>(a, s);
-            return launch_t<64, 2, 3>(a, s);
-        case 72:
-            if (tiny) return big ? launch_t<72, 2, 0>(a, s) : launch_t<72, 1, 0>(a, s);
-            return launch_t<72, 2, 3>(a, s);
-        case 80:
-            if (tiny) return big ? launch_t<80, 2, 0>(a, s) : launch_t<80, 1, 0>(a, s);
-            return launch_t<80, 2, 3>(a, s);
-        case 128: return launch_t<128, 1, 0>(a, s);
-        default:  return hipErrorInvalidValue;
+        case 64: case 72: case 80:
+            if (tiny) return {ATTN_ROUTE_TILED, a.head_dim, big ? 2 : 1, 0};
+            return {ATTN_ROUTE_TILED, a.head_dim, 2, 3};
+        case 128: return {ATTN_ROUTE_TILED, 128, 1, 0};
+        default:  return {ATTN_ROUTE_REFUSED, 0, 0, 0};
     }
+}
+
+hipError_t launch_attention(const AttnArgs& a_in, hipStream_t s) {
+    const AttnRoute r = attention_route(a_in);
+    if (r.kind == ATTN_ROUTE_NONE) return hipSuccess;
+    if (r.kind == ATTN_ROUTE_REFUSED) return hipErrorInvalidValue;
+    AttnArgs a = a_in;
+    // q rows that already carry scale * log2(e): attention_w.hip takes them as they are, the other kernels multiply the scores by
+    // scale * log2(e) themselves — hand them the scale that makes that factor 1
+    if (a.q_prescaled && r.kind != ATTN_ROUTE_72W) a.scale = 1.0f / 1.44269504088896340736f;
+    if (r.kind == ATTN_ROUTE_SMALL) return launch_attention_small(a, s);
+    if (r.kind == ATTN_ROUTE_72W) return launch_attention72w(a, s);
+#define VR_TILED(HD_, QF_, PIPE_) \
+    if (r.head_dim == HD_ && r.qf == QF_ && r.pipe == PIPE_) return launch_t<HD_, QF_, PIPE_>(a, s);
+    VR_TILED(64, 1, 0) VR_TILED(64, 2, 0) VR_TILED(64, 2, 3)
+    VR_TILED(72, 1, 0) VR_TILED(72, 2, 0) VR_TILED(72, 2, 3)
+    VR_TILED(80, 1, 0) VR_TILED(80, 2, 0) VR_TILED(80, 2, 3)
+    VR_TILED(128, 1, 0)
+#undef VR_TILED
+    return hipErrorInvalidValue;            // a tiled form attention_route names and nobody instantiated
 }
 
 }  // namespace vr

@@ -109,6 +109,11 @@ struct AttnArgs {
                                      // max folded in) — lets a caller merge attention over separately processed KV ranges
 };
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
+// the kernel launch_attention reaches with these arguments (it dispatches on this): attention_small.hip, attention_w.hip, or
+// attention.hip's attention_kernel<head_dim, qf, pipe>
+enum AttnRouteKind { ATTN_ROUTE_REFUSED = -1, ATTN_ROUTE_NONE = 0, ATTN_ROUTE_SMALL = 1, ATTN_ROUTE_72W = 2, ATTN_ROUTE_TILED = 3 };
+struct AttnRoute { int kind, head_dim, qf, pipe; };       // qf, pipe: the tiled form's template arguments (0 otherwise)
+AttnRoute attention_route(const AttnArgs& a);
 
 // ---- MiniCPM-V 2.0 answer generation (chat_kernels.hip; host side vr_chat_* in chat.hip) ------
 constexpr int CHAT_MAX_ROWS = 16;   // rows (prompts x beams) of one decode step

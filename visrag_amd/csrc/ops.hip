@@ -168,12 +168,9 @@ extern "C" int vr_op_norm(int device_id, int32_t kind, const float* x, int32_t r
     return VR_OK;
 }
 
-extern "C" int vr_op_attention_ex(int device_id, const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v,
-                                  int32_t ldv, void* out, int32_t ldo, const int32_t* cu_q, const int32_t* cu_kv, int32_t B,
-                                  int32_t heads, int32_t head_dim, int32_t max_q, int32_t causal, int32_t q_shared,
-                                  float scale, const vr_attn_extras_t* extras, void* stream) {
-    if (!q || !k || !v || !out || !cu_q || !cu_kv) return fail(VR_ERR_INVALID, "NULL argument");
-    VRCHK(set_dev(device_id));
+static AttnArgs attn_args_of(const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v, int32_t ldv, void* out,
+                             int32_t ldo, const int32_t* cu_q, const int32_t* cu_kv, int32_t B, int32_t heads, int32_t head_dim,
+                             int32_t max_q, int32_t causal, int32_t q_shared, float scale, const vr_attn_extras_t* extras) {
     AttnArgs a{};
     a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldk; a.v = v; a.ldv = ldv; a.out = out; a.ldo = ldo; a.cu_q = cu_q;
     a.cu_kv = cu_kv; a.B = B; a.heads = heads; a.head_dim = head_dim; a.max_q = max_q; a.causal = causal;
@@ -182,8 +179,37 @@ extern "C" int vr_op_attention_ex(int device_id, const void* q, int32_t ldq, con
         a.kv_group = extras->kv_group; a.kv_end = extras->kv_end; a.q_in_rows = extras->q_in_rows;
         a.q_head_stride = extras->q_head_stride; a.q_prescaled = extras->q_prescaled; a.lse = extras->lse;
     }
+    return a;
+}
+
+extern "C" int vr_op_attention_ex(int device_id, const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v,
+                                  int32_t ldv, void* out, int32_t ldo, const int32_t* cu_q, const int32_t* cu_kv, int32_t B,
+                                  int32_t heads, int32_t head_dim, int32_t max_q, int32_t causal, int32_t q_shared,
+                                  float scale, const vr_attn_extras_t* extras, void* stream) {
+    if (!q || !k || !v || !out || !cu_q || !cu_kv) return fail(VR_ERR_INVALID, "NULL argument");
+    VRCHK(set_dev(device_id));
+    const AttnArgs a = attn_args_of(q, ldq, k, ldk, v, ldv, out, ldo, cu_q, cu_kv, B, heads, head_dim, max_q, causal, q_shared, scale,
+                                    extras);
     HIPCHK(launch_attention(a, (hipStream_t)stream));
     return VR_OK;
+}
+
+// the kernel that call would reach: no device is selected, nothing is launched, no pointer is dereferenced
+extern "C" int vr_op_attention_route(int device_id, const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v,
+                                     int32_t ldv, void* out, int32_t ldo, const int32_t* cu_q, const int32_t* cu_kv, int32_t B,
+                                     int32_t heads, int32_t head_dim, int32_t max_q, int32_t causal, int32_t q_shared,
+                                     float scale, const vr_attn_extras_t* extras) {
+    (void)device_id;
+    if (!q || !k || !v || !out || !cu_q || !cu_kv) return VR_ATTN_ROUTE_REFUSED;
+    const AttnRoute r = attention_route(attn_args_of(q, ldq, k, ldk, v, ldv, out, ldo, cu_q, cu_kv, B, heads, head_dim, max_q, causal,
+                                                     q_shared, scale, extras));
+    switch (r.kind) {
+        case ATTN_ROUTE_NONE:  return VR_ATTN_ROUTE_NONE;
+        case ATTN_ROUTE_SMALL: return VR_ATTN_ROUTE_SMALL;
+        case ATTN_ROUTE_72W:   return VR_ATTN_ROUTE_72W;
+        case ATTN_ROUTE_TILED: return VR_ATTN_ROUTE_TILED(r.head_dim, r.qf, r.pipe);
+        default:               return VR_ATTN_ROUTE_REFUSED;
+    }
 }
 
 extern "C" int vr_op_attention(int device_id, const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v,
