@@ -236,6 +236,32 @@ int vr_chat_step(vr_chat_t ch, int32_t n, const int32_t* slots, const int32_t* r
 int vr_chat_select(vr_chat_t ch, int32_t mode, int32_t n_groups, const int32_t* group_offsets, const int32_t* rows,
                    const float* beam_scores, int32_t k, float repetition_penalty, float temperature, int32_t top_k,
                    uint64_t seed, int32_t step, float* out_scores, int32_t* out_tokens, int32_t* out_parents, void* stream);
+/* The nucleus sampler: one draw per row from the current logits of rows[0..n), with ANY top_k (0 = off) and top_p, by a radix
+ * select over the row (csrc/chat_sample.hip) — its cost does not grow with top_k.  vr_chat_select(VR_CHAT_SAMPLE) stays as it is.
+ * Definition, per row: logits x[0..V) fp32, the row's seen set, repetition_penalty > 0, temperature > 0, top_k >= 0, 0 < top_p <= 1.
+ *   1. s_t = the penalised logit VR_CHAT_SAMPLE scores with (x_t * penalty if x_t < 0 else x_t / penalty on seen ids);
+ *      z_t = s_t * (1 / temperature), the rounded fp32 product — the value VR_CHAT_SAMPLE adds its noise to.
+ *   2. A token whose z_t is -inf or NaN is no candidate.  Candidates are ordered by z descending, then token ascending.
+ *   3. C = the number of candidates; K = C when top_k = 0, else min(top_k, C).
+ *   4. m = the first candidate's z; w_t = the mass exp(z_t - m) as an unsigned 64-bit fixed-point integer of scale 2^40 (fp32
+ *      exponential, truncated); Z = the integer sum of w over the first K candidates; A_j = the integer sum over the
+ *      candidates ahead of position j.  Integer sums do not depend on the order of addition: the kept set is a function of
+ *      the row alone.
+ *   5. The candidate at position j is KEPT iff j < K and (top_p == 1 or A_j < top_p * Z, the product and the comparison in
+ *      fp64).  Position 0 is always kept; top_p == 1 applies no mass filter at all (HF builds no TopPLogitsWarper then).
+ *   6. The draw is the kept token of largest fma(s_t, 1 / temperature, noise(seed, step, t)) — the Gumbel-max and the noise
+ *      of VR_CHAT_SAMPLE, bit for bit; among equal values the better-ranked candidate wins.
+ * This is transformers 4.40.2's chain in order (repetition penalty, TemperatureLogitsWarper, TopKLogitsWarper,
+ * TopPLogitsWarper with min_tokens_to_keep = 1, softmax, one multinomial draw) with two stated differences: where the k-th
+ * value is exactly tied HF keeps every tied token and this keeps the lower ids (the library's tie rule everywhere); the noise
+ * is counter-based, so a seed reproduces a run.
+ * Host outputs [n]: out_scores = s of the drawn token, out_tokens, out_kept = the number of kept candidates, out_cut = the
+ * last kept token in the order; a row without candidates gives (-inf, -1, 0, -1).  Every check comes before any launch and an
+ * error leaves the outputs untouched: NULL pointers, n < 1, a penalty or temperature that is not positive, top_k < 0, top_p
+ * outside (0, 1] or NaN are VR_ERR_INVALID; n > 16 or n > max_rows is VR_ERR_CAPACITY; a row without logits is VR_ERR_STATE. */
+int vr_chat_sample(vr_chat_t ch, int32_t n, const int32_t* rows, float repetition_penalty, float temperature, int32_t top_k,
+                   double top_p, uint64_t seed, int32_t step, float* out_scores, int32_t* out_tokens, int32_t* out_kept,
+                   int32_t* out_cut, void* stream);
 /* Row rows[i] becomes a copy of row parents[i] (slot, tail, seen set), all read before any is written; the prompt's K / V
  * are never copied. */
 int vr_chat_reorder(vr_chat_t ch, int32_t n, const int32_t* rows, const int32_t* parents, void* stream);
@@ -1102,6 +1128,12 @@ int vr_op_chat_select(int device_id, int32_t mode, const float* logits, int32_t 
                       int32_t words, int32_t n_groups, const int32_t* group_offsets, const float* beam_scores, int32_t K,
                       int32_t kout, float repetition_penalty, float temperature, uint64_t seed, int32_t step,
                       float* out_scores, int32_t* out_tokens, int32_t* out_parents, void* stream);
+/* vr_chat_sample's kernel on the caller's buffers: logits f32 [n][ld] and seen bit sets u32 [n][words] on the device, one draw
+ * per row, n <= 16; the definition, the outputs (host arrays [n]) and the error codes are vr_chat_sample's, plus V >= 1,
+ * ld >= V, words >= ceil(V / 32) (VR_ERR_INVALID).  Synchronises the stream. */
+int vr_op_chat_sample(int device_id, const float* logits, int32_t ld, int32_t V, const uint32_t* seen, int32_t words, int32_t n,
+                      float repetition_penalty, float temperature, int32_t top_k, double top_p, uint64_t seed, int32_t step,
+                      float* out_scores, int32_t* out_tokens, int32_t* out_kept, int32_t* out_cut, void* stream);
 /* The batched prefill's per-layer K / V scatter (chat_kernels.hip) on the caller's buffers, ONE layer's planes: qkv bf16
  * [seq_offsets[B]][ld], row t = q | k | v of a packed token (k at column E, v at 2 E; ld >= 3 E; E, ld multiples of 8);
  * kplane / vplane bf16 [n_slots][max_len][E].  Token t of prompt b (seq_offsets[b] <= t < seq_offsets[b + 1]) goes to

@@ -170,6 +170,8 @@ SIGNATURES = {
                                        C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _i32, _vp, _vp]),
     "vr_op_chat_select": (C.c_int, [C.c_int, _i32, _vp, _i32, _i32, _vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_f32), _i32, _i32,
                                     _f32, _f32, C.c_uint64, _i32, C.POINTER(_f32), C.POINTER(_i32), C.POINTER(_i32), _vp]),
+    "vr_op_chat_sample": (C.c_int, [C.c_int, _vp, _i32, _i32, _vp, _i32, _i32, _f32, _f32, _i32, C.c_double, C.c_uint64, _i32,
+                                    C.POINTER(_f32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp]),
     "vr_op_chat_prompt_scatter": (C.c_int, [C.c_int, _vp, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _vp, _vp, _vp]),
     "vr_op_gen_mrope_cache": (C.c_int, [C.c_int, _vp, _vp, _i32, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32,
                                         _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
@@ -189,6 +191,8 @@ SIGNATURES = {
     "vr_chat_step": (C.c_int, [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp]),
     "vr_chat_select": (C.c_int, [_vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_f32), _i32, _f32, _f32, _i32,
                                  C.c_uint64, _i32, C.POINTER(_f32), C.POINTER(_i32), C.POINTER(_i32), _vp]),
+    "vr_chat_sample": (C.c_int, [_vp, _i32, C.POINTER(_i32), _f32, _f32, _i32, C.c_double, C.c_uint64, _i32, C.POINTER(_f32),
+                                 C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp]),
     "vr_chat_reorder": (C.c_int, [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32), _vp]),
     "vr_chat_logits": (C.c_int, [_vp, _i32, _vp, _vp]),
     "vr_chat_row_len": (C.c_int, [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32)]),

@@ -57,7 +57,12 @@ def answer_weighted_selection(model, tokenizer, msgs, pages: Sequence[Image.Imag
 
 
 def answer_page_concatenation(model, tokenizer, msgs, pages: Sequence[Image.Image], kind: str = "horizontal",
-                              max_new_tokens: int = 20, **kw) -> str:
-    """generate.py's page_concatenation task for one query: one beam-search chat on the concatenated image."""
+                              max_new_tokens: int = 20, sampling: bool = False, **kw) -> str:
+    """generate.py's page_concatenation task for one query: one beam-search chat on the concatenated image.  sampling=True:
+    the sampled answer of the answer-generation package's chat instead (nucleus top_p 0.8 / top_k 100, temperature 0.7,
+    repetition_penalty 1.05; `seed` in kw selects the noise)."""
     image = concat_pages(pages, kind)
+    if sampling:
+        return model.chat([image], [msgs], tokenizer, sampling=True, max_new_tokens=max_new_tokens, assistant_turn=True,
+                          answer_defaults=True, **kw)[0]
     return model.chat([image], [msgs], tokenizer, sampling=False, max_new_tokens=max_new_tokens, assistant_turn=True, **kw)[0]

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstring>
 #include <vector>
 
 #include "model.h"
@@ -384,6 +385,42 @@ extern "C" int vr_chat_select(vr_chat_t ch, int32_t mode, int32_t n_groups, cons
     HIPCHK(hipMemcpyAsync(out_tokens, o_tok, cnt * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(out_parents, o_par, cnt * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
+}
+
+extern "C" int vr_chat_sample(vr_chat_t ch, int32_t n, const int32_t* rows, float repetition_penalty, float temperature, int32_t top_k,
+                              double top_p, uint64_t seed, int32_t step, float* out_scores, int32_t* out_tokens, int32_t* out_kept,
+                              int32_t* out_cut, void* stream) {
+    if (!ch || !rows || !out_scores || !out_tokens || !out_kept || !out_cut) return fail(VR_ERR_INVALID, "NULL argument");
+    if (n < 1) return fail(VR_ERR_INVALID, "n must be positive");
+    if (n > CHAT_MAX_ROWS || n > ch->c.max_rows) return fail(VR_ERR_CAPACITY, "%d rows exceed max_rows", n);
+    if (!(repetition_penalty > 0.f)) return fail(VR_ERR_INVALID, "repetition_penalty must be positive");
+    if (!(temperature > 0.f)) return fail(VR_ERR_INVALID, "temperature must be positive");
+    if (top_k < 0) return fail(VR_ERR_INVALID, "top_k must be 0 (off) or positive");
+    if (!(top_p > 0.0 && top_p <= 1.0)) return fail(VR_ERR_INVALID, "top_p must be in (0, 1]");
+    ChatSel sel{};
+    sel.n = n; sel.groups = n;
+    for (int i = 0; i < n; ++i) {
+        const int r = rows[i];
+        if (r < 0 || r >= ch->c.max_rows || ch->lpos[r] < 0) return fail(VR_ERR_STATE, "row %d has no logits", r);
+        sel.lrow[i] = ch->lpos[r]; sel.srow[i] = r; sel.g_lo[i] = i;
+    }
+    sel.g_lo[n] = n;
+    VRCHK(set_dev(ch->model->device));
+    hipStream_t s = (hipStream_t)stream;
+    float* o_score = ch->w_out.as<float>();                   // (w_out holds 3 x 16 x 64 words: four runs of 16 fit)
+    int* o_tok = (int*)(o_score + CHAT_MAX_ROWS);
+    int* o_kept = o_tok + CHAT_MAX_ROWS;
+    int* o_cut = o_kept + CHAT_MAX_ROWS;
+    HIPCHK(launch_chat_sample(sel, ch->w_logits.as<float>(), ch->Vpad, ch->V, ch->seen.as<unsigned>(), ch->words, repetition_penalty,
+                              temperature, top_k, top_p, (unsigned long long)seed, (unsigned)step, o_score, o_tok, o_kept, o_cut, s));
+    int32_t host[4 * CHAT_MAX_ROWS];                          // one copy for the four runs
+    HIPCHK(hipMemcpyAsync(host, o_score, sizeof(host), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    memcpy(out_scores, host, (size_t)n * 4);
+    memcpy(out_tokens, host + CHAT_MAX_ROWS, (size_t)n * 4);
+    memcpy(out_kept, host + 2 * CHAT_MAX_ROWS, (size_t)n * 4);
+    memcpy(out_cut, host + 3 * CHAT_MAX_ROWS, (size_t)n * 4);
     return VR_OK;
 }
 

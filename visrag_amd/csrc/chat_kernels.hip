@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "chat_score.h"
 #include "common.h"
 #include "gen_math.h"
 #include "kernels.h"
@@ -17,13 +18,6 @@ namespace {
 __device__ __forceinline__ size_t cache_off(int l, int kv, int idx, int count, int cap, int E) {
     return (((size_t)l * 2 + kv) * count + idx) * (size_t)cap * E;
 }
-
-// order-preserving map of a float to 32 bits, and back
-__device__ __forceinline__ unsigned f2ord(float f) {
-    const unsigned b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o); }
 
 __device__ __forceinline__ unsigned long long key_max(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
 
@@ -283,15 +277,6 @@ __global__ __launch_bounds__(256) void chat_lse_kernel(ChatSel sel, const float*
     if (tid == 0) lse[blockIdx.x] = m + logf((red[0] + red[1]) + (red[2] + red[3]));
 }
 
-// Candidate score of token `tok` of selected row r (HF order: log_softmax first for beams, then the repetition penalty on the
-// row's generated ids, then the running beam score)
-__device__ __forceinline__ float chat_score(int mode, float x, bool seen, float pen, float lse, float bs) {
-    if (mode == CHAT_SEL_BEAM) x = x - lse;
-    if (seen) x = x < 0.f ? x * pen : x / pen;
-    if (mode == CHAT_SEL_BEAM) x = x + bs;
-    return x;
-}
-
 // Top-K keys (score, -flat index) of group g's candidates: flat index f = r * V + tok over the group's rows.  Grid
 // (CHAT_SEL_WGS, groups): workgroup w takes a slice of the flat range and finds its K best by K rounds of a max below the
 // previous round's key (keys are distinct: the index is part of them).  Key 0 = no candidate; a score of -inf is none either.
@@ -364,7 +349,7 @@ __global__ __launch_bounds__(256) void chat_topk_final_kernel(const unsigned lon
     int tok = -1, par = -1;
     if (tid < K) {
         decode(top[tid], s, tok, par);
-        if (tok >= 0) v = s * inv_t + gumbel_noise(seed, step, (unsigned)tok);
+        if (tok >= 0) v = chat_noisy(s, inv_t, gumbel_noise(seed, step, (unsigned)tok));
     }
     // argmax over the lanes (ties: the lower lane = the better-ranked candidate)
     unsigned long long key = tok >= 0 ? ((unsigned long long)f2ord(v) << 32) | (unsigned)(~(unsigned)tid) : 0ull;

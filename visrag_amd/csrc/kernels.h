@@ -165,6 +165,13 @@ hipError_t launch_chat_move(const ChatMove& mv, void* tails, void* scratch, int 
 hipError_t launch_chat_select(const ChatSel& sel, int mode, const float* logits, int ld, int V, const unsigned* seen, int words, float pen,
                               float temperature, int K, int kout, unsigned long long seed, unsigned step, float* lse,
                               unsigned long long* part, float* o_score, int* o_tok, int* o_par, hipStream_t s);
+// The nucleus sampler (chat_sample.hip; definition at vr_chat_sample in include/visrag_hip.h): one draw per selected row i
+// (sel.n rows; groups are not used) among the kept candidates of logits row lrow[i] under seen set srow[i].  top_k 0 = off,
+// 0 < top_p <= 1.  o_* [sel.n] on the device: penalised logit, token, kept candidates, last kept token; a row without
+// candidates gives (-inf, -1, 0, -1).  One workgroup per row; reads logits and seen, writes the four outputs, nothing else.
+hipError_t launch_chat_sample(const ChatSel& sel, const float* logits, int ld, int V, const unsigned* seen, int words, float pen,
+                              float temperature, int top_k, double top_p, unsigned long long seed, unsigned step, float* o_score,
+                              int* o_tok, int* o_kept, int* o_cut, hipStream_t s);
 
 // ---- EVisRAG generator (gen_kernels.hip) ---------------------------------------------------
 constexpr int GEN_ATT_SPLITS = 16;  // most KV ranges one decode step's attention is cut into

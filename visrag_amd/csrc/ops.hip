@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cstring>
 #include <map>
 #include <tuple>
 #include <vector>
@@ -382,6 +383,40 @@ extern "C" int vr_op_chat_select(int device_id, int32_t mode, const float* logit
     HIPCHK(hipMemcpyAsync(out_tokens, o_tok, cnt * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(out_parents, o_par, cnt * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
+}
+
+extern "C" int vr_op_chat_sample(int device_id, const float* logits, int32_t ld, int32_t V, const uint32_t* seen, int32_t words, int32_t n,
+                                 float repetition_penalty, float temperature, int32_t top_k, double top_p, uint64_t seed, int32_t step,
+                                 float* out_scores, int32_t* out_tokens, int32_t* out_kept, int32_t* out_cut, void* stream) {
+    if (!logits || !seen || !out_scores || !out_tokens || !out_kept || !out_cut) return fail(VR_ERR_INVALID, "NULL argument");
+    if (V < 1 || ld < V || words < (V + 31) / 32) return fail(VR_ERR_INVALID, "need V >= 1, ld >= V, words >= ceil(V / 32)");
+    if (n < 1) return fail(VR_ERR_INVALID, "n must be positive");
+    if (n > CHAT_MAX_ROWS) return fail(VR_ERR_CAPACITY, "%d rows exceed %d", n, CHAT_MAX_ROWS);
+    if (!(repetition_penalty > 0.f)) return fail(VR_ERR_INVALID, "repetition_penalty must be positive");
+    if (!(temperature > 0.f)) return fail(VR_ERR_INVALID, "temperature must be positive");
+    if (top_k < 0) return fail(VR_ERR_INVALID, "top_k must be 0 (off) or positive");
+    if (!(top_p > 0.0 && top_p <= 1.0)) return fail(VR_ERR_INVALID, "top_p must be in (0, 1]");
+    ChatSel sel{};
+    sel.n = n; sel.groups = n;
+    for (int i = 0; i < n; ++i) { sel.lrow[i] = i; sel.srow[i] = i; sel.g_lo[i] = i; }
+    sel.g_lo[n] = n;
+    VRCHK(set_dev(device_id));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t b_out = (size_t)4 * CHAT_MAX_ROWS * 4;
+    DevBuf& sc = g_chat_op_scratch[device_id];
+    if (sc.bytes < b_out) { HIPCHK(hipStreamSynchronize(s)); VRCHK(sc.reserve(b_out)); }
+    float* o_score = sc.as<float>();
+    int* o_tok = (int*)(o_score + CHAT_MAX_ROWS);
+    HIPCHK(launch_chat_sample(sel, logits, ld, V, (const unsigned*)seen, words, repetition_penalty, temperature, top_k, top_p,
+                              (unsigned long long)seed, (unsigned)step, o_score, o_tok, o_tok + CHAT_MAX_ROWS, o_tok + 2 * CHAT_MAX_ROWS, s));
+    int32_t host[4 * CHAT_MAX_ROWS];                          // one copy for the four runs
+    HIPCHK(hipMemcpyAsync(host, o_score, sizeof(host), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    memcpy(out_scores, host, (size_t)n * 4);
+    memcpy(out_tokens, host + CHAT_MAX_ROWS, (size_t)n * 4);
+    memcpy(out_kept, host + 2 * CHAT_MAX_ROWS, (size_t)n * 4);
+    memcpy(out_cut, host + 3 * CHAT_MAX_ROWS, (size_t)n * 4);
     return VR_OK;
 }
 

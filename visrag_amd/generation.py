@@ -17,6 +17,9 @@ Mirrors the reference's `MiniCPMV.generate` / `chat` (src/openmatch/modeling/mod
 * sampling (`chat(sampling=True)`: temperature 0.7, repetition_penalty 1.02): penalty, / temperature, top_k 50 (HF's
   default), softmax, one draw — here from counter-based noise selected by (seed, step), so a seed reproduces a run; the
   reference draws from torch's global generator.
+* nucleus sampling (the answer-generation package's `chat(sampling=True)`: top_p 0.8, top_k 100, temperature 0.7,
+  repetition_penalty 1.05): penalty, / temperature, top-k, top-p (min_tokens_to_keep 1), softmax, one draw — a second
+  sampler (`NucleusSampling`, `HipChat.sample`, `generate_items(nucleus=...)`) beside the one above, same noise.
 * Generation starts from `inputs_embeds` (modeling_minicpmv.py:218-226), so HF starts `input_ids` EMPTY: the repetition
   penalty only ever sees generated tokens, never the prompt.
 
@@ -73,6 +76,32 @@ def chat_generation_config(sampling: bool, kwargs: Dict) -> Dict:
         cfg = {"num_beams": 3, "repetition_penalty": 1.2}
     cfg.update((k, kwargs[k]) for k in cfg.keys() & kwargs.keys())
     return cfg
+
+
+def answer_chat_generation_config(sampling: bool, kwargs: Dict) -> Dict:
+    """The chat defaults of the reference's answer-generation package (weighted_selection/MiniCPMV20/modeling_minicpmv.py:
+    361-377) and its merge rule: the defaults of the mode, and only THEIR keys overridden from kwargs.  Its sampled answer is
+    a nucleus: top_p 0.8 over the top_k 100 (generate_items(nucleus=NucleusSampling(top_p, top_k)))."""
+    if sampling:
+        cfg = {"top_p": 0.8, "top_k": 100, "temperature": 0.7, "do_sample": True, "repetition_penalty": 1.05}
+    else:
+        cfg = {"num_beams": 3, "repetition_penalty": 1.2}
+    cfg.update((k, kwargs[k]) for k in cfg.keys() & kwargs.keys())
+    return cfg
+
+
+@dataclass(frozen=True)
+class NucleusSampling:
+    """top_p over the top_k best (top_k = 0: over the whole vocabulary) — the sampler of vr_chat_sample (include/visrag_hip.h
+    holds the definition).  Checked as the C ABI checks: 0 < top_p <= 1, top_k >= 0."""
+    top_p: float = 0.8
+    top_k: int = 100
+
+    def __post_init__(self):
+        if isinstance(self.top_k, bool) or int(self.top_k) != self.top_k or self.top_k < 0:
+            raise ValueError(f"top_k={self.top_k!r}: 0 (off) or a positive integer")
+        if not (0.0 < float(self.top_p) <= 1.0):                 # (a NaN fails both comparisons)
+            raise ValueError(f"top_p={self.top_p!r}: must be in (0, 1]")
 
 
 def decode_text(result_ids: Sequence[Sequence[int]], tokenizer) -> List[str]:
@@ -310,6 +339,19 @@ class HipChat:
                                            sc.ctypes.data_as(C.POINTER(C.c_float)), p32(tk), p32(pa), self._stream()), "vr_chat_select")
         return sc, tk, pa
 
+    def sample(self, rows: Sequence[int], repetition_penalty: float = 1.0, temperature: float = 1.0, top_k: int = 100,
+               top_p: float = 0.8, seed: int = 0, step: int = 0):
+        """One nucleus draw per row (vr_chat_sample) -> (scores, tokens, kept, cut), each [len(rows)] numpy."""
+        n = len(rows)
+        sc = np.zeros(n, dtype=np.float32)
+        tk, kept, cut = (np.zeros(n, dtype=np.int32) for _ in range(3))
+        p32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_int32))
+        _lib.check(self.lib.vr_chat_sample(self._h, n, (C.c_int32 * n)(*[int(r) for r in rows]), float(repetition_penalty),
+                                           float(temperature), int(top_k), float(top_p), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                           int(step), sc.ctypes.data_as(C.POINTER(C.c_float)), p32(tk), p32(kept), p32(cut),
+                                           self._stream()), "vr_chat_sample")
+        return sc, tk, kept, cut
+
     def reorder(self, rows: Sequence[int], parents: Sequence[int]) -> None:
         n = len(rows)
         a = lambda v: (C.c_int32 * n)(*[int(x) for x in v])
@@ -334,7 +376,7 @@ _NEUTRAL = {"top_p": 1.0, "length_penalty": 1.0, "min_new_tokens": 0, "no_repeat
 def generate_items(chat: HipChat, items: Sequence, max_new_tokens: int = 20, num_beams: int = 1, do_sample: bool = False,
                    repetition_penalty: float = 1.0, temperature: float = 1.0, top_k: int = 50, seed: int = 0,
                    eos: int = EOS_ID, details: bool = False, prefill: str = "single", num_return_sequences: int = 1,
-                   **kwargs) -> List:
+                   nucleus: Optional[NucleusSampling] = None, **kwargs) -> List:
     """Generate every PreparedItem independently, the items of a batch in lockstep (one decode step streams the weights once
     for all their rows).  Returns the output ids per item (HF's sequences without the empty prompt part), or with
     details=True the rule's result per item (tokens, score, per-step candidates; beam search: "hyps", the
@@ -344,7 +386,18 @@ def generate_items(chat: HipChat, items: Sequence, max_new_tokens: int = 20, num
     prefill: "single" runs one prefill pass per item — an item's output is then a function of the item alone, bit for
     bit, whatever else is in flight.  "batched" packs the prompts of a chunk into as few passes as the encoder workspace
     (max_tokens, max_seqs) allows: the decoder's tile and split-K choices follow the packed token count, so an item's logits
-    then agree with its lone run to bf16 accuracy only — for callers whose unit of work is the group (weighted selection)."""
+    then agree with its lone run to bf16 accuracy only — for callers whose unit of work is the group (weighted selection).
+
+    nucleus: a NucleusSampling sends every step's draw to HipChat.sample (top_p over any top_k; 0 = the whole vocabulary).  It
+    needs do_sample=True, num_beams == 1 and the top_k argument left at its default (the nucleus carries its own).  Without
+    it the HF-named options keep their refusals (top_p, top_k outside 1..64)."""
+    if nucleus is not None:
+        if not isinstance(nucleus, NucleusSampling):
+            raise ValueError(f"nucleus={nucleus!r}: a NucleusSampling or None")
+        if not do_sample or int(num_beams) != 1:
+            raise ValueError("nucleus sampling needs do_sample=True and num_beams == 1")
+        if top_k != 50:
+            raise ValueError(f"top_k={top_k!r} next to nucleus=: the nucleus carries its own top_k")
     for k, v in kwargs.items():
         if k not in _NEUTRAL or v != _NEUTRAL[k]:
             raise NotImplementedError(f"generation option {k}={v!r} is not supported")
@@ -370,7 +423,7 @@ def generate_items(chat: HipChat, items: Sequence, max_new_tokens: int = 20, num
     out: List[List[int]] = []
     for lo in range(0, len(items), per):
         res = _generate_chunk(chat, items[lo:lo + per], max_new_tokens, nb, do_sample, repetition_penalty, temperature, top_k, seed, eos,
-                              prefill)
+                              prefill, nucleus)
         for r in res:
             if "hyps" in r:
                 r["hyps"] = r["hyps"][:nret]
@@ -398,7 +451,7 @@ def prefill_groups(lengths: Sequence[int], max_tokens: int, max_seqs: int) -> Li
     return groups
 
 
-def _generate_chunk(chat, items, max_new, nb, do_sample, pen, temp, top_k, seed, eos, prefill="single"):
+def _generate_chunk(chat, items, max_new, nb, do_sample, pen, temp, top_k, seed, eos, prefill="single", nucleus=None):
     """Every item's rule is a generator of select / advance requests; each round serves all pending requests of one kind in
     ONE device call (advances first: a select must see the appended token), so the items advance in lockstep."""
     rules, rows, reqs, results = [], [], [], [None] * len(items)
@@ -418,7 +471,13 @@ def _generate_chunk(chat, items, max_new, nb, do_sample, pen, temp, top_k, seed,
         kind = "advance" if any(reqs[i][0] == "advance" for i in live) else "select"
         sel = [i for i in live if reqs[i][0] == kind]
         answers = {}
-        if kind == "select":
+        if kind == "select" and nucleus is not None:         # one draw per pending item (each holds one row), in one call
+            sc, tk, _, _ = chat.sample([rows[i][0] for i in sel], repetition_penalty=pen, temperature=temp, top_k=nucleus.top_k,
+                                       top_p=nucleus.top_p, seed=seed, step=step)
+            step += 1
+            for j, i in enumerate(sel):
+                answers[i] = [(float(sc[j]), int(tk[j]), 0)] if tk[j] >= 0 else []
+        elif kind == "select":
             k = reqs[sel[0]][3]
             groups = [rows[i][:reqs[i][1]] for i in sel]
             sc, tk, pa = chat.select(mode, groups, k, [s for i in sel for s in reqs[i][2]], repetition_penalty=pen,

@@ -294,7 +294,7 @@ class VisRAGRet:
     def generate(self, data_list=None, img_list=None, tokenizer=None, max_inp_length: Optional[int] = None,
                  vision_hidden_states=None, return_vision_hidden_states=False, **kwargs):
         """data_list: prompts that already hold their image placeholders; img_list: per prompt the PIL slices in placeholder
-        order.  kwargs: max_new_tokens, num_beams, do_sample, temperature, repetition_penalty, top_k, seed."""
+        order.  kwargs: max_new_tokens, num_beams, do_sample, temperature, repetition_penalty, top_k, seed, nucleus."""
         from .generation import decode_text, generate_items
         if data_list is None:
             raise ValueError("data_list is required")
@@ -312,13 +312,17 @@ class VisRAGRet:
         return decode_text(ids, tokenizer)
 
     def chat(self, image_list, msgs_list, tokenizer, vision_hidden_states=None, max_new_tokens: int = 1024, sampling: bool = True,
-             max_inp_length: int = 2048, seed: int = 0, assistant_turn: bool = False, return_scores: bool = False, **kwargs):
+             max_inp_length: int = 2048, seed: int = 0, assistant_turn: bool = False, return_scores: bool = False,
+             answer_defaults: bool = False, **kwargs):
         """The reference's chat (modeling_minicpmv.py:321-398).  `seed` (not in the reference, whose draws come from torch's
         global generator) selects the sampling noise: chat(sampling=True) with one seed returns the same answer each call.
         assistant_turn=True ends the prompt with "<AI>", as the chat of the reference's answer-generation package does;
         return_scores=True (beam search only) returns (answers, scores): per item the sequence scores of its finished
-        hypotheses, best first — that package's `sequences_scores` (it asks for num_return_sequences=2)."""
-        from .generation import chat_generation_config, decode_text, generate_items
+        hypotheses, best first — that package's `sequences_scores` (it asks for num_return_sequences=2).
+        answer_defaults=True takes the generation defaults of that package's chat (answer_chat_generation_config): its
+        sampled answer is a nucleus, top_p 0.8 over top_k 100 at temperature 0.7, repetition_penalty 1.05."""
+        from .generation import (NucleusSampling, answer_chat_generation_config, chat_generation_config, decode_text,
+                                 generate_items)
         if return_scores and sampling:
             raise NotImplementedError("return_scores needs beam search (sampling=False): sampling yields no sequence scores")
         prompts, images = [], []
@@ -326,7 +330,12 @@ class VisRAGRet:
             p, imgs = chat_prompt(msgs, image, tokenizer, self.config)
             prompts.append(p + ("<AI>" if assistant_turn else ""))
             images.append(imgs)
-        gen = chat_generation_config(sampling, kwargs)
+        if answer_defaults:
+            gen = answer_chat_generation_config(sampling, kwargs)
+            if sampling:
+                gen["nucleus"] = NucleusSampling(gen.pop("top_p"), gen.pop("top_k"))
+        else:
+            gen = chat_generation_config(sampling, kwargs)
         if not return_scores:
             return self.generate(data_list=prompts, img_list=images, tokenizer=tokenizer, max_inp_length=max_inp_length,
                                  vision_hidden_states=vision_hidden_states, max_new_tokens=max_new_tokens, seed=seed, **gen)
