@@ -424,6 +424,29 @@ def test_an_edited_index_answers_as_a_fresh_one():
     ix.close(); fresh.close()
 
 
+def test_the_store_grows_in_the_second_block_and_a_capacity_failure_there():
+    """800 rows in 400 documents of two, 300 queries (two blocks); thresholds -4 (every document) for queries 0..155 and 256..299, 4
+    (none) between them.  Block 0 packs 62 400 entries into the first reservation of 65 536; block 1's 17 600 make the store grow
+    with those kept.  A fresh index per caller, so that the device caller and the host caller each grow it.  With max_total one
+    short the failure is raised in block 1: no result is left."""
+    C, Q = R.unit(800, 64, 1), R.unit(300, 64, 2)
+    off = np.arange(0, 801, 2)
+    t = np.where((np.arange(300) < 156) | (np.arange(300) >= 256), -4.0, 4.0).astype(np.float32)
+    for cuda in (True, False):
+        ix = _index(C, off)
+        want = N.group_range_ref(_scores(ix, Q), off, None, t)
+        assert want[0][256] == 62400 and want[0][300] == 80000
+        q_in, t_in = (torch.tensor(Q).cuda(), torch.tensor(t).cuda()) if cuda else (Q, t)
+        _same(ix.search_groups_range(q_in, t_in, sort=False), want, cuda)
+        st, _, total = _raw(ix, Q, t, max_total=79999)
+        assert st == VR_ERR_CAPACITY and total == -7 and "query block 1" in _lib.load().vr_last_error().decode()
+        assert _raw_results(ix, 0)[0] == VR_ERR_STATE and _raw_results(ix, 1)[0] == VR_ERR_STATE
+        st, lims, total = _raw(ix, Q, t, max_total=80000)                # exactly enough
+        assert st == VR_OK and total == 80000
+        _same((lims,) + tuple(_raw_results(ix, total)[1:]), want)
+        ix.close()
+
+
 def test_capacity_argument_checks_and_the_other_searches_state():
     n = 600
     C, Q = R.unit(n, 64, 1), R.unit(4, 64, 2)

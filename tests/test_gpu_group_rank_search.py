@@ -168,6 +168,30 @@ def test_flat_lims_queries_without_targets_and_a_block_without_pairs():
     ix.close()
 
 
+def test_a_filter_on_the_queries_of_a_second_block():
+    """600 rows, 257 queries (a second block of one query), a half-density and an empty filter mixed per query: the block's filter
+    ids start at its first query.  Query 256 is on filter 0.  Counts and ranks, from host arrays and cuda tensors."""
+    C, Q = R.unit(600, 64, 1), R.unit(257, 64, 2)
+    off = R.random_offsets(600, 3)
+    ng = len(off) - 1
+    M = np.concatenate([F.random_filters(600, (0.5,), seed=11), np.zeros((1, 600), dtype=bool)])
+    foq = (np.arange(257) % 3 - 1).astype(np.int32)                      # -1 (no filter), 0, 1 (allows nothing), ...
+    assert foq[256] == 0
+    ix = _index(C, off, M)
+    S32 = _scores(ix, Q)
+    mask = _masks_of(M, foq, 600)
+    T = _every(257, ng)
+    want = K.group_rank_ref(S32, off, mask, T)
+    t = _thresholds(want[0], [0, ng // 2, ng - 1])
+    ref = K.group_count_ref(S32, off, mask, t)
+    assert 0 < ref[256, -1] < K.group_count_ref(S32, off, None, t)[256, -1] and (ref[foq == 1] == 0).all()
+    for cuda in (False, True):
+        q_in, f_in = (torch.tensor(Q).cuda(), torch.tensor(foq).cuda()) if cuda else (Q, foq)
+        _check_counts(ix, q_in, S32, off, mask, t, f_in)
+        _same(ix.rank_groups(q_in, T, filter_of_query=f_in), want)
+    ix.close()
+
+
 # ------------------------------------------------------------------- 2. cross-checks against the searches that stand ---
 @pytest.fixture(scope="module")
 def filtered():

@@ -194,6 +194,24 @@ def test_windows_under_filters(filtered):
     _same(plain, tuple(x[:, 10:] for x in ix.search_groups(Q, 30)))
 
 
+def test_a_filter_on_the_queries_of_a_second_block():
+    """600 rows, 257 queries (a second block of one query), a half-density and an empty filter mixed per query, per-query offsets:
+    the block's filter ids and offsets start at its first query.  Query 256 is on filter 0."""
+    C, Q = R.unit(600, 64, 1), R.unit(257, 64, 2)
+    off = R.random_offsets(600, 3)
+    M = np.concatenate([F.random_filters(600, (0.5,), seed=11), np.zeros((1, 600), dtype=bool)])
+    foq = (np.arange(257) % 3 - 1).astype(np.int64)                      # -1 (no filter), 0, 1 (allows nothing), ...
+    ix = _index(C, off, M)
+    full = _ranking(_scores(ix, Q), off, _masks_of(M, foq, 600), 30)
+    present = (full[2] >= 0).sum(1)
+    assert foq[256] == 0 and 10 < present[256] < len(off) - 1 and (present[foq == 1] == 0).all()
+    o = (np.arange(257) % 5).astype(np.int64)
+    want = _slices(full, o, 20)
+    _same(ix.search_groups_window(Q, o, 20, foq), want)
+    _same(ix.search_groups_window(torch.tensor(Q).cuda(), torch.tensor(o), 20, torch.tensor(foq).cuda()), want)
+    ix.close()
+
+
 def test_a_filter_with_pages_in_three_documents_and_one_that_forbids_the_best_pages(filtered):
     ix, C, Q, off, M, S32 = filtered
     n = len(C)

@@ -305,6 +305,29 @@ def test_questions_under_filters(filtered):
         _same(ix.search_multi_groups(Q, lims, 20, fuse, -1, evidence=True), _np(*ix.search_multi_groups(Q, lims, 20, fuse, evidence=True)))
 
 
+def test_filters_on_the_questions_of_a_second_block():
+    """600 rows, 300 sub-queries in questions of 1, 3, 8, 2, 5: two blocks of sub-queries, the second one's filters expanded from the
+    questions that start past sub-query 256.  A half-density and an empty filter mixed per question, with and without evidence."""
+    C, Q = R.unit(600, 64, 1), R.unit(300, 64, 2)
+    off = R.random_offsets(600, 3)
+    lims = M.layout(300, (1, 3, 8, 2, 5))
+    Mk = np.concatenate([F.random_filters(600, (0.5,), seed=11), np.zeros((1, 600), dtype=bool)])
+    fog = (np.arange(len(lims) - 1) % 3 - 1).astype(np.int64)             # -1 (no filter), 0, 1 (allows nothing), ...
+    late = lims[:-1] >= 256
+    assert (fog[late] == 0).any() and (fog[late] == 1).any()
+    ix = _index(C, off, Mk)
+    S32 = _scores(ix, Q)
+    for fuse in FUSES:
+        want = M.multi_group_ref(S32, lims, off, 10, fuse, _masks_of(Mk, fog, 600))
+        assert (want[2][fog == 1] == -1).all() and (want[2][fog != 1] >= 0).all()
+        for q_in, l_in, f_in in _both(Q, lims, fog):
+            _same(ix.search_multi_groups(q_in, l_in, 10, fuse, f_in, evidence=True), want)
+            four = ix.search_multi_groups(q_in, l_in, 10, fuse, f_in)
+            assert len(four) == 4
+            _same(tuple(four) + (want[4], want[5]), want)
+    ix.close()
+
+
 def test_a_filter_with_pages_in_three_documents_and_one_that_forbids_the_best_pages(filtered):
     ix, C, Q, off, Mk, S32, lims = filtered
     n = len(C)

@@ -405,6 +405,33 @@ def test_errors_leave_everything_else_alone():
     ix.close()
 
 
+def test_the_store_grows_in_the_second_block_and_a_capacity_failure_there():
+    """400 rows, 300 queries (two blocks); thresholds -4 (every row) for queries 0..155 and 256..299, 4 (no row) between them.
+    Block 0 packs 62 400 entries into the first reservation of 65 536; block 1's 17 600 make the store grow with those kept.  A
+    fresh index per caller, so that the device caller and the host caller each grow it.  With max_total one short the failure is
+    raised in block 1: no result is left."""
+    C, Q = R.unit(400, 64, 1), R.unit(300, 64, 2)
+    t = np.where((np.arange(300) < 156) | (np.arange(300) >= 256), -4.0, 4.0).astype(np.float32)
+    ref = X.range_ref(Q, C, t)
+    assert ref[0][256] == 62400 and ref[0][300] == 80000
+    first = None
+    for cuda in (True, False):
+        ix = _index(C)
+        q_in, t_in = (torch.tensor(Q).cuda(), torch.tensor(t).cuda()) if cuda else (Q, t)
+        got = ix.search_range(q_in, t_in, sort=False)
+        lims, sc, ids = _np(*got)
+        assert np.array_equal(lims, ref[0]) and np.array_equal(ids, ref[2])
+        np.testing.assert_allclose(sc, ref[1], atol=ATOL, rtol=0)
+        first = first or _bits(got)
+        assert _bits(got) == first                                       # host and device callers: the same bits
+        st, _, tot = _raw_range(ix, q_in, t_in, max_total=79999)
+        assert st == VR_ERR_CAPACITY and tot == -7 and "query block 1" in _lib.load().vr_last_error().decode()
+        assert _raw_results(ix, 0)[0] == VR_ERR_STATE and _raw_results(ix, 1)[0] == VR_ERR_STATE
+        st, lims, tot = _raw_range(ix, q_in, t_in, max_total=80000)       # exactly enough
+        assert st == VR_OK and tot == 80000 and np.array_equal(lims, ref[0]) and np.array_equal(_raw_results(ix, tot)[2], ref[2])
+        ix.close()
+
+
 def test_existing_searches_are_untouched():
     C, Q, t, S = X.random_case(5000, 37, 256, CYCLE_A)
     M = F.random_filters(len(C), (0.5, 0.05, 0.002), seed=11)

@@ -274,6 +274,32 @@ def test_documents():
     ix.close()
 
 
+def test_filtered_pools_of_two_blocks_leave_the_document_window_search_as_it_was():
+    """600 rows in documents of about three, 300 sub-queries — the search that makes the pool runs two blocks — and a per-group mix
+    of no filter, a half-density and an empty one.  The lists are search_filtered's and, with documents, search_groups_window's;
+    and the nested call leaves nothing behind: the document window search from host arrays, filter ids included, returns the same
+    bits after every rank fusion as before."""
+    C, Q = R.unit(600, 64, 1), R.unit(300, 64, 2)
+    off = R.random_offsets(600, 3)
+    lims = M.layout(300, (1, 3, 8, 2, 5))
+    masks = np.concatenate([F.random_filters(600, (0.5,), seed=11), np.zeros((1, 600), dtype=bool)])
+    ix = _index(C, masks)
+    ix.set_groups(off)
+    fog = ((np.arange(len(lims) - 1) % 3) - 1).astype(np.int64)          # -1 (no filter), 0, 1 (allows nothing), ...
+    foq = np.repeat(fog, np.diff(lims))
+    assert (foq[256:] == 0).any() and (foq[256:] == 1).any()
+    before = ix.search_groups_window(Q, 0, 20, foq)
+    rows = ix.search_filtered(Q, 20, foq)[1]
+    assert (before[2][foq == 1] == -1).all() and (before[2][foq != 1] >= 0).all()
+    for documents, lists in ((True, before[2]), (False, rows)):
+        want = RR.rrf_ref(lists, lims, 10)
+        for got in _search_both(ix, Q, lims, 10, 20, 60.0, None, fog, documents):
+            _same(got, want)
+            after = ix.search_groups_window(Q, 0, 20, foq)
+            assert all(a.dtype == b.dtype and a.tobytes() == b.tobytes() for a, b in zip(after, before))
+    ix.close()
+
+
 # ------------------------------------------------------------------------------------------- 6. other index states ---
 def test_tie_tier():
     C, Q, _ = R.tie_tier()

@@ -347,17 +347,24 @@ class HipIndex:
         return q, cuda
 
     def _grouped_queries(self, queries, lims):
-        """the sub-queries of search_multi / search_rrf -> (q flat [n_sub][dim] where it lives, cuda, lims int64 host): flat
-        `queries` with `lims` [n_groups + 1], or [n_groups][m][dim] with `lims=None`"""
+        """the sub-queries of search_multi / search_multi_groups / search_rrf -> (q flat [n_sub][dim] where it lives, cuda, lims
+        int64 host, n_groups, n_sub): flat `queries` with `lims` [n_groups + 1], or [n_groups][m][dim] with `lims=None`"""
         if lims is None:
             q, cuda = self._queries(queries, 3, f"[n_groups][m][{self.dim}] when lims is None")
             lim = np.arange(q.shape[0] + 1, dtype=np.int64) * q.shape[1]
-            return q.reshape(-1, self.dim), cuda, lim
-        q, cuda = self._queries(queries, 2, f"[n_sub][{self.dim}] with lims")
-        lim = np.ascontiguousarray(self._row_ids(lims), dtype=np.int64)
-        if len(lim) < 1:
-            raise ValueError("lims must hold n_groups + 1 entries")
-        return q, cuda, lim
+            q = q.reshape(-1, self.dim)
+        else:
+            q, cuda = self._queries(queries, 2, f"[n_sub][{self.dim}] with lims")
+            lim = np.ascontiguousarray(self._row_ids(lims), dtype=np.int64)
+            if len(lim) < 1:
+                raise ValueError("lims must hold n_groups + 1 entries")
+        return q, cuda, lim, len(lim) - 1, int(q.shape[0])
+
+    def _filter_of_group(self, q, cuda: bool, ng: int, filter_of_group):
+        """`filter_of_group` of those searches, one entry per group, where the queries live -> (keep-alive, pointer); None: no filter"""
+        if filter_of_group is None:
+            return None, C.c_void_p(None)
+        return self._filter_of_query(torch.empty((ng, 0), device=q.device) if cuda else np.empty((ng, 0)), filter_of_group)
 
     def _stats3(self, fn, names, reset: bool) -> Dict[str, int]:
         """the three counters of one search's `*_search_stats` under `names`, cleared with `reset`"""
@@ -498,6 +505,11 @@ class HipIndex:
         no filter (none need to be set).  `max_total=None`: min(nq * rows, 2 ** 26) entries; a larger result raises
         (VR_ERR_CAPACITY).  `sort=True`: every segment by score descending, then id ascending — the library's ranking order;
         `sort=False`: the ABI's ascending-id order."""
+        return self._range_call(False, queries, threshold, filter_of_query, max_total, sort)
+
+    def _range_call(self, grouped: bool, queries, threshold, filter_of_query, max_total, sort):
+        """search_range, or with `grouped` search_groups_range: the thresholds, `max_total`, the search and its `*_results` call,
+        then every segment sorted by the search's own key"""
         q, cuda = self._queries(queries)
         nq = int(q.shape[0])
         if isinstance(threshold, torch.Tensor):
@@ -508,7 +520,9 @@ class HipIndex:
             raise ValueError(f"{len(thr)} thresholds for {nq} queries")
         keep, fptr = (None, C.c_void_p(None)) if filter_of_query is None else self._filter_of_query(q, filter_of_query)
         if max_total is None:
-            max_total = max(1, min(nq * len(self), 2 ** 26))
+            max_total = max(1, min(nq * (self.n_groups if grouped else len(self)), 2 ** 26))
+        search, results = ("vr_index_search_groups_range", "vr_index_group_range_results") if grouped else \
+                          ("vr_index_search_range", "vr_index_range_results")
         total = C.c_int64(0)
         stream = C.c_void_p(_stream_ptr(self.device))
         if cuda:
@@ -518,29 +532,36 @@ class HipIndex:
         else:
             lims = np.empty(nq + 1, dtype=np.int64)
             ptrs = (q.ctypes.data, thr.ctypes.data, lims.ctypes.data)
-        _lib.check(self.lib.vr_index_search_range(self._h, C.c_void_p(ptrs[0]), nq, C.c_void_p(ptrs[1]), fptr, int(max_total),
-                                                  C.c_void_p(ptrs[2]), C.byref(total), 1 if cuda else 0, stream), "vr_index_search_range")
+        _lib.check(getattr(self.lib, search)(self._h, C.c_void_p(ptrs[0]), nq, C.c_void_p(ptrs[1]), fptr, int(max_total),
+                                             C.c_void_p(ptrs[2]), C.byref(total), 1 if cuda else 0, stream), search)
         n = int(total.value)
-        if cuda:
-            scores = torch.empty(n, dtype=torch.float32, device=q.device)
-            ids = torch.empty(n, dtype=torch.int64, device=q.device)
-            optrs = (scores.data_ptr(), ids.data_ptr())
+        if cuda:       # scores, (best) rows and with `grouped` groups
+            outs = [torch.empty(n, dtype=d, device=q.device) for d in (torch.float32, torch.int64, torch.int64)[:3 if grouped else 2]]
+            optrs = [C.c_void_p(x.data_ptr()) for x in outs]
         else:
-            scores, ids = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.int64)
-            optrs = (scores.ctypes.data, ids.ctypes.data)
-        _lib.check(self.lib.vr_index_range_results(self._h, C.c_void_p(optrs[0]), C.c_void_p(optrs[1]), n, 1 if cuda else 0, stream),
-                   "vr_index_range_results")
+            outs = [np.empty(n, dtype=d) for d in (np.float32, np.int64, np.int64)[:3 if grouped else 2]]
+            optrs = [C.c_void_p(x.ctypes.data) for x in outs]
+        _lib.check(getattr(self.lib, results)(self._h, *optrs, n, 1 if cuda else 0, stream), results)
         del keep
         if sort and n > 1:
+            scores = outs[0]
             if cuda:
                 seg = torch.repeat_interleave(torch.arange(nq, device=q.device), lims[1:] - lims[:-1])
-                o1 = torch.sort(scores, descending=True, stable=True)[1]     # ids ascend already: the stable sorts keep that
+                key = scores
+                if grouped:     # the ranking's order of floats is that of the keys' orderable bits (-0.0 < +0.0)
+                    bits = scores.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+                    key = torch.where(bits >= 0x80000000, 0xFFFFFFFF - bits, bits + 0x80000000)
+                o1 = torch.sort(key, descending=True, stable=True)[1]        # ids (groups) ascend already: the stable sorts keep that
                 order = o1[torch.sort(seg[o1], stable=True)[1]]
             else:
                 seg = np.repeat(np.arange(nq), np.diff(lims))
-                order = np.lexsort((ids, -scores.astype(np.float64), seg))
-            scores, ids = scores[order], ids[order]
-        return lims, scores, ids
+                if grouped:
+                    bits = scores.view(np.uint32).astype(np.int64)
+                    order = np.lexsort((outs[2], -np.where(bits >= 0x80000000, 0xFFFFFFFF - bits, bits + 0x80000000), seg))
+                else:
+                    order = np.lexsort((outs[1], -scores.astype(np.float64), seg))
+            outs = [x[order] for x in outs]
+        return (lims, *outs)
 
     def range_search_stats(self, reset: bool = False) -> Dict[str, int]:
         """Range searches since the last reset: queries, candidate rows re-scored in fp32 (the rows inside the error band below
@@ -572,30 +593,32 @@ class HipIndex:
             lims = np.arange(nq + 1, dtype=np.int64) * (1 if v.ndim == 1 else v.shape[1])
         return np.ascontiguousarray(v.reshape(-1), dtype=dtype), lims, shape
 
-    def _rank_call(self, queries, flat, lims, shape, filter_of_query, strict):
-        """vr_index_rank_rows (int64 targets) or vr_index_count_range (float32 thresholds) -> (scores or None, counts)"""
+    def _rank_call(self, grouped: bool, queries, flat, lims, shape, filter_of_query, strict):
+        """The rank search of rows (vr_index_rank_rows / vr_index_count_range) or with `grouped` of documents (vr_index_rank_groups /
+        vr_index_count_groups_range): int64 targets -> (scores, best rows — documents only — and ranks), float32 thresholds ->
+        counts"""
         q, cuda = self._queries(queries)
         nq, n = int(q.shape[0]), len(flat)
         ranks = flat.dtype == np.int64
         keep, fptr = (None, C.c_void_p(None)) if filter_of_query is None else self._filter_of_query(q, filter_of_query)
         if cuda:
-            scores = torch.empty(n, dtype=torch.float32, device=q.device)
-            counts = torch.empty(n, dtype=torch.int64, device=q.device)
-            ptrs = (q.data_ptr(), scores.data_ptr(), counts.data_ptr())
+            outs = [torch.empty(n, dtype=d, device=q.device) for d in (torch.float32, torch.int64, torch.int64)]
+            ptrs = [C.c_void_p(x.data_ptr()) for x in [q] + outs]
         else:
-            scores, counts = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.int64)
-            ptrs = (q.ctypes.data, scores.ctypes.data, counts.ctypes.data)
-        stream = C.c_void_p(_stream_ptr(self.device))
+            outs = [np.empty(n, dtype=d) for d in (np.float32, np.int64, np.int64)]
+            ptrs = [C.c_void_p(x.ctypes.data) for x in [q] + outs]
         if ranks:
-            _lib.check(self.lib.vr_index_rank_rows(self._h, C.c_void_p(ptrs[0]), nq, C.c_void_p(lims.ctypes.data), C.c_void_p(flat.ctypes.data),
-                                                   fptr, C.c_void_p(ptrs[1]), C.c_void_p(ptrs[2]), 1 if cuda else 0, stream),
-                       "vr_index_rank_rows")
+            name = "vr_index_rank_groups" if grouped else "vr_index_rank_rows"
+            args = [fptr, ptrs[1]] + ([ptrs[2]] if grouped else []) + [ptrs[3]]
         else:
-            _lib.check(self.lib.vr_index_count_range(self._h, C.c_void_p(ptrs[0]), nq, C.c_void_p(lims.ctypes.data),
-                                                     C.c_void_p(flat.ctypes.data), 1 if strict else 0, fptr, C.c_void_p(ptrs[2]),
-                                                     1 if cuda else 0, stream), "vr_index_count_range")
+            name = "vr_index_count_groups_range" if grouped else "vr_index_count_range"
+            args = [1 if strict else 0, fptr, ptrs[3]]
+        _lib.check(getattr(self.lib, name)(self._h, ptrs[0], nq, C.c_void_p(lims.ctypes.data), C.c_void_p(flat.ctypes.data), *args,
+                                           1 if cuda else 0, C.c_void_p(_stream_ptr(self.device))), name)
         del keep
-        return (scores.reshape(shape) if ranks else None), counts.reshape(shape)
+        if not ranks:
+            return outs[2].reshape(shape)
+        return tuple(x.reshape(shape) for x in (outs if grouped else (outs[0], outs[2])))
 
     def rank_rows(self, queries, ids, lims=None, filter_of_query=None):
         """Where the named rows stand (include/visrag_hip.h: vr_index_rank_rows) -> (scores f32, ranks i64) shaped as `ids`: the
@@ -605,7 +628,7 @@ class HipIndex:
         as in `search_filtered`: the rank among the rows the filter allows — for a target the filter forbids, the position it
         WOULD take.  cuda queries -> cuda tensors, numpy / cpu -> numpy."""
         flat, lims, shape = self._pairs(ids, lims, int(queries.shape[0]), np.int64, "ids")
-        return self._rank_call(queries, flat, lims, shape, filter_of_query, False)
+        return self._rank_call(False, queries, flat, lims, shape, filter_of_query, False)
 
     def count_range(self, queries, thresholds, lims=None, filter_of_query=None, strict: bool = False):
         """How many rows reach a threshold (include/visrag_hip.h: vr_index_count_range) -> counts i64 shaped as `thresholds`
@@ -613,13 +636,24 @@ class HipIndex:
         the rows.  `thresholds`: a scalar, [nq], [nq][T], or flat with `lims`.  `filter_of_query` as in `search_filtered`.
         cuda queries -> a cuda tensor, numpy / cpu -> numpy."""
         flat, lims, shape = self._pairs(thresholds, lims, int(queries.shape[0]), np.float32, "thresholds")
-        return self._rank_call(queries, flat, lims, shape, filter_of_query, strict)[1]
+        return self._rank_call(False, queries, flat, lims, shape, filter_of_query, strict)
 
     def rank_search_stats(self, reset: bool = False) -> Dict[str, int]:
         """Rank searches and counts since the last reset: (query, bar) pairs, rows of the error bands re-scored in fp32, rows counted."""
         return self._stats3(self.lib.vr_index_rank_search_stats, ("pairs", "candidates", "counted"), reset)
 
     # ---- windowed search (include/visrag_hip.h: vr_index_search_window) ----
+    def _offsets(self, offset, nq: int) -> np.ndarray:
+        """`offset` of the window searches as int64 [nq]: an int is every query's"""
+        off = self._row_ids(offset)
+        if off.size == 1 and nq != 1:
+            off = np.full(nq, off[0], dtype=np.int64)
+        if len(off) != nq:
+            raise ValueError(f"{len(off)} offsets for {nq} queries")
+        if (off < 0).any():
+            raise ValueError("offsets must be >= 0")
+        return off
+
     def search_window(self, queries, offset, k: int, filter_of_query=None):
         """The rows at ranks [offset, offset + k) of every query's fp32 ranking (include/visrag_hip.h: vr_index_search_window)
         -> (scores [nq,k] f32, ids [nq,k] i64): entry j is the row of rank offset + j — score descending, then lower id first,
@@ -628,14 +662,7 @@ class HipIndex:
         (any int sequence or tensor), each >= 0, however deep; slots at or past the number of allowed rows are (-inf, -1).
         1 <= k <= 1000: page for more.  `filter_of_query` as in `search_filtered`, None = no filter (none need to be set).
         cuda in -> cuda out, numpy / cpu in -> numpy out."""
-        nq = int(queries.shape[0])
-        off = self._row_ids(offset)
-        if off.size == 1 and nq != 1:
-            off = np.full(nq, off[0], dtype=np.int64)
-        if len(off) != nq:
-            raise ValueError(f"{len(off)} offsets for {nq} queries")
-        if (off < 0).any():
-            raise ValueError("offsets must be >= 0")
+        off = self._offsets(offset, int(queries.shape[0]))
         keep, fptr = (None, C.c_void_p(None)) if filter_of_query is None else self._filter_of_query(queries, filter_of_query)
 
         def fn(h, q, n, kk, out_scores, out_ids, on_device, stream):
@@ -658,14 +685,7 @@ class HipIndex:
         `search_groups(q, k)` bit for bit.  `offset`: an int (every query's) or one per query (any int sequence or tensor), each
         >= 0, however deep.  1 <= k <= 1000: page for more.  `filter_of_query` as in `search_filtered`, None = no filter (none
         need to be set).  cuda in -> cuda out, numpy / cpu in -> numpy out."""
-        nq = int(queries.shape[0])
-        off = self._row_ids(offset)
-        if off.size == 1 and nq != 1:
-            off = np.full(nq, off[0], dtype=np.int64)
-        if len(off) != nq:
-            raise ValueError(f"{len(off)} offsets for {nq} queries")
-        if (off < 0).any():
-            raise ValueError("offsets must be >= 0")
+        off = self._offsets(offset, int(queries.shape[0]))
         keep, fptr = (None, C.c_void_p(None)) if filter_of_query is None else self._filter_of_query(queries, filter_of_query)
 
         def fn(h, q, n, kk, out_scores, out_ids, out_groups, on_device, stream):
@@ -679,30 +699,6 @@ class HipIndex:
         return self._stats3(self.lib.vr_index_group_window_search_stats, ("queries", "documents", "page_dots"), reset)
 
     # ---- document rank search (include/visrag_hip.h: vr_index_rank_groups / vr_index_count_groups_range) ----
-    def _group_rank_call(self, queries, flat, lims, shape, filter_of_query, strict):
-        """vr_index_rank_groups (int64 targets) -> (scores, best rows, ranks), or vr_index_count_groups_range (float32 thresholds)
-        -> counts"""
-        q, cuda = self._queries(queries)
-        nq, n = int(q.shape[0]), len(flat)
-        ranks = flat.dtype == np.int64
-        keep, fptr = (None, C.c_void_p(None)) if filter_of_query is None else self._filter_of_query(q, filter_of_query)
-        if cuda:
-            outs = [torch.empty(n, dtype=d, device=q.device) for d in (torch.float32, torch.int64, torch.int64)]
-            ptrs = [C.c_void_p(x.data_ptr()) for x in [q] + outs]
-        else:
-            outs = [np.empty(n, dtype=d) for d in (np.float32, np.int64, np.int64)]
-            ptrs = [C.c_void_p(x.ctypes.data) for x in [q] + outs]
-        stream = C.c_void_p(_stream_ptr(self.device))
-        if ranks:
-            _lib.check(self.lib.vr_index_rank_groups(self._h, ptrs[0], nq, C.c_void_p(lims.ctypes.data), C.c_void_p(flat.ctypes.data),
-                                                     fptr, ptrs[1], ptrs[2], ptrs[3], 1 if cuda else 0, stream), "vr_index_rank_groups")
-        else:
-            _lib.check(self.lib.vr_index_count_groups_range(self._h, ptrs[0], nq, C.c_void_p(lims.ctypes.data),
-                                                            C.c_void_p(flat.ctypes.data), 1 if strict else 0, fptr, ptrs[3],
-                                                            1 if cuda else 0, stream), "vr_index_count_groups_range")
-        del keep
-        return tuple(x.reshape(shape) for x in outs) if ranks else outs[2].reshape(shape)
-
     def rank_groups(self, queries, groups, lims=None, filter_of_query=None):
         """Where the named documents stand (include/visrag_hip.h: vr_index_rank_groups) -> (scores f32, best rows i64, ranks i64)
         shaped as `groups`.  The ranking is `search_groups_window`'s: a group (`set_groups`) is present if the query's filter
@@ -715,7 +711,7 @@ class HipIndex:
         target per query), [nq][T], or flat with `lims` [nq + 1]; duplicates allowed.  `filter_of_query` as in `search_filtered`,
         None = no filter.  cuda queries -> cuda tensors, numpy / cpu -> numpy."""
         flat, lims, shape = self._pairs(groups, lims, int(queries.shape[0]), np.int64, "groups")
-        return self._group_rank_call(queries, flat, lims, shape, filter_of_query, False)
+        return self._rank_call(True, queries, flat, lims, shape, filter_of_query, False)
 
     def count_groups_range(self, queries, thresholds, lims=None, filter_of_query=None, strict: bool = False):
         """How many documents reach a threshold (include/visrag_hip.h: vr_index_count_groups_range) -> counts i64 shaped as
@@ -723,7 +719,7 @@ class HipIndex:
         `thresholds`: a scalar, [nq], [nq][T], or flat with `lims`; finite; -0.0 counts as +0.0.  `filter_of_query` as in
         `search_filtered`.  cuda queries -> a cuda tensor, numpy / cpu -> numpy."""
         flat, lims, shape = self._pairs(thresholds, lims, int(queries.shape[0]), np.float32, "thresholds")
-        return self._group_rank_call(queries, flat, lims, shape, filter_of_query, strict)
+        return self._rank_call(True, queries, flat, lims, shape, filter_of_query, strict)
 
     def group_rank_search_stats(self, reset: bool = False) -> Dict[str, int]:
         """Document rank searches and counts since the last reset: (query, bar) pairs, documents of the error bands re-scored (a
@@ -742,56 +738,7 @@ class HipIndex:
         set).  `max_total=None`: min(nq * groups, 2 ** 26) entries, at least 1; a larger result raises (VR_ERR_CAPACITY).
         `sort=True`: every segment in `search_groups_window`'s order, score descending, then lower group first; `sort=False`: the
         ABI's ascending-group order."""
-        q, cuda = self._queries(queries)
-        nq = int(q.shape[0])
-        if isinstance(threshold, torch.Tensor):
-            threshold = threshold.detach().cpu().numpy()
-        thr = np.array(threshold, dtype=np.float32).reshape(-1)          # (a copy: the caller's array may be read-only)
-        thr = np.full(nq, thr[0], dtype=np.float32) if thr.size == 1 else np.ascontiguousarray(thr)
-        if len(thr) != nq:
-            raise ValueError(f"{len(thr)} thresholds for {nq} queries")
-        keep, fptr = (None, C.c_void_p(None)) if filter_of_query is None else self._filter_of_query(q, filter_of_query)
-        if max_total is None:
-            max_total = max(1, min(nq * self.n_groups, 2 ** 26))
-        total = C.c_int64(0)
-        stream = C.c_void_p(_stream_ptr(self.device))
-        if cuda:
-            thr_d = torch.from_numpy(thr).to(q.device)
-            lims = torch.empty(nq + 1, dtype=torch.int64, device=q.device)
-            ptrs = (q.data_ptr(), thr_d.data_ptr(), lims.data_ptr())
-        else:
-            lims = np.empty(nq + 1, dtype=np.int64)
-            ptrs = (q.ctypes.data, thr.ctypes.data, lims.ctypes.data)
-        _lib.check(self.lib.vr_index_search_groups_range(self._h, C.c_void_p(ptrs[0]), nq, C.c_void_p(ptrs[1]), fptr, int(max_total),
-                                                         C.c_void_p(ptrs[2]), C.byref(total), 1 if cuda else 0, stream),
-                   "vr_index_search_groups_range")
-        n = int(total.value)
-        if cuda:
-            scores = torch.empty(n, dtype=torch.float32, device=q.device)
-            rows = torch.empty(n, dtype=torch.int64, device=q.device)
-            groups = torch.empty(n, dtype=torch.int64, device=q.device)
-            optrs = (scores.data_ptr(), rows.data_ptr(), groups.data_ptr())
-        else:
-            scores, rows, groups = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int64)
-            optrs = (scores.ctypes.data, rows.ctypes.data, groups.ctypes.data)
-        _lib.check(self.lib.vr_index_group_range_results(self._h, C.c_void_p(optrs[0]), C.c_void_p(optrs[1]), C.c_void_p(optrs[2]), n,
-                                                         1 if cuda else 0, stream), "vr_index_group_range_results")
-        del keep
-        if sort and n > 1:
-            # the ranking's order of floats is that of the keys' orderable bits (-0.0 < +0.0); groups ascend already
-            if cuda:
-                bits = scores.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
-                key = torch.where(bits >= 0x80000000, 0xFFFFFFFF - bits, bits + 0x80000000)
-                seg = torch.repeat_interleave(torch.arange(nq, device=q.device), lims[1:] - lims[:-1])
-                o1 = torch.sort(key, descending=True, stable=True)[1]
-                order = o1[torch.sort(seg[o1], stable=True)[1]]
-            else:
-                bits = scores.view(np.uint32).astype(np.int64)
-                key = np.where(bits >= 0x80000000, 0xFFFFFFFF - bits, bits + 0x80000000)
-                seg = np.repeat(np.arange(nq), np.diff(lims))
-                order = np.lexsort((groups, -key, seg))
-            scores, rows, groups = scores[order], rows[order], groups[order]
-        return lims, scores, rows, groups
+        return self._range_call(True, queries, threshold, filter_of_query, max_total, sort)
 
     def group_range_search_stats(self, reset: bool = False) -> Dict[str, int]:
         """Document range searches since the last reset: queries, documents of the error bands re-scored (everything that can
@@ -811,12 +758,8 @@ class HipIndex:
         out, numpy / cpu in -> numpy out."""
         if fuse not in ("max", "min"):
             raise ValueError("fuse must be 'max' or 'min'")
-        q, cuda, lim = self._grouped_queries(queries, lims)
-        ng, n_sub = len(lim) - 1, int(q.shape[0])
-        if filter_of_group is None:
-            keep, fptr = None, C.c_void_p(None)
-        else:
-            keep, fptr = self._filter_of_query(torch.empty((ng, 0), device=q.device) if cuda else np.empty((ng, 0)), filter_of_group)
+        q, cuda, lim, ng, n_sub = self._grouped_queries(queries, lims)
+        keep, fptr = self._filter_of_group(q, cuda, ng, filter_of_group)
         if cuda:
             outs = [torch.empty((ng, k), dtype=d, device=q.device) for d in (torch.float32, torch.int64, torch.int32)]
             ptrs = [x.data_ptr() for x in [q] + outs]
@@ -851,12 +794,8 @@ class HipIndex:
         [n_questions][k][m].  1 <= k <= 1000.  cuda in -> cuda out, numpy / cpu in -> numpy out."""
         if fuse not in ("max", "min"):
             raise ValueError("fuse must be 'max' or 'min'")
-        q, cuda, lim = self._grouped_queries(queries, lims)
-        ng, n_sub = len(lim) - 1, int(q.shape[0])
-        if filter_of_group is None:
-            keep, fptr = None, C.c_void_p(None)
-        else:
-            keep, fptr = self._filter_of_query(torch.empty((ng, 0), device=q.device) if cuda else np.empty((ng, 0)), filter_of_group)
+        q, cuda, lim, ng, n_sub = self._grouped_queries(queries, lims)
+        keep, fptr = self._filter_of_group(q, cuda, ng, filter_of_group)
         kk = max(k, 0)
         if cuda:
             outs = [torch.empty((ng, kk), dtype=d, device=q.device) for d in (torch.float32, torch.int64, torch.int64, torch.int32)]
@@ -897,13 +836,9 @@ class HipIndex:
         `lims=None`.  `weights`: one float per sub-query, None = 1.  Groups hold 1..256 sub-queries and at most
         `rrf_max_entries()` list slots, 1 <= k, depth <= 1000.  `filter_of_group` as in `search_multi`.  cuda in -> cuda out,
         numpy / cpu in -> numpy out."""
-        q, cuda, lim = self._grouped_queries(queries, lims)
-        ng, n_sub = len(lim) - 1, int(q.shape[0])
+        q, cuda, lim, ng, n_sub = self._grouped_queries(queries, lims)
         w, wptr = _rrf_weights(weights, n_sub)
-        if filter_of_group is None:
-            keep, fptr = None, C.c_void_p(None)
-        else:
-            keep, fptr = self._filter_of_query(torch.empty((ng, 0), device=q.device) if cuda else np.empty((ng, 0)), filter_of_group)
+        keep, fptr = self._filter_of_group(q, cuda, ng, filter_of_group)
         if cuda:
             outs = [torch.empty((ng, k), dtype=d, device=q.device) for d in (torch.float32, torch.int64, torch.int32)]
             ptrs = [x.data_ptr() for x in [q] + outs]
