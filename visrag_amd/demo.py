@@ -34,6 +34,7 @@ HipIndex.  The generation step of answer.py (MiniCPM-V-2.6 chat) is outside this
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import List, Optional, Sequence
 
@@ -106,6 +107,60 @@ def load_knowledge_base(knowledge_base_path: str, device: Optional[int] = None):
     return ix, names
 
 
+@contextlib.contextmanager
+def _base(knowledge_base_path: str, index, names, model, documents: bool = False, groups: Optional[str] = None):
+    """-> (index, names) for the length of one call.  `index is None`: the base on disk, loaded (`documents`: as a document base,
+    load_document_base) and closed again however the call ends.  A caller's index stays open; `documents` and no groups set on
+    it: they are set from the names — `groups="always"`: whenever it has none, `groups="rows"`: only if it holds rows, None:
+    left to the caller — and rows that are not adjacent per document raise ValueError."""
+    if index is None:
+        load = load_document_base if documents else load_knowledge_base
+        index, names = load(knowledge_base_path, model.encoder.device if model is not None else None)
+        try:
+            yield index, names
+        finally:
+            index.close()
+        return
+    if documents and groups and not index.n_groups and (groups == "always" or len(index)):
+        order, offsets, _ = group_rows([doc_of_page(n) for n in names])
+        if not np.array_equal(order, np.arange(len(order))):
+            raise ValueError("the pages of a document are not adjacent in this index: load it with load_document_base()")
+        index.set_groups(offsets)
+    yield index, names
+
+
+def _query_rows(query, model, tokenizer, dim: Optional[int] = None):
+    """One question — a string, or its embedding ([dim] or [1, dim]) — -> [1, dim]; with `dim` SEVERAL questions — a list of
+    strings, or their embeddings [m, dim] — -> contiguous float32 [m, dim].  Strings are encoded behind QUERY_INSTRUCTION."""
+    if dim is None and isinstance(query, str):
+        return encode(model, tokenizer, [QUERY_INSTRUCTION + query])
+    if dim is not None and isinstance(query, (list, tuple)) and all(isinstance(x, str) for x in query):
+        q = encode(model, tokenizer, [QUERY_INSTRUCTION + x for x in query])
+    else:
+        q = np.asarray(query.detach().cpu() if isinstance(query, torch.Tensor) else query, dtype=np.float32)
+    return q.reshape(1, -1) if dim is None else np.ascontiguousarray(np.asarray(q, dtype=np.float32).reshape(-1, dim))
+
+
+def _documents_mask(names, n: int, documents, strict: bool):
+    """`documents` (None: no filter, -> None) -> the one filter of a question, bool [n]: the pages of those documents.  A name no
+    page carries allows nothing; with `strict` (the document-level functions) it raises ValueError."""
+    if documents is None:
+        return None
+    docs = [doc_of_page(nm) for nm in names[:n]]
+    wanted = set(documents)
+    unknown = sorted(wanted - set(docs)) if strict else []
+    if unknown:
+        raise ValueError(f"no page of the base belongs to {unknown[0]!r}" + (f" (and {len(unknown) - 1} more)" if len(unknown) > 1 else ""))
+    return label_filters(docs, [wanted])
+
+
+def _paths(knowledge_base_path: str, names, ids, scores):
+    """one question's row ids and scores -> (paths of the taken slots (id >= 0), their scores)"""
+    ids, scores = (x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in (ids, scores))
+    keep = [int(i) for i in ids if i >= 0]
+    return [os.path.join(knowledge_base_path, names[i]) for i in keep], [float(s) for s in scores[: len(keep)]]
+
+
 @torch.no_grad()
 def retrieve(knowledge_base_path: str, query: str, topk: int, model, tokenizer, index=None, names=None,
              return_scores: bool = False, documents=None, diverse=None, pool=None, offset: int = 0):
@@ -125,76 +180,35 @@ def retrieve(knowledge_base_path: str, query: str, topk: int, model, tokenizer, 
         return None
     if offset < 0:
         raise ValueError("offset must be >= 0")
-    if offset > 0:
-        if diverse is not None:
-            raise ValueError("offset and diverse exclude each other: MMR picks have no ranks to page through")
-        return _retrieve_window(knowledge_base_path, query, topk, model, tokenizer, index, names, return_scores, documents, int(offset))
-    if diverse is not None:
-        return _retrieve_diverse(knowledge_base_path, query, topk, model, tokenizer, index, names, return_scores, documents,
-                                 float(diverse), pool)
-    if documents is not None:
-        return _retrieve_filtered(knowledge_base_path, query, topk, model, tokenizer, index, names, return_scores, documents)
-    own = index is None
-    if own:
-        index, names = load_knowledge_base(knowledge_base_path, model.encoder.device)
-    q = encode(model, tokenizer, [QUERY_INSTRUCTION + query])
-    sc, ids = index.search(q, min(topk, max(len(index), 1)))
-    if own:
-        index.close()
-    keep = [int(i) for i in ids[0] if i >= 0]
-    paths = [os.path.join(knowledge_base_path, names[i]) for i in keep]
-    return (paths, [float(s) for s in sc[0][: len(keep)]]) if return_scores else paths
-
-
-def _retrieve_filtered(knowledge_base_path, query, topk, model, tokenizer, index, names, return_scores, documents):
-    """retrieve() among the pages of `documents`: one filter, set for this question (it replaces the index's filters)"""
-    own = index is None
-    if own:
-        index, names = load_knowledge_base(knowledge_base_path, model.encoder.device if model is not None else None)
-    n = len(index)
-    mask = label_filters([doc_of_page(nm) for nm in names[:n]], [documents])
-    if isinstance(query, str):
-        q = encode(model, tokenizer, [QUERY_INSTRUCTION + query])
-    else:
-        q = np.asarray(query.detach().cpu() if isinstance(query, torch.Tensor) else query, dtype=np.float32).reshape(1, -1)
-    allowed = int(mask.sum())
-    if allowed == 0 or topk <= 0:
+    if offset > 0 and diverse is not None:
+        raise ValueError("offset and diverse exclude each other: MMR picks have no ranks to page through")
+    offset = int(offset)
+    with _base(knowledge_base_path, index, names, model) as (index, names):
+        n = len(index)
+        if documents is None and diverse is None and offset == 0:         # the reference's call: a string, the plain search
+            sc, ids = index.search(encode(model, tokenizer, [QUERY_INSTRUCTION + query]), min(topk, max(n, 1)))
+            paths, scores = _paths(knowledge_base_path, names, ids[0], sc[0])
+            return (paths, scores) if return_scores else paths
+        q = _query_rows(query, model, tokenizer)
+        mask = _documents_mask(names, n, documents, strict=False)        # one filter, set for this question (it replaces the index's)
+        rows, f = (n, None) if mask is None else (int(mask.sum()), 0)
         paths, scores = [], []
-    else:
-        index.set_filters(mask)
-        sc, ids = index.search_filtered(q, min(topk, allowed), 0)
-        keep = [int(i) for i in ids[0] if i >= 0]
-        paths = [os.path.join(knowledge_base_path, names[i]) for i in keep]
-        scores = [float(s) for s in sc[0][: len(keep)]]
-    if own:
-        index.close()
-    return (paths, scores) if return_scores else paths
-
-
-def _retrieve_window(knowledge_base_path, query, topk, model, tokenizer, index, names, return_scores, documents, offset):
-    """retrieve() at ranks [offset, offset + topk); `documents` given: among their pages, through one filter set for this question"""
-    own = index is None
-    if own:
-        index, names = load_knowledge_base(knowledge_base_path, model.encoder.device if model is not None else None)
-    n = len(index)
-    if isinstance(query, str):
-        q = encode(model, tokenizer, [QUERY_INSTRUCTION + query])
-    else:
-        q = np.asarray(query.detach().cpu() if isinstance(query, torch.Tensor) else query, dtype=np.float32).reshape(1, -1)
-    mask = None if documents is None else label_filters([doc_of_page(nm) for nm in names[:n]], [documents])
-    rows = n if mask is None else int(mask.sum())
-    paths, scores = [], []
-    if topk > 0 and offset < rows:
-        if mask is not None:
-            index.set_filters(mask)
-        for o in range(offset, min(offset + topk, rows), 1000):           # a list longer than one window: paged
-            sc, ids = index.search_window(q, o, min(1000, offset + topk - o, rows - o), None if mask is None else 0)
-            sc, ids = (x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in (sc, ids))
-            keep = [int(i) for i in ids[0] if i >= 0]
-            paths += [os.path.join(knowledge_base_path, names[i]) for i in keep]
-            scores += [float(s) for s in sc[0][: len(keep)]]
-    if own:
-        index.close()
+        if topk > 0 and offset < rows:
+            if mask is not None:
+                index.set_filters(mask)
+            if diverse is not None:                                       # MMR picks, in pick order
+                k = min(topk, rows)
+                sc, ids = index.search_diverse(q, k, None if pool is None else max(int(pool), k), float(diverse), f)
+                paths, scores = _paths(knowledge_base_path, names, ids[0], sc[0])
+            elif offset > 0:                                              # ranks [offset, offset + topk)
+                for o in range(offset, min(offset + topk, rows), 1000):   # a list longer than one window: paged
+                    sc, ids = index.search_window(q, o, min(1000, offset + topk - o, rows - o), f)
+                    page = _paths(knowledge_base_path, names, ids[0], sc[0])
+                    paths += page[0]
+                    scores += page[1]
+            else:
+                sc, ids = index.search_filtered(q, min(topk, rows), 0)
+                paths, scores = _paths(knowledge_base_path, names, ids[0], sc[0])
     return (paths, scores) if return_scores else paths
 
 
@@ -211,28 +225,18 @@ def retrieve_any(knowledge_base_path: str, questions, topk: int, model, tokenize
     to keep the index resident."""
     if not os.path.exists(knowledge_base_path):
         return None
-    own = index is None
-    if own:
-        index, names = load_knowledge_base(knowledge_base_path, model.encoder.device if model is not None else None)
-    n = len(index)
-    if isinstance(questions, (list, tuple)) and all(isinstance(x, str) for x in questions):
-        q = encode(model, tokenizer, [QUERY_INSTRUCTION + x for x in questions])
-    else:
-        q = np.asarray(questions.detach().cpu() if isinstance(questions, torch.Tensor) else questions, dtype=np.float32)
-    q = np.ascontiguousarray(np.asarray(q, dtype=np.float32).reshape(-1, index.dim))
-    mask = None if documents is None else label_filters([doc_of_page(nm) for nm in names[:n]], [documents])
-    k = min(topk, n if mask is None else int(mask.sum()), 1000)
-    paths, scores, deciding = [], [], []
-    if k > 0 and len(q) > 0:
-        if mask is not None:
-            index.set_filters(mask)
-        sc, ids, which = index.search_multi(q, [0, len(q)], k, fuse, None if mask is None else 0)
-        keep = [int(i) for i in ids[0] if i >= 0]
-        paths = [os.path.join(knowledge_base_path, names[i]) for i in keep]
-        scores = [float(s) for s in sc[0][: len(keep)]]
-        deciding = [int(w) for w in which[0][: len(keep)]]
-    if own:
-        index.close()
+    with _base(knowledge_base_path, index, names, model) as (index, names):
+        n = len(index)
+        q = _query_rows(questions, model, tokenizer, index.dim)
+        mask = _documents_mask(names, n, documents, strict=False)
+        k = min(topk, n if mask is None else int(mask.sum()), 1000)
+        paths, scores, deciding = [], [], []
+        if k > 0 and len(q) > 0:
+            if mask is not None:
+                index.set_filters(mask)
+            sc, ids, which = index.search_multi(q, [0, len(q)], k, fuse, None if mask is None else 0)
+            paths, scores = _paths(knowledge_base_path, names, ids[0], sc[0])
+            deciding = [int(w) for w in which[0][: len(paths)]]
     return (paths, scores, deciding) if return_scores else paths
 
 
@@ -249,57 +253,19 @@ def retrieve_rrf(knowledge_base_path: str, questions, topk: int, model, tokenize
     load_knowledge_base(path)` to keep the index resident."""
     if not os.path.exists(knowledge_base_path):
         return None
-    own = index is None
-    if own:
-        index, names = load_knowledge_base(knowledge_base_path, model.encoder.device if model is not None else None)
-    n = len(index)
-    if isinstance(questions, (list, tuple)) and all(isinstance(x, str) for x in questions):
-        q = encode(model, tokenizer, [QUERY_INSTRUCTION + x for x in questions])
-    else:
-        q = np.asarray(questions.detach().cpu() if isinstance(questions, torch.Tensor) else questions, dtype=np.float32)
-    q = np.ascontiguousarray(np.asarray(q, dtype=np.float32).reshape(-1, index.dim))
-    mask = None if documents is None else label_filters([doc_of_page(nm) for nm in names[:n]], [documents])
-    k = min(topk, n if mask is None else int(mask.sum()), 1000)
-    paths, scores, hits = [], [], []
-    if k > 0 and len(q) > 0:
-        if mask is not None:
-            index.set_filters(mask)
-        sc, ids, h = index.search_rrf(q, [0, len(q)], k, depth, c, weights, None if mask is None else 0)
-        keep = [int(i) for i in ids[0] if i >= 0]
-        paths = [os.path.join(knowledge_base_path, names[i]) for i in keep]
-        scores = [float(s) for s in sc[0][: len(keep)]]
-        hits = [int(x) for x in h[0][: len(keep)]]
-    if own:
-        index.close()
+    with _base(knowledge_base_path, index, names, model) as (index, names):
+        n = len(index)
+        q = _query_rows(questions, model, tokenizer, index.dim)
+        mask = _documents_mask(names, n, documents, strict=False)
+        k = min(topk, n if mask is None else int(mask.sum()), 1000)
+        paths, scores, hits = [], [], []
+        if k > 0 and len(q) > 0:
+            if mask is not None:
+                index.set_filters(mask)
+            sc, ids, h = index.search_rrf(q, [0, len(q)], k, depth, c, weights, None if mask is None else 0)
+            paths, scores = _paths(knowledge_base_path, names, ids[0], sc[0])
+            hits = [int(x) for x in h[0][: len(paths)]]
     return (paths, scores, hits) if return_scores else paths
-
-
-def _retrieve_diverse(knowledge_base_path, query, topk, model, tokenizer, index, names, return_scores, documents, lam, pool):
-    """retrieve() with MMR picks; `documents` given: among their pages, through one filter set for this question"""
-    own = index is None
-    if own:
-        index, names = load_knowledge_base(knowledge_base_path, model.encoder.device if model is not None else None)
-    n = len(index)
-    if isinstance(query, str):
-        q = encode(model, tokenizer, [QUERY_INSTRUCTION + query])
-    else:
-        q = np.asarray(query.detach().cpu() if isinstance(query, torch.Tensor) else query, dtype=np.float32).reshape(1, -1)
-    mask = None if documents is None else label_filters([doc_of_page(nm) for nm in names[:n]], [documents])
-    rows = n if mask is None else int(mask.sum())
-    k = min(topk, rows)
-    if k <= 0:
-        paths, scores = [], []
-    else:
-        if mask is not None:
-            index.set_filters(mask)
-        sc, ids = index.search_diverse(q, k, None if pool is None else max(int(pool), k), lam, None if mask is None else 0)
-        sc, ids = (x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in (sc, ids))
-        keep = [int(i) for i in ids[0] if i >= 0]
-        paths = [os.path.join(knowledge_base_path, names[i]) for i in keep]
-        scores = [float(s) for s in sc[0][: len(keep)]]
-    if own:
-        index.close()
-    return (paths, scores) if return_scores else paths
 
 
 def load_document_base(knowledge_base_path: str, device: Optional[int] = None):
@@ -337,29 +303,15 @@ def retrieve_documents(knowledge_base_path: str, query, topk: int, model, tokeni
         return None
     if offset < 0:
         raise ValueError("offset must be >= 0")
-    own = index is None
-    if own:
-        index, names = load_document_base(knowledge_base_path, model.encoder.device if model is not None else None)
-    elif not index.n_groups:
-        order, offsets, _ = group_rows([doc_of_page(n) for n in names])
-        if not np.array_equal(order, np.arange(len(order))):
-            raise ValueError("the pages of a document are not adjacent in this index: load it with load_document_base()")
-        index.set_groups(offsets)
-    if isinstance(query, str):
-        q = encode(model, tokenizer, [QUERY_INSTRUCTION + query])
-    else:
-        q = np.asarray(query.detach().cpu() if isinstance(query, torch.Tensor) else query, dtype=np.float32).reshape(1, -1)
-    if documents is not None or offset > 0:
-        paths, scores = _document_window(knowledge_base_path, q, topk, index, names, documents, int(offset))
-    elif len(index) == 0:
-        paths, scores = [], []
-    else:
-        sc, ids, _ = index.search_groups(q, max(1, min(topk, index.n_groups)))
-        keep = [int(i) for i in ids[0][:topk] if i >= 0]
-        paths = [os.path.join(knowledge_base_path, names[i]) for i in keep]
-        scores = [float(s) for s in sc[0][: len(keep)]]
-    if own:
-        index.close()
+    with _base(knowledge_base_path, index, names, model, documents=True, groups="always") as (index, names):
+        q = _query_rows(query, model, tokenizer)
+        if documents is not None or offset > 0:
+            paths, scores = _document_window(knowledge_base_path, q, topk, index, names, documents, int(offset))
+        elif len(index) == 0:
+            paths, scores = [], []
+        else:
+            sc, ids, _ = index.search_groups(q, max(1, min(topk, index.n_groups)))
+            paths, scores = _paths(knowledge_base_path, names, ids[0][:topk], sc[0])
     return (paths, scores) if return_scores else paths
 
 
@@ -376,68 +328,40 @@ def retrieve_documents_any(knowledge_base_path: str, questions, topk: int, model
     the document's best page for that question, its score) — the pages to hand to the generator."""
     if not os.path.exists(knowledge_base_path):
         return None
-    own = index is None
-    if own:
-        index, names = load_document_base(knowledge_base_path, model.encoder.device if model is not None else None)
-    elif not index.n_groups:
-        order, offsets, _ = group_rows([doc_of_page(n) for n in names])
-        if not np.array_equal(order, np.arange(len(order))):
-            raise ValueError("the pages of a document are not adjacent in this index: load it with load_document_base()")
-        index.set_groups(offsets)
-    n = len(index)
-    if isinstance(questions, (list, tuple)) and all(isinstance(x, str) for x in questions):
-        q = encode(model, tokenizer, [QUERY_INSTRUCTION + x for x in questions])
-    else:
-        q = np.asarray(questions.detach().cpu() if isinstance(questions, torch.Tensor) else questions, dtype=np.float32)
-    q = np.ascontiguousarray(np.asarray(q, dtype=np.float32).reshape(-1, index.dim))
-    mask, present = None, int(index.n_groups) if n else 0
-    if documents is not None:
-        docs = [doc_of_page(nm) for nm in names[:n]]
-        wanted = set(documents)
-        unknown = sorted(wanted - set(docs))
-        if unknown:
-            raise ValueError(f"no page of the base belongs to {unknown[0]!r}" + (f" (and {len(unknown) - 1} more)" if len(unknown) > 1 else ""))
-        mask = label_filters(docs, [wanted])
-        present = len(wanted)
-    k = min(topk, present, 1000)
-    paths, scores, evidence = [], [], []
-    if k > 0 and len(q) > 0:
-        if mask is not None:
-            index.set_filters(mask)
-        sc, rows, _, _, ev_s, ev_r = (x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in
-                                      index.search_multi_groups(q, [0, len(q)], k, fuse, None if mask is None else 0, evidence=True))
-        keep = [int(i) for i in rows[0] if i >= 0]
-        paths = [os.path.join(knowledge_base_path, names[i]) for i in keep]
-        scores = [float(s) for s in sc[0][: len(keep)]]
-        ev_s, ev_r = ev_s.reshape(k, len(q)), ev_r.reshape(k, len(q))
-        evidence = [[(os.path.join(knowledge_base_path, names[int(r)]), float(s)) for r, s in zip(ev_r[i], ev_s[i])] for i in range(len(keep))]
-    if own:
-        index.close()
+    with _base(knowledge_base_path, index, names, model, documents=True, groups="always") as (index, names):
+        n = len(index)
+        q = _query_rows(questions, model, tokenizer, index.dim)
+        wanted = None if documents is None else set(documents)
+        mask = _documents_mask(names, n, wanted, strict=True)
+        present = (int(index.n_groups) if n else 0) if mask is None else len(wanted)
+        k = min(topk, present, 1000)
+        paths, scores, evidence = [], [], []
+        if k > 0 and len(q) > 0:
+            if mask is not None:
+                index.set_filters(mask)
+            sc, rows, _, _, ev_s, ev_r = (x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in
+                                          index.search_multi_groups(q, [0, len(q)], k, fuse, None if mask is None else 0, evidence=True))
+            paths, scores = _paths(knowledge_base_path, names, rows[0], sc[0])
+            ev_s, ev_r = ev_s.reshape(k, len(q)), ev_r.reshape(k, len(q))
+            evidence = [[(os.path.join(knowledge_base_path, names[int(r)]), float(s)) for r, s in zip(ev_r[i], ev_s[i])] for i in range(len(paths))]
     return (paths, scores, evidence) if return_evidence else paths
 
 
 def _document_window(knowledge_base_path, q, topk, index, names, documents, offset):
     """retrieve_documents() at ranks [offset, offset + topk); `documents` given: among them, through one filter set for this question"""
     n = len(index)
-    mask, present = None, int(index.n_groups) if n else 0
-    if documents is not None:
-        docs = [doc_of_page(nm) for nm in names[:n]]
-        wanted = set(documents)
-        unknown = sorted(wanted - set(docs))
-        if unknown:
-            raise ValueError(f"no page of the base belongs to {unknown[0]!r}" + (f" (and {len(unknown) - 1} more)" if len(unknown) > 1 else ""))
-        mask = label_filters(docs, [wanted])
-        present = len(wanted)
+    wanted = None if documents is None else set(documents)
+    mask = _documents_mask(names, n, wanted, strict=True)
+    present = (int(index.n_groups) if n else 0) if mask is None else len(wanted)
     paths, scores = [], []
     if topk > 0 and offset < present:
         if mask is not None:
             index.set_filters(mask)
         for o in range(offset, min(offset + topk, present), 1000):        # a list longer than one window: paged
             sc, ids, _ = index.search_groups_window(q, o, min(1000, offset + topk - o, present - o), None if mask is None else 0)
-            sc, ids = (x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in (sc, ids))
-            keep = [int(i) for i in ids[0] if i >= 0]
-            paths += [os.path.join(knowledge_base_path, names[i]) for i in keep]
-            scores += [float(v) for v in sc[0][: len(keep)]]
+            page = _paths(knowledge_base_path, names, ids[0], sc[0])
+            paths += page[0]
+            scores += page[1]
     return paths, scores
 
 
@@ -451,27 +375,16 @@ def retrieve_above(knowledge_base_path: str, query, min_score: float, model, tok
     question, or its embedding ([dim] or [1, dim]).  Pass `index, names = load_knowledge_base(path)` to keep the index resident."""
     if not os.path.exists(knowledge_base_path):
         return None
-    own = index is None
-    if own:
-        index, names = load_knowledge_base(knowledge_base_path, model.encoder.device if model is not None else None)
-    n = len(index)
-    if isinstance(query, str):
-        q = encode(model, tokenizer, [QUERY_INSTRUCTION + query])
-    else:
-        q = np.asarray(query.detach().cpu() if isinstance(query, torch.Tensor) else query, dtype=np.float32).reshape(1, -1)
-    mask = None if documents is None else label_filters([doc_of_page(nm) for nm in names[:n]], [documents])
-    if n == 0 or (mask is not None and not mask.any()) or (max_pages is not None and max_pages <= 0):
+    with _base(knowledge_base_path, index, names, model) as (index, names):
+        n = len(index)
+        q = _query_rows(query, model, tokenizer)
+        mask = _documents_mask(names, n, documents, strict=False)
         paths, scores = [], []
-    else:
-        if mask is not None:
-            index.set_filters(mask)
-        _, sc, ids = index.search_range(q, float(min_score), None if mask is None else 0)
-        if max_pages is not None:
-            sc, ids = sc[:max_pages], ids[:max_pages]
-        paths = [os.path.join(knowledge_base_path, names[int(i)]) for i in ids]
-        scores = [float(s) for s in sc]
-    if own:
-        index.close()
+        if n and (mask is None or mask.any()) and (max_pages is None or max_pages > 0):
+            if mask is not None:
+                index.set_filters(mask)
+            _, sc, ids = index.search_range(q, float(min_score), None if mask is None else 0)
+            paths, scores = _paths(knowledge_base_path, names, ids[:max_pages], sc[:max_pages])
     return (paths, scores) if return_scores else paths
 
 
@@ -487,40 +400,16 @@ def retrieve_documents_above(knowledge_base_path: str, query, min_score: float, 
     embedding ([dim] or [1, dim])."""
     if not os.path.exists(knowledge_base_path):
         return None
-    own = index is None
-    if own:
-        index, names = load_document_base(knowledge_base_path, model.encoder.device if model is not None else None)
-    elif not index.n_groups and len(index):
-        order, offsets, _ = group_rows([doc_of_page(n) for n in names])
-        if not np.array_equal(order, np.arange(len(order))):
-            raise ValueError("the pages of a document are not adjacent in this index: load it with load_document_base()")
-        index.set_groups(offsets)
-    n = len(index)
-    if isinstance(query, str):
-        q = encode(model, tokenizer, [QUERY_INSTRUCTION + query])
-    else:
-        q = np.asarray(query.detach().cpu() if isinstance(query, torch.Tensor) else query, dtype=np.float32).reshape(1, -1)
-    mask = None
-    if documents is not None:
-        docs = [doc_of_page(nm) for nm in names[:n]]
-        wanted = set(documents)
-        unknown = sorted(wanted - set(docs))
-        if unknown:
-            raise ValueError(f"no page of the base belongs to {unknown[0]!r}" + (f" (and {len(unknown) - 1} more)" if len(unknown) > 1 else ""))
-        mask = label_filters(docs, [wanted])
-    if n == 0 or (mask is not None and not mask.any()) or (max_documents is not None and max_documents <= 0):
+    with _base(knowledge_base_path, index, names, model, documents=True, groups="rows") as (index, names):
+        n = len(index)
+        q = _query_rows(query, model, tokenizer)
+        mask = _documents_mask(names, n, documents, strict=True)
         paths, scores = [], []
-    else:
-        if mask is not None:
-            index.set_filters(mask)
-        _, sc, rows, _ = index.search_groups_range(q, float(min_score), None if mask is None else 0)
-        sc, rows = (x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in (sc, rows))
-        if max_documents is not None:
-            sc, rows = sc[:max_documents], rows[:max_documents]
-        paths = [os.path.join(knowledge_base_path, names[int(i)]) for i in rows]
-        scores = [float(s) for s in sc]
-    if own:
-        index.close()
+        if n and (mask is None or mask.any()) and (max_documents is None or max_documents > 0):
+            if mask is not None:
+                index.set_filters(mask)
+            _, sc, rows, _ = index.search_groups_range(q, float(min_score), None if mask is None else 0)
+            paths, scores = _paths(knowledge_base_path, names, rows[:max_documents], sc[:max_documents])
     return (paths, scores) if return_scores else paths
 
 
@@ -535,10 +424,7 @@ def explain(knowledge_base_path: str, query, pages, documents=None, index=None, 
     names = load_knowledge_base(path)` to keep the index resident."""
     if not os.path.exists(knowledge_base_path):
         return None
-    own = index is None
-    if own:
-        index, names = load_knowledge_base(knowledge_base_path, model.encoder.device if model is not None else None)
-    try:
+    with _base(knowledge_base_path, index, names, model) as (index, names):
         n = len(index)
         one = isinstance(pages, str)
         wanted = [pages] if one else list(pages)
@@ -546,22 +432,16 @@ def explain(knowledge_base_path: str, query, pages, documents=None, index=None, 
         missing = [nm for nm in wanted if nm not in row_of]
         if missing:
             raise ValueError(f"no such page in {knowledge_base_path}: {missing[0]}")
-        if isinstance(query, str):
-            q = encode(model, tokenizer, [QUERY_INSTRUCTION + query])
-        else:
-            q = np.asarray(query.detach().cpu() if isinstance(query, torch.Tensor) else query, dtype=np.float32).reshape(1, -1)
+        q = _query_rows(query, model, tokenizer)
         if not wanted:
             return []
         foq = None
         if documents is not None:
-            index.set_filters(label_filters([doc_of_page(nm) for nm in names[:n]], [documents]))
+            index.set_filters(_documents_mask(names, n, documents, strict=False))
             foq = 0
         sc, rk = index.rank_rows(q, np.asarray([[row_of[nm] for nm in wanted]], dtype=np.int64), filter_of_query=foq)
         out = [(float(s), int(r)) for s, r in zip(sc[0], rk[0])]
         return out[0] if one else out
-    finally:
-        if own:
-            index.close()
 
 
 @torch.no_grad()
@@ -576,10 +456,7 @@ def explain_documents(knowledge_base_path: str, query, wanted, documents=None, i
     load_document_base(path)` to keep the index resident; an index of your own must hold every document's pages adjacently."""
     if not os.path.exists(knowledge_base_path):
         return None
-    own = index is None
-    if own:
-        index, names = load_document_base(knowledge_base_path, model.encoder.device if model is not None else None)
-    try:
+    with _base(knowledge_base_path, index, names, model, documents=True) as (index, names):
         n = len(index)
         one = isinstance(wanted, str)
         want = [wanted] if one else list(wanted)
@@ -591,12 +468,9 @@ def explain_documents(knowledge_base_path: str, query, wanted, documents=None, i
         unknown = [d for d in list(want) + list(documents or ()) if d not in group_of]
         if unknown:
             raise ValueError(f"no page of the base belongs to {unknown[0]!r}")
-        if not index.n_groups and n:
+        if not index.n_groups and n:                                      # after the names are known to be the base's
             index.set_groups(offsets)
-        if isinstance(query, str):
-            q = encode(model, tokenizer, [QUERY_INSTRUCTION + query])
-        else:
-            q = np.asarray(query.detach().cpu() if isinstance(query, torch.Tensor) else query, dtype=np.float32).reshape(1, -1)
+        q = _query_rows(query, model, tokenizer)
         if not want:
             return []
         foq = None
@@ -607,9 +481,6 @@ def explain_documents(knowledge_base_path: str, query, wanted, documents=None, i
         sc, rows, rk = (x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in (sc, rows, rk))
         out = [(float(s), names[int(r)] if r >= 0 else None, int(k)) for s, r, k in zip(sc[0], rows[0], rk[0])]
         return out[0] if one else out
-    finally:
-        if own:
-            index.close()
 
 
 def duplicate_pages(knowledge_base_path: str, threshold: float, index=None, names=None, batch: int = 256) -> Optional[List[List[str]]]:
@@ -620,21 +491,17 @@ def duplicate_pages(knowledge_base_path: str, threshold: float, index=None, name
     passed in must hold the rows of reps.npy in their order on disk (`load_knowledge_base`)."""
     if not os.path.exists(knowledge_base_path):
         return None
-    own = index is None
-    if own:
-        index, names = load_knowledge_base(knowledge_base_path)
-    n_disk = len(np.load(os.path.join(knowledge_base_path, "reps.npy"), mmap_mode="r"))
-    n = len(index)
-    if n_disk != n:
-        raise ValueError(f"{n_disk} rows in {knowledge_base_path} but {n} in the index")
-    lims, ids = [np.zeros(1, np.int64)], []
-    batch = max(int(batch), 1)
-    for lo in range(0, n, batch):                  # the queries are the index's own fp32 rows, read back: no host copy of the base
-        l, _, i = index.search_range(index.rows(np.arange(lo, min(lo + batch, n))), float(threshold), sort=False)
-        lims.append(l[1:] + lims[-1][-1])
-        ids.append(i)
-    if own:
-        index.close()
+    with _base(knowledge_base_path, index, names, None) as (index, names):
+        n_disk = len(np.load(os.path.join(knowledge_base_path, "reps.npy"), mmap_mode="r"))
+        n = len(index)
+        if n_disk != n:
+            raise ValueError(f"{n_disk} rows in {knowledge_base_path} but {n} in the index")
+        lims, ids = [np.zeros(1, np.int64)], []
+        batch = max(int(batch), 1)
+        for lo in range(0, n, batch):              # the queries are the index's own fp32 rows, read back: no host copy of the base
+            l, _, i = index.search_range(index.rows(np.arange(lo, min(lo + batch, n))), float(threshold), sort=False)
+            lims.append(l[1:] + lims[-1][-1])
+            ids.append(i)
     groups = duplicate_groups(np.concatenate(lims), np.concatenate(ids) if ids else np.zeros(0, np.int64), n)
     return [[names[r] for r in g] for g in groups]
 

@@ -32,9 +32,9 @@ from typing import Callable, Dict, Hashable, List, Optional, Tuple
 import numpy as np
 import torch
 
-from .documents import collection_filters, group_rows, label_filters
-from .engine import HipIndex, topk_merge_keys
-from .utils import list_shards, read_shard, shard_rank
+from .documents import collection_filters, group_rows, label_filters, window_negatives
+from .engine import HipIndex, rrf_fuse, topk_merge_keys
+from .utils import list_shards, read_shard, shard_rank as _shard_rank
 
 logger = logging.getLogger(__name__)
 
@@ -76,9 +76,6 @@ def _load_queries(args, rank="own") -> Tuple[np.ndarray, List[str], List[bool]]:
     return np.concatenate(reps), ids, mine
 
 
-_shard_rank = shard_rank
-
-
 def _sharded_requested(args, sharded: Optional[bool]) -> bool:
     if sharded is None:
         sharded = getattr(args, "sharded_corpus", None)
@@ -97,6 +94,105 @@ def _collective_wanted(group=None) -> bool:
     return dist.get_world_size(group) > 1 or os.environ.get("VISRAG_SHARDED_RETRIEVE", "") == "force"
 
 
+def _corpus(args) -> Tuple[np.ndarray, List[str], List[str]]:
+    """-> (queries, qids, corpus_parts): this rank's queries and the files of ALL corpus shards; missing queries are reported
+    before missing documents"""
+    queries, qids, _ = _load_queries(args)
+    corpus_parts = list_shards(args.output_dir, "corpus")
+    if len(corpus_parts) == 0:
+        raise ValueError("No pre-computed document embeddings found")
+    logger.info("corpus_all_partitions = %s", corpus_parts)
+    return queries, qids, corpus_parts
+
+
+def _whole_corpus(corpus_parts) -> Tuple[List[np.ndarray], List[str]]:
+    """-> (the float32 rows of every shard that has some, their ids in one list): what ONE index over all shards holds"""
+    reps, ids = [], []
+    for p in corpus_parts:
+        r, i = read_shard(p)
+        if len(i):
+            reps.append(np.asarray(r, dtype=np.float32))
+            ids.extend(i)
+    return reps, ids
+
+
+def _filter_index(keys, labels_of: Callable) -> Tuple[List[Optional[frozenset]], np.ndarray]:
+    """-> (the DISTINCT label sets `labels_of(key)` in the order they first appear, None = everything; int32 [len(keys)]: the set
+    of each key): one filter is built per distinct set"""
+    sets: List[Optional[frozenset]] = []
+    which: Dict[Optional[frozenset], int] = {}
+    filter_of = np.empty(len(keys), dtype=np.int32)
+    for i, key in enumerate(keys):
+        wanted = labels_of(key)
+        labels = None if wanted is None else frozenset(wanted)
+        if labels not in which:
+            which[labels] = len(sets)
+            sets.append(labels)
+        filter_of[i] = which[labels]
+    return sets, filter_of
+
+
+def _document_index(make_index, dim, reps, page_ids, doc_of, dev, keys=(), label_of_doc=None, labels_of=None, grouping=None):
+    """ONE index over the pages of all shards, reordered so that every document's pages are adjacent (documents.group_rows of
+    `doc_of`, or `grouping` if the caller has it already), the documents set as its groups; with `label_of_doc` and `labels_of`
+    one filter per distinct label set of `keys`.  -> (ix, order, docs, filter_of): row r of the index is page `page_ids[order[r]]`,
+    `filter_of` the filter of each key, None without labels.  The caller closes the index."""
+    order, offsets, docs = grouping or group_rows([doc_of(i) for i in page_ids])
+    ix = make_index(dim, len(page_ids), dev)
+    ix.add(np.concatenate(reps)[order])
+    ix.set_groups(offsets)
+    filter_of = None
+    if label_of_doc is not None and labels_of is not None:
+        sets, filter_of = _filter_index(keys, labels_of)
+        ix.set_filters(collection_filters(offsets, [label_of_doc(d) for d in docs], sets))
+    return ix, order, docs, filter_of
+
+
+def _each_shard(shards, make_index, dim, dev, as_float32: bool = True):
+    """`shards`: (reps, ids) pairs, read as they are asked for -> yields (ix, ids) per shard that has rows, the index filled with
+    that shard alone and closed when the consumer moves on (or stops): the index never holds more than one shard"""
+    for reps, ids in shards:
+        if len(ids) == 0:
+            continue
+        ix = make_index(dim, len(ids), dev)
+        try:
+            ix.add(np.asarray(reps, dtype=np.float32) if as_float32 else reps)
+            yield ix, ids
+        finally:
+            ix.close()
+
+
+def _shard_lists(shards, make_index, dim, dev, search: Callable) -> Tuple[List[np.ndarray], List[np.ndarray], List[str]]:
+    """`search(ix, ids) -> (scores [n][d], rows [n][d], ...)` over one shard at a time -> (the scores of every shard, its rows as
+    GLOBAL positions — shifted by the rows of the shards before, -1 kept — and the ids of all shards): what merge_pages_host takes"""
+    all_ids: List[str] = []
+    lists_s, lists_p = [], []
+    for ix, ids in _each_shard(shards, make_index, dim, dev):
+        sc, rows = search(ix, ids)[:2]
+        rows = np.asarray(rows, dtype=np.int64)
+        lists_s.append(np.asarray(sc, dtype=np.float32))
+        lists_p.append(np.where(rows >= 0, rows + len(all_ids), -1))
+        all_ids.extend(ids)
+    return lists_s, lists_p, all_ids
+
+
+def _fill(result: Dict, keys, scores, ids, names) -> Dict:
+    """result[key][names[id]] = score for the taken slots (id >= 0) of every key's list, in list order"""
+    for row, key in enumerate(keys):
+        for s, j in zip(scores[row], ids[row]):
+            if j >= 0:
+                result[key][names[int(j)]] = float(s)
+    return result
+
+
+def _fill_documents(scores: Dict, pages: Dict, key, sc, rows, groups, docs, page_ids, order) -> None:
+    """one key's document list: scores[key][doc] = score, pages[key][doc] = the id of its best page, for the taken slots"""
+    for s, r, g in zip(sc, rows, groups):
+        if r >= 0:
+            scores[key][docs[int(g)]] = float(s)
+            pages[key][docs[int(g)]] = page_ids[int(order[int(r)])]
+
+
 def distributed_parallel_retrieve(args, topk: int, global_topk: bool = False, sharded: Optional[bool] = None,
                                   index_factory: Optional[Callable] = None, merge_keys: Optional[Callable] = None
                                   ) -> Dict[str, Dict[str, float]]:
@@ -105,27 +201,14 @@ def distributed_parallel_retrieve(args, topk: int, global_topk: bool = False, sh
     make_index = index_factory or HipIndex
     if _sharded_requested(args, sharded):
         return _retrieve_corpus_sharded(args, topk, global_topk, make_index, merge_keys)
-    queries, qids, _ = _load_queries(args)
-    corpus_parts = list_shards(args.output_dir, "corpus")
-    if len(corpus_parts) == 0:
-        raise ValueError("No pre-computed document embeddings found")
-    logger.info("corpus_all_partitions = %s", corpus_parts)
+    queries, qids, corpus_parts = _corpus(args)
     dev = _device_index(args)
     result: Dict[str, Dict[str, float]] = {q: {} for q in qids}
     dim = queries.shape[1]
     if not global_topk:
-        for p in corpus_parts:
-            reps, ids = read_shard(p)
-            if len(ids) == 0:
-                continue
-            ix = make_index(dim, len(ids), dev)
-            ix.add(reps)
+        for ix, ids in _each_shard(map(read_shard, corpus_parts), make_index, dim, dev, as_float32=False):
             sc, idx = ix.search(queries, topk)
-            ix.close()
-            for qi, q in enumerate(qids):
-                for s, j in zip(sc[qi], idx[qi]):
-                    if j >= 0:
-                        result[q][ids[int(j)]] = float(s)
+            _fill(result, qids, sc, idx, ids)
         return result
     shards = [read_shard(p) for p in corpus_parts]
     total = sum(len(i) for _, i in shards)
@@ -137,11 +220,7 @@ def distributed_parallel_retrieve(args, topk: int, global_topk: bool = False, sh
             all_ids.extend(ids)
     sc, idx = ix.search(queries, topk)
     ix.close()
-    for qi, q in enumerate(qids):
-        for s, j in zip(sc[qi], idx[qi]):
-            if j >= 0:
-                result[q][all_ids[int(j)]] = float(s)
-    return result
+    return _fill(result, qids, sc, idx, all_ids)
 
 
 def retrieve_documents(args, topk: int, doc_of: Callable[[str], str], index_factory: Optional[Callable] = None
@@ -155,31 +234,17 @@ def retrieve_documents(args, topk: int, doc_of: Callable[[str], str], index_fact
     Replicated form only: every rank holds the whole corpus.  Corpus-sharded multi-GPU grouped search is out of scope — a
     document may straddle the shards of two ranks, and a per-rank best page is not a document's best page."""
     make_index = index_factory or HipIndex
-    queries, qids, _ = _load_queries(args)
-    corpus_parts = list_shards(args.output_dir, "corpus")
-    if len(corpus_parts) == 0:
-        raise ValueError("No pre-computed document embeddings found")
-    reps, page_ids = [], []
-    for p in corpus_parts:
-        r, i = read_shard(p)
-        if len(i):
-            reps.append(np.asarray(r, dtype=np.float32))
-            page_ids.extend(i)
+    queries, qids, corpus_parts = _corpus(args)
+    reps, page_ids = _whole_corpus(corpus_parts)
     scores: Dict[str, Dict[str, float]] = {q: {} for q in qids}
     pages: Dict[str, Dict[str, str]] = {q: {} for q in qids}
     if not page_ids or topk <= 0:
         return scores, pages
-    order, offsets, docs = group_rows([doc_of(i) for i in page_ids])
-    ix = make_index(queries.shape[1], len(page_ids), _device_index(args))
-    ix.add(np.concatenate(reps)[order])
-    ix.set_groups(offsets)
+    ix, order, docs, _ = _document_index(make_index, queries.shape[1], reps, page_ids, doc_of, _device_index(args))
     sc, rows, groups = ix.search_groups(queries, min(topk, len(docs)))
     ix.close()
     for qi, q in enumerate(qids):
-        for s, r, g in zip(sc[qi], rows[qi], groups[qi]):
-            if r >= 0:
-                scores[q][docs[int(g)]] = float(s)
-                pages[q][docs[int(g)]] = page_ids[int(order[int(r)])]
+        _fill_documents(scores, pages, q, sc[qi], rows[qi], groups[qi], docs, page_ids, order)
     return scores, pages
 
 
@@ -193,39 +258,18 @@ def retrieve_filtered(args, topk: int, label_of: Callable[[str], object], labels
 
     Replicated form only, like retrieve_documents: every rank holds the whole corpus."""
     make_index = index_factory or HipIndex
-    queries, qids, _ = _load_queries(args)
-    corpus_parts = list_shards(args.output_dir, "corpus")
-    if len(corpus_parts) == 0:
-        raise ValueError("No pre-computed document embeddings found")
-    reps, doc_ids = [], []
-    for p in corpus_parts:
-        r, i = read_shard(p)
-        if len(i):
-            reps.append(np.asarray(r, dtype=np.float32))
-            doc_ids.extend(i)
+    queries, qids, corpus_parts = _corpus(args)
+    reps, doc_ids = _whole_corpus(corpus_parts)
     result: Dict[str, Dict[str, float]] = {q: {} for q in qids}
     if not doc_ids or topk <= 0:
         return result
-    sets: List[Optional[frozenset]] = []
-    which: Dict[Optional[frozenset], int] = {}
-    filter_of_query = np.empty(len(qids), dtype=np.int32)
-    for qi, q in enumerate(qids):
-        wanted = labels_of_query(q)
-        key = None if wanted is None else frozenset(wanted)
-        if key not in which:
-            which[key] = len(sets)
-            sets.append(key)
-        filter_of_query[qi] = which[key]
+    sets, filter_of_query = _filter_index(qids, labels_of_query)
     ix = make_index(queries.shape[1], len(doc_ids), _device_index(args))
     ix.add(np.concatenate(reps))
     ix.set_filters(label_filters([label_of(i) for i in doc_ids], sets))
     sc, rows = ix.search_filtered(queries, min(topk, len(doc_ids)), filter_of_query)
     ix.close()
-    for qi, q in enumerate(qids):
-        for s, r in zip(sc[qi], rows[qi]):
-            if r >= 0:
-                result[q][doc_ids[int(r)]] = float(s)
-    return result
+    return _fill(result, qids, sc, rows, doc_ids)
 
 
 def retrieve_documents_filtered(args, topk: int, doc_of: Callable[[str], str], label_of_doc: Callable[[str], object],
@@ -243,42 +287,18 @@ def retrieve_documents_filtered(args, topk: int, doc_of: Callable[[str], str], l
     if offset < 0:
         raise ValueError("offset must be >= 0")
     make_index = index_factory or HipIndex
-    queries, qids, _ = _load_queries(args)
-    corpus_parts = list_shards(args.output_dir, "corpus")
-    if len(corpus_parts) == 0:
-        raise ValueError("No pre-computed document embeddings found")
-    reps, page_ids = [], []
-    for p in corpus_parts:
-        r, i = read_shard(p)
-        if len(i):
-            reps.append(np.asarray(r, dtype=np.float32))
-            page_ids.extend(i)
+    queries, qids, corpus_parts = _corpus(args)
+    reps, page_ids = _whole_corpus(corpus_parts)
     scores: Dict[str, Dict[str, float]] = {q: {} for q in qids}
     pages: Dict[str, Dict[str, str]] = {q: {} for q in qids}
     if not page_ids or topk <= 0:
         return scores, pages
-    order, offsets, docs = group_rows([doc_of(i) for i in page_ids])
-    sets: List[Optional[frozenset]] = []
-    which: Dict[Optional[frozenset], int] = {}
-    filter_of_query = np.empty(len(qids), dtype=np.int32)
-    for qi, q in enumerate(qids):
-        wanted = labels_of_query(q)
-        key = None if wanted is None else frozenset(wanted)
-        if key not in which:
-            which[key] = len(sets)
-            sets.append(key)
-        filter_of_query[qi] = which[key]
-    ix = make_index(queries.shape[1], len(page_ids), _device_index(args))
-    ix.add(np.concatenate(reps)[order])
-    ix.set_groups(offsets)
-    ix.set_filters(collection_filters(offsets, [label_of_doc(d) for d in docs], sets))
+    ix, order, docs, filter_of_query = _document_index(make_index, queries.shape[1], reps, page_ids, doc_of, _device_index(args),
+                                                       qids, label_of_doc, labels_of_query)
     for o in range(int(offset), min(int(offset) + topk, len(docs)), WINDOW_PAGE):     # a list longer than one window: paged
         sc, rows, groups = ix.search_groups_window(queries, o, min(WINDOW_PAGE, int(offset) + topk - o, len(docs) - o), filter_of_query)
         for qi, q in enumerate(qids):
-            for s_, r, g in zip(sc[qi], rows[qi], groups[qi]):
-                if r >= 0:
-                    scores[q][docs[int(g)]] = float(s_)
-                    pages[q][docs[int(g)]] = page_ids[int(order[int(r)])]
+            _fill_documents(scores, pages, q, sc[qi], rows[qi], groups[qi], docs, page_ids, order)
     ix.close()
     return scores, pages
 
@@ -300,43 +320,21 @@ def rank_documents(args, docs_of_query, doc_of: Callable[[str], str], label_of_d
     if (label_of_doc is None) != (labels_of_query is None):
         raise ValueError("label_of_doc and labels_of_query go together")
     make_index = index_factory or HipIndex
-    queries, qids, _ = _load_queries(args)
-    corpus_parts = list_shards(args.output_dir, "corpus")
-    if len(corpus_parts) == 0:
-        raise ValueError("No pre-computed document embeddings found")
-    reps, page_ids = [], []
-    for p in corpus_parts:
-        r, i = read_shard(p)
-        if len(i):
-            reps.append(np.asarray(r, dtype=np.float32))
-            page_ids.extend(i)
+    queries, qids, corpus_parts = _corpus(args)
+    reps, page_ids = _whole_corpus(corpus_parts)
     get = docs_of_query if callable(docs_of_query) else (lambda q: docs_of_query.get(q, ()))
     wanted = [list(dict.fromkeys(get(q))) for q in qids]                  # a document named twice counts once
     lims = np.concatenate([np.zeros(1, np.int64), np.cumsum([len(w) for w in wanted])]).astype(np.int64)
     flat = [d for w in wanted for d in w]
     if not flat:
         return {q: {} for q in qids}
-    order, offsets, docs = group_rows([doc_of(i) for i in page_ids])
-    group_of = {d: g for g, d in enumerate(docs)}
+    grouping = group_rows([doc_of(i) for i in page_ids])
+    group_of = {d: g for g, d in enumerate(grouping[2])}
     missing = [d for d in flat if d not in group_of]
     if missing:
         raise ValueError(f"no such document in the corpus shards: {missing[0]}")
-    ix = make_index(queries.shape[1], len(page_ids), _device_index(args))
-    ix.add(np.concatenate(reps)[order])
-    ix.set_groups(offsets)
-    filter_of_query = None
-    if labels_of_query is not None:
-        sets: List[Optional[frozenset]] = []
-        which: Dict[Optional[frozenset], int] = {}
-        filter_of_query = np.empty(len(qids), dtype=np.int32)
-        for qi, q in enumerate(qids):
-            labels = labels_of_query(q)
-            key = None if labels is None else frozenset(labels)
-            if key not in which:
-                which[key] = len(sets)
-                sets.append(key)
-            filter_of_query[qi] = which[key]
-        ix.set_filters(collection_filters(offsets, [label_of_doc(d) for d in docs], sets))
+    ix, order, _, filter_of_query = _document_index(make_index, queries.shape[1], reps, page_ids, doc_of, _device_index(args),
+                                                    qids, label_of_doc, labels_of_query, grouping)
     sc, rows, rk = ix.rank_groups(queries, np.asarray([group_of[d] for d in flat], dtype=np.int64), lims, filter_of_query)
     ix.close()
     return {q: {d: (float(sc[j]), page_ids[int(order[int(rows[j])])] if rows[j] >= 0 else None, int(rk[j]))
@@ -362,46 +360,21 @@ def retrieve_documents_range(args, threshold: float, doc_of: Callable[[str], str
     if (label_of_doc is None) != (labels_of_query is None):
         raise ValueError("label_of_doc and labels_of_query go together")
     make_index = index_factory or HipIndex
-    queries, qids, _ = _load_queries(args)
-    corpus_parts = list_shards(args.output_dir, "corpus")
-    if len(corpus_parts) == 0:
-        raise ValueError("No pre-computed document embeddings found")
-    reps, page_ids = [], []
-    for p in corpus_parts:
-        r, i = read_shard(p)
-        if len(i):
-            reps.append(np.asarray(r, dtype=np.float32))
-            page_ids.extend(i)
+    queries, qids, corpus_parts = _corpus(args)
+    reps, page_ids = _whole_corpus(corpus_parts)
     scores: Dict[str, Dict[str, float]] = {q: {} for q in qids}
     pages: Dict[str, Dict[str, str]] = {q: {} for q in qids}
     if not page_ids or (max_per_query is not None and max_per_query <= 0):
         return scores, pages
-    order, offsets, docs = group_rows([doc_of(i) for i in page_ids])
-    ix = make_index(queries.shape[1], len(page_ids), _device_index(args))
-    ix.add(np.concatenate(reps)[order])
-    ix.set_groups(offsets)
-    filter_of_query = None
-    if labels_of_query is not None:
-        sets: List[Optional[frozenset]] = []
-        which: Dict[Optional[frozenset], int] = {}
-        filter_of_query = np.empty(len(qids), dtype=np.int32)
-        for qi, q in enumerate(qids):
-            wanted = labels_of_query(q)
-            key = None if wanted is None else frozenset(wanted)
-            if key not in which:
-                which[key] = len(sets)
-                sets.append(key)
-            filter_of_query[qi] = which[key]
-        ix.set_filters(collection_filters(offsets, [label_of_doc(d) for d in docs], sets))
+    ix, order, docs, filter_of_query = _document_index(make_index, queries.shape[1], reps, page_ids, doc_of, _device_index(args),
+                                                       qids, label_of_doc, labels_of_query)
     lims, sc, rows, groups = ix.search_groups_range(queries, float(threshold), filter_of_query)
     ix.close()
     for qi, q in enumerate(qids):
         a, b = int(lims[qi]), int(lims[qi + 1])
         if max_per_query is not None:
             b = min(b, a + int(max_per_query))
-        for s_, r, g in zip(sc[a:b], rows[a:b], groups[a:b]):
-            scores[q][docs[int(g)]] = float(s_)
-            pages[q][docs[int(g)]] = page_ids[int(order[int(r)])]
+        _fill_documents(scores, pages, q, sc[a:b], rows[a:b], groups[a:b], docs, page_ids, order)
     return scores, pages
 
 
@@ -415,20 +388,10 @@ def retrieve_range(args, threshold: float, max_per_query: Optional[int] = None, 
 
     Replicated form only, like retrieve_documents: every rank sees the whole corpus."""
     make_index = index_factory or HipIndex
-    queries, qids, _ = _load_queries(args)
-    corpus_parts = list_shards(args.output_dir, "corpus")
-    if len(corpus_parts) == 0:
-        raise ValueError("No pre-computed document embeddings found")
-    dev = _device_index(args)
+    queries, qids, corpus_parts = _corpus(args)
     found: List[List[Tuple[float, str]]] = [[] for _ in qids]
-    for p in corpus_parts:
-        reps, ids = read_shard(p)
-        if len(ids) == 0:
-            continue
-        ix = make_index(queries.shape[1], len(ids), dev)
-        ix.add(np.asarray(reps, dtype=np.float32))
+    for ix, ids in _each_shard(map(read_shard, corpus_parts), make_index, queries.shape[1], _device_index(args)):
         lims, sc, rows = ix.search_range(queries, float(threshold))
-        ix.close()
         for qi in range(len(qids)):
             found[qi].extend((float(s), ids[int(r)]) for s, r in zip(sc[lims[qi]:lims[qi + 1]], rows[lims[qi]:lims[qi + 1]]))
     result: Dict[str, Dict[str, float]] = {}
@@ -452,10 +415,7 @@ def rank_rows(args, targets_of_query, index_factory: Optional[Callable] = None) 
 
     Replicated form only, like retrieve_documents: every rank sees the whole corpus."""
     make_index = index_factory or HipIndex
-    queries, qids, _ = _load_queries(args)
-    corpus_parts = list_shards(args.output_dir, "corpus")
-    if len(corpus_parts) == 0:
-        raise ValueError("No pre-computed document embeddings found")
+    queries, qids, corpus_parts = _corpus(args)
     dev = _device_index(args)
     get = targets_of_query if callable(targets_of_query) else (lambda q: targets_of_query.get(q, ()))
     wanted = [list(dict.fromkeys(get(q))) for q in qids]                  # a docid named twice counts once
@@ -544,36 +504,17 @@ def retrieve_deep(args, depth: int, index_factory: Optional[Callable] = None) ->
 
     Replicated form only, like retrieve_documents: every rank sees the whole corpus."""
     make_index = index_factory or HipIndex
-    queries, qids, _ = _load_queries(args)
-    corpus_parts = list_shards(args.output_dir, "corpus")
-    if len(corpus_parts) == 0:
-        raise ValueError("No pre-computed document embeddings found")
+    queries, qids, corpus_parts = _corpus(args)
     depth = int(depth)
     result: Dict[str, Dict[str, float]] = {q: {} for q in qids}
     if depth <= 0:
         return result
-    dev = _device_index(args)
-    all_ids: List[str] = []
-    lists_s, lists_p = [], []
-    for p in corpus_parts:
-        reps, ids = read_shard(p)
-        if len(ids) == 0:
-            continue
-        ix = make_index(queries.shape[1], len(ids), dev)
-        ix.add(np.asarray(reps, dtype=np.float32))
-        sc, rows = _shard_pages(ix, queries, 0, min(depth, len(ids)))
-        ix.close()
-        lists_s.append(sc)
-        lists_p.append(np.where(rows >= 0, rows + len(all_ids), -1))
-        all_ids.extend(ids)
+    lists_s, lists_p, all_ids = _shard_lists(map(read_shard, corpus_parts), make_index, queries.shape[1], _device_index(args),
+                                             lambda ix, ids: _shard_pages(ix, queries, 0, min(depth, len(ids))))
     if not lists_s:
         return result
     sc, pos = merge_pages_host(lists_s, lists_p, depth)
-    for qi, q in enumerate(qids):
-        for s, j in zip(sc[qi], pos[qi]):
-            if j >= 0:
-                result[q][all_ids[int(j)]] = float(s)
-    return result
+    return _fill(result, qids, sc, pos, all_ids)
 
 
 def retrieve_fused(args, group_of_query: Callable, topk: int, fuse: str = "max", index_factory: Optional[Callable] = None
@@ -589,39 +530,19 @@ def retrieve_fused(args, group_of_query: Callable, topk: int, fuse: str = "max",
 
     Replicated form only, like retrieve_deep: every rank sees the whole corpus."""
     make_index = index_factory or HipIndex
-    queries, qids, _ = _load_queries(args)
-    corpus_parts = list_shards(args.output_dir, "corpus")
-    if len(corpus_parts) == 0:
-        raise ValueError("No pre-computed document embeddings found")
+    queries, qids, corpus_parts = _corpus(args)
     topk = int(topk)
     order, lims, groups = group_rows([group_of_query(q) for q in qids])
     result: Dict[Hashable, Dict[str, float]] = {g: {} for g in groups}
     if len(groups) == 0 or topk <= 0:
         return result
     grouped = np.ascontiguousarray(np.asarray(queries, dtype=np.float32)[order])
-    dev = _device_index(args)
-    all_ids: List[str] = []
-    lists_s, lists_p = [], []
-    for p in corpus_parts:
-        reps, ids = read_shard(p)
-        if len(ids) == 0:
-            continue
-        ix = make_index(queries.shape[1], len(ids), dev)
-        ix.add(np.asarray(reps, dtype=np.float32))
-        sc, rows, _ = ix.search_multi(grouped, lims, topk, fuse)
-        ix.close()
-        rows = np.asarray(rows, dtype=np.int64)
-        lists_s.append(np.asarray(sc, dtype=np.float32))
-        lists_p.append(np.where(rows >= 0, rows + len(all_ids), -1))
-        all_ids.extend(ids)
+    lists_s, lists_p, all_ids = _shard_lists(map(read_shard, corpus_parts), make_index, queries.shape[1], _device_index(args),
+                                             lambda ix, ids: ix.search_multi(grouped, lims, topk, fuse))
     if not lists_s:
         return result
     sc, pos = merge_pages_host(lists_s, lists_p, topk)
-    for gi, g in enumerate(groups):
-        for s, j in zip(sc[gi], pos[gi]):
-            if j >= 0:
-                result[g][all_ids[int(j)]] = float(s)
-    return result
+    return _fill(result, groups, sc, pos, all_ids)
 
 
 def retrieve_documents_fused(args, group_of_query: Callable, topk: int, doc_of: Callable[[str], str], fuse: str = "max",
@@ -642,40 +563,17 @@ def retrieve_documents_fused(args, group_of_query: Callable, topk: int, doc_of: 
     Replicated form only: the shards go into one index reordered so that every document's pages are adjacent, as
     retrieve_documents_filtered builds it."""
     make_index = index_factory or HipIndex
-    queries, qids, _ = _load_queries(args)
-    corpus_parts = list_shards(args.output_dir, "corpus")
-    if len(corpus_parts) == 0:
-        raise ValueError("No pre-computed document embeddings found")
+    queries, qids, corpus_parts = _corpus(args)
     topk = int(topk)
     q_order, lims, groups = group_rows([group_of_query(q) for q in qids])
     scores: Dict[Hashable, Dict[str, float]] = {g: {} for g in groups}
     pages: Dict[Hashable, Dict[str, List[str]]] = {g: {} for g in groups}
-    reps, page_ids = [], []
-    for p in corpus_parts:
-        r, i = read_shard(p)
-        if len(i):
-            reps.append(np.asarray(r, dtype=np.float32))
-            page_ids.extend(i)
+    reps, page_ids = _whole_corpus(corpus_parts)
     if not page_ids or len(groups) == 0 or topk <= 0:
         return scores, pages
     grouped = np.ascontiguousarray(np.asarray(queries, dtype=np.float32)[q_order])
-    order, offsets, docs = group_rows([doc_of(i) for i in page_ids])
-    ix = make_index(queries.shape[1], len(page_ids), _device_index(args))
-    ix.add(np.concatenate(reps)[order])
-    ix.set_groups(offsets)
-    filter_of_group = None
-    if label_of_doc is not None and labels_of_group is not None:
-        sets: List[Optional[frozenset]] = []
-        which: Dict[Optional[frozenset], int] = {}
-        filter_of_group = np.empty(len(groups), dtype=np.int32)
-        for gi, g in enumerate(groups):
-            wanted = labels_of_group(g)
-            key = None if wanted is None else frozenset(wanted)
-            if key not in which:
-                which[key] = len(sets)
-                sets.append(key)
-            filter_of_group[gi] = which[key]
-        ix.set_filters(collection_filters(offsets, [label_of_doc(d) for d in docs], sets))
+    ix, order, docs, filter_of_group = _document_index(make_index, queries.shape[1], reps, page_ids, doc_of, _device_index(args),
+                                                       groups, label_of_doc, labels_of_group)      # a lone label argument: no filter
     k = min(topk, len(docs))
     sc, _, dd, _, _, ev_r = ix.search_multi_groups(grouped, lims, k, fuse, filter_of_group, evidence=True)
     ix.close()
@@ -704,12 +602,7 @@ def retrieve_rrf(args, group_of_query: Callable, topk: int, depth: int = 100, c:
 
     Replicated form only, like retrieve_deep: every rank sees the whole corpus."""
     make_index = index_factory or HipIndex
-    if fuse_lists is None:
-        from .engine import rrf_fuse as fuse_lists
-    queries, qids, _ = _load_queries(args)
-    corpus_parts = list_shards(args.output_dir, "corpus")
-    if len(corpus_parts) == 0:
-        raise ValueError("No pre-computed document embeddings found")
+    queries, qids, corpus_parts = _corpus(args)
     topk, depth = int(topk), int(depth)
     order, lims, groups = group_rows([group_of_query(q) for q in qids])
     result: Dict[Hashable, Dict[str, float]] = {g: {} for g in groups}
@@ -718,29 +611,13 @@ def retrieve_rrf(args, group_of_query: Callable, topk: int, depth: int = 100, c:
     grouped = np.ascontiguousarray(np.asarray(queries, dtype=np.float32)[order])
     weights = None if weight_of_query is None else np.asarray([weight_of_query(qids[i]) for i in order], dtype=np.float32)
     dev = _device_index(args)
-    all_ids: List[str] = []
-    lists_s, lists_p = [], []
-    for p in corpus_parts:
-        reps, ids = read_shard(p)
-        if len(ids) == 0:
-            continue
-        ix = make_index(queries.shape[1], len(ids), dev)
-        ix.add(np.asarray(reps, dtype=np.float32))
-        sc, rows = ix.search(grouped, depth)
-        ix.close()
-        rows = np.asarray(rows, dtype=np.int64)
-        lists_s.append(np.asarray(sc, dtype=np.float32))
-        lists_p.append(np.where(rows >= 0, rows + len(all_ids), -1))
-        all_ids.extend(ids)
+    lists_s, lists_p, all_ids = _shard_lists(map(read_shard, corpus_parts), make_index, queries.shape[1], dev,
+                                             lambda ix, ids: ix.search(grouped, depth))
     if not lists_s:
         return result
     _, pos = merge_pages_host(lists_s, lists_p, depth)                # every query's global list, best first
-    sc, ids, _ = fuse_lists(pos, lims, topk, c, weights, dev)
-    for gi, g in enumerate(groups):
-        for s, j in zip(np.asarray(sc)[gi], np.asarray(ids)[gi]):
-            if j >= 0:
-                result[g][all_ids[int(j)]] = float(s)
-    return result
+    sc, ids, _ = (fuse_lists or rrf_fuse)(pos, lims, topk, c, weights, dev)
+    return _fill(result, groups, np.asarray(sc), np.asarray(ids), all_ids)
 
 
 def mine_negatives(args, positives_of_query, start: int, count: int, index_factory: Optional[Callable] = None
@@ -754,34 +631,20 @@ def mine_negatives(args, positives_of_query, start: int, count: int, index_facto
     order), over a single shard or several: the rows of ranks below start + count + positives of every shard are merged.
 
     Replicated form only, like retrieve_documents: every rank sees the whole corpus."""
-    from .documents import window_negatives
     make_index = index_factory or HipIndex
-    queries, qids, _ = _load_queries(args)
-    corpus_parts = list_shards(args.output_dir, "corpus")
-    if len(corpus_parts) == 0:
-        raise ValueError("No pre-computed document embeddings found")
+    queries, qids, corpus_parts = _corpus(args)
     start, count = int(start), int(count)
     if start < 0 or count < 0:
         raise ValueError("start and count must be >= 0")
     get = positives_of_query if callable(positives_of_query) else (lambda q: positives_of_query.get(q, ()))
     positives = [list(dict.fromkeys(get(q))) for q in qids]
     width = count + max((len(p) for p in positives), default=0)
-    dev = _device_index(args)
-    shards = [(p, *read_shard(p)) for p in corpus_parts]
-    shards = [s for s in shards if len(s[2])]
-    all_ids: List[str] = []
-    lists_s, lists_p = [], []
-    for _, reps, ids in shards:
-        ix = make_index(queries.shape[1], len(ids), dev)
-        ix.add(np.asarray(reps, dtype=np.float32))
-        if len(shards) == 1:                      # the window itself
-            sc, rows = _shard_pages(ix, queries, start, width)
-        else:                                     # every row that can stand above the window's end
-            sc, rows = _shard_pages(ix, queries, 0, min(start + width, len(ids)))
-        ix.close()
-        lists_s.append(sc)
-        lists_p.append(np.where(rows >= 0, rows + len(all_ids), -1))
-        all_ids.extend(ids)
+    shards = [s for s in map(read_shard, corpus_parts) if len(s[1])]
+    if len(shards) == 1:                          # the window itself
+        search = lambda ix, ids: _shard_pages(ix, queries, start, width)      # noqa: E731
+    else:                                         # every row that can stand above the window's end
+        search = lambda ix, ids: _shard_pages(ix, queries, 0, min(start + width, len(ids)))      # noqa: E731
+    lists_s, lists_p, all_ids = _shard_lists(shards, make_index, queries.shape[1], _device_index(args), search)
     if not lists_s or width == 0:
         return {q: [] for q in qids}
     if len(shards) == 1:
