@@ -878,7 +878,9 @@ int vr_resize_bicubic(int device_id, const uint8_t* src, int32_t src_on_device, 
  *   2 f32  out = acc + bias            5 bf16 out = rope(acc) for col < rope_cols (head 64)
  * bias (f32[N]) and resid (f32[M][ldo]) may be NULL.  variant: 3 = the engine's own choice,
  * 0 = 128x128 tile, 7 = 256x192 tile (N % 192 == 0), 9 = 256x256 tile (8 waves), 12 = 256x256 tile with one
- * wave per SIMD (what the engine uses for its big GEMMs), 13 = its 256x192 form (N % 192 == 0; epilogues 2, 3).
+ * wave per SIMD (what the engine uses for its big GEMMs), 13 = its 256x192 form (N % 192 == 0; epilogues 2, 3),
+ * 16 = its 256x288 form (N % 288 == 0; epilogue 3 and none of vr_op_gemm_ex's fields but raster_gm: anything else is
+ * VR_ERR_INVALID here).
  * Buffers padded to a multiple of 256 rows for the 256-row tiles. */
 int vr_op_gemm(int device_id, const void* A, int32_t lda, const void* W, int32_t ldw,
                int32_t M, int32_t N, int32_t K, int32_t epilogue, const float* bias,
@@ -890,19 +892,19 @@ int vr_op_gemm(int device_id, const void* A, int32_t lda, const void* W, int32_t
  * launchers REFUSE the call (VR_ERR_HIP, hipErrorInvalidValue) before anything is launched — for every variant and for 3
  * (the rule applies to the variant the engine's choice lands on):
  *   rowmap (i32 [M], device: output row of input row m, -1 = drop; EPI_RESID reads the residual at the mapped row)
- *                   honoured by 0, 7, 9, 12, 13 for each epilogue the variant has; refused by 14 / 15
+ *                   honoured by 0, 7, 9, 12, 13 for each epilogue the variant has; refused by 14 / 15 / 16
  *   rowbias (f32 [rowbias_period][rowbias_ld], device: row m % rowbias_period is added to the columns n < rowbias_cols)
  *                   honoured with epilogues 0, 1, 2 on 0, 7, 9, 12 and with epilogue 2 on 13; refused with epilogues 3, 4, 5,
- *                   with rowbias_period < 1, and by 14 / 15
+ *                   with rowbias_period < 1, and by 14 / 15 / 16
  *   ksplit > 1      (split s covers the K columns [s, s + 1) * K / ksplit and writes its fp32 plane to out + s * split_stride
  *                   floats; the bias rides with plane 0) honoured by 9, 12, 13 with epilogue 2 and K % (ksplit * 64) == 0;
- *                   refused everywhere else (0, 7, 14, 15, any other epilogue) and together with rowmap / rowbias
+ *                   refused everywhere else (0, 7, 14, 15, 16, any other epilogue) and together with rowmap / rowbias
  *   m_dev, m_sub    (i32 on the device: only the rows m < *m_dev - m_sub exist; 256-row tiles at or past that count are not
  *                   computed, rows between the count and the next multiple of 256 are unspecified) honoured by 9; refused
  *                   everywhere else
  *   col_scale, col_scale_n   (columns n < col_scale_n leave as bf16((acc + bias + rowbias) * col_scale)) honoured with epilogue 0
  *                   and col_scale_n a non-negative multiple of 64 on 0, 7, 9, 12; refused otherwise (any other epilogue, any
- *                   other col_scale_n) and, whatever the epilogue, by 14 / 15
+ *                   other col_scale_n) and, whatever the epilogue, by 14 / 15 / 16
  *   raster_gm       (m-tiles per rasterisation group, 0 = the launcher's choice) honoured everywhere: the order of the tiles
  *                   never changes a result bit */
 typedef struct vr_gemm_extras {
@@ -926,7 +928,7 @@ int vr_op_gemm_ex(int device_id, const void* A, int32_t lda, const void* W, int3
  *   warm, warm_bytes   (a device region the launch only REQUESTS while it runs: one dword of each of its 128-byte lines, counted from
  *                   its first byte, each line once, so that the launch behind this one finds the region in the memory-side cache —
  *                   nothing is computed from it, nothing outside it is read, no output bit depends on it) honoured by 12 for
- *                   every epilogue; refused by 0, 7, 9, 13, 14, 15 (and by 3 where the engine's choice lands on one of them) and for a region of
+ *                   every epilogue; refused by 0, 7, 9, 13, 14, 15, 16 (and by 3 where the engine's choice lands on one of them) and for a region of
  *                   2 GiB or more; warm NULL or
  *                   warm_bytes 0: absent, i.e. vr_op_gemm_ex */
 int vr_op_gemm_warm(int device_id, const void* A, int32_t lda, const void* W, int32_t ldw,
@@ -934,6 +936,14 @@ int vr_op_gemm_warm(int device_id, const void* A, int32_t lda, const void* W, in
                     const float* resid, float alpha, void* out, int32_t ldo,
                     const int32_t* rope_pos, const float* rope_table, int32_t rope_cols,
                     int32_t variant, const vr_gemm_extras_t* extras, const void* warm, uint64_t warm_bytes, void* stream);
+/* The variant a vr_op_gemm_warm call with these arguments reaches: `variant` itself, what 3 (the engine's choice) resolves to
+ * for this shape, or VR_GEMM_ROUTE_REFUSED where the entry or the launchers refuse the call (a variant that does not exist, a
+ * shape off its tile, a field the variant does not honour).  The launch dispatches on the same function.  Host arithmetic only:
+ * no device is selected, nothing is launched, the pointers of `extras` are compared with NULL and never dereferenced
+ * (extras NULL: all zero); warm_bytes != 0 stands for a region to warm. */
+#define VR_GEMM_ROUTE_REFUSED (-1)
+int vr_op_gemm_route(int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t variant, int32_t lda, int32_t ldw, int32_t ldo,
+                     const vr_gemm_extras_t* extras, uint64_t warm_bytes);
 /* y = LN(x) (kind 0, affine, eps) or RMSNorm(x) (kind 1): x f32 [rows][dim] -> bf16 [rows][ldo]. */
 int vr_op_norm(int device_id, int32_t kind, const float* x, int32_t rows, int32_t dim,
                const float* weight, const float* bias, float eps, void* out, int32_t ldo,

@@ -19,7 +19,7 @@ for sh in shapes:
     variant, BN = (13, 192) if (epi == 3 and N % 192 == 0) else (12, 256)      # the product's choice for the N = 1152 residual GEMMs
     BM = 256
     if len(sh) > 4:
-        variant, BN = sh[4], (192 if sh[4] in (13, 14) else 256)
+        variant, BN = sh[4], (288 if sh[4] == 16 else 192 if sh[4] in (13, 14) else 256)
     BM = 128 if variant in (14, 15) else 256
     Np = (N + BN - 1) // BN * BN
     A = torch.randn(((M + 255) // 256 * 256, K), device="cuda").to(torch.bfloat16)

@@ -145,6 +145,7 @@ SIGNATURES = {
                                 _vp, _i32, _vp, _vp, _i32, _i32, C.POINTER(VRGemmExtras), _vp]),
     "vr_op_gemm_warm": (C.c_int, [C.c_int, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _f32,
                                   _vp, _i32, _vp, _vp, _i32, _i32, C.POINTER(VRGemmExtras), _vp, C.c_uint64, _vp]),
+    "vr_op_gemm_route": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(VRGemmExtras), C.c_uint64]),
     "vr_op_norm": (C.c_int, [C.c_int, _i32, _vp, _i32, _i32, _vp, _vp, _f32, _vp, _i32, _vp]),
     "vr_op_norm_ex": (C.c_int, [C.c_int, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _f32, _vp, _i32, _vp]),
     "vr_op_text_rmsnorm_split": (C.c_int, [C.c_int, _vp, _i32, _i32, _vp, _f32, _vp, _vp, _vp]),

@@ -31,7 +31,8 @@ FILE_FLAGS = {"attention.hip": ["-fno-honor-nans"], "attention_w.hip": ["-fno-ho
 # the generated code: outside the kernel's own asm there must be no accumulation-register traffic at all.
 AGPR_CHECKED = {"gemm256w.hip", "gemm128w.hip", "search256w.hip", "attention_w.hip"}
 # ... and whose score MFMAs are asm statements on arch VGPRs: the listing is also walked for operand hazards (mfma_operand_hazards)
-MFMA_HAZARD_CHECKED = {"attention_w.hip"}
+# (gemm256w.hip: the ninth fragments of its 256 x 288 tile are arch VGPRs written by asm MFMAs)
+MFMA_HAZARD_CHECKED = {"attention_w.hip", "gemm256w.hip"}
 
 
 def lib_path(tag: str = "") -> str:

@@ -145,6 +145,9 @@ bool gemm_args_refused(const GemmArgs& a, int epi, int variant) {
     const bool split_tile = variant == GEMM_VARIANT_256IL || variant == GEMM_VARIANT_256W || variant == GEMM_VARIANT_192W;
     // the half-height tiles carry no per-row lookups at all
     if (half_tile && (a.rowmap || a.rowbias)) return true;
+    // the 256x288 tile carries the lookup-free residual epilogue and nothing else (a row bias, split K, column scaling, a device-side
+    // row count and a region to warm fall to the rules below: none of them names this variant)
+    if (variant == GEMM_VARIANT_288W && (epi != EPI_RESID || a.rowmap)) return true;
     // a row bias is added by the bf16 / GELU / fp32 epilogues; the residual, SwiGLU and RoPE epilogues have no such term
     if (a.rowbias && ((epi != EPI_BF16 && epi != EPI_GELU && epi != EPI_F32) || a.rowbias_period < 1)) return true;
     // split K: fp32 planes of the 256-row tiles, K a whole number of steps per split, no per-row lookups in the plane epilogue
@@ -159,6 +162,15 @@ bool gemm_args_refused(const GemmArgs& a, int epi, int variant) {
 int gemm_auto_variant(const GemmArgs& a, int epi) {
     // N = 1152 (SigLIP proj / fc2): 6 x 192 columns, big M -> the 256x192 kernel
     if (a.N % 192 == 0 && a.N % 256 != 0 && a.N <= 1536 && a.M >= 4096 && epi <= EPI_RESID) {
+        // ... or, where N is also a multiple of 288 (1152 = 4 x 288), the 256x288 form of the same kernel: whichever needs fewer
+        // rounds of the 256 CUs x tile columns (the K-loop of a tile lasts as long as it is wide), ties to the wider tile, which
+        // moves fewer operand bytes per output.  32 768 rows: 2 x 288 against 3 x 192; 16 384: 1 x 288 against 2 x 192; 10 260
+        // and 4 096 rows fill one round either way and stay on 192 columns.
+        if (epi == EPI_RESID && !a.rowmap && a.N % 288 == 0 && gemm256w_fits(a, 288) && !gemm_args_refused(a, epi, GEMM_VARIANT_288W)) {
+            const long tm = (a.M + 255) / 256;
+            const long c288 = (tm * (a.N / 288) + 255) / 256 * 288, c192 = (tm * (a.N / 192) + 255) / 256 * 192;
+            if (c288 <= c192) return GEMM_VARIANT_288W;
+        }
         if (epi == EPI_RESID && !a.rowmap && gemm256w_fits(a, 192)) return GEMM_VARIANT_192W;
         return GEMM_VARIANT_192;
     }
@@ -183,16 +195,37 @@ int gemm_auto_variant(const GemmArgs& a, int epi) {
     return (n_ok && e256 > e128) ? (w_ok ? GEMM_VARIANT_256W : GEMM_VARIANT_256IL) : GEMM_VARIANT_GLDS;
 }
 
+// The host's tests of each variant's launcher, gathered: what AUTO resolves to, then whether that variant takes the launch.
+int gemm_route(const GemmArgs& a, int epi, int variant) {
+    if (epi < EPI_BF16 || epi > EPI_ROPE) return GEMM_ROUTE_REFUSED;
+    if (variant == GEMM_VARIANT_AUTO) variant = gemm_auto_variant(a, epi);
+    bool ok = false;
+    switch (variant) {
+        case GEMM_VARIANT_GLDS: case GEMM_VARIANT_256IL: ok = true; break;
+        case GEMM_VARIANT_192: ok = a.N % 192 == 0 && epi <= EPI_RESID; break;
+        case GEMM_VARIANT_256W: ok = gemm256w_fits(a, 256); break;
+        case GEMM_VARIANT_192W: ok = a.N % 192 == 0 && ((epi == EPI_RESID && a.ksplit <= 1) || epi == EPI_F32) && gemm256w_fits(a, 192); break;
+        case GEMM_VARIANT_288W: ok = a.N % 288 == 0 && epi == EPI_RESID && gemm256w_fits(a, 288); break;
+        case GEMM_VARIANT_128W_192: ok = epi == EPI_RESID && gemm128w_fits(a, 192); break;
+        case GEMM_VARIANT_128W_256:
+            ok = (epi == EPI_RESID || ((epi == EPI_BF16 || epi == EPI_GELU || epi == EPI_SWIGLU) && (a.ldo & 7) == 0 && a.col_scale_n == 0)) && gemm128w_fits(a, 256);
+            break;
+        default: break;
+    }
+    return ok && !gemm_args_refused(a, epi, variant) ? variant : GEMM_ROUTE_REFUSED;
+}
+
 hipError_t launch_gemm(const GemmArgs& a, int epi, int variant, hipStream_t s) {
     if (a.M <= 0) return hipSuccess;
-    // (each variant launcher applies gemm_args_refused to itself; AUTO is judged as the variant it picks)
-    if (variant == GEMM_VARIANT_AUTO) variant = gemm_auto_variant(a, epi);
+    // (each variant launcher applies its tests to itself as well: a direct caller gets the same answer)
+    variant = gemm_route(a, epi, variant);
+    if (variant == GEMM_ROUTE_REFUSED) return hipErrorInvalidValue;
     if (variant == GEMM_VARIANT_192) return launch_gemm192(a, epi, s);
     if (variant == GEMM_VARIANT_256W) return launch_gemm256w(a, epi, s);
     if (variant == GEMM_VARIANT_192W) return launch_gemm192w(a, epi, s);
+    if (variant == GEMM_VARIANT_288W) return launch_gemm288w(a, epi, s);
     if (variant == GEMM_VARIANT_128W_192) return launch_gemm128w(a, epi, 192, s);
     if (variant == GEMM_VARIANT_128W_256) return launch_gemm128w(a, epi, 256, s);
-    if (gemm_args_refused(a, epi, variant)) return hipErrorInvalidValue;
     switch (epi) {
         case EPI_BF16: return launch_epi<EPI_BF16>(a, variant, s);
         case EPI_GELU: return launch_epi<EPI_GELU>(a, variant, s);

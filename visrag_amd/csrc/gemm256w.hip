@@ -41,8 +41,19 @@
 //     (buffer descriptors instead of predicates, branches and 64-bit address arithmetic: gemm256w_kernel.h, gemm_epilogue.h).
 //
 // NJ = 16-column fragments per wave: 8 -> 256 x 256 tile, 6 -> 256 x 192 tile (N = 1152 = 6 x 192: SigLIP proj / fc2,
-// residual epilogue only).  Slot s = strip * NJ + fragment numbers the MFMAs of a phase; the numbers in the
-// schedule above are those of NJ = 8, the NJ = 6 ones are scaled (see the constants in the kernel).
+// residual and fp32 epilogues), 9 -> 256 x 288 tile (1152 = 4 x 288: 512 tiles at 32 768 rows, two full rounds of the
+// 256 CUs where 192 columns take three; the lookup-free residual epilogue only).  Slot s = strip * NJ + fragment numbers
+// the MFMAs of a phase; the numbers in the schedule above are those of NJ = 8, the others are scaled (see the constants
+// in the kernel: NJ = 9 has 72 slots, 17 loads, barriers at slots 45 and 9, five loads in phase 1, vmcnt(17) / vmcnt(5)).
+// NJ = 9 per K-step and wave: 144 MFMAs on 17 LDS-DMA instructions and 34 fragment reads (0.35 auxiliaries per MFMA; NJ = 6:
+// 0.44, NJ = 8: 0.375), (256 + 288) / (256 * 288) operand bytes per output (0.81 of NJ = 6's).  Its 288 accumulators do not
+// fit the accumulation-register file: strip i's ninth fragment is eight "+v" operands (W_MFMA_V, gemm256w_acc.h) in arch
+// VGPRs — 136 fragment registers + 32 + addressing = 204, no scratch.  The K-loop of that instantiation runs whole PAIRS of
+// steps and the odd step behind them: with an exit between the two steps of the loop hipcc copied the 32 registers to
+// another set in one step and back in the next (16 v_mov_b64 per step, each reading an MFMA result the hardware does not
+// interlock); build.py walks the listing for such reads (mfma_operand_hazards).  A stage is A 32 KiB + W 36 KiB; two
+// stages + staging + dump slots = 156 672 B of the 160 KiB a workgroup may declare.  Epilogue pieces of 32 rows x 48
+// columns, twelve per wave, through the same descriptors, register ring and expression as NJ = 6: bit-identical outputs.
 //
 // LDS image, swizzle and epilogues are those of the 8-wave kernel (gemm_core.h, gemm_epilogue.h);
 // the accumulators are kept as two 64-column halves so the epilogue helpers apply unchanged.
@@ -60,6 +71,8 @@ bool gemm256w_fits(const GemmArgs& a, int bn);
 namespace {
 
 constexpr int W_STAGE = 2 * G256_TILE_BYTES;       // A tile + W tile = 64 KiB
+// ... of a tile of 32 nj columns: the 288-column tile's W rows take 36 KiB, the 192-column tile keeps the 256-column stride
+constexpr int w_stage_bytes(int nj) { return nj > 8 ? G256_TILE_BYTES + nj * 32 * GEMM_BK * 2 : W_STAGE; }
 constexpr unsigned W_OOB = 0x80000000u;            // per-lane offset beyond the descriptor's range
 
 }  // namespace
@@ -69,6 +82,8 @@ constexpr unsigned W_OOB = 0x80000000u;            // per-lane offset beyond the
 constexpr int W_STAGING = 4096;                            // epilogue staging per wave: one piece of 32 rows x 64 bf16
 constexpr int W_WARM_DUMP = 256;                           // where a wave's GemmArgs::warm requests land: 64 lanes x 4 bytes nobody reads
 constexpr int W_SMEM_BYTES = 2 * W_STAGE + 4 * W_STAGING + 4 * W_WARM_DUMP;  // two stages + staging + dump slots = 145 KiB
+constexpr int w_smem_bytes(int nj) { return 2 * w_stage_bytes(nj) + 4 * W_STAGING + 4 * W_WARM_DUMP; }
+static_assert(w_smem_bytes(8) == W_SMEM_BYTES && w_smem_bytes(6) == W_SMEM_BYTES && w_smem_bytes(9) == 156672 && w_smem_bytes(9) <= 160 * 1024, "LDS a workgroup may declare");
 
 // GemmArgs::warm: walking the workgroups and their waves in order, each share starts where the one before ended (ordered, disjoint,
 // no gap) and the last one ends with the region's last line — every line is requested exactly once, whatever the grid
@@ -109,15 +124,17 @@ template <int EPI, bool PLAIN, int NJ>
 static hipError_t launch_wp(GemmArgs a, hipStream_t s) {
     constexpr int BN = 32 * NJ;
     const int tn = (a.N + BN - 1) / BN, tm = (a.M + G256_BM - 1) / G256_BM;
-    if (a.raster_gm <= 0) a.raster_gm = tm <= 16 ? tm : 4;
+    // (four tile columns of 288: the 32 tiles an XCD runs together as 8 rows x 4 columns — the least operand rows, r * 256 + c * 288,
+    // among the r x c = 32 blocks of whole tile columns)
+    if (a.raster_gm <= 0) a.raster_gm = tm <= 16 ? tm : (NJ == 9 ? 8 : 4);
     if (!gemm256w_fits(a, BN)) return hipErrorInvalidValue;
-    if (gemm_args_refused(a, EPI, NJ == 6 ? GEMM_VARIANT_192W : GEMM_VARIANT_256W)) return hipErrorInvalidValue;
+    if (gemm_args_refused(a, EPI, NJ == 9 ? GEMM_VARIANT_288W : NJ == 6 ? GEMM_VARIANT_192W : GEMM_VARIANT_256W)) return hipErrorInvalidValue;
     int total = tn * tm;
     if (a.ksplit > 1) total *= a.ksplit;
     auto k = gemm256w_bf16_kernel<EPI, PLAIN, NJ>;
     static unsigned long long attr = 0;     // bit d: set on device d
-    set_max_dynamic_lds((const void*)k, W_SMEM_BYTES, attr);
-    hipLaunchKernelGGL(k, dim3(total), dim3(256), W_SMEM_BYTES, s, a);
+    set_max_dynamic_lds((const void*)k, w_smem_bytes(NJ), attr);
+    hipLaunchKernelGGL(k, dim3(total), dim3(256), w_smem_bytes(NJ), s, a);
     return hipGetLastError();
 }
 
@@ -161,6 +178,13 @@ hipError_t launch_gemm192w(const GemmArgs& a, int epi, hipStream_t s) {
     if (epi == EPI_RESID && a.ksplit <= 1) return launch_wp<EPI_RESID, false, 6>(a, s);
     if (epi == EPI_F32) return launch_wp<EPI_F32, false, 6>(a, s);          // incl. split-K partial products
     return hipErrorInvalidValue;
+}
+
+// 256 x 288 tile: N % 288 == 0 (1152 = 4 x 288: two full rounds of 256 CUs at 32 768 rows where 192 columns take three), the
+// lookup-free residual epilogue and nothing else (gemm_args_refused): no tile has a column edge, no row is mapped
+hipError_t launch_gemm288w(const GemmArgs& a, int epi, hipStream_t s) {
+    if (a.N % 288 || epi != EPI_RESID) return hipErrorInvalidValue;
+    return launch_wp<EPI_RESID, false, 9>(a, s);
 }
 
 }  // namespace vr

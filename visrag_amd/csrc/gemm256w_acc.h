@@ -87,4 +87,9 @@
 #define W_READ(V, C0, C1, C2, C3) \
     asm volatile("v_accvgpr_read_b32 %0, " C0 "\n\tv_accvgpr_read_b32 %1, " C1 "\n\tv_accvgpr_read_b32 %2, " C2 \
                  "\n\tv_accvgpr_read_b32 %3, " C3 : "=v"(V[0]), "=v"(V[1]), "=v"(V[2]), "=v"(V[3]))
-
+// A ninth fragment per strip (the 256 x 288 tile of gemm256w.hip) does not fit the accumulation-register file, which ends at
+// a255: those eight accumulators are compiler-allocated arch VGPRs, tied in and out of the same instruction.  Eight values in a
+// file with room to spare are not the 64 that fill theirs — hipcc leaves them where they are (the build's listing check
+// reports a spill; a copy in the K-loop would show in the listing as a v_mov_b32 between the MFMAs).
+#define W_MFMA_V(CV, WV, AV) \
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(CV) : "v"(WV), "v"(AV))

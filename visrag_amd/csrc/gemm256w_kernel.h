@@ -1,16 +1,20 @@
 // The kernel text of gemm256w.hip (W_KERNEL_TEMPLATE / W_KERNEL_NAME are set by the includer).
 W_KERNEL_TEMPLATE
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void W_KERNEL_NAME(GemmArgs p) {
-    static_assert(NJ == 8 || (NJ == 6 && !PLAIN), "wave tile 128 x 128 or 128 x 96");
+    static_assert(NJ == 8 || (NJ == 6 && !PLAIN) || (NJ == 9 && !PLAIN && EPI == EPI_RESID), "wave tile 128 x 128, 128 x 96 or 128 x 144");
     constexpr int BN = 32 * NJ;                 // tile columns
     constexpr int NS = 8 * NJ;                  // MFMAs per phase (slots)
     constexpr int NR = 8 + NJ;                  // fragment reads per k-half = LDS-DMA loads per K-step and wave
-    constexpr int DS = NJ == 8 ? 5 : 4;         // one load per DS slots
+    constexpr int DS = NJ >= 8 ? 5 : 4;         // one load per DS slots
     constexpr int SB1 = NS * 5 / 8;             // slot of the phase-1 barrier (the k-half-1 reads end at slot 2 NR - 2)
     constexpr int D1 = (NS - 1 - (SB1 + 2)) / DS + 1;   // loads issued in phase 1 (slots SB1 + 2, + DS, ...)
     constexpr int SB2 = NJ;                     // slot of the phase-2 barrier
-    constexpr int NF = NJ / 2;                  // fragments per epilogue piece: 64 or 48 columns
+    constexpr int NF = NJ == 9 ? 3 : NJ / 2;    // fragments per epilogue piece: 64 or 48 columns
+    constexpr int NH = NJ / NF;                 // pieces across the wave's columns: 2, or 3 of the 144
+    constexpr int NP = 4 * NH;                  // pieces per wave
+    constexpr int STAGE = w_stage_bytes(NJ);    // A tile + W tile of one stage
     static_assert(SB2 + 3 + DS * (NR - D1 - 1) < NS && SB2 + 2 + 2 * (NR - 1) < NS && 2 * NR - 2 < SB1, "schedule fits");
+    static_assert(D1 == (NJ == 6 ? 4 : 5) && NR <= 17, "the vmcnt immediates below");
     extern __shared__ __attribute__((aligned(16))) char smem[];
 #ifdef VR_W_TIMING                   // tile anatomy (tools/w_anatomy.py, tagged builds only, one tile per workgroup)
     const unsigned long long tm0 = __builtin_amdgcn_s_memrealtime();
@@ -58,8 +62,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
     // one of the NR loads of a K-step: d < 8 -> A row group d, else W row group d - 8
     auto dma = [&](int stage, int d, unsigned vA, unsigned vW) {
-        if (d < 8) __builtin_amdgcn_raw_ptr_buffer_load_lds(arsrc, VR_LDS(dmaA + stage * W_STAGE + d * 1024), 16, vA, sA0 + d * rgA, 0, 0);
-        else __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, VR_LDS(dmaW + stage * W_STAGE + (d - 8) * 1024), 16, vW, sW0 + (d - 8) * rgW, 0, 0);
+        if (d < 8) __builtin_amdgcn_raw_ptr_buffer_load_lds(arsrc, VR_LDS(dmaA + stage * STAGE + d * 1024), 16, vA, sA0 + d * rgA, 0, 0);
+        else __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, VR_LDS(dmaW + stage * STAGE + (d - 8) * 1024), 16, vW, sW0 + (d - 8) * rgW, 0, 0);
     };
 
     // ---- fragment addressing: row = strip * 16 + fr, chunk (kk * 4 + fq) ^ (row & 7).  One LDS pointer per
@@ -71,12 +75,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
             const int ch = ((kk * 4 + fq) ^ (fr & 7)) << 4;
-            pA[st][kk] = (frag_p)VR_LDS(smem + st * W_STAGE + (wm * 128 + fr) * 128 + ch);
-            pW[st][kk] = (frag_p)VR_LDS(smem + st * W_STAGE + G256_TILE_BYTES + (wn * 16 * NJ + fr) * 128 + ch);
+            pA[st][kk] = (frag_p)VR_LDS(smem + st * STAGE + (wm * 128 + fr) * 128 + ch);
+            pW[st][kk] = (frag_p)VR_LDS(smem + st * STAGE + G256_TILE_BYTES + (wn * 16 * NJ + fr) * 128 + ch);
             asm volatile("" : "+v"(pA[st][kk]), "+v"(pW[st][kk]));
         }
 
     bf16x8 a0[8], w0[NJ], a1[8], w1[NJ];
+    f32x4 c9[8];                     // NJ == 9: strip i's ninth fragment, in arch VGPRs (W_MFMA_V)
+    (void)c9;
     int m0, n0, split;
     coords(my_first, m0, n0, split);
     unsigned curA = tile_off_a(m0, split), curW = tile_off_w(n0, split);
@@ -98,7 +104,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             }
         }
         W_FOR_EACH_ACC(W_ZERO)
-        if constexpr (NJ == 8) VR_WAIT_VM_BARRIER(16); else VR_WAIT_VM_BARRIER(14);
+        if constexpr (NJ == 9) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) c9[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        // (the NR loads of K-step 1 stay in flight)
+        if constexpr (NJ == 9) VR_WAIT_VM_BARRIER(17); else if constexpr (NJ == 8) VR_WAIT_VM_BARRIER(16); else VR_WAIT_VM_BARRIER(14);
 #pragma unroll
         for (int j = 0; j < NJ; ++j) w0[j] = pW[0][0][j * 128];
 #pragma unroll
@@ -142,21 +153,36 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 }
                 __builtin_amdgcn_sched_barrier(0);
             };
-            // ---- phase 1: k-half 0, phase 2: k-half 1 (accumulator n: strip n / 8, fragment n % 8 < NJ)
+            // ---- phase 1: k-half 0, phase 2: k-half 1 (accumulator n: strip n / 8, fragment n % 8 < NJ; with NJ == 9 the
+            //      strip's ninth fragment follows its eighth, slot strip * 9 + 8)
+            constexpr int J9 = NJ == 9 ? 8 : 0;
 #define W_P1(n, R, C0, C1, C2, C3) \
-            if (((n) & 7) < NJ) { W_MFMA(R, C0, C1, C2, C3, w0[(n) & 7], a0[(n) >> 3]); aux1(((n) >> 3) * NJ + ((n) & 7)); }
+            if (((n) & 7) < NJ) { W_MFMA(R, C0, C1, C2, C3, w0[(n) & 7], a0[(n) >> 3]); aux1(((n) >> 3) * NJ + ((n) & 7)); } \
+            if (NJ == 9 && ((n) & 7) == 7) { W_MFMA_V(c9[(n) >> 3], w0[J9], a0[(n) >> 3]); aux1(((n) >> 3) * NJ + 8); }
 #define W_P2(n, R, C0, C1, C2, C3) \
-            if (((n) & 7) < NJ) { W_MFMA(R, C0, C1, C2, C3, w1[(n) & 7], a1[(n) >> 3]); aux2(((n) >> 3) * NJ + ((n) & 7)); }
+            if (((n) & 7) < NJ) { W_MFMA(R, C0, C1, C2, C3, w1[(n) & 7], a1[(n) >> 3]); aux2(((n) >> 3) * NJ + ((n) & 7)); } \
+            if (NJ == 9 && ((n) & 7) == 7) { W_MFMA_V(c9[(n) >> 3], w1[J9], a1[(n) >> 3]); aux2(((n) >> 3) * NJ + 8); }
             W_FOR_EACH_ACC(W_P1)
             W_FOR_EACH_ACC(W_P2)
 #undef W_P1
 #undef W_P2
         };
 
-        for (int kt = 0; kt < nk; kt += 2) {
-            step(std::integral_constant<int, 0>{}, kt);
-            if (kt + 1 >= nk) break;
-            step(std::integral_constant<int, 1>{}, kt + 1);
+        if constexpr (NJ == 9) {
+            // (whole pairs of steps, then the odd one: with an exit between the two steps of the loop hipcc moves the ninth
+            // fragments to other registers in one step and back in the next)
+            int kt = 0;
+            for (; kt + 1 < nk; kt += 2) {
+                step(std::integral_constant<int, 0>{}, kt);
+                step(std::integral_constant<int, 1>{}, kt + 1);
+            }
+            if (kt < nk) step(std::integral_constant<int, 0>{}, kt);
+        } else {
+            for (int kt = 0; kt < nk; kt += 2) {
+                step(std::integral_constant<int, 0>{}, kt);
+                if (kt + 1 >= nk) break;
+                step(std::integral_constant<int, 1>{}, kt + 1);
+            }
         }
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // MFMA results -> VALU reads (see the W_MFMA note)
 #ifdef VR_W_TIMING
@@ -169,7 +195,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         //      Pieces of 32 accumulator registers are read back into VGPRs one after the other; the scheduling
         //      barriers keep hipcc from pulling later read-backs up and running out of VGPRs.
         const int mrow0 = m0 + wm * 128, nb0 = n0 + wn * (16 * NJ);
-        char* const wl0 = smem + 2 * W_STAGE + wave * W_STAGING;
+        char* const wl0 = smem + 2 * STAGE + wave * W_STAGING;
         bool plain_resid = false;
         if constexpr (EPI == EPI_RESID) plain_resid = !p.rowmap;
         // fp32 tiles without a column edge (every encode-path shape) leave through BUFFER loads / stores: the descriptor
@@ -207,7 +233,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     const unsigned long long wa = (unsigned long long)uni_ptr(p.warm);
                     const auto wrs = __builtin_amdgcn_make_buffer_rsrc((void*)wa, 0, uni32((unsigned)p.warm_bytes), 0x00020000);
                     const unsigned pad = (0u - (unsigned)wa) & 3u;      // (a region that starts off a dword: the requests are aligned ones)
-                    char* const dump = smem + 2 * W_STAGE + 4 * W_STAGING + wave * W_WARM_DUMP;
+                    char* const dump = smem + 2 * STAGE + 4 * W_STAGING + wave * W_WARM_DUMP;
                     auto request = [&](unsigned l) {
                         const unsigned line = l + (unsigned)lane;
                         __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, VR_LDS(dump), 4, line < warm_hi ? line * WARM_LINE + pad : W_OOB, 0, 0, 0);
@@ -222,11 +248,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             }
         };
         bool buf_tile = false;
-        if constexpr (EPI == EPI_RESID) buf_tile = plain_resid && n0 + BN <= p.N;
+        if constexpr (EPI == EPI_RESID) buf_tile = NJ == 9 || (plain_resid && n0 + BN <= p.N);     // (NJ == 9: the launcher admits nothing else)
         if constexpr (EPI == EPI_F32) buf_tile = !p.rowmap && !p.rowbias && n0 + BN <= p.N;
         if constexpr (EPI == EPI_RESID || EPI == EPI_F32) {
             if (buf_tile) {
-                constexpr int MI = 2;           // pieces of 32 rows x 16 NF columns: 8 per wave
+                constexpr int MI = 2;           // pieces of 32 rows x 16 NF columns: NP (8 or 12) per wave
                 const float alpha = __builtin_bit_cast(float, uni32(__builtin_bit_cast(unsigned, p.alpha)));
                 const unsigned ldb = uni32((unsigned)p.ldo * 4u);
                 const unsigned nrec = uni32((unsigned)min(G256_BM, p.M - m0) * ldb);
@@ -243,11 +269,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 if constexpr (EPI == EPI_RESID) {
                     // out = resid + alpha * (acc + bias), in place; the residual of piece q + RD is in flight while piece q
                     // is combined and stored
-                    constexpr int RD = NJ == 6 ? 3 : 2;
+                    constexpr int RD = NF == 3 ? 3 : 2;
                     const auto rrs = __builtin_amdgcn_make_buffer_rsrc(uni_ptr(p.resid + (size_t)m0 * p.ldo), 0, nrec, 0x00020000);
                     f32x4 rs[RD + 1][MI][NF];
                     auto load_piece = [&](int q, f32x4 (&dst)[MI][NF]) {
-                        const int h = q & 1, sg = q >> 1;
+                        const int h = q % NH, sg = q / NH;
 #pragma unroll
                         for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -259,14 +285,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     for (int q = 0; q < RD; ++q) load_piece(q, rs[q]);
                     warm_requests();
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const int h = q & 1, sg = q >> 1;
-                        if (q + RD < 8) load_piece(q + RD, rs[(q + RD) % (RD + 1)]);
+                    for (int q = 0; q < NP; ++q) {
+                        const int h = q % NH, sg = q / NH;
+                        if (q + RD < NP) load_piece(q + RD, rs[(q + RD) % (RD + 1)]);
                         f32x4 acc[MI][NF];
 #define W_RD(n, R, C0, C1, C2, C3) \
                         if (((n) & 7) < NJ && ((n) & 7) / NF == h && ((n) >> 4) == sg) W_READ(acc[((n) >> 3) & 1][((n) & 7) % NF], C0, C1, C2, C3);
                         W_FOR_EACH_ACC(W_RD)
 #undef W_RD
+                        if constexpr (NJ == 9) {        // the ninth fragments are where the MFMAs left them
+                            if (h == NH - 1) { acc[0][NF - 1] = c9[sg * MI]; acc[1][NF - 1] = c9[sg * MI + 1]; }
+                        }
 #pragma unroll
                         for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -299,7 +328,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 }
             }
         }
-        if constexpr (EPI == EPI_RESID) {
+        if constexpr (EPI == EPI_RESID && NJ != 9) {
             // the general form (a column edge): out = resid + alpha * (acc + bias), fp32, in place, piece by piece.  Addresses
             // are clamped for rows >= M / columns >= N, the stores predicated.
             if (plain_resid && !buf_tile) {
@@ -351,7 +380,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 }
             }
         }
-        if (!plain_resid && !buf_tile) {
+        if constexpr (NJ != 9) if (!plain_resid && !buf_tile) {
             // (lookup-free bf16 epilogues: the tile's output rows behind one descriptor, the wave's bias columns loaded once —
             // an empty descriptor without a bias, ending at N: see gemm_epilogue_tile_lds_plain_buf)
             const unsigned ldo2 = uni32((unsigned)p.ldo * 2u);

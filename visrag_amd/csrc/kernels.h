@@ -13,8 +13,9 @@ enum GemmEpilogue { EPI_BF16 = 0, EPI_GELU = 1, EPI_F32 = 2, EPI_RESID = 3, EPI_
 // multiple of 256 rows); 192: 256x192 tile for N % 192 == 0; AUTO picks by shape.  (The gaps in the ids are
 // retired round-1 experiment variants: DESIGN.md ledger row 5.)
 // 128W_192 / 128W_256: the half-height one-wave tiles of gemm128w.hip (few rows: the decoder's o / down projections).
+// 288W: the 256x288 form of the one-wave tile (N % 288 == 0, the lookup-free residual epilogue only).
 enum GemmVariant { GEMM_VARIANT_GLDS = 0, GEMM_VARIANT_AUTO = 3, GEMM_VARIANT_192 = 7, GEMM_VARIANT_256IL = 9, GEMM_VARIANT_256W = 12,
-                   GEMM_VARIANT_192W = 13, GEMM_VARIANT_128W_192 = 14, GEMM_VARIANT_128W_256 = 15 };
+                   GEMM_VARIANT_192W = 13, GEMM_VARIANT_128W_192 = 14, GEMM_VARIANT_128W_256 = 15, GEMM_VARIANT_288W = 16 };
 
 struct GemmArgs {
     const void* A; int lda;          // bf16 [M_pad][lda]
@@ -51,6 +52,10 @@ hipError_t launch_gemm(const GemmArgs& a, int epilogue, int variant, hipStream_t
 bool gemm_args_refused(const GemmArgs& a, int epilogue, int variant);
 // the concrete variant GEMM_VARIANT_AUTO resolves to for this launch (a caller that sets a field only one variant honours asks first)
 int gemm_auto_variant(const GemmArgs& a, int epilogue);
+// the concrete variant launch_gemm reaches with these arguments (it dispatches on this), or GEMM_ROUTE_REFUSED where the launch
+// is refused by a test of the host's; integer and null tests only, no pointer is dereferenced
+constexpr int GEMM_ROUTE_REFUSED = -1;
+int gemm_route(const GemmArgs& a, int epilogue, int variant);
 // 256x192 tile (gemm192.hip): N % 192 == 0, epilogues BF16 / GELU / F32 / RESID only
 hipError_t launch_gemm192(const GemmArgs& a, int epilogue, hipStream_t s);
 // 256x256 tile, one wave per SIMD (gemm256w.hip): same contract as the 256-tile path of launch_gemm
@@ -58,6 +63,8 @@ hipError_t launch_gemm256w(const GemmArgs& a, int epilogue, hipStream_t s);
 bool gemm256w_fits(const GemmArgs& a, int tile_cols);   // its 32-bit LDS-DMA offsets cover both operands
 // its 256x192 form: N % 192 == 0, EPI_RESID and EPI_F32 (incl. ksplit)
 hipError_t launch_gemm192w(const GemmArgs& a, int epilogue, hipStream_t s);
+// its 256x288 form: N % 288 == 0, EPI_RESID without a row map (every other optional field is refused)
+hipError_t launch_gemm288w(const GemmArgs& a, int epilogue, hipStream_t s);
 // 128 x 192 / 128 x 256 tile, one wave per SIMD, three LDS stages (gemm128w.hip): N % tile_cols == 0, no row map / row bias /
 // split K; tile_cols 192: EPI_RESID, 256: EPI_RESID / BF16 / GELU / SWIGLU
 hipError_t launch_gemm128w(const GemmArgs& a, int epilogue, int tile_cols, hipStream_t s);

@@ -115,6 +115,12 @@ extern "C" int vr_streams_overlap(int device_id, void* stream_a, void* stream_b,
 }
 
 // ------------------------------------------------------------------------------ op-level ---
+// the shape test of the GEMM entries: the tile columns of the variant asked for divide N (AUTO: 128), K whole steps, rows
+static bool gemm_shape_refused(int32_t M, int32_t N, int32_t K, int32_t variant) {
+    const int cols = variant == GEMM_VARIANT_288W ? 288 : (variant == GEMM_VARIANT_192 || variant == GEMM_VARIANT_192W || variant == GEMM_VARIANT_128W_192) ? 192 : 128;
+    return N % cols || K % 64 || M <= 0;
+}
+
 // (extras: the fields of GemmArgs beyond vr_op_gemm's arguments, copied as they are — what is legal is the launchers' decision)
 extern "C" int vr_op_gemm_warm(int device_id, const void* A, int32_t lda, const void* W, int32_t ldw, int32_t M, int32_t N,
                                int32_t K, int32_t epilogue, const float* bias, const float* resid, float alpha, void* out,
@@ -122,9 +128,9 @@ extern "C" int vr_op_gemm_warm(int device_id, const void* A, int32_t lda, const 
                                int32_t variant, const vr_gemm_extras_t* extras, const void* warm, uint64_t warm_bytes, void* stream) {
     if (!A || !W || !out) return fail(VR_ERR_INVALID, "NULL argument");
     if (variant != GEMM_VARIANT_GLDS && variant != GEMM_VARIANT_AUTO && variant != GEMM_VARIANT_192 && variant != GEMM_VARIANT_256IL && variant != GEMM_VARIANT_256W && variant != GEMM_VARIANT_192W &&
-        variant != GEMM_VARIANT_128W_192 && variant != GEMM_VARIANT_128W_256)
-        return fail(VR_ERR_INVALID, "variant %d: 0 (128^2 tile), 3 (auto), 7 (256x192 tile), 9 (256^2 tile), 12 / 13 (256^2 / 256x192 tile, one wave per SIMD), 14 / 15 (128x192 / 128x256 tile, one wave per SIMD)", variant);
-    if (((variant == 7 || variant == 13 || variant == 14) ? N % 192 : N % 128) || K % 64 || M <= 0) return fail(VR_ERR_INVALID, "need N %% 128 == 0 (192 for variant 7), K %% 64 == 0");
+        variant != GEMM_VARIANT_128W_192 && variant != GEMM_VARIANT_128W_256 && variant != GEMM_VARIANT_288W)
+        return fail(VR_ERR_INVALID, "variant %d: 0 (128^2 tile), 3 (auto), 7 (256x192 tile), 9 (256^2 tile), 12 / 13 / 16 (256^2 / 256x192 / 256x288 tile, one wave per SIMD), 14 / 15 (128x192 / 128x256 tile, one wave per SIMD)", variant);
+    if (gemm_shape_refused(M, N, K, variant)) return fail(VR_ERR_INVALID, "need N %% 128 == 0 (192 for variants 7, 13 and 14, 288 for variant 16), K %% 64 == 0");
     if (epilogue == EPI_RESID && !resid) return fail(VR_ERR_INVALID, "EPI_RESID needs resid");
     if (epilogue == EPI_ROPE && (!rope_pos || !rope_table)) return fail(VR_ERR_INVALID, "EPI_ROPE needs tables");
     VRCHK(set_dev(device_id));
@@ -140,6 +146,9 @@ extern "C" int vr_op_gemm_warm(int device_id, const void* A, int32_t lda, const 
         a.raster_gm = extras->raster_gm;
     }
     a.warm = warm; a.warm_bytes = (size_t)warm_bytes;
+    // (the 256x288 tile is one epilogue form and no optional field: what it does not take is an argument error of this entry)
+    if (variant == GEMM_VARIANT_288W && gemm_route(a, epilogue, variant) == GEMM_ROUTE_REFUSED)
+        return fail(VR_ERR_INVALID, "variant 16 takes the residual epilogue without a row map, row bias, split K, column scale, device-side row count or region to warm");
     HIPCHK(launch_gemm(a, epilogue, variant, (hipStream_t)stream));
     return VR_OK;
 }
@@ -158,6 +167,29 @@ extern "C" int vr_op_gemm(int device_id, const void* A, int32_t lda, const void*
                           int32_t variant, void* stream) {
     return vr_op_gemm_ex(device_id, A, lda, W, ldw, M, N, K, epilogue, bias, resid, alpha, out, ldo, rope_pos, rope_table, rope_cols,
                          variant, nullptr, stream);
+}
+
+// the variant that call reaches (AUTO resolved), or VR_GEMM_ROUTE_REFUSED: no device is selected, nothing is launched, no
+// pointer is dereferenced (those of `extras` are compared with null); launch_gemm dispatches on the same function
+extern "C" int vr_op_gemm_route(int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t variant, int32_t lda, int32_t ldw,
+                                int32_t ldo, const vr_gemm_extras_t* extras, uint64_t warm_bytes) {
+    if (variant != GEMM_VARIANT_GLDS && variant != GEMM_VARIANT_AUTO && variant != GEMM_VARIANT_192 && variant != GEMM_VARIANT_256IL && variant != GEMM_VARIANT_256W && variant != GEMM_VARIANT_192W &&
+        variant != GEMM_VARIANT_128W_192 && variant != GEMM_VARIANT_128W_256 && variant != GEMM_VARIANT_288W)
+        return VR_GEMM_ROUTE_REFUSED;
+    if (gemm_shape_refused(M, N, K, variant)) return VR_GEMM_ROUTE_REFUSED;
+    GemmArgs a{};
+    a.lda = lda; a.ldw = ldw; a.M = M; a.N = N; a.K = K; a.ldo = ldo;
+    if (extras) {
+        a.rowmap = extras->rowmap;
+        a.rowbias = extras->rowbias; a.rowbias_period = extras->rowbias_period; a.rowbias_ld = extras->rowbias_ld; a.rowbias_cols = extras->rowbias_cols;
+        a.col_scale = extras->col_scale; a.col_scale_n = extras->col_scale_n;
+        a.ksplit = extras->ksplit; a.split_stride = (size_t)extras->split_stride;
+        a.m_dev = extras->m_dev; a.m_sub = extras->m_sub;
+        a.raster_gm = extras->raster_gm;
+    }
+    if (warm_bytes) { a.warm = &a; a.warm_bytes = (size_t)warm_bytes; }      // (any non-null address: the launchers compare it with null)
+    const int r = gemm_route(a, epilogue, variant);
+    return r == GEMM_ROUTE_REFUSED ? VR_GEMM_ROUTE_REFUSED : r;
 }
 
 extern "C" int vr_op_norm(int device_id, int32_t kind, const float* x, int32_t rows, int32_t dim, const float* weight,
