@@ -269,6 +269,25 @@ int vr_chat_reorder(vr_chat_t ch, int32_t n, const int32_t* rows, const int32_t*
 int vr_chat_logits(vr_chat_t ch, int32_t row, float* out, void* stream);
 /* The prompt slot of `row` (-1: none) and the number of tokens in its tail. */
 int vr_chat_row_len(vr_chat_t ch, int32_t row, int32_t* slot, int32_t* generated);
+/* Teacher-forced scoring: how likely are GIVEN continuations?  B sequences (prompt + continuation each, the arguments of
+ * vr_chat_prefill_batch) run in ONE packed causal pass on the bf16 route; the last cont_len[b] tokens of sequence b are its
+ * continuation, 1 <= cont_len[b] < T_b.  For the continuation token at position p the hidden state of position p - 1 goes
+ * through the final RMSNorm (the chat's scaled weight, as in vr_chat_prefill) and the fused head (csrc/head_score.hip), which
+ * reduces each row's logits x without writing them:
+ *   out_logit      x[token]                         (bf16 x bf16 products, fp32 accumulation)
+ *   out_lse        log sum_{v < vocab_size} exp x[v]    (so log p(token) = out_logit - out_lse, before any penalty)
+ *   out_top_logit  max_v x[v],  out_top_token its id (lowest id among exact ties)
+ * Host arrays, flat [sum_b cont_len[b]], sequence after sequence.  Synchronises the stream.
+ *   Stateless with respect to generation: no slot, row, tail, seen set or logits row is touched; vr_chat_row_len and
+ * vr_chat_logits of every row return what they returned before, a generation in progress continues with the same tokens.
+ * The row and partial buffers are allocated at the first call.
+ *   Checked before any launch, the outputs untouched: a NULL pointer, B < 1, an empty sequence, cont_len out of range, a token
+ * id outside [0, vocab_size): VR_ERR_INVALID; more than the model's max_seqs sequences or max_tokens packed tokens:
+ * VR_ERR_CAPACITY; no head loaded: VR_ERR_STATE. */
+int vr_chat_score(vr_chat_t ch, int32_t B, const uint8_t* const* slices, const int32_t* slice_hw, int32_t n_slices,
+                  int32_t slices_on_device, const int32_t* input_ids, const int32_t* seq_offsets, const int32_t* vision_rows,
+                  const int32_t* cont_len, float* out_logit, float* out_lse, float* out_top_logit, int32_t* out_top_token,
+                  void* stream);
 
 /* ---- index: replaces torch.matmul + torch.topk over pickle shards -------------------- */
 /* Reference: _retrieve_one_shard / distributed_parallel_retrieve
@@ -1151,6 +1170,15 @@ int vr_op_chat_sample(int device_id, const float* logits, int32_t ld, int32_t V,
  * 1..max_len rows, B <= 16; seq_offsets and slots are host arrays, all pointers 16-byte aligned.  Synchronises the stream. */
 int vr_op_chat_prompt_scatter(int device_id, const void* qkv, int32_t ld, int32_t E, int32_t B, const int32_t* seq_offsets,
                               const int32_t* slots, int32_t n_slots, int32_t max_len, void* kplane, void* vplane, void* stream);
+/* vr_chat_score's head (csrc/head_score.hip) on the caller's buffers, all on the device: A bf16 [pad256(M)][lda] (rows >= M
+ * are read, never counted or written), W bf16 [pad256(V)][ldw] (columns >= V never count, whatever they hold), K a multiple
+ * of 64, lda / ldw >= K and multiples of 8, A and W 16-byte aligned; targets int32 [M].  Outputs [M] each as vr_chat_score's;
+ * a target outside [0, V) leaves its out_logit entry unwritten.  No M x V buffer is allocated: the scratch is
+ * 3 * ceil(V / 256) * M words.  M < 1, V < 1 or a NULL pointer: VR_ERR_INVALID; a shape the launcher refuses: VR_ERR_HIP.
+ * Synchronises the stream. */
+int vr_op_head_score(int device_id, const void* A, int32_t lda, const void* W, int32_t ldw, int32_t M, int32_t V, int32_t K,
+                     const int32_t* targets, float* out_logit, float* out_lse, float* out_top_logit, int32_t* out_top_token,
+                     void* stream);
 
 /* ---- the EVisRAG generator's small kernels (csrc/gen_kernels.hip; the model calls them through vg_*, include/visrag_gen.h) ----
  * Thin forwards to the launchers gen.hip / gen_vision.hip call.  The entries check NULL pointers and counts (VR_ERR_INVALID); a

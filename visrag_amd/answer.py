@@ -56,6 +56,13 @@ def answer_weighted_selection(model, tokenizer, msgs, pages: Sequence[Image.Imag
     return model.weighted_selection(list(pages), msgs, list(scores), tokenizer, max_new_tokens=max_new_tokens, sampling=False, **kw)
 
 
+def answer_marginal_selection(model, tokenizer, msgs, pages: Sequence[Image.Image], scores: Sequence[float],
+                              max_new_tokens: int = 20, **kw):
+    """Weighted selection with every candidate answer scored on every page (VisRAGRet.marginal_selection): pages that agree
+    reinforce each other instead of competing.  `pages` and `scores` as top_pages orders them."""
+    return model.marginal_selection(list(pages), msgs, list(scores), tokenizer, max_new_tokens=max_new_tokens, **kw)
+
+
 def answer_page_concatenation(model, tokenizer, msgs, pages: Sequence[Image.Image], kind: str = "horizontal",
                               max_new_tokens: int = 20, sampling: bool = False, **kw) -> str:
     """generate.py's page_concatenation task for one query: one beam-search chat on the concatenated image.  sampling=True:

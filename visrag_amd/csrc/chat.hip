@@ -22,6 +22,9 @@ struct vr_chat_s {
     DevBuf prompt, tails, seen;           // caches; seen-id bit sets [max_rows][words]
     DevBuf w_h, w_xn, w_q, w_att, w_act, w_part, w_po, w_pml, w_logits, w_lse, w_sel, w_out, w_reps, w_move, w_move_seen;
     DevBuf w_pxn;                         // bf16 [2 * CHAT_MAX_ROWS][E]: the normed last rows of a batched prefill (the head reads 16 rows from any of the first 16)
+    // vr_chat_score (allocated at its first call): bf16 [pad256(max_tokens)][k_pad] normed rows, the head's partials,
+    // targets int32 [max_tokens], results 4 x [max_tokens] words, pooled reps of the pass f32 [max_seqs][E] (unused)
+    DevBuf s_xn, s_part, s_tgt, s_out, s_reps;
     std::vector<int> plen;                // per slot: prompt tokens (0 = none)
     std::vector<int> row_slot, row_len;   // per row: its prompt slot (-1 = unbound), generated tokens in its tail
     std::vector<int> lpos;                // per row: its logits row in w_logits (-1 = none)
@@ -467,6 +470,75 @@ extern "C" int vr_chat_logits(vr_chat_t ch, int32_t row, float* out, void* strea
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipMemcpyAsync(out, ch->w_logits.as<float>() + (size_t)ch->lpos[row] * ch->Vpad, (size_t)ch->V * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
+}
+
+// ---- teacher-forced scoring: the packed pass of a prefill without its cache side, every continuation position through the
+// fused head (head_score.hip).  Touches none of the generation state: its rows, targets and results live in buffers of its own.
+extern "C" int vr_chat_score(vr_chat_t ch, int32_t B, const uint8_t* const* slices, const int32_t* slice_hw, int32_t n_slices,
+                             int32_t slices_on_device, const int32_t* input_ids, const int32_t* seq_offsets,
+                             const int32_t* vision_rows, const int32_t* cont_len, float* out_logit, float* out_lse,
+                             float* out_top_logit, int32_t* out_top_token, void* stream) {
+    if (!ch || !input_ids || !seq_offsets || !cont_len || !out_logit || !out_lse || !out_top_logit || !out_top_token)
+        return fail(VR_ERR_INVALID, "NULL argument");
+    if (n_slices > 0 && (!slices || !slice_hw || !vision_rows)) return fail(VR_ERR_INVALID, "NULL slice arguments");
+    if (!ch->head.has_w) return fail(VR_ERR_STATE, "vr_chat_load_head has not run");
+    if (B < 1) return fail(VR_ERR_INVALID, "B must be positive");
+    vr_model_s* w = ch->work;
+    // ---- every check before any launch
+    if (B > w->c.max_seqs) return fail(VR_ERR_CAPACITY, "%d sequences exceed the model's max_seqs=%d", B, w->c.max_seqs);
+    if (seq_offsets[0] != 0) return fail(VR_ERR_INVALID, "seq_offsets[0] must be 0");
+    for (int b = 0; b < B; ++b)
+        if (seq_offsets[b + 1] <= seq_offsets[b]) return fail(VR_ERR_INVALID, "empty sequence %d", b);
+    const int Ttot = seq_offsets[B];
+    if (Ttot > w->c.max_tokens) return fail(VR_ERR_CAPACITY, "%d packed tokens exceed the model's max_tokens=%d", Ttot, w->c.max_tokens);
+    int M = 0;
+    for (int b = 0; b < B; ++b) {
+        const int T = seq_offsets[b + 1] - seq_offsets[b];
+        if (cont_len[b] < 1 || cont_len[b] >= T) return fail(VR_ERR_INVALID, "sequence %d: cont_len %d outside 1..%d", b, cont_len[b], T - 1);
+        M += cont_len[b];
+    }
+    for (int t = 0; t < Ttot; ++t)
+        if (input_ids[t] < 0 || input_ids[t] >= ch->V) return fail(VR_ERR_INVALID, "token id %d out of range at %d", input_ids[t], t);
+    VRCHK(set_dev(ch->model->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int E = ch->E, Kp = ch->head.k_pad, cap = w->c.max_tokens;
+    if (!ch->s_xn.p) {
+        int rc;
+        if ((rc = ch->s_xn.alloc((size_t)pad256(cap) * Kp * 2)) || (rc = ch->s_part.alloc(head_score_part_words(cap, ch->V) * 4)) ||
+            (rc = ch->s_tgt.alloc((size_t)cap * 4)) || (rc = ch->s_out.alloc((size_t)4 * cap * 4)) ||
+            (rc = ch->s_reps.alloc((size_t)w->c.max_seqs * E * 4))) {
+            ch->s_xn.free();
+            return rc;
+        }
+    }
+    EncodeHook hook;
+    hook.bf16_route = true;                              // the route of the prefill; no layer hook: nothing is cached
+    w->arena_open = false;
+    int rc = encode_impl(w, slices, slice_hw, n_slices, slices_on_device, input_ids, seq_offsets, B, vision_rows, ch->s_reps.as<float>(), 1,
+                         stream, nullptr, 0, &hook);
+    arena_close(w, stream);
+    if (rc) return rc;
+    // continuation token at position p: the hidden state of p - 1 -> final RMSNorm (scaled weight); a sequence's rows are adjacent
+    std::vector<int32_t> tgt(M);
+    for (int b = 0, m = 0; b < B; ++b) {
+        const int first = seq_offsets[b + 1] - cont_len[b];          // packed position of the first continuation token
+        HIPCHK(launch_rmsnorm(w->w_h.as<float>() + (size_t)(first - 1) * E, cont_len[b], E, E, ch->norm_w.as<float>(), w->c.rms_norm_eps,
+                              ch->s_xn.as<char>() + (size_t)m * Kp * 2, Kp, s));
+        for (int j = 0; j < cont_len[b]; ++j) tgt[m + j] = input_ids[first + j];
+        m += cont_len[b];
+    }
+    HIPCHK(hipMemcpyAsync(ch->s_tgt.p, tgt.data(), (size_t)M * 4, hipMemcpyHostToDevice, s));
+    float* o = ch->s_out.as<float>();
+    HIPCHK(launch_head_score(ch->s_xn.p, Kp, ch->head.w.p, Kp, M, ch->V, Kp, ch->s_tgt.as<int>(), ch->s_part.p, o, o + cap, o + 2 * (size_t)cap,
+                             (int*)(o + 3 * (size_t)cap), s));
+    std::vector<int32_t> host((size_t)4 * M);
+    for (int a = 0; a < 4; ++a) HIPCHK(hipMemcpyAsync(host.data() + (size_t)a * M, o + (size_t)a * cap, (size_t)M * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    memcpy(out_logit, host.data(), (size_t)M * 4);
+    memcpy(out_lse, host.data() + M, (size_t)M * 4);
+    memcpy(out_top_logit, host.data() + 2 * (size_t)M, (size_t)M * 4);
+    memcpy(out_top_token, host.data() + 3 * (size_t)M, (size_t)M * 4);
     return VR_OK;
 }
 

@@ -82,6 +82,15 @@ hipError_t launch_gemm_skinny(const GemmArgs& a, hipStream_t s, bool swiglu = fa
 hipError_t launch_swiglu_sum(const float* parts, int n_parts, size_t plane_stride, int ldp, int M, int I, void* act, int lda,
                              hipStream_t s);
 
+// ---- fused LM head for scoring (head_score.hip) ------------------------------------------
+// x = A [M][lda] . W [V][ldw]^T over K (bf16, fp32 accumulation; A readable up to pad256(M) rows, W up to pad256(V) rows) is
+// reduced per row without being written: x_t = x[m][target[m]], lse = log sum_{v < V} exp x, top_x / top_id = the largest logit
+// and its token (lowest id among ties).  part: head_score_part_words(M, V) 4-byte words of scratch.  A target outside [0, V)
+// leaves its x_t entry unwritten.  Every pointer is a device pointer.
+size_t head_score_part_words(int M, int V);
+hipError_t launch_head_score(const void* A, int lda, const void* W, int ldw, int M, int V, int K, const int* target, void* part,
+                             float* x_t, float* lse, float* top_x, int* top_id, hipStream_t s);
+
 // ---- norms (norm.hip) --------------------------------------------------------------------
 // x f32 [rows][ldx] (dim used) -> bf16 [rows][ldo]; columns [dim, ldo) are written as zero.
 hipError_t launch_layernorm(const float* x, int rows, int dim, int ldx, const float* w, const float* b,

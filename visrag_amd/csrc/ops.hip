@@ -480,6 +480,24 @@ extern "C" int vr_op_chat_prompt_scatter(int device_id, const void* qkv, int32_t
     return VR_OK;
 }
 
+// grow-only scratch per (device, stream) for the head's partials
+static std::map<std::pair<int, void*>, DevBuf> g_head_score_scratch;
+
+extern "C" int vr_op_head_score(int device_id, const void* A, int32_t lda, const void* W, int32_t ldw, int32_t M, int32_t V,
+                                int32_t K, const int32_t* targets, float* out_logit, float* out_lse, float* out_top_logit,
+                                int32_t* out_top_token, void* stream) {
+    if (!A || !W || !targets || !out_logit || !out_lse || !out_top_logit || !out_top_token) return fail(VR_ERR_INVALID, "NULL argument");
+    if (M < 1 || V < 1) return fail(VR_ERR_INVALID, "need M >= 1 and V >= 1");
+    VRCHK(set_dev(device_id));
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf& sc = g_head_score_scratch[std::make_pair(device_id, stream)];
+    const size_t need = head_score_part_words(M, V) * 4;
+    if (sc.bytes < need) { HIPCHK(hipStreamSynchronize(s)); VRCHK(sc.reserve(need)); }
+    HIPCHK(launch_head_score(A, lda, W, ldw, M, V, K, targets, sc.p, out_logit, out_lse, out_top_logit, out_top_token, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
+}
+
 // ---- the fp32 text path (hp_text.hip) and the encode glue kernels (misc.hip, patch_embed.hip, norm.hip) ---
 // Thin forwards: only NULL pointers are checked here; what a kernel cannot do is the launcher's to refuse (VR_ERR_HIP).
 extern "C" int vr_op_norm_ex(int device_id, int32_t kind, const float* x, int32_t rows, int32_t dim, int32_t ldx, const float* weight,

@@ -23,6 +23,10 @@ Mirrors the reference's `MiniCPMV.generate` / `chat` (src/openmatch/modeling/mod
 * Generation starts from `inputs_embeds` (modeling_minicpmv.py:218-226), so HF starts `input_ids` EMPTY: the repetition
   penalty only ever sees generated tokens, never the prompt.
 
+* scoring (`HipChat.score`, `score_items`, `sequence_score`): the log-probs of GIVEN continuations from one packed
+  teacher-forced pass (vr_chat_score); since the penalty follows the log-softmax, the beam's sequence score of a forced
+  continuation is a host function of per-position (logit, log-sum-exp) alone.
+
 Batches: every item is generated independently — an item's output is a function of the item alone.  The reference
 right-pads a batch (`_process_list(padding_side="right")`) and a shorter item then continues after pad rows of the longer
 ones; that behaviour is NOT reproduced (parity is defined per item).
@@ -367,6 +371,49 @@ class HipChat:
         _lib.check(self.lib.vr_chat_row_len(self._h, int(row), C.byref(s), C.byref(g)), "vr_chat_row_len")
         return int(s.value), int(g.value)
 
+    def score(self, items: Sequence, cont_lens: Sequence[int]) -> List[Dict[str, np.ndarray]]:
+        """Teacher-forced scoring of PreparedItems in ONE packed pass (vr_chat_score): the last cont_lens[b] tokens of item b
+        are its continuation.  Per item dict(logit, lse, top_logit, top_token), numpy [cont_lens[b]]: the logit of each
+        continuation token, the log-sum-exp of its row, the row's largest logit and its token.  Touches no slot, row or
+        logits of a generation in progress.  The caller keeps the batch inside the encoder workspace (max_tokens, max_seqs)."""
+        B, Q = len(items), self.enc.cfg.query_num
+        if B < 1 or B != len(cont_lens):
+            raise ValueError("score needs at least one item and one continuation length per item")
+        ids = np.ascontiguousarray(np.concatenate([np.asarray(it.input_ids, dtype=np.int32) for it in items]))
+        off = np.zeros(B + 1, dtype=np.int32)
+        off[1:] = np.cumsum([len(it.input_ids) for it in items])
+        cl = np.ascontiguousarray(np.asarray([int(c) for c in cont_lens], dtype=np.int32))
+        keep, vrows = [], []
+        for b, it in enumerate(items):
+            n = len(it.slices)
+            keep += [np.ascontiguousarray(s, dtype=np.uint8) for s in it.slices]
+            r = np.full((n, Q), -1, dtype=np.int32)
+            for k, (b0, b1) in enumerate(it.image_bound[:n]):
+                m = max(0, min(Q, b1 - b0))
+                r[k, :m] = int(off[b]) + b0 + np.arange(m, dtype=np.int32)
+            vrows.append(r.reshape(-1))
+        n = len(keep)
+        if n:
+            ptrs = (C.c_void_p * n)(*[C.c_void_p(a.ctypes.data) for a in keep])
+            hw = (C.c_int32 * (2 * n))(*[v for a in keep for v in (a.shape[0], a.shape[1])])
+            vr = np.ascontiguousarray(np.concatenate(vrows))
+            rp = vr.ctypes.data_as(C.POINTER(C.c_int32))
+        else:
+            ptrs, hw, rp = None, None, None
+        M = int(np.clip(cl, 0, None).sum())
+        logit, lse, top = (np.zeros(max(M, 1), dtype=np.float32) for _ in range(3))
+        tok = np.zeros(max(M, 1), dtype=np.int32)
+        p32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_int32))
+        pf = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))
+        _lib.check(self.lib.vr_chat_score(self._h, B, ptrs, hw, n, 0, p32(ids), p32(off), rp, p32(cl), pf(logit), pf(lse), pf(top),
+                                          p32(tok), self._stream()), "vr_chat_score")
+        out, m = [], 0
+        for c in cl.tolist():
+            out.append({"logit": logit[m:m + c].copy(), "lse": lse[m:m + c].copy(), "top_logit": top[m:m + c].copy(),
+                        "top_token": tok[m:m + c].copy()})
+            m += c
+        return out
+
 
 # what HF generate would accept but this generator does not implement: refused rather than silently dropped
 _NEUTRAL = {"top_p": 1.0, "length_penalty": 1.0, "min_new_tokens": 0, "no_repeat_ngram_size": 0,
@@ -502,3 +549,65 @@ def _generate_chunk(chat, items, max_new, nb, do_sample, pen, temp, top_k, seed,
             except StopIteration as stop:
                 results[i], reqs[i] = stop.value, None
     return results
+
+
+# ------------------------------------------------------------------------------------------ scoring ---
+def sequence_score(token_logprobs, tokens: Sequence[int], repetition_penalty: float = 1.0, length_penalty: float = 1.0,
+                   return_sum: bool = False):
+    """The beam's sequence score of a forced continuation from its per-token log-probs (pure numpy, fp64).  HF's order:
+    log-softmax first, then the repetition penalty on the ids generated SO FAR — the log-prob of tokens[t] is multiplied by
+    the penalty iff that id occurs in tokens[:t] (log-probs are <= 0: the `negative score * penalty` branch).  The sum is
+    divided by len(tokens) ** length_penalty: the score `beam_rule` / `_Hyps.add` gives a hypothesis whose output ids, eos
+    included, are `tokens`.  return_sum=True -> (score, penalised sum)."""
+    lp = np.asarray(token_logprobs, dtype=np.float64).reshape(-1)
+    toks = [int(t) for t in tokens]
+    if len(toks) != lp.shape[0] or not toks:
+        raise ValueError("sequence_score needs one log-prob per token and at least one token")
+    if not repetition_penalty > 0:
+        raise ValueError("repetition_penalty must be positive")
+    seen, total = set(), 0.0
+    for t, x in zip(toks, lp.tolist()):
+        total += x * float(repetition_penalty) if t in seen else x
+        seen.add(t)
+    score = total / (len(toks) ** float(length_penalty))
+    return (score, total) if return_sum else score
+
+
+def score_items(chat, items: Sequence, continuations: Sequence[Sequence[int]], repetition_penalty: float = 1.0,
+                length_penalty: float = 1.0) -> List[Dict]:
+    """How likely is continuations[i] after the prompt items[i]?  Every (prompt + continuation) runs as one sequence of a
+    packed causal pass (`chat.score`; as many passes as `prefill_groups` cuts the batch into), every continuation position
+    through the fused head.  Per item {"token_logprobs": fp64 logit - lse per token (no penalty), "sum": their sum with the
+    repetition penalty of `sequence_score`, "score": sum / len ** length_penalty, "greedy_match": per position whether the
+    token is the row's argmax, "top_tokens": that argmax}.  Sampling warpers (temperature, top-k, top-p) have no part in it."""
+    from dataclasses import replace
+    items, conts = list(items), [[int(t) for t in c] for c in continuations]
+    if len(items) != len(conts):
+        raise ValueError(f"{len(items)} items but {len(conts)} continuations")
+    for i, c in enumerate(conts):
+        if not c:
+            raise ValueError(f"continuation {i} is empty")
+    full = [replace(it, input_ids=[int(t) for t in it.input_ids] + c) for it, c in zip(items, conts)]
+    out: List[Dict] = []
+    for g in prefill_groups([len(it.input_ids) for it in full], chat.enc.max_tokens, chat.enc.max_seqs):
+        res = chat.score([full[i] for i in g], [len(conts[i]) for i in g])
+        for i, r in zip(g, res):
+            lp = np.asarray(r["logit"], dtype=np.float64) - np.asarray(r["lse"], dtype=np.float64)
+            score, total = sequence_score(lp, conts[i], repetition_penalty, length_penalty, return_sum=True)
+            top = np.asarray(r["top_token"], dtype=np.int64)
+            out.append({"token_logprobs": lp, "sum": total, "score": score,
+                        "greedy_match": top == np.asarray(conts[i], dtype=np.int64), "top_tokens": top})
+    return out
+
+
+def marginal_weights(S, doc_scores):
+    """RAG-Sequence marginalisation over pages: S[a][i] = score of candidate answer a on page i, p = softmax(doc_scores) in
+    fp64 (select_weighted's), weight[a] = sum_i p_i * exp(S[a][i]).  -> (index of the first largest weight, weights, p)."""
+    S = np.asarray(S, dtype=np.float64)
+    d = np.asarray(doc_scores, dtype=np.float64)
+    if S.ndim != 2 or S.shape[0] < 1 or S.shape[1] != d.shape[0] or d.shape[0] < 1:
+        raise ValueError("marginal_weights needs S [answers][pages] and one doc score per page")
+    e = np.exp(d - d.max())
+    p = e / e.sum()
+    weights = [float(np.sum(p * np.exp(S[a]))) for a in range(S.shape[0])]
+    return weights.index(max(weights)), weights, p.tolist()

@@ -383,6 +383,79 @@ class VisRAGRet:
         return answers[index], {"answers": answers, "scores": [[sc for sc, _ in r["hyps"]] for r in res], "weights": weights,
                                 "doc_probs": p, "index": index, "tokens": [r["tokens"] for r in res], "results": res}
 
+    # ---- answer scoring: teacher-forced log-probs of GIVEN answers (vr_chat_score, the fused head of csrc/head_score.hip) ---
+    def _scoring_chat(self, what: str):
+        if getattr(self, "_chat", None) is None:
+            raise RuntimeError(f"{what}() needs an LM head: call attach_generator() first (or load_generator())")
+        return self._chat
+
+    def score_answers(self, image_list, msgs_list, answers_list, tokenizer, max_inp_length: int = 2048, append_eos: bool = True,
+                      repetition_penalty: float = 1.0, length_penalty: float = 1.0):
+        """How likely is each given answer after (page, question)?  Prompts are built as chat(assistant_turn=True) builds
+        them; every answer of answers_list[i] is tokenised without BOS (append_eos: followed by the eos the generator would
+        close it with) and scored on item i in a packed teacher-forced pass.  Returns per item the list of
+        `generation.score_items` dicts of its answers (token_logprobs, sum, score, greedy_match, top_tokens).  The
+        penalties are those of `generation.sequence_score`; sampling warpers have no part in it."""
+        from .generation import score_items
+        chat = self._scoring_chat("score_answers")
+        image_list, msgs_list, answers_list = list(image_list), list(msgs_list), [list(a) for a in answers_list]
+        if not (len(image_list) == len(msgs_list) == len(answers_list)):
+            raise ValueError(f"{len(image_list)} images, {len(msgs_list)} message lists and {len(answers_list)} answer lists")
+        items, conts, owner = [], [], []
+        for i, (msgs, image, answers) in enumerate(zip(msgs_list, image_list, answers_list)):
+            p, imgs = chat_prompt(msgs, image, tokenizer, self.config)
+            item = _prompt_item(p + "<AI>", imgs, tokenizer, max_inp_length)
+            for a in answers:
+                items.append(item); conts.append(answer_ids(a, tokenizer, append_eos)); owner.append(i)
+        out = [[] for _ in answers_list]
+        if items:
+            for i, r in zip(owner, score_items(chat, items, conts, repetition_penalty, length_penalty)):
+                out[i].append(r)
+        return out
+
+    def choose(self, image, msgs, options, tokenizer, normalise: bool = True, **kwargs):
+        """Multiple choice: score every option as an answer to (image, msgs) and take the best -> (index, scores).  The
+        argmax is over `score` (the length-normalised sum) when normalise is true, over `sum` otherwise; the first option wins
+        among equals.  kwargs: score_answers' (max_inp_length, append_eos, repetition_penalty, length_penalty)."""
+        options = list(options)
+        if not options:
+            raise ValueError("choose needs at least one option")
+        scores = self.score_answers([image], [msgs], [options], tokenizer, **kwargs)[0]
+        keys = [float(s["score" if normalise else "sum"]) for s in scores]
+        return keys.index(max(keys)), scores
+
+    def marginal_selection(self, image_list, msgs, doc_scores, tokenizer, normalise: bool = True, details: bool = False, **kwargs):
+        """Weighted selection in its RAG-Sequence form: weighted_selection's generation as it is, then every candidate answer
+        (the distinct output id lists of the pages' best hypotheses, in first-seen order) is scored on EVERY page —
+        S[a][i] = score_items of candidate a on page i under the beam's repetition_penalty (`score` when normalise is true,
+        `sum` otherwise) — and weight[a] = sum_i softmax(doc_scores)_i * exp(S[a][i]) in fp64.  The answer is the first
+        largest weight: two pages that agree reinforce each other where weighted selection lets them compete.
+        details=True -> (answer, {"S", "weights", "candidates", "index", "doc_probs", "answers": per candidate,
+        "weighted_selection": (answer, details) of the plain selection}).  kwargs: weighted_selection's."""
+        from .generation import chat_generation_config, decode_text, marginal_weights, score_items
+        chat = self._scoring_chat("marginal_selection")
+        image_list = list(image_list)
+        ws_answer, ws = self.weighted_selection(image_list, msgs, doc_scores, tokenizer, details=True, **kwargs)
+        candidates = []
+        for toks in ws["tokens"]:
+            if list(toks) not in candidates:
+                candidates.append(list(toks))
+        items = []
+        for image in image_list:
+            p, imgs = chat_prompt(msgs, image, tokenizer, self.config)
+            items.append(_prompt_item(p + "<AI>", imgs, tokenizer, kwargs.get("max_inp_length", 2048)))
+        pen = chat_generation_config(False, kwargs)["repetition_penalty"]
+        n = len(items)
+        res = score_items(chat, [it for _ in candidates for it in items], [c for c in candidates for _ in items], pen, 1.0)
+        key = "score" if normalise else "sum"
+        S = [[float(res[a * n + i][key]) for i in range(n)] for a in range(len(candidates))]
+        index, weights, p = marginal_weights(S, [float(x) for x in doc_scores])
+        answers = decode_text(candidates, tokenizer)
+        if not details:
+            return answers[index]
+        return answers[index], {"S": S, "weights": weights, "candidates": candidates, "index": index, "doc_probs": p,
+                                "answers": answers, "weighted_selection": (ws_answer, ws)}
+
 
 def select_weighted(seq_scores, doc_scores):
     """-> (index, weights, p): p = softmax(doc_scores) in fp64, weights[i] = p[i] * exp(seq_scores[i]), index = the first
@@ -435,6 +508,19 @@ def _prompt_item(text, images, tokenizer, max_inp_length):
     bound = [(int(s), int(e)) for s, e in zip(starts, ends)]
     slices = [np.asarray(im if im.mode == "RGB" else im.convert("RGB"), dtype=np.uint8) for im in images]
     return PreparedItem(input_ids=ids, image_bound=bound, slices=slices)
+
+
+def answer_ids(text: str, tokenizer, append_eos: bool = True) -> List[int]:
+    """An answer's token ids as the generator would emit them: no BOS (the tokenizer's own leading bos is dropped, none is
+    added), no eos of the tokenizer's (add_eos_token), then one eos when append_eos.  An answer without a token: ValueError."""
+    ids = [int(t) for t in tokenizer.encode(text)]
+    if getattr(tokenizer, "add_bos_token", True) and ids and ids[0] == tokenizer.bos_id:
+        ids = ids[1:]
+    if getattr(tokenizer, "add_eos_token", False) and ids and ids[-1] == tokenizer.eos_id:
+        ids = ids[:-1]
+    if not ids:
+        raise ValueError(f"answer {text!r} holds no token")
+    return ids + [int(tokenizer.eos_id)] if append_eos else ids
 
 
 def load_generator(path: str, device=None, **cache) -> "VisRAGRet":
