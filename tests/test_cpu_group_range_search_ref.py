@@ -230,5 +230,7 @@ def test_the_three_symbols_are_declared_in_every_layer():
     assert callable(demo.retrieve_documents_above) and callable(retriever.retrieve_documents_range) and callable(split_document_ranges)
     # the row loop of the document rank search is shared, not copied
     csrc = os.path.join(root, "visrag_amd", "csrc")
-    defs = [f for f in sorted(os.listdir(csrc)) if "uint64_t group_rank_best(" in open(os.path.join(csrc, f)).read()]
-    assert defs == ["search_band.h"]
+    defs = [f for f in sorted(os.listdir(csrc)) if "uint64_t group_best_row(" in open(os.path.join(csrc, f)).read()]
+    assert defs == ["search_rescore.h"]
+    walks = [f for f in sorted(os.listdir(csrc)) if f.startswith("search_") and "__ffsll" in open(os.path.join(csrc, f)).read()]
+    assert walks == ["search_rescore.h", "search_select.h"]              # (search_select.h: select_kth's bin scan)

@@ -150,27 +150,4 @@ __device__ __forceinline__ int band_pass_in_place(const SearchArgs& p, int q, fl
     return n_band;
 }
 
-// ---- a document's band rows (search_group_rank.hip, search_group_range.hip) ----
-// (E_g, best row) of group rows [glo, ghi) as a key: every row with b >= lim re-scored in fp32 by the whole wave, the largest
-// make_key(e, row) kept; *dots += rows re-scored.  The row that attains B_g passes lim: the result is a key.
-__device__ __forceinline__ uint64_t group_rank_best(const SearchArgs& a, const f32x4 (&qv)[MERGE_MAXV], const float* srow, int glo,
-                                                    int ghi, float lim, int nv, int lane, unsigned* dots) {
-    uint64_t best = KEY_NONE;
-    for (int i0 = glo; i0 < ghi; i0 += 64) {
-        const int i = i0 + lane;
-        unsigned long long in = __ballot(i < ghi && srow[i] >= lim);
-        *dots += (unsigned)__popcll(in);
-        while (in) {                                                       // (wave-uniform)
-            const int id = i0 + __ffsll((long long)in) - 1;
-            in &= in - 1ull;
-            f32x4 dv[MERGE_MAXV];
-            load_row_regs(dv, a.index_f32 + (size_t)id * a.dim, nv, lane);
-            const float s = wave_sum(dot_regs(qv, dv, nv, lane));
-            const uint64_t key = make_key(s, (uint32_t)id);
-            best = key > best ? key : best;
-        }
-    }
-    return best;
-}
-
 }  // namespace vr

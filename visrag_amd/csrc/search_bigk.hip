@@ -29,56 +29,30 @@ int search_bigk_max() { return SEL_CAND - SEL_MARGIN; }
 __global__ __launch_bounds__(256) void bigk_select_kernel(SearchArgs p, const float* __restrict__ S, size_t ldS, int kp_want,
                                                           int exact, int sub, int max_slots) {
     __shared__ SelectLds L;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     // exact: a fixed grid walks entries [sub, sub + max_slots) of the flag list
     const int n_slots = exact ? flag_slots(p.flag_count, sub, max_slots) : (int)gridDim.x;
     for (int slot = blockIdx.x; slot < n_slots; slot += gridDim.x) {
     const int q = exact ? p.flag_list[sub + slot] : slot;
     const float* row = S + (size_t)slot * ldS;
     const int n_docs = (int)p.n_docs, k = p.k, dim = p.dim;
-    int kp = min(n_docs, kp_want);
     __syncthreads();                                                    // (LDS of the previous slot is free)
 
-    // ---- 2. the kp best bf16 scores' rows in row order (search_select.h)
-    const KthKey kth = select_kth<true>(row, n_docs, kp, L);       // (a NaN score sorts last: never a candidate before a number)
-    const unsigned T = kth.T;
-    gather_ordered<true>(row, n_docs, T, kp - kth.need_eq, kth.need_eq, SEL_CAND, L);
-    // ---- 3. exact fp32 re-scoring, sort
+    // ---- 2.-4. candidates, exact fp32 re-scoring, certification (search_select.h: certified_select; rows outside the re-scored
+    // set have a bf16 score <= the K'-th).  A NaN score sorts last: never a candidate before a number, and never ranks.
+    int kp = min(n_docs, kp_want);
+    const KthKey kth = top_positions<true>(row, n_docs, kp, L);
     const int nv = dim >> 2;
     f32x4 qv[MERGE_MAXV];
     load_query_regs(qv, p.q_f32 + (size_t)q * dim, nv, lane);
-    auto rescore_sort = [&](int m) {
-        int n2 = 1;
-        while (n2 < m) n2 <<= 1;
-        for (int c = m + tid; c < n2; c += 256) L.keys[c] = KEY_NONE;
-        for (int c = wave; c < m; c += 4) {
-            const int id = L.cand[c];
-            const float a = wave_sum(dot_lane(qv, p.index_f32 + (size_t)id * dim, nv, lane));
-            if (lane == 0) L.keys[c] = make_key_ranked(a, (uint32_t)id);
-        }
-        __syncthreads();
-        block_bitonic_desc(L.keys, n2, tid, 256);
-    };
-    rescore_sort(kp);
-    // ---- 4. certification (rows outside the re-scored set have a bf16 score <= T's)
-    if (!exact && (p.eps_data || p.eps_rel >= 0.f)) {
-        int what = 0;
-        float tau = -INFINITY;
-        // (fewer than k numbers among the re-scored kp: NaN scores sort last, so the candidates hold EVERY row that ranks — a NaN
-        // query, or an index with fewer than k rows free of NaN — and the result stands as it is)
-        if (kp < n_docs && L.keys[k - 1] != KEY_NONE) {
-            const float eps = query_eps(p, qv);
-            tau = key_score(L.keys[k - 1]) - eps;                       // kp >= k here (kp < n_docs => kp = k + margin)
-            if (!(orderable_f32(T) < tau)) {
-                // every row whose bf16 score is >= tau (strictly above the key just below tau's)
-                __syncthreads();
-                const unsigned tk = f32_orderable(tau);
-                const int m = gather_ordered<true>(row, n_docs, tk ? tk - 1u : 0u, 0, 0, SEL_CAND, L);
-                __syncthreads();
-                if (m <= SEL_CAND && m >= kp) { rescore_sort(m); kp = m; what = 1; }
-                else what = 2;
-            }
-        }
+    const bool certify = !exact && (p.eps_data || p.eps_rel >= 0.f);
+    int what;
+    float tau;
+    kp = certified_select<true, false>(
+        row, n_docs, n_docs, kp, kth.T, k, certify,
+        [&](int id) { return make_key_ranked(wave_sum(dot_lane(qv, p.index_f32 + (size_t)id * dim, nv, lane)), (uint32_t)id); },
+        [&] { return query_eps(p, qv); }, L, &what, &tau);
+    if (certify) {
         if (tid == 0 && p.stats) atomicAdd(&p.stats[what], 1u);
         __syncthreads();
         flag_query(p, q, what == 2, tau, &L.rank);

@@ -28,6 +28,9 @@ __device__ __forceinline__ float one_ulp_up(float x) {
     const uint32_t o = f32_orderable(x);
     return o != 0xFFFFFFFFu ? orderable_f32(o + 1u) : x;
 }
+// the edges of a band of bf16 scores around v: what lies within 2 eps of it, rounded outward
+__device__ __forceinline__ float band_lo(float v, float eps) { return one_ulp_down(v - 2.f * eps); }
+__device__ __forceinline__ float band_hi(float v, float eps) { return one_ulp_up(v + 2.f * eps); }
 // sort key: larger key = better candidate (higher score, then LOWER id)
 __device__ __forceinline__ uint64_t make_key(float score, uint32_t id) {
     return ((uint64_t)f32_orderable(score) << 32) | (uint32_t)(~id);
@@ -105,7 +108,7 @@ __device__ __forceinline__ float dot_lane(const f32x4 (&qv)[MERGE_MAXV], const f
     return a;
 }
 // The same chain with the row in registers: a kernel that wants every load of a row out before the first fma waits for one
-// loads it with load_row_regs and runs dot_regs over it (search_rank.hip, search_window.hip, search_band.h).  search_multi.hip's
+// loads it with load_row_regs and runs dot_regs over it (exact_row_score below, search_band.h).  search_multi.hip's
 // multi_fused_score holds the row in registers and reads its queries from memory: dot_regs does not fit it, its chain is this one.
 __device__ __forceinline__ void load_row_regs(f32x4 (&dv)[MERGE_MAXV], const float* row, int nv, int lane) {
     load_query_regs(dv, row, nv, lane);
@@ -119,11 +122,20 @@ __device__ __forceinline__ float dot_regs(const f32x4 (&qv)[MERGE_MAXV], const f
     }
     return a;
 }
+// the fp32 score of index row `id` for the query the wave holds in qv, the row's loads in front of the fma chain; called by a
+// whole wave, every lane gets the score
+__device__ __forceinline__ float exact_row_score(const SearchArgs& a, const f32x4 (&qv)[MERGE_MAXV], int id, int nv, int lane) {
+    f32x4 dv[MERGE_MAXV];
+    load_row_regs(dv, a.index_f32 + (size_t)id * a.dim, nv, lane);
+    return wave_sum(dot_regs(qv, dv, nv, lane));
+}
 
+// a filter entry that names rows: -1 (all of them) or a filter of the store; anything else allows nothing
+__device__ __forceinline__ bool filter_index_ok(int f, int n_filters) { return f == -1 || (unsigned)f < (unsigned)n_filters; }
 // rows a query on filter f may see: all of them (-1), the filter's count, or none (an entry outside [-1, n_filters)); a caller
 // without a filter array passes -1
 __device__ __forceinline__ int rows_allowed(int64_t n_docs, int n_filters, const int* allowed, int f) {
-    return f == -1 ? (int)n_docs : ((unsigned)f < (unsigned)n_filters ? allowed[f] : 0);
+    return f == -1 ? (int)n_docs : (filter_index_ok(f, n_filters) ? allowed[f] : 0);
 }
 
 // Column `col` of every lane with `in` set goes on the LDS candidate list cand[0, *n_cand), in no particular order: one atomic

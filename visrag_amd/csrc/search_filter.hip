@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void filter_mask_kernel(float* __restrict__ S,
 __global__ __launch_bounds__(256) void filter_select_kernel(FilterSearchArgs p, const float* __restrict__ S, size_t ldS,
                                                             int kp_want, int exact, int sub, int max_slots) {
     __shared__ SelectLds L;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     const SearchArgs& a = p.a;
     const int n_slots = exact ? flag_slots(a.flag_count, sub, max_slots) : (int)gridDim.x;
     for (int slot = blockIdx.x; slot < n_slots; slot += gridDim.x) {
@@ -90,7 +90,6 @@ __global__ __launch_bounds__(256) void filter_select_kernel(FilterSearchArgs p, 
     const float* row = S + (size_t)slot * ldS;
     const int n_docs = (int)a.n_docs, k = a.k, dim = a.dim;
     const int na = rows_allowed(a.n_docs, p.n_filters, p.allowed, p.filter_of_query[q]);    // (workgroup-uniform)
-    int kp = min(na, kp_want);
     __syncthreads();                                                    // (LDS of the previous slot is free)
     if (na == 0) {                                                      // nothing allowed: k empty slots, certified
         for (int c = tid; c < k; c += 256) emit_slot(a, q, c, KEY_NONE);
@@ -98,44 +97,22 @@ __global__ __launch_bounds__(256) void filter_select_kernel(FilterSearchArgs p, 
         continue;
     }
 
-    // ---- 3a. the kp best masked bf16 scores' rows in row order (search_select.h): kp <= na, so T is a finite score
-    const KthKey kth = select_kth(row, n_docs, kp, L);
-    const unsigned T = kth.T;
-    gather_ordered(row, n_docs, T, kp - kth.need_eq, kth.need_eq, SEL_CAND, L);
-    // ---- 3b. exact fp32 re-scoring, sort
+    // ---- 3. candidates among the masked row (K' <= na, so the K'-th is a finite score and no masked column is gathered),
+    // exact fp32 re-scoring, certification (search_select.h: certified_select with na in the place of the row count; an allowed
+    // row outside the re-scored set has a bf16 score <= the K'-th; K' == na: there is none)
+    int kp = min(na, kp_want);
+    const KthKey kth = top_positions(row, n_docs, kp, L);
     const int nv = dim >> 2;
     f32x4 qv[MERGE_MAXV];
     load_query_regs(qv, a.q_f32 + (size_t)q * dim, nv, lane);
-    auto rescore_sort = [&](int m) {
-        int n2 = 1;
-        while (n2 < m) n2 <<= 1;
-        for (int c = m + tid; c < n2; c += 256) L.keys[c] = KEY_NONE;
-        for (int c = wave; c < m; c += 4) {
-            const int id = L.cand[c];
-            const float s = wave_sum(dot_lane(qv, a.index_f32 + (size_t)id * dim, nv, lane));
-            if (lane == 0) L.keys[c] = make_key(s, (uint32_t)id);
-        }
-        __syncthreads();
-        block_bitonic_desc(L.keys, n2, tid, 256);
-    };
-    rescore_sort(kp);
-    // ---- 3c. certification (an allowed row outside the re-scored set has a bf16 score <= T's; kp == na: there is none)
-    if (!exact && p.certify) {
-        int what = 0;
-        if (kp < na) {
-            const float eps = query_eps(a, qv);
-            const float tau = one_ulp_down(key_score(L.keys[k - 1]) - eps);  // kp >= k here (kp < na => kp = k + margin)
-            if (!(orderable_f32(T) < tau)) {
-                // every allowed row whose bf16 score is >= tau (strictly above the key just below tau's; tau is finite,
-                // the masked columns are not)
-                __syncthreads();
-                const unsigned tk = f32_orderable(tau);
-                const int m = gather_ordered(row, n_docs, tk ? tk - 1u : 0u, 0, 0, SEL_CAND, L);
-                __syncthreads();
-                if (m <= SEL_CAND && m >= kp) { rescore_sort(m); kp = m; what = 1; }
-                else what = 2;
-            }
-        }
+    const bool certify = !exact && p.certify;
+    int what;
+    float tau;
+    kp = certified_select<false, true>(
+        row, n_docs, na, kp, kth.T, k, certify,
+        [&](int id) { return make_key(wave_sum(dot_lane(qv, a.index_f32 + (size_t)id * dim, nv, lane)), (uint32_t)id); },
+        [&] { return query_eps(a, qv); }, L, &what, &tau);
+    if (certify) {
         if (tid == 0) atomicAdd(&p.stats[what], 1u);
         __syncthreads();
         flag_query(a, q, what == 2, 0.f, &L.rank);

@@ -17,7 +17,7 @@
 #include <algorithm>
 
 #include "kernels.h"
-#include "search_select.h"
+#include "search_rescore.h"
 
 namespace vr {
 
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void group_max_kernel(const float* __restrict_
 __global__ __launch_bounds__(256) void group_select_kernel(GroupSearchArgs p, const float* __restrict__ S, size_t ldS,
                                                            int kp_want, int exact, int sub, int max_slots) {
     __shared__ SelectLds L;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     const SearchArgs& a = p.a;
     const int n_slots = exact ? flag_slots(a.flag_count, sub, max_slots) : (int)gridDim.x;
     for (int slot = blockIdx.x; slot < n_slots; slot += gridDim.x) {
@@ -71,60 +71,25 @@ __global__ __launch_bounds__(256) void group_select_kernel(GroupSearchArgs p, co
     const float* srow = S + (size_t)slot * ldS;
     const float* brow = p.B + (size_t)slot * p.ldB;
     const int n_groups = p.n_groups, k = a.k, dim = a.dim;
-    int kp = min(n_groups, kp_want);
     __syncthreads();                                                    // (LDS of the previous slot is free)
 
-    // ---- 3a. the kp largest group maxima's groups in group order (search_select.h)
-    const KthKey kth = select_kth(brow, n_groups, kp, L);
-    const unsigned T = kth.T;
-    gather_ordered(brow, n_groups, T, kp - kth.need_eq, kth.need_eq, SEL_CAND, L);
-    // ---- 3b. per candidate group: exact fp32 score of every row that can be the group's best; sort the groups' keys
+    // ---- 3. candidate groups by B, per candidate the exact fp32 score of every row that can be the group's best, certification
+    // (search_select.h: certified_select with groups in the place of rows; a group outside the re-scored set has B <= the K'-th)
+    int kp = min(n_groups, kp_want);
+    const KthKey kth = top_positions(brow, n_groups, kp, L);
     const int nv = dim >> 2;
     f32x4 qv[MERGE_MAXV];
     load_query_regs(qv, a.q_f32 + (size_t)q * dim, nv, lane);
     const float eps = exact ? 0.f : query_eps(a, qv);
-    const float band = 2.f * eps;
-    auto rescore_sort = [&](int m) {
-        int n2 = 1;
-        while (n2 < m) n2 <<= 1;
-        for (int c = m + tid; c < n2; c += 256) L.keys[c] = KEY_NONE;
-        for (int c = wave; c < m; c += 4) {                              // one wave per candidate group
-            const int g = L.cand[c];
-            const int lo = p.goff[g], hi = p.goff[g + 1];
-            const float lim = one_ulp_down(brow[g] - band);               // (the subtraction may have rounded up)
-            uint64_t best = KEY_NONE;
-            for (int i0 = lo; i0 < hi; i0 += 64) {
-                const int i = i0 + lane;
-                unsigned long long in = __ballot(i < hi && srow[i] >= lim);
-                while (in) {                                             // (wave-uniform)
-                    const int id = i0 + __ffsll((long long)in) - 1;
-                    in &= in - 1ull;
-                    const float s = wave_sum(dot_lane(qv, a.index_f32 + (size_t)id * dim, nv, lane));
-                    const uint64_t key = make_key(s, (uint32_t)id);
-                    best = key > best ? key : best;
-                }
-            }
-            if (lane == 0) L.keys[c] = best;
-        }
-        __syncthreads();
-        block_bitonic_desc(L.keys, n2, tid, 256);
-    };
-    rescore_sort(kp);
-    // ---- 3c. certification (a group outside the re-scored set has B <= T's score)
-    if (!exact && p.certify) {
-        int what = 0;
-        if (kp < n_groups) {
-            const float tau = one_ulp_down(key_score(L.keys[k - 1]) - eps);  // kp >= k here (kp < n_groups => kp = k + margin)
-            if (!(orderable_f32(T) < tau)) {
-                // every group whose B is >= tau (strictly above the key just below tau's)
-                __syncthreads();
-                const unsigned tk = f32_orderable(tau);
-                const int m = gather_ordered(brow, n_groups, tk ? tk - 1u : 0u, 0, 0, SEL_CAND, L);
-                __syncthreads();
-                if (m <= SEL_CAND && m >= kp) { rescore_sort(m); kp = m; what = 1; }
-                else what = 2;
-            }
-        }
+    const bool certify = !exact && p.certify;
+    unsigned dots = 0;                                                  // (not counted here)
+    int what;
+    float tau;
+    kp = certified_select<false, true>(
+        brow, n_groups, n_groups, kp, kth.T, k, certify,
+        [&](int g) { return group_best_row(a, qv, srow, p.goff[g], p.goff[g + 1], band_lo(brow[g], eps), nv, lane, &dots); },
+        [&] { return eps; }, L, &what, &tau);
+    if (certify) {
         if (tid == 0) atomicAdd(&p.stats[what], 1u);
         __syncthreads();
         flag_query(a, q, what == 2, 0.f, &L.rank);

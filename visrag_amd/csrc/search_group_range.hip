@@ -24,9 +24,9 @@
 //      -inf; group_max_kernel (search_group.hip, as it is) gives B[q][g] in a buffer of this search's own, -inf for a group
 //      without an allowed row;
 //   2. group_range_rescore_kernel, grid (chunk of 4096 groups, query): eps from the query in registers, bound = one_ulp_down(t -
-//      eps).  The groups with B_g >= bound are compacted into an LDS list (band_append) and re-scored one group per wave with the
-//      row loop of the document rank search (search_band.h: group_rank_best): the wave walks the group's rows 64 at a time,
-//      ballots b_i >= one_ulp_down(B_g - 2 eps) and gives each such row one fp32 dot, the row's loads in front of the fma chain.
+//      eps).  The groups with B_g >= bound are compacted into an LDS list (search_rescore.h: chunk_scan) and re-scored one
+//      group per wave by group_best_row: the wave walks the group's rows 64 at a time, ballots b_i >= one_ulp_down(B_g - 2 eps)
+//      and gives each such row one fp32 dot, the row's loads in front of the fma chain.
 //      The result goes back IN PLACE: B[g] = E_g where E_g >= t, -inf where not, the best row into the int32 side row R[q][g].  A
 //      group below the bound keeps its B < t, an absent group its -inf: from here on "B[q][g] >= t" is exactly membership and the
 //      stored value is the score to return.  Kept groups are counted per 1024 groups (a wave's share of the pack).  A band column
@@ -42,78 +42,49 @@
 // No kernel waits for another workgroup; stream order between the launches is the only ordering.  No kernel reads a B or R
 // column at or past n_groups, or an S column at or past n_docs.  S is only read.
 #include "kernels.h"
-#include "search_band.h"
+#include "search_rescore.h"
 
 namespace vr {
 
-constexpr int GRNG_CHUNK = 4096;            // groups per workgroup (the document window and rank searches' chunk): a 16 KB list
-constexpr int GRNG_SUB = 1024;              // groups per wave of the pack = granularity of the counts and the scan (range_scan_slots)
-constexpr int GRNG_SUBS = GRNG_CHUNK / GRNG_SUB;
-
-struct GroupRangeLds {
-    int cand[GRNG_CHUNK];                   // groups inside the band, any order
-    int n_cand;
-    int kept[GRNG_SUBS];
-    unsigned long long dots;                // fp32 row dots of this workgroup
-};
-
-// the threshold of query q, or NaN for a query that gets an empty segment (workgroup-uniform)
-__device__ __forceinline__ float group_range_threshold(const GroupRangeArgs& p, int q) {
-    const float t = p.thresholds[q];
-    const int f = p.filter_of_query ? p.filter_of_query[q] : -1;
-    const bool ok = t == t && fabsf(t) != INFINITY && (f == -1 || (unsigned)f < (unsigned)p.n_filters);
-    return ok ? t : __builtin_nanf("");
-}
-
 __global__ __launch_bounds__(256) void group_range_rescore_kernel(GroupRangeArgs p, const float* __restrict__ S, size_t ldS,
                                                                   int* __restrict__ counts) {
-    __shared__ GroupRangeLds L;
+    __shared__ ChunkLds L;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const SearchArgs& a = p.a;
     const int q = blockIdx.y, ng = p.n_groups, nv = a.dim >> 2;
-    const int c0 = blockIdx.x * GRNG_CHUNK, c1 = min(c0 + GRNG_CHUNK, ng);
-    const int64_t nsub = ((int64_t)ng + GRNG_SUB - 1) / GRNG_SUB;
-    int* cnt = counts + (size_t)q * nsub + (size_t)blockIdx.x * GRNG_SUBS;
-    const int my_subs = (c1 - c0 + GRNG_SUB - 1) / GRNG_SUB;               // 1..4 counts belong to this workgroup
+    const int c0 = blockIdx.x * RESCORE_CHUNK, c1 = min(c0 + RESCORE_CHUNK, ng);
+    const int64_t nsub = ((int64_t)ng + RESCORE_SUB - 1) / RESCORE_SUB;
+    int* cnt = counts + (size_t)q * nsub + (size_t)blockIdx.x * RESCORE_SUBS;
+    const int my_subs = (c1 - c0 + RESCORE_SUB - 1) / RESCORE_SUB;         // 1..4 counts belong to this workgroup
     if (blockIdx.x == 0 && tid == 0) atomicAdd(&p.stats[0], 1ull);
-    const float t = group_range_threshold(p, q);
+    const float t = range_threshold(p.thresholds, p.filter_of_query, p.n_filters, q);
     if (t != t) {                                                          // (workgroup-uniform) an empty segment
         if (tid < my_subs) cnt[tid] = 0;
         return;
     }
-    if (tid == 0) { L.n_cand = 0; L.dots = 0ull; }
-    if (tid < GRNG_SUBS) L.kept[tid] = 0;
     f32x4 qv[MERGE_MAXV];
     load_query_regs(qv, a.q_f32 + (size_t)q * a.dim, nv, lane);
     const float eps = query_eps(a, qv);                                    // (every wave computes the same value)
     const float bound = one_ulp_down(t - eps);                             // (the subtraction may have rounded up)
-    __syncthreads();
     // ---- the band: groups with B >= bound (an absent group is -inf, the bound is finite)
     float* brow = p.B + (size_t)q * p.ldB;
-    for (int g0 = c0; g0 < c1; g0 += 256) {
-        const int g = g0 + tid;
-        const bool valid = g < c1;
-        const float b = valid ? brow[g] : 0.f;
-        band_append(valid && b >= bound, g, L.cand, &L.n_cand);            // (< GRNG_CHUNK: one slot per group)
-    }
+    chunk_scan<1, false>(brow, c0, c1, bound, INFINITY, L);
     __syncthreads();
     // ---- the band: one wave per group, one fp32 dot for every row that can attain E_g
     const int m = L.n_cand;
     if (m > 0) {                                                           // (workgroup-uniform)
-        const float band = 2.f * eps;
         const float* srow = S + (size_t)q * ldS;
         int* rrow = p.R + (size_t)q * p.ldB;
         unsigned dots = 0;
         for (int c = wave; c < m; c += 4) {
             const int g = L.cand[c];
-            const float lim = one_ulp_down(brow[g] - band);                // (the subtraction may have rounded up)
-            const uint64_t best = group_rank_best(a, qv, srow, p.goff[g], p.goff[g + 1], lim, nv, lane, &dots);
+            const uint64_t best = group_best_row(a, qv, srow, p.goff[g], p.goff[g + 1], band_lo(brow[g], eps), nv, lane, &dots);
             if (lane == 0) {                                               // (the row that attains B_g passed lim: best is a key)
                 const float e = key_score(best);
                 const bool keep = e >= t;
                 brow[g] = keep ? e : -INFINITY;
                 rrow[g] = (int)(~(uint32_t)best);
-                if (keep) atomicAdd(&L.kept[(g - c0) / GRNG_SUB], 1);
+                if (keep) atomicAdd(&L.kept[(g - c0) / RESCORE_SUB], 1);
             }
         }
         if (lane == 0 && dots) atomicAdd(&L.dots, (unsigned long long)dots);
@@ -130,10 +101,10 @@ __global__ __launch_bounds__(256) void group_range_pack_kernel(GroupRangeArgs p,
                                                                const int* __restrict__ offs, const int64_t* __restrict__ lims) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = blockIdx.y, ng = p.n_groups;
-    const int s0 = blockIdx.x * GRNG_CHUNK + wave * GRNG_SUB, s1 = min(s0 + GRNG_SUB, ng);
+    const int s0 = blockIdx.x * RESCORE_CHUNK + wave * RESCORE_SUB, s1 = min(s0 + RESCORE_SUB, ng);
     if (s0 >= ng) return;                                                  // (wave-uniform, no barrier below)
-    const int64_t nsub = ((int64_t)ng + GRNG_SUB - 1) / GRNG_SUB;
-    const size_t slot = (size_t)q * nsub + (size_t)blockIdx.x * GRNG_SUBS + wave;
+    const int64_t nsub = ((int64_t)ng + RESCORE_SUB - 1) / RESCORE_SUB;
+    const size_t slot = (size_t)q * nsub + (size_t)blockIdx.x * RESCORE_SUBS + wave;
     if (counts[slot] == 0) return;                                         // (also: every query with an empty segment)
     const float t = p.thresholds[q];
     int64_t run = lims[q] + offs[slot];                                    // (lims: the block's first query's entry, as the scan got it)
@@ -156,15 +127,13 @@ __global__ __launch_bounds__(256) void group_range_pack_kernel(GroupRangeArgs p,
 }
 
 static bool group_range_args_ok(const GroupRangeArgs& p, int nq_block) {
-    const SearchArgs& a = p.a;
-    return nq_block >= 1 && nq_block <= 256 && p.n_groups >= 1 && a.n_docs >= p.n_groups && a.n_docs < ((int64_t)1 << 31) &&
-           range_dim_ok(a.dim) && a.index_f32 && a.q_f32 && a.dmax && (a.eps_data || a.eps_rel >= 0.f) && p.goff && p.B && p.R &&
+    return rescore_args_ok(p.a, nq_block) && p.n_groups >= 1 && p.a.n_docs >= p.n_groups && p.goff && p.B && p.R &&
            (int64_t)p.ldB >= p.n_groups && p.thresholds && p.stats && (!p.filter_of_query || p.n_filters >= 1);
 }
 
 hipError_t launch_group_range_rescore(const GroupRangeArgs& p, const float* S, size_t ldS, int nq_block, int* counts, hipStream_t s) {
     if (!group_range_args_ok(p, nq_block) || !S || (int64_t)ldS < p.a.n_docs || !counts) return hipErrorInvalidValue;
-    const unsigned chunks = (unsigned)((p.n_groups + GRNG_CHUNK - 1) / GRNG_CHUNK);
+    const unsigned chunks = (unsigned)((p.n_groups + RESCORE_CHUNK - 1) / RESCORE_CHUNK);
     hipLaunchKernelGGL(group_range_rescore_kernel, dim3(chunks, (unsigned)nq_block), dim3(256), 0, s, p, S, ldS, counts);
     return hipGetLastError();
 }
@@ -173,7 +142,7 @@ hipError_t launch_group_range_pack(const GroupRangeArgs& p, int nq_block, const 
                                    hipStream_t s) {
     if (!group_range_args_ok(p, nq_block) || !counts || !offs || !lims || !p.out_scores || !p.out_rows || !p.out_groups)
         return hipErrorInvalidValue;
-    const unsigned chunks = (unsigned)((p.n_groups + GRNG_CHUNK - 1) / GRNG_CHUNK);
+    const unsigned chunks = (unsigned)((p.n_groups + RESCORE_CHUNK - 1) / RESCORE_CHUNK);
     hipLaunchKernelGGL(group_range_pack_kernel, dim3(chunks, (unsigned)nq_block), dim3(256), 0, s, p, counts, offs, lims);
     return hipGetLastError();
 }

@@ -32,7 +32,7 @@
 //      filter index out of range leaves it there (dead as well);
 //   3. group_rank_count_kernel, one workgroup per (chunk of 4096 groups, pair): lo = one_ulp_down(t - eps), hi = one_ulp_up(t +
 //      eps).  B_h > hi: counted from B alone; B_h < lo: skipped; the groups in [lo, hi] are compacted into an LDS list
-//      (band_append) and re-scored one group per wave with the row loop of group_window_rescore_kernel: a rank compares
+//      (search_rescore.h: chunk_scan) and re-scored one group per wave by the same group_best_row: a rank compares
 //      make_key(E_h, h) with the bar, a count compares floats (>= t, or > t when strict).  B and S are only read — several pairs
 //      share a query's rows.  The workgroup's total is one 64-bit integer add into the pair's count: integer adds commute, the
 //      result does not depend on the order.  A group longer than a chunk of rows — the whole index may be one group — is still
@@ -41,19 +41,11 @@
 // splits.  No kernel waits for another workgroup; stream order between the launches is the only ordering.  No kernel reads a B
 // column at or past n_groups, or an S column at or past n_docs.
 #include "kernels.h"
-#include "search_band.h"
+#include "search_rescore.h"
 
 namespace vr {
 
-constexpr int GRNK_CHUNK = 4096;            // groups per workgroup of the count (the document window search's chunk)
 constexpr int64_t GRNK_MAX_WGS = (int64_t)1 << 22;   // workgroups per launch of the counting kernel
-
-struct GroupRankLds {
-    int cand[GRNK_CHUNK];                   // groups inside the band, any order
-    int n_cand;
-    unsigned ahead;                         // groups of this chunk ahead of the bar
-    unsigned long long dots;                // fp32 row dots of this workgroup
-};
 
 __global__ __launch_bounds__(256) void group_rank_bar_kernel(GroupRankArgs p, const float* __restrict__ S, size_t ldS, int n_pairs) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -65,8 +57,7 @@ __global__ __launch_bounds__(256) void group_rank_bar_kernel(GroupRankArgs p, co
     f32x4 qv[MERGE_MAXV];
     load_query_regs(qv, a.q_f32 + (size_t)q * a.dim, nv, lane);
     float eps = query_eps(a, qv);
-    const int f = p.filter_of_query ? p.filter_of_query[q] : -1;
-    const bool no_filter = !(f == -1 || (unsigned)f < (unsigned)p.n_filters);   // nothing is allowed
+    const bool no_filter = !filter_index_ok(p.filter_of_query ? p.filter_of_query[q] : -1, p.n_filters);   // nothing allowed
     if (no_filter) eps = __builtin_nanf("");
     unsigned long long bar;
     long long count = 0;
@@ -78,8 +69,7 @@ __global__ __launch_bounds__(256) void group_rank_bar_kernel(GroupRankArgs p, co
         bar = KEY_NONE;
         if (bg > -INFINITY) {                                              // (wave-uniform) a present target
             unsigned dots = 0;
-            const float lim = one_ulp_down(bg - 2.f * eps);                // (the subtraction may have rounded up)
-            const uint64_t best = group_rank_best(a, qv, S + (size_t)q * ldS, p.goff[g], p.goff[g + 1], lim, nv, lane, &dots);
+            const uint64_t best = group_best_row(a, qv, S + (size_t)q * ldS, p.goff[g], p.goff[g + 1], band_lo(bg, eps), nv, lane, &dots);
             score = key_score(best); row = (long long)(~(uint32_t)best);
             bar = make_key(score, (uint32_t)g);
             if (lane == 0) {
@@ -104,43 +94,32 @@ __global__ __launch_bounds__(256) void group_rank_bar_kernel(GroupRankArgs p, co
 
 __global__ __launch_bounds__(256) void group_rank_count_kernel(GroupRankArgs p, const float* __restrict__ S, size_t ldS, int pair0,
                                                                int chunks) {
-    __shared__ GroupRankLds L;
+    __shared__ ChunkLds L;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const SearchArgs& a = p.a;
     const int pair = pair0 + (int)(blockIdx.x / (unsigned)chunks), chunk = (int)(blockIdx.x % (unsigned)chunks);
     const float eps = p.bar_eps[pair];
     if (eps != eps) return;                                                // (workgroup-uniform) a dead pair: its slot is final
     const int q = p.pair_query[pair], ng = p.n_groups, nv = a.dim >> 2;
-    const int c0 = chunk * GRNK_CHUNK, c1 = min(c0 + GRNK_CHUNK, ng);
+    const int c0 = chunk * RESCORE_CHUNK, c1 = min(c0 + RESCORE_CHUNK, ng);
     const unsigned long long bar = p.bars[pair];
     const bool by_key = p.pair_group != nullptr;
     const float t = by_key ? key_score(bar) : __uint_as_float((uint32_t)bar);
     const float lo = one_ulp_down(t - eps), hi = one_ulp_up(t + eps);
-    if (tid == 0) { L.n_cand = 0; L.ahead = 0u; L.dots = 0ull; }
-    __syncthreads();
     // ---- certainly ahead: B > hi; the band: lo <= B <= hi (an absent group is -inf, lo is finite)
     const float* brow = p.B + (size_t)q * p.ldB;
-    unsigned mine = 0;                      // groups ahead of the bar this wave found (every lane holds the wave's count)
-    for (int g0 = c0; g0 < c1; g0 += 256) {
-        const int g = g0 + tid;
-        const bool valid = g < c1;
-        const float b = valid ? brow[g] : 0.f;
-        mine += (unsigned)__popcll(__ballot(valid && b > hi));
-        band_append(valid && b >= lo && b <= hi, g, L.cand, &L.n_cand);    // (< GRNK_CHUNK: one slot per group)
-    }
+    unsigned mine = chunk_scan<1, false>(brow, c0, c1, lo, hi, L);         // groups ahead of the bar this wave found
     __syncthreads();
     // ---- the band: one wave per group, one fp32 dot for every row that can attain E_h
     const int m = L.n_cand;
     if (m > 0) {                                                           // (workgroup-uniform)
         f32x4 qv[MERGE_MAXV];
         load_query_regs(qv, a.q_f32 + (size_t)q * a.dim, nv, lane);
-        const float band = 2.f * eps;
         const float* srow = S + (size_t)q * ldS;
         unsigned dots = 0;
         for (int c = wave; c < m; c += 4) {
             const int h = L.cand[c];
-            const float lim = one_ulp_down(brow[h] - band);                // (the subtraction may have rounded up)
-            const uint64_t best = group_rank_best(a, qv, srow, p.goff[h], p.goff[h + 1], lim, nv, lane, &dots);
+            const uint64_t best = group_best_row(a, qv, srow, p.goff[h], p.goff[h + 1], band_lo(brow[h], eps), nv, lane, &dots);
             const float e = key_score(best);
             const bool ahead = by_key ? make_key(e, (uint32_t)h) > bar : (p.strict ? e > t : e >= t);
             mine += ahead ? 1u : 0u;                                       // (every lane holds the same e)
@@ -160,12 +139,10 @@ __global__ __launch_bounds__(256) void group_rank_count_kernel(GroupRankArgs p, 
 }
 
 static bool group_rank_args_ok(const GroupRankArgs& p, const float* S, size_t ldS, int nq_block, int64_t n_pairs) {
-    const SearchArgs& a = p.a;
-    return nq_block >= 1 && nq_block <= 256 && n_pairs >= 1 && n_pairs < ((int64_t)1 << 31) && p.n_groups >= 1 &&
-           a.n_docs >= p.n_groups && a.n_docs < ((int64_t)1 << 31) && range_dim_ok(a.dim) && a.index_f32 && a.q_f32 && a.dmax &&
-           (a.eps_data || a.eps_rel >= 0.f) && p.goff && p.B && (int64_t)p.ldB >= p.n_groups && p.pair_query &&
+    return rescore_args_ok(p.a, nq_block) && n_pairs >= 1 && n_pairs < ((int64_t)1 << 31) && p.n_groups >= 1 &&
+           p.a.n_docs >= p.n_groups && p.goff && p.B && (int64_t)p.ldB >= p.n_groups && p.pair_query &&
            ((p.pair_group != nullptr) != (p.pair_thr != nullptr)) && (!p.pair_group || (p.out_scores && p.out_rows)) && p.bars &&
-           p.bar_eps && p.out_counts && p.stats && S && (int64_t)ldS >= a.n_docs && (!p.filter_of_query || p.n_filters >= 1);
+           p.bar_eps && p.out_counts && p.stats && S && (int64_t)ldS >= p.a.n_docs && (!p.filter_of_query || p.n_filters >= 1);
 }
 
 hipError_t launch_group_rank_bars(const GroupRankArgs& p, const float* S, size_t ldS, int nq_block, int64_t n_pairs, hipStream_t s) {
@@ -176,7 +153,7 @@ hipError_t launch_group_rank_bars(const GroupRankArgs& p, const float* S, size_t
 
 hipError_t launch_group_rank_count(const GroupRankArgs& p, const float* S, size_t ldS, int nq_block, int64_t n_pairs, hipStream_t s) {
     if (!group_rank_args_ok(p, S, ldS, nq_block, n_pairs)) return hipErrorInvalidValue;
-    const int64_t chunks = ((int64_t)p.n_groups + GRNK_CHUNK - 1) / GRNK_CHUNK;
+    const int64_t chunks = ((int64_t)p.n_groups + RESCORE_CHUNK - 1) / RESCORE_CHUNK;
     const int64_t per_launch = GRNK_MAX_WGS / chunks;                      // (chunks < 2^19: at least 8 pairs)
     for (int64_t p0 = 0; p0 < n_pairs; p0 += per_launch) {
         const int64_t np = n_pairs - p0 < per_launch ? n_pairs - p0 : per_launch;

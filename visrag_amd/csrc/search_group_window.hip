@@ -29,11 +29,11 @@
 //      lo = one_ulp_down(v_z - 2 eps), hi = one_ulp_up(v_a + 2 eps);
 //   3. group_window_rescore_kernel, grid (chunk of 4096 groups, query): the B row is REWRITTEN in place so that it alone defines
 //      the answer: +inf for B_g > hi (certainly ahead), -inf for B_g < lo (certainly behind, or absent), and for the groups in
-//      [lo, hi] — compacted into an LDS list by ballot + popcount, one wave per group — E_g, with the best row in the int32 side
-//      row R[q][g].  The wave walks the group's rows 64 at a time, ballots b_i >= one_ulp_down(B_g - 2 eps) and gives each such
-//      row one fp32 dot, the row's loads issued in front of the fma chain; it keeps the largest key.  A group longer than a chunk
-//      of rows — the whole index may be one group — is still one wave's loop, as in group_select_kernel.  A column is written
-//      by one thread only: a group outside the band by the thread that classified it, a band group by lane 0 of its wave;
+//      [lo, hi] — compacted into an LDS list (search_rescore.h: chunk_scan), one wave per group — E_g, with the best row in the
+//      int32 side row R[q][g]: group_best_row gives every row with b_i >= one_ulp_down(B_g - 2 eps) one fp32 dot and keeps the
+//      largest key.  A group longer than a chunk of rows — the whole index may be one group — is still one wave's loop, as in
+//      group_select_kernel.  A column is written by one thread only: a group outside the band by the thread that classified it,
+//      a band group by lane 0 of its wave;
 //   4. group_window_select_kernel, one workgroup per query: radix selects for rank o (when o > 0) and rank min(o + k, nd) of the
 //      rewritten row, gather_window (search_select.h), keys make_key(B[g], g), block_bitonic_desc, k slots (B[g], R[g], g)
 //      emitted, (-inf, -1, -1) past the present groups.  The A groups of +inf hold ranks 0 .. A - 1 of the rewritten row, so
@@ -41,17 +41,9 @@
 // No kernel waits for another workgroup; stream order between the launches is the only ordering.  No kernel reads a B or R
 // column at or past n_groups, or an S column at or past n_docs, as a value or writes one.
 #include "kernels.h"
-#include "search_select.h"
+#include "search_rescore.h"
 
 namespace vr {
-
-constexpr int GWIN_CHUNK = 4096;            // groups per workgroup of the re-scoring (the windowed search's chunk)
-
-struct GroupWindowLds {
-    int cand[GWIN_CHUNK];                   // groups inside the band, any order
-    int n_cand;
-    unsigned long long dots;                // fp32 row dots of this workgroup
-};
 
 __global__ __launch_bounds__(256) void group_window_edge_kernel(GroupWindowArgs p) {
     __shared__ SelectLds L;
@@ -61,22 +53,8 @@ __global__ __launch_bounds__(256) void group_window_edge_kernel(GroupWindowArgs 
     const int q = blockIdx.x, ng = p.n_groups, nv = a.dim >> 2;
     if (q == 0 && tid == 0) atomicAdd(&p.stats[0], (unsigned long long)gridDim.x);
     const float* brow = p.B + (size_t)q * p.ldB;
-    const int f = p.filter_of_query ? p.filter_of_query[q] : -1;
-    int nd = ng;
-    if (f != -1 && (unsigned)f >= (unsigned)p.n_filters) {                 // (workgroup-uniform) no such filter: nothing is allowed, and
-        nd = 0;                                                            // the mask left the row alone — nobody reads it
-    } else if (f != -1) {                                                  // (workgroup-uniform) the groups with an allowed row
-        if (tid == 0) s_present = 0;
-        __syncthreads();
-        int mine = 0;                       // (complete in lane 0: every lane of a wave holds the wave's count)
-        for (int g0 = 0; g0 < ng; g0 += 256) {
-            const int g = g0 + tid;
-            mine += __popcll(__ballot(g < ng && brow[g] > -INFINITY));
-        }
-        if (lane == 0 && mine) atomicAdd(&s_present, mine);
-        __syncthreads();
-        nd = s_present;
-    }
+    // nd = the groups with an allowed row (workgroup-uniform)
+    const int nd = present_count(brow, ng, p.filter_of_query ? p.filter_of_query[q] : -1, p.n_filters, &s_present);
     if (tid == 0) p.present[q] = nd;
     const int64_t o = p.offsets[q];
     if (o >= (int64_t)nd) {                                                // (workgroup-uniform) an empty window: a row of tails
@@ -87,66 +65,34 @@ __global__ __launch_bounds__(256) void group_window_edge_kernel(GroupWindowArgs 
     load_query_regs(qv, a.q_f32 + (size_t)q * a.dim, nv, lane);
     const float eps = query_eps(a, qv);                                    // (every wave computes the same value)
     const int kz = (int)min(o + (int64_t)a.k, (int64_t)nd);                // 1 <= o + 1 <= kz <= nd
-    const KthKey ka = select_kth(brow, ng, (int)o + 1, L);
-    __syncthreads();
-    const KthKey kz_key = select_kth(brow, ng, kz, L);
-    if (tid == 0) {
-        const float va = orderable_f32(ka.T), vz = orderable_f32(kz_key.T);
-        p.edges[2 * q] = one_ulp_down(vz - 2.f * eps);
-        p.edges[2 * q + 1] = one_ulp_up(va + 2.f * eps);
-    }
+    const BandEdges e = window_edges(brow, ng, (int)o, kz, eps, L);
+    if (tid == 0) { p.edges[2 * q] = e.lo; p.edges[2 * q + 1] = e.hi; }
 }
 
 __global__ __launch_bounds__(256) void group_window_rescore_kernel(GroupWindowArgs p, const float* __restrict__ S, size_t ldS) {
-    __shared__ GroupWindowLds L;
+    __shared__ ChunkLds L;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const SearchArgs& a = p.a;
     const int q = blockIdx.y, ng = p.n_groups, nv = a.dim >> 2;
     const float lo = p.edges[2 * q], hi = p.edges[2 * q + 1];
     if (lo != lo) return;                                                  // (workgroup-uniform) an empty window
-    const int c0 = blockIdx.x * GWIN_CHUNK, c1 = min(c0 + GWIN_CHUNK, ng);
-    if (tid == 0) { L.n_cand = 0; L.dots = 0ull; }
-    __syncthreads();
+    const int c0 = blockIdx.x * RESCORE_CHUNK, c1 = min(c0 + RESCORE_CHUNK, ng);
     // ---- certainly ahead: B > hi -> +inf; certainly behind or absent: B < lo -> -inf; the band lo <= B <= hi: listed
     float* brow = p.B + (size_t)q * p.ldB;
-    for (int g0 = c0; g0 < c1; g0 += 256) {
-        const int g = g0 + tid;
-        const bool valid = g < c1;
-        const float b = valid ? brow[g] : 0.f;
-        const bool in = valid && b >= lo && b <= hi;
-        if (valid && !in) brow[g] = b > hi ? INFINITY : -INFINITY;         // (a band column is written by the wave that re-scores it)
-        band_append(in, g, L.cand, &L.n_cand);                             // (< GWIN_CHUNK: one slot per group)
-    }
+    chunk_scan<1, true>(brow, c0, c1, lo, hi, L);
     __syncthreads();
     // ---- the band: one wave per group, one fp32 dot for every row that can attain E_g
     const int m = L.n_cand;
     if (m > 0) {                                                           // (workgroup-uniform)
         f32x4 qv[MERGE_MAXV];
         load_query_regs(qv, a.q_f32 + (size_t)q * a.dim, nv, lane);
-        const float band = 2.f * query_eps(a, qv);                         // (the edge kernel's value)
+        const float eps = query_eps(a, qv);                                // (the edge kernel's value)
         const float* srow = S + (size_t)q * ldS;
         int* rrow = p.R + (size_t)q * p.ldB;
         unsigned dots = 0;
         for (int c = wave; c < m; c += 4) {
             const int g = L.cand[c];
-            const int glo = p.goff[g], ghi = p.goff[g + 1];
-            const float lim = one_ulp_down(brow[g] - band);                // (the subtraction may have rounded up)
-            uint64_t best = KEY_NONE;
-            for (int i0 = glo; i0 < ghi; i0 += 64) {
-                const int i = i0 + lane;
-                unsigned long long in = __ballot(i < ghi && srow[i] >= lim);
-                dots += (unsigned)__popcll(in);
-                while (in) {                                               // (wave-uniform)
-                    const int id = i0 + __ffsll((long long)in) - 1;
-                    in &= in - 1ull;
-                    f32x4 dv[MERGE_MAXV];
-                    load_row_regs(dv, a.index_f32 + (size_t)id * a.dim, nv, lane);
-                    const float s = wave_sum(dot_regs(qv, dv, nv, lane));
-                    const uint64_t key = make_key(s, (uint32_t)id);
-                    best = key > best ? key : best;
-                }
-            }
-            // (the row that attains B_g passes lim: best is a key)
+            const uint64_t best = group_best_row(a, qv, srow, p.goff[g], p.goff[g + 1], band_lo(brow[g], eps), nv, lane, &dots);
             if (lane == 0) { brow[g] = key_score(best); rrow[g] = (int)(~(uint32_t)best); }
         }
         if (lane == 0 && dots) atomicAdd(&L.dots, (unsigned long long)dots);
@@ -185,30 +131,13 @@ __global__ __launch_bounds__(256) void group_window_select_kernel(GroupWindowArg
     const int nd = p.present[q];
     const int o = (int)p.offsets[q];                                       // (< nd: the edge kernel saw it)
     const int kz = (int)min((int64_t)o + k, (int64_t)nd);
-    KthKey ka{0xFFFFFFFFu, 0};
-    if (o > 0) {
-        ka = select_kth(brow, ng, o, L.s);
-        __syncthreads();
-    }
-    const KthKey kzk = select_kth(brow, ng, kz, L.s);
-    __syncthreads();
-    const int n_sel = min(gather_window(brow, ng, ka, o > 0, kzk, L), SEL_CAND);
-    for (int c = tid; c < n_sort; c += 256) {
-        uint64_t key = KEY_NONE;
-        if (c < n_sel) { const int g = L.s.cand[c]; key = make_key(brow[g], (uint32_t)g); }
-        L.s.keys[c] = key;
-    }
-    __syncthreads();
-    block_bitonic_desc(L.s.keys, n_sort, tid, 256);
+    sort_gathered(brow, window_positions(brow, ng, o, kz, L), n_sort, L.s);
     for (int c = tid; c < k; c += 256) emit(c, L.s.keys[c]);
 }
 
 static bool group_window_args_ok(const GroupWindowArgs& p, int nq_block) {
-    const SearchArgs& a = p.a;
-    return nq_block >= 1 && nq_block <= 256 && p.n_groups >= 1 && a.n_docs >= p.n_groups && a.n_docs < ((int64_t)1 << 31) &&
-           range_dim_ok(a.dim) && a.index_f32 && a.q_f32 && a.dmax && (a.eps_data || a.eps_rel >= 0.f) && a.k >= 1 &&
-           a.k <= SEL_CAND - SEL_MARGIN && a.out_scores && a.out_ids && !a.out_keys && p.out_groups && p.goff && p.B && p.R &&
-           (int64_t)p.ldB >= p.n_groups && p.offsets && p.edges && p.present && p.stats;
+    return rescore_args_ok(p.a, nq_block) && topk_out_ok(p.a) && p.n_groups >= 1 && p.a.n_docs >= p.n_groups && p.out_groups &&
+           p.goff && p.B && p.R && (int64_t)p.ldB >= p.n_groups && p.offsets && p.edges && p.present && p.stats;
 }
 
 hipError_t launch_group_window_edges(const GroupWindowArgs& p, int nq_block, hipStream_t s) {
@@ -219,16 +148,14 @@ hipError_t launch_group_window_edges(const GroupWindowArgs& p, int nq_block, hip
 
 hipError_t launch_group_window_rescore(const GroupWindowArgs& p, const float* S, size_t ldS, int nq_block, hipStream_t s) {
     if (!group_window_args_ok(p, nq_block) || !S || (int64_t)ldS < p.a.n_docs) return hipErrorInvalidValue;
-    const unsigned chunks = (unsigned)((p.n_groups + GWIN_CHUNK - 1) / GWIN_CHUNK);
+    const unsigned chunks = (unsigned)((p.n_groups + RESCORE_CHUNK - 1) / RESCORE_CHUNK);
     hipLaunchKernelGGL(group_window_rescore_kernel, dim3(chunks, (unsigned)nq_block), dim3(256), 0, s, p, S, ldS);
     return hipGetLastError();
 }
 
 hipError_t launch_group_window_select(const GroupWindowArgs& p, int nq_block, hipStream_t s) {
     if (!group_window_args_ok(p, nq_block)) return hipErrorInvalidValue;
-    int n_sort = 64;                                                       // the power of two that holds k keys
-    while (n_sort < p.a.k) n_sort <<= 1;
-    hipLaunchKernelGGL(group_window_select_kernel, dim3((unsigned)nq_block), dim3(256), 0, s, p, n_sort);
+    hipLaunchKernelGGL(group_window_select_kernel, dim3((unsigned)nq_block), dim3(256), 0, s, p, sort_width(p.a.k));
     return hipGetLastError();
 }
 

@@ -22,7 +22,7 @@
 //      count na; na == 0 (an empty filter, or a device caller's filter index outside [-1, n_filters)): the group is empty
 //      (lo = NaN).  Otherwise a radix select over the fused row gives v_z (rank <= na: not a masked -inf) and lo;
 //   4. multi_rescore_kernel, grid (column chunk of 4096, group): the fused row is REWRITTEN in place: -inf below lo, and for the
-//      columns at or above it — compacted into an LDS list by ballot + popcount, one candidate per wave, the row's loads issued
+//      columns at or above it — compacted into an LDS list (search_rescore.h: chunk_scan), one candidate per wave, the row's loads issued
 //      in front of the fma chains and held in registers while the kernel loops over the group's sub-queries — the fp32 fused
 //      score.  Every dot product keeps dot_lane's summation order.  A column is written by one thread only;
 //   5. multi_select_kernel, one workgroup per group: radix select at rank min(k, na) of the rewritten row, gather_ordered
@@ -31,21 +31,13 @@
 // No kernel waits for another workgroup; stream order between the launches is the only ordering.  No kernel reads a column at
 // or past n_docs as a value or writes one.
 #include "kernels.h"
-#include "search_select.h"
+#include "search_rescore.h"
 
 namespace vr {
 
-constexpr int MULTI_CHUNK = 4096;           // columns per workgroup of the re-scoring (the window search's chunk)
-constexpr int MULTI_FUSE_COLS = 256 * 4;    // columns per workgroup of the fusion: one 16-byte load per thread and sub-row
-
-struct MultiLds {
-    int cand[MULTI_CHUNK];                  // columns at or above lo, any order
-    int n_cand;
-};
-
 struct MultiEdgeLds {
     SelectLds s;
-    float eps[4];                           // the largest query_eps every wave met
+    float eps[4];                           // group_eps: the largest query_eps every wave met
 };
 
 // rows group g may see (search_common.h: rows_allowed); no filter array: every group is on -1
@@ -63,29 +55,16 @@ __global__ __launch_bounds__(256) void multi_expand_kernel(const int* __restrict
 __global__ __launch_bounds__(256) void multi_fuse_kernel(MultiSearchArgs p, float* __restrict__ S, size_t ldS) {
     const int g = blockIdx.y, n_docs = (int)p.a.n_docs;
     const int s0 = p.lims[g] - p.sub_base, m = p.lims[g + 1] - p.lims[g];
-    const int i0 = (blockIdx.x * 256 + threadIdx.x) * 4;                   // (a multiple of 4, as ldS: aligned; < ldS)
-    if (m < 2 || i0 >= n_docs) return;
-    float* row = S + (size_t)s0 * ldS + i0;
-    f32x4 v = *reinterpret_cast<const f32x4*>(row);
-    for (int j = 1; j < m; ++j) {
-        const f32x4 w = *reinterpret_cast<const f32x4*>(row + (size_t)j * ldS);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = multi_pick(v[e], w[e], p.fuse);
-    }
-    if (i0 + 4 <= n_docs) {
-        *reinterpret_cast<f32x4*>(row) = v;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (i0 + e < n_docs) row[e] = v[e];
-    }
+    if (m < 2) return;                                                     // a group of one: its row is its own fusion
+    float* row = S + (size_t)s0 * ldS;
+    fuse_columns(row, ldS, m, row, n_docs, p.fuse);
 }
 
 __global__ __launch_bounds__(256) void multi_edge_kernel(MultiSearchArgs p, const float* __restrict__ S, size_t ldS) {
     __shared__ MultiEdgeLds L;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const SearchArgs& a = p.a;
-    const int g = blockIdx.x, n_docs = (int)a.n_docs, nv = a.dim >> 2;
+    const int g = blockIdx.x, n_docs = (int)a.n_docs;
     if (g == 0 && tid == 0) atomicAdd(&p.stats[0], (unsigned long long)gridDim.x);
     const int na = group_rows(p, g);
     if (na <= 0) {                                                         // (workgroup-uniform) nothing allowed: a row of tails
@@ -93,31 +72,17 @@ __global__ __launch_bounds__(256) void multi_edge_kernel(MultiSearchArgs p, cons
         return;
     }
     const int s0 = p.lims[g] - p.sub_base, m = p.lims[g + 1] - p.lims[g];
-    float eps = 0.f;
-    for (int j = wave; j < m; j += 4) {                                    // (wave-uniform)
-        f32x4 qv[MERGE_MAXV];
-        load_query_regs(qv, a.q_f32 + (size_t)(s0 + j) * a.dim, nv, lane);
-        eps = fmaxf(eps, query_eps(a, qv));
-    }
-    if (lane == 0) L.eps[wave] = eps;
-    const KthKey kz = select_kth(S + (size_t)s0 * ldS, n_docs, min(a.k, na), L.s);      // (its barriers publish L.eps too)
-    if (tid == 0) {
-        const float eps_g = fmaxf(fmaxf(L.eps[0], L.eps[1]), fmaxf(L.eps[2], L.eps[3]));
-        p.edges[g] = one_ulp_down(orderable_f32(kz.T) - 2.f * eps_g);
-    }
+    const float eps_g = group_eps(a, s0, m, nullptr, L.eps);
+    const KthKey kz = select_kth(S + (size_t)s0 * ldS, n_docs, min(a.k, na), L.s);
+    if (tid == 0) p.edges[g] = band_lo(orderable_f32(kz.T), eps_g);
 }
 
 // the fused fp32 score of row `id` for the group's m sub-queries (first: qrow), and — want_which — the lowest j whose score has
 // exactly the bits `target`; called by a whole wave, the result is wave-uniform
 __device__ __forceinline__ float multi_fused_score(const SearchArgs& a, const float* qrow, int m, int fuse, int id, int nv, int lane,
                                                    bool want_which, float target, int* which) {
-    const f32x4* dr = reinterpret_cast<const f32x4*>(a.index_f32 + (size_t)id * a.dim);
     f32x4 dv[MERGE_MAXV];
-#pragma unroll
-    for (int i = 0; i < MERGE_MAXV; ++i) {
-        const int cc = lane + i * 64;
-        dv[i] = (cc < nv) ? dr[cc] : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
+    load_row_regs(dv, a.index_f32 + (size_t)id * a.dim, nv, lane);
     float best = 0.f;
     int w = -1;
     for (int j = 0; j < m; ++j) {
@@ -137,36 +102,17 @@ __device__ __forceinline__ float multi_fused_score(const SearchArgs& a, const fl
 }
 
 __global__ __launch_bounds__(256) void multi_rescore_kernel(MultiSearchArgs p, float* __restrict__ S, size_t ldS) {
-    __shared__ MultiLds L;
+    __shared__ ChunkLds L;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const SearchArgs& a = p.a;
     const int g = blockIdx.y, n_docs = (int)a.n_docs, nv = a.dim >> 2;
     const float lo = p.edges[g];
     if (lo != lo) return;                                                  // (workgroup-uniform) an empty group
     const int s0 = p.lims[g] - p.sub_base, m = p.lims[g + 1] - p.lims[g];
-    const int c0 = blockIdx.x * MULTI_CHUNK, c1 = min(c0 + MULTI_CHUNK, n_docs);
-    if (tid == 0) L.n_cand = 0;
-    __syncthreads();
+    const int c0 = blockIdx.x * RESCORE_CHUNK, c1 = min(c0 + RESCORE_CHUNK, n_docs);
     // ---- certainly behind or masked: B < lo -> -inf; the band B >= lo: listed
     float* row = S + (size_t)s0 * ldS;
-    for (int i0 = c0 + tid * 4; i0 < c1; i0 += 256 * 4) {                  // (c0 and ldS are multiples of 4: aligned; < ldS)
-        const f32x4 b = *reinterpret_cast<const f32x4*>(row + i0);
-        bool any_band = false;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const bool in = i0 + e < c1 && b[e] >= lo;
-            any_band |= in;
-            band_append(in, i0 + e, L.cand, &L.n_cand);                    // (< MULTI_CHUNK: one slot per column)
-        }
-        // a band column is written by the wave that re-scores it, a column at or past n_docs by nobody
-        if (i0 + 4 <= c1 && !any_band) {
-            *reinterpret_cast<f32x4*>(row + i0) = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (i0 + e < c1 && !(b[e] >= lo)) row[i0 + e] = -INFINITY;
-        }
-    }
+    chunk_scan<4, true>(row, c0, c1, lo, INFINITY, L);
     __syncthreads();
     // ---- fp32 re-scoring of the band, one candidate per wave, every sub-query of the group against the row in registers
     const int n = L.n_cand;
@@ -196,15 +142,8 @@ __global__ __launch_bounds__(256) void multi_select_kernel(MultiSearchArgs p, co
     const int s0 = p.lims[g] - p.sub_base, m = p.lims[g + 1] - p.lims[g];
     const int kz = min(k, group_rows(p, g));                               // >= 1: at least kz columns hold a finite fp32 score
     const float* row = S + (size_t)s0 * ldS;
-    const KthKey kth = select_kth(row, n_docs, kz, L);
-    gather_ordered(row, n_docs, kth.T, kz - kth.need_eq, kth.need_eq, SEL_CAND, L);
-    for (int c = tid; c < n_sort; c += 256) {
-        uint64_t key = KEY_NONE;
-        if (c < kz) { const int i = L.cand[c]; key = make_key(row[i], (uint32_t)i); }
-        L.keys[c] = key;
-    }
-    __syncthreads();
-    block_bitonic_desc(L.keys, n_sort, tid, 256);
+    top_positions(row, n_docs, kz, L);
+    sort_gathered(row, kz, n_sort, L);
     for (int c = tid; c < k; c += 256) {
         emit_slot(a, g, c, L.keys[c]);
         if (c >= kz) which[c] = -1;
@@ -221,10 +160,8 @@ __global__ __launch_bounds__(256) void multi_select_kernel(MultiSearchArgs p, co
 
 static bool multi_args_ok(const MultiSearchArgs& p, size_t ldS, int n_groups) {
     const SearchArgs& a = p.a;
-    return n_groups >= 1 && n_groups <= 256 && a.nq >= n_groups && a.nq <= 256 && a.n_docs >= 1 && a.n_docs < ((int64_t)1 << 31) &&
-           range_dim_ok(a.dim) && a.index_f32 && a.q_f32 && a.dmax && (a.eps_data || a.eps_rel >= 0.f) && a.k >= 1 &&
-           a.k <= SEL_CAND - SEL_MARGIN && a.out_scores && a.out_ids && !a.out_keys && p.out_which && p.lims && p.sub_base >= 0 &&
-           (p.fuse == 0 || p.fuse == 1) && p.edges && p.stats && ldS % 4 == 0 && (int64_t)ldS >= a.n_docs &&
+    return rescore_args_ok(a, n_groups) && topk_out_ok(a) && a.nq >= n_groups && a.nq <= 256 && p.out_which && p.lims &&
+           p.sub_base >= 0 && (p.fuse == 0 || p.fuse == 1) && p.edges && p.stats && ldS % 4 == 0 && (int64_t)ldS >= a.n_docs &&
            (!p.filter_of_group || (p.n_filters >= 1 && p.allowed));
 }
 
@@ -238,7 +175,7 @@ hipError_t launch_multi_expand(const int* lims, const int* filter_of_group, int 
 hipError_t launch_multi_fuse(const MultiSearchArgs& p, float* S, size_t ldS, int n_groups, hipStream_t s) {
     if (!multi_args_ok(p, ldS, n_groups) || !S) return hipErrorInvalidValue;
     if (p.a.nq == n_groups) return hipSuccess;                             // groups of one: every row is its own fusion
-    const unsigned chunks = (unsigned)((p.a.n_docs + MULTI_FUSE_COLS - 1) / MULTI_FUSE_COLS);
+    const unsigned chunks = (unsigned)((p.a.n_docs + FUSE_COLS - 1) / FUSE_COLS);
     hipLaunchKernelGGL(multi_fuse_kernel, dim3(chunks, (unsigned)n_groups), dim3(256), 0, s, p, S, ldS);
     return hipGetLastError();
 }
@@ -251,16 +188,14 @@ hipError_t launch_multi_edges(const MultiSearchArgs& p, const float* S, size_t l
 
 hipError_t launch_multi_rescore(const MultiSearchArgs& p, float* S, size_t ldS, int n_groups, hipStream_t s) {
     if (!multi_args_ok(p, ldS, n_groups) || !S) return hipErrorInvalidValue;
-    const unsigned chunks = (unsigned)((p.a.n_docs + MULTI_CHUNK - 1) / MULTI_CHUNK);
+    const unsigned chunks = (unsigned)((p.a.n_docs + RESCORE_CHUNK - 1) / RESCORE_CHUNK);
     hipLaunchKernelGGL(multi_rescore_kernel, dim3(chunks, (unsigned)n_groups), dim3(256), 0, s, p, S, ldS);
     return hipGetLastError();
 }
 
 hipError_t launch_multi_select(const MultiSearchArgs& p, const float* S, size_t ldS, int n_groups, hipStream_t s) {
     if (!multi_args_ok(p, ldS, n_groups) || !S) return hipErrorInvalidValue;
-    int n_sort = 64;                                                       // the power of two that holds k keys
-    while (n_sort < p.a.k) n_sort <<= 1;
-    hipLaunchKernelGGL(multi_select_kernel, dim3((unsigned)n_groups), dim3(256), 0, s, p, S, ldS, n_sort);
+    hipLaunchKernelGGL(multi_select_kernel, dim3((unsigned)n_groups), dim3(256), 0, s, p, S, ldS, sort_width(p.a.k));
     return hipGetLastError();
 }
 

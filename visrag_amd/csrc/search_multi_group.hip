@@ -33,10 +33,9 @@
 //      alone and from here on nobody reads them); none present: the question is empty (lo = NaN).  Otherwise a radix select over
 //      the F row gives v_z (rank <= present: not an absent document's -inf) and lo;
 //   4. multi_group_rescore_kernel, grid (chunk of 4096 documents, question): the F row is REWRITTEN in place: -inf below lo (or
-//      absent), and for the band — compacted into an LDS list by ballot + popcount, one wave per document — F(D).  The wave loops
-//      over the question's sub-queries; for each it walks the document's pages 64 at a time, ballots
-//      b_j(i) >= one_ulp_down(B_j(D) - 2 eps_j) and gives each such page one fp32 dot, the row's loads issued in front of the fma
-//      chain.  A document longer than a chunk of pages — the whole index may be one — is still one wave's loop.  A column is
+//      absent), and for the band — compacted into an LDS list (search_rescore.h: chunk_scan), one wave per document — F(D).  The
+//      wave loops over the question's sub-queries; for each, group_best_row gives every page of the document with
+//      b_j(i) >= one_ulp_down(B_j(D) - 2 eps_j) one fp32 dot, the row's loads issued in front of the fma chain.  A document longer than a chunk of pages — the whole index may be one — is still one wave's loop.  A column is
 //      written by one thread only: below the band by the thread that classified it, inside by lane 0 of its wave;
 //   5. multi_group_select_kernel, one workgroup per question: radix select at rank min(k, present) of the rewritten row,
 //      gather_ordered (lowest documents first inside the last tie tier), keys make_key(F, document), block_bitonic_desc, k slots;
@@ -45,136 +44,54 @@
 // No kernel waits for another workgroup; stream order between the launches is the only ordering.  No kernel reads as a value, or
 // writes, an S column at or past n_docs or a B / F column at or past n_groups.
 #include "kernels.h"
-#include "search_select.h"
+#include "search_rescore.h"
 
 namespace vr {
 
-constexpr int MGRP_CHUNK = 4096;            // documents per workgroup of the re-scoring (the document window search's chunk)
-constexpr int MGRP_FUSE_COLS = 256 * 4;     // documents per workgroup of the fusion: one 16-byte load per thread and sub-row
-
-struct MultiGroupLds {
-    int cand[MGRP_CHUNK];                   // documents inside the band, any order
-    int n_cand;
-    unsigned long long dots;                // fp32 page dots of this workgroup
-};
-
 struct MultiGroupEdgeLds {
     SelectLds s;
-    float eps[4];                           // the largest query_eps every wave met
+    float eps[4];                           // group_eps: the largest query_eps every wave met
     int present;
 };
-
-// (E_j(D), row_j(D)) as a key for the sub-query whose float4 chunks the wave holds in qv: every page of rows [glo, ghi) whose
-// bf16 score in srow reaches `lim` gets one fp32 dot.  Called by a whole wave, the result is wave-uniform; *dots counts the pages.
-__device__ __forceinline__ uint64_t mgrp_best_page(const SearchArgs& a, const f32x4 (&qv)[MERGE_MAXV], const float* __restrict__ srow,
-                                                   int glo, int ghi, float lim, int nv, int lane, unsigned* dots) {
-    uint64_t best = KEY_NONE;
-    for (int i0 = glo; i0 < ghi; i0 += 64) {
-        const int i = i0 + lane;
-        unsigned long long in = __ballot(i < ghi && srow[i] >= lim);
-        *dots += (unsigned)__popcll(in);
-        while (in) {                                                       // (wave-uniform)
-            const int id = i0 + __ffsll((long long)in) - 1;
-            in &= in - 1ull;
-            f32x4 dv[MERGE_MAXV];
-            load_row_regs(dv, a.index_f32 + (size_t)id * a.dim, nv, lane);
-            const float s = wave_sum(dot_regs(qv, dv, nv, lane));
-            const uint64_t key = make_key(s, (uint32_t)id);
-            best = key > best ? key : best;
-        }
-    }
-    return best;                                                           // (the page that attains B_j(D) passes lim: a key)
-}
 
 __global__ __launch_bounds__(256) void multi_group_fuse_kernel(MultiGroupArgs p) {
     const int g = blockIdx.y, ng = p.n_groups;
     const int s0 = p.lims[g] - p.sub_base, m = p.lims[g + 1] - p.lims[g];
-    const int d0 = (blockIdx.x * 256 + threadIdx.x) * 4;                   // (a multiple of 4, as ldB: aligned; < ldB)
-    if (d0 >= ng) return;
-    const float* brow = p.B + (size_t)s0 * p.ldB + d0;
-    float* frow = p.F + (size_t)g * p.ldB + d0;
-    if (d0 + 4 <= ng) {
-        f32x4 v = *reinterpret_cast<const f32x4*>(brow);
-        for (int j = 1; j < m; ++j) {
-            const f32x4 w = *reinterpret_cast<const f32x4*>(brow + (size_t)j * p.ldB);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = multi_pick(v[e], w[e], p.fuse);
-        }
-        *reinterpret_cast<f32x4*>(frow) = v;
-    } else {                                                               // the last documents: no column at or past n_groups
-        for (int e = 0; d0 + e < ng; ++e) {
-            float v = brow[e];
-            for (int j = 1; j < m; ++j) v = multi_pick(v, brow[(size_t)j * p.ldB + e], p.fuse);
-            frow[e] = v;
-        }
-    }
+    fuse_columns(p.B + (size_t)s0 * p.ldB, p.ldB, m, p.F + (size_t)g * p.ldB, ng, p.fuse);
 }
 
 __global__ __launch_bounds__(256) void multi_group_edge_kernel(MultiGroupArgs p) {
     __shared__ MultiGroupEdgeLds L;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const SearchArgs& a = p.a;
-    const int g = blockIdx.x, ng = p.n_groups, nv = a.dim >> 2;
+    const int g = blockIdx.x, ng = p.n_groups;
     if (g == 0 && tid == 0) atomicAdd(&p.stats[0], (unsigned long long)gridDim.x);
     const float* frow = p.F + (size_t)g * p.ldB;
-    const int f = p.filter_of_group ? p.filter_of_group[g] : -1;
-    int nd = ng;
-    if (f != -1 && (unsigned)f >= (unsigned)p.n_filters) {                 // (workgroup-uniform) no such filter: nothing is allowed
-        nd = 0;
-    } else if (f != -1) {                                                  // (workgroup-uniform) the documents with an allowed page
-        if (tid == 0) L.present = 0;
-        __syncthreads();
-        int mine = 0;                       // (every lane of a wave holds the wave's count)
-        for (int d0 = 0; d0 < ng; d0 += 256) {
-            const int d = d0 + tid;
-            mine += __popcll(__ballot(d < ng && frow[d] > -INFINITY));
-        }
-        if (lane == 0 && mine) atomicAdd(&L.present, mine);
-        __syncthreads();
-        nd = L.present;
-    }
+    // nd = the documents with an allowed page (workgroup-uniform)
+    const int nd = present_count(frow, ng, p.filter_of_group ? p.filter_of_group[g] : -1, p.n_filters, &L.present);
     if (tid == 0) p.present[g] = nd;
     if (nd <= 0) {                                                         // (workgroup-uniform) nothing present: a row of tails
         if (tid == 0) p.edges[g] = __builtin_nanf("");
         return;
     }
     const int s0 = p.lims[g] - p.sub_base, m = p.lims[g + 1] - p.lims[g];
-    float eps = 0.f;
-    for (int j = wave; j < m; j += 4) {                                    // (wave-uniform)
-        f32x4 qv[MERGE_MAXV];
-        load_query_regs(qv, a.q_f32 + (size_t)(s0 + j) * a.dim, nv, lane);
-        const float e = query_eps(a, qv);
-        if (lane == 0) p.eps_sub[s0 + j] = e;
-        eps = fmaxf(eps, e);
-    }
-    if (lane == 0) L.eps[wave] = eps;
-    const KthKey kz = select_kth(frow, ng, min(a.k, nd), L.s);             // (its barriers publish L.eps too)
-    if (tid == 0) {
-        const float eps_g = fmaxf(fmaxf(L.eps[0], L.eps[1]), fmaxf(L.eps[2], L.eps[3]));
-        p.edges[g] = one_ulp_down(orderable_f32(kz.T) - 2.f * eps_g);
-    }
+    const float eps_g = group_eps(a, s0, m, p.eps_sub, L.eps);
+    const KthKey kz = select_kth(frow, ng, min(a.k, nd), L.s);
+    if (tid == 0) p.edges[g] = band_lo(orderable_f32(kz.T), eps_g);
 }
 
 __global__ __launch_bounds__(256) void multi_group_rescore_kernel(MultiGroupArgs p, const float* __restrict__ S, size_t ldS) {
-    __shared__ MultiGroupLds L;
+    __shared__ ChunkLds L;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const SearchArgs& a = p.a;
     const int g = blockIdx.y, ng = p.n_groups, nv = a.dim >> 2;
     const float lo = p.edges[g];
     if (lo != lo) return;                                                  // (workgroup-uniform) an empty question
     const int s0 = p.lims[g] - p.sub_base, m = p.lims[g + 1] - p.lims[g];
-    const int c0 = blockIdx.x * MGRP_CHUNK, c1 = min(c0 + MGRP_CHUNK, ng);
-    if (tid == 0) { L.n_cand = 0; L.dots = 0ull; }
-    __syncthreads();
+    const int c0 = blockIdx.x * RESCORE_CHUNK, c1 = min(c0 + RESCORE_CHUNK, ng);
     // ---- certainly behind or absent: BF < lo -> -inf; the band BF >= lo: listed
     float* frow = p.F + (size_t)g * p.ldB;
-    for (int d0 = c0; d0 < c1; d0 += 256) {
-        const int d = d0 + tid;
-        const bool valid = d < c1;
-        const bool in = valid && frow[d] >= lo;
-        if (valid && !in) frow[d] = -INFINITY;                             // (a band column is written by the wave that re-scores it)
-        band_append(in, d, L.cand, &L.n_cand);                             // (< MGRP_CHUNK: one slot per document)
-    }
+    chunk_scan<1, true>(frow, c0, c1, lo, INFINITY, L);
     __syncthreads();
     // ---- the band: one wave per document, every sub-query of the question, one fp32 dot for every page that can attain E_j(D)
     const int n = L.n_cand;
@@ -186,8 +103,8 @@ __global__ __launch_bounds__(256) void multi_group_rescore_kernel(MultiGroupArgs
         for (int j = 0; j < m; ++j) {
             f32x4 qv[MERGE_MAXV];
             load_query_regs(qv, a.q_f32 + (size_t)(s0 + j) * a.dim, nv, lane);
-            const float lim = one_ulp_down(p.B[(size_t)(s0 + j) * p.ldB + d] - 2.f * p.eps_sub[s0 + j]);   // (the subtraction may have rounded up)
-            const float e = key_score(mgrp_best_page(a, qv, S + (size_t)(s0 + j) * ldS, glo, ghi, lim, nv, lane, &dots));
+            const float lim = band_lo(p.B[(size_t)(s0 + j) * p.ldB + d], p.eps_sub[s0 + j]);
+            const float e = key_score(group_best_row(a, qv, S + (size_t)(s0 + j) * ldS, glo, ghi, lim, nv, lane, &dots));
             fused = j == 0 ? e : multi_pick(fused, e, p.fuse);
         }
         if (lane == 0) frow[d] = fused;
@@ -220,15 +137,8 @@ __global__ __launch_bounds__(256) void multi_group_select_kernel(MultiGroupArgs 
     if (kz == 0) return;
     const int s0 = p.lims[g] - p.sub_base;
     const float* frow = p.F + (size_t)g * p.ldB;
-    const KthKey kth = select_kth(frow, ng, kz, L);                        // (>= kz columns hold a fp32 fused score)
-    gather_ordered(frow, ng, kth.T, kz - kth.need_eq, kth.need_eq, SEL_CAND, L);
-    for (int c = tid; c < n_sort; c += 256) {
-        uint64_t key = KEY_NONE;
-        if (c < kz) { const int d = L.cand[c]; key = make_key(frow[d], (uint32_t)d); }
-        L.keys[c] = key;
-    }
-    __syncthreads();
-    block_bitonic_desc(L.keys, n_sort, tid, 256);
+    top_positions(frow, ng, kz, L);                                        // (>= kz columns hold a fp32 fused score)
+    sort_gathered(frow, kz, n_sort, L);
     // ---- the winners: which sub-query decided, its page, and the evidence — a wave per slot, the re-scoring's walk again
     unsigned dots = 0;
     for (int c = wave; c < kz; c += 4) {
@@ -241,8 +151,8 @@ __global__ __launch_bounds__(256) void multi_group_select_kernel(MultiGroupArgs 
         for (int j = 0; j < m; ++j) {
             f32x4 qv[MERGE_MAXV];
             load_query_regs(qv, a.q_f32 + (size_t)(s0 + j) * a.dim, nv, lane);
-            const float lim = one_ulp_down(p.B[(size_t)(s0 + j) * p.ldB + d] - 2.f * p.eps_sub[s0 + j]);
-            const uint64_t best = mgrp_best_page(a, qv, S + (size_t)(s0 + j) * ldS, glo, ghi, lim, nv, lane, &dots);
+            const float lim = band_lo(p.B[(size_t)(s0 + j) * p.ldB + d], p.eps_sub[s0 + j]);
+            const uint64_t best = group_best_row(a, qv, S + (size_t)(s0 + j) * ldS, glo, ghi, lim, nv, lane, &dots);
             const float e = key_score(best);
             const long long row = (long long)(~(uint32_t)best);
             if (w < 0 && __float_as_uint(e) == fbits) { w = j; wrow = row; }
@@ -256,17 +166,15 @@ __global__ __launch_bounds__(256) void multi_group_select_kernel(MultiGroupArgs 
 
 static bool multi_group_args_ok(const MultiGroupArgs& p, int n_questions) {
     const SearchArgs& a = p.a;
-    return n_questions >= 1 && n_questions <= 256 && a.nq >= n_questions && a.nq <= 256 && p.n_groups >= 1 && a.n_docs >= p.n_groups &&
-           a.n_docs < ((int64_t)1 << 31) && range_dim_ok(a.dim) && a.index_f32 && a.q_f32 && a.dmax && (a.eps_data || a.eps_rel >= 0.f) &&
-           a.k >= 1 && a.k <= SEL_CAND - SEL_MARGIN && a.out_scores && a.out_ids && !a.out_keys && p.out_docs && p.out_which &&
-           (p.out_ev_scores != nullptr) == (p.out_ev_rows != nullptr) && p.lims && p.sub_base >= 0 && (p.fuse == 0 || p.fuse == 1) &&
-           p.goff && p.B && p.F && p.ldB % 4 == 0 && (int64_t)p.ldB >= p.n_groups && p.eps_sub && p.edges && p.present && p.stats &&
-           (!p.filter_of_group || p.n_filters >= 1);
+    return rescore_args_ok(a, n_questions) && topk_out_ok(a) && a.nq >= n_questions && a.nq <= 256 && p.n_groups >= 1 &&
+           a.n_docs >= p.n_groups && p.out_docs && p.out_which && (p.out_ev_scores != nullptr) == (p.out_ev_rows != nullptr) &&
+           p.lims && p.sub_base >= 0 && (p.fuse == 0 || p.fuse == 1) && p.goff && p.B && p.F && p.ldB % 4 == 0 &&
+           (int64_t)p.ldB >= p.n_groups && p.eps_sub && p.edges && p.present && p.stats && (!p.filter_of_group || p.n_filters >= 1);
 }
 
 hipError_t launch_multi_group_fuse(const MultiGroupArgs& p, int n_questions, hipStream_t s) {
     if (!multi_group_args_ok(p, n_questions)) return hipErrorInvalidValue;
-    const unsigned chunks = (unsigned)((p.n_groups + MGRP_FUSE_COLS - 1) / MGRP_FUSE_COLS);
+    const unsigned chunks = (unsigned)((p.n_groups + FUSE_COLS - 1) / FUSE_COLS);
     hipLaunchKernelGGL(multi_group_fuse_kernel, dim3(chunks, (unsigned)n_questions), dim3(256), 0, s, p);
     return hipGetLastError();
 }
@@ -279,16 +187,14 @@ hipError_t launch_multi_group_edges(const MultiGroupArgs& p, int n_questions, hi
 
 hipError_t launch_multi_group_rescore(const MultiGroupArgs& p, const float* S, size_t ldS, int n_questions, hipStream_t s) {
     if (!multi_group_args_ok(p, n_questions) || !S || (int64_t)ldS < p.a.n_docs) return hipErrorInvalidValue;
-    const unsigned chunks = (unsigned)((p.n_groups + MGRP_CHUNK - 1) / MGRP_CHUNK);
+    const unsigned chunks = (unsigned)((p.n_groups + RESCORE_CHUNK - 1) / RESCORE_CHUNK);
     hipLaunchKernelGGL(multi_group_rescore_kernel, dim3(chunks, (unsigned)n_questions), dim3(256), 0, s, p, S, ldS);
     return hipGetLastError();
 }
 
 hipError_t launch_multi_group_select(const MultiGroupArgs& p, const float* S, size_t ldS, int n_questions, hipStream_t s) {
     if (!multi_group_args_ok(p, n_questions) || !S || (int64_t)ldS < p.a.n_docs) return hipErrorInvalidValue;
-    int n_sort = 64;                                                       // the power of two that holds k keys
-    while (n_sort < p.a.k) n_sort <<= 1;
-    hipLaunchKernelGGL(multi_group_select_kernel, dim3((unsigned)n_questions), dim3(256), 0, s, p, S, ldS, n_sort);
+    hipLaunchKernelGGL(multi_group_select_kernel, dim3((unsigned)n_questions), dim3(256), 0, s, p, S, ldS, sort_width(p.a.k));
     return hipGetLastError();
 }
 

@@ -6,7 +6,7 @@
 //   1. score rows S[q][row] on the bf16 MFMA GEMM (the deep path's launch); with filters launch_filter_mask turns the columns a
 //      query may not see into -inf in place, so that they can never be candidates;
 //   2. range_rescore_kernel, grid (column chunk of 4096, query): the columns with b >= one_ulp_down(t - eps) are compacted into
-//      an LDS list (ballot + popcount), re-scored one candidate per wave with the query in registers (dot_lane + wave_sum: the
+//      an LDS list (search_rescore.h: chunk_scan), re-scored one candidate per wave with the query in registers (dot_lane + wave_sum: the
 //      library's one fp32 dot product, so a row carries the score bits vr_index_search returns for it) and written back into S:
 //      e where e >= t, -inf where not.  A non-candidate keeps its b < t - eps <= t.  From here on "S[q][row] >= t" is exactly
 //      membership and the stored value is the score to return.  Kept rows are counted per 1024 columns (a wave's share of the
@@ -20,59 +20,34 @@
 // A threshold that is not finite, or a filter index outside [-1, n_filters) (on the device neither can be seen before the
 // launch): an empty segment, nothing of S, of the index or of the filter store is read for that query.
 #include "kernels.h"
-#include "search_common.h"
+#include "search_rescore.h"
 
 namespace vr {
 
-constexpr int RANGE_CHUNK = 4096;           // columns per workgroup: 100 000 rows x 256 queries = 6 400 workgroups
-constexpr int RANGE_SUB = 1024;             // columns per wave of the pack = granularity of the counts and the scan
-constexpr int RANGE_SUBS = RANGE_CHUNK / RANGE_SUB;
-
-struct RangeLds {
-    int cand[RANGE_CHUNK];                  // columns inside the band (any order: their results go back into S by column)
-    int n_cand;
-    int kept[RANGE_SUBS];
-};
-
-// the threshold of query q, or NaN for a query that gets an empty segment (workgroup-uniform)
-__device__ __forceinline__ float range_threshold(const RangeSearchArgs& p, int q) {
-    const float t = p.thresholds[q];
-    const int f = p.filter_of_query ? p.filter_of_query[q] : -1;
-    const bool ok = t == t && fabsf(t) != INFINITY && (f == -1 || (unsigned)f < (unsigned)p.n_filters);
-    return ok ? t : __builtin_nanf("");
-}
-
-__device__ __forceinline__ int64_t range_subs(int64_t n_docs) { return (n_docs + RANGE_SUB - 1) / RANGE_SUB; }
+__device__ __forceinline__ int64_t range_subs(int64_t n_docs) { return (n_docs + RESCORE_SUB - 1) / RESCORE_SUB; }
 
 __global__ __launch_bounds__(256) void range_rescore_kernel(RangeSearchArgs p, float* __restrict__ S, size_t ldS,
                                                             int* __restrict__ counts) {
-    __shared__ RangeLds L;
+    __shared__ ChunkLds L;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const SearchArgs& a = p.a;
     const int q = blockIdx.y, n_docs = (int)a.n_docs, nv = a.dim >> 2;
-    const int c0 = blockIdx.x * RANGE_CHUNK, c1 = min(c0 + RANGE_CHUNK, n_docs);
+    const int c0 = blockIdx.x * RESCORE_CHUNK, c1 = min(c0 + RESCORE_CHUNK, n_docs);
     const int64_t nsub = range_subs(a.n_docs);
-    int* cnt = counts + (size_t)q * nsub + (size_t)blockIdx.x * RANGE_SUBS;
-    const int my_subs = (c1 - c0 + RANGE_SUB - 1) / RANGE_SUB;             // 1..4 counts belong to this workgroup
+    int* cnt = counts + (size_t)q * nsub + (size_t)blockIdx.x * RESCORE_SUBS;
+    const int my_subs = (c1 - c0 + RESCORE_SUB - 1) / RESCORE_SUB;         // 1..4 counts belong to this workgroup
     if (blockIdx.x == 0 && tid == 0) atomicAdd(&p.stats[0], 1ull);
-    const float t = range_threshold(p, q);
+    const float t = range_threshold(p.thresholds, p.filter_of_query, p.n_filters, q);
     if (t != t) {                                                          // (workgroup-uniform) an empty segment
         if (tid < my_subs) cnt[tid] = 0;
         return;
     }
-    if (tid == 0) L.n_cand = 0;
-    if (tid < RANGE_SUBS) L.kept[tid] = 0;
     f32x4 qv[MERGE_MAXV];
     load_query_regs(qv, a.q_f32 + (size_t)q * a.dim, nv, lane);
     const float bound = one_ulp_down(t - query_eps(a, qv));
-    __syncthreads();
     // ---- the band: columns with b >= bound (a masked column is -inf, the bound is finite)
     float* row = S + (size_t)q * ldS;
-    for (int i0 = c0 + tid * 4; i0 < c1; i0 += 256 * 4) {                  // (c0 and ldS are multiples of 4: aligned; < ldS)
-        const f32x4 b = *reinterpret_cast<const f32x4*>(row + i0);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) band_append(i0 + e < c1 && b[e] >= bound, i0 + e, L.cand, &L.n_cand);   // (< RANGE_CHUNK: one slot per column)
-    }
+    chunk_scan<4, false>(row, c0, c1, bound, INFINITY, L);
     __syncthreads();
     // ---- fp32 re-scoring, one candidate per wave
     const int m = L.n_cand;
@@ -82,7 +57,7 @@ __global__ __launch_bounds__(256) void range_rescore_kernel(RangeSearchArgs p, f
         if (lane == 0) {
             const bool keep = s >= t;
             row[id] = keep ? s : -INFINITY;
-            if (keep) atomicAdd(&L.kept[(id - c0) / RANGE_SUB], 1);
+            if (keep) atomicAdd(&L.kept[(id - c0) / RESCORE_SUB], 1);
         }
     }
     __syncthreads();
@@ -143,10 +118,10 @@ __global__ __launch_bounds__(256) void range_pack_kernel(RangeSearchArgs p, cons
                                                          const int64_t* __restrict__ lims) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = blockIdx.y, n_docs = (int)p.a.n_docs;
-    const int s0 = blockIdx.x * RANGE_CHUNK + wave * RANGE_SUB, s1 = min(s0 + RANGE_SUB, n_docs);
+    const int s0 = blockIdx.x * RESCORE_CHUNK + wave * RESCORE_SUB, s1 = min(s0 + RESCORE_SUB, n_docs);
     if (s0 >= n_docs) return;                                              // (wave-uniform, no barrier below)
     const int64_t nsub = range_subs(p.a.n_docs);
-    const size_t slot = (size_t)q * nsub + (size_t)blockIdx.x * RANGE_SUBS + wave;
+    const size_t slot = (size_t)q * nsub + (size_t)blockIdx.x * RESCORE_SUBS + wave;
     if (counts[slot] == 0) return;                                         // (also: every query with an empty segment)
     const float t = p.thresholds[q];
     int64_t run = lims[q] + offs[slot];                                    // (lims: the block's first query's entry, as the scan got it)
@@ -177,18 +152,16 @@ __global__ __launch_bounds__(256) void range_pack_kernel(RangeSearchArgs p, cons
 }
 
 bool range_dim_ok(int dim) { return dim >= 4 && dim % 4 == 0 && dim <= 64 * 4 * MERGE_MAXV; }
-int64_t range_scan_slots(int64_t n_docs) { return (n_docs + RANGE_SUB - 1) / RANGE_SUB; }
+int64_t range_scan_slots(int64_t n_docs) { return (n_docs + RESCORE_SUB - 1) / RESCORE_SUB; }
 
 static bool range_args_ok(const RangeSearchArgs& p, size_t ldS, int nq_block) {
-    const SearchArgs& a = p.a;
-    return nq_block >= 1 && nq_block <= 256 && a.n_docs >= 1 && a.n_docs < ((int64_t)1 << 31) && range_dim_ok(a.dim) && a.index_f32 &&
-           a.q_f32 && a.dmax && (a.eps_data || a.eps_rel >= 0.f) && p.thresholds && p.stats && ldS % 4 == 0 &&
-           (int64_t)ldS >= a.n_docs && (!p.filter_of_query || p.n_filters >= 1);
+    return rescore_args_ok(p.a, nq_block) && p.thresholds && p.stats && ldS % 4 == 0 && (int64_t)ldS >= p.a.n_docs &&
+           (!p.filter_of_query || p.n_filters >= 1);
 }
 
 hipError_t launch_range_rescore(const RangeSearchArgs& p, float* S, size_t ldS, int nq_block, int* counts, hipStream_t s) {
     if (!range_args_ok(p, ldS, nq_block) || !S || !counts) return hipErrorInvalidValue;
-    const unsigned chunks = (unsigned)((p.a.n_docs + RANGE_CHUNK - 1) / RANGE_CHUNK);
+    const unsigned chunks = (unsigned)((p.a.n_docs + RESCORE_CHUNK - 1) / RESCORE_CHUNK);
     hipLaunchKernelGGL(range_rescore_kernel, dim3(chunks, (unsigned)nq_block), dim3(256), 0, s, p, S, ldS, counts);
     return hipGetLastError();
 }
@@ -204,7 +177,7 @@ hipError_t launch_range_scan(const int* counts, int* offs, int64_t n_docs, int n
 hipError_t launch_range_pack(const RangeSearchArgs& p, const float* S, size_t ldS, int nq_block, const int* counts, const int* offs,
                              const int64_t* lims, hipStream_t s) {
     if (!range_args_ok(p, ldS, nq_block) || !S || !counts || !offs || !p.out_scores || !p.out_ids || !lims) return hipErrorInvalidValue;
-    const unsigned chunks = (unsigned)((p.a.n_docs + RANGE_CHUNK - 1) / RANGE_CHUNK);
+    const unsigned chunks = (unsigned)((p.a.n_docs + RESCORE_CHUNK - 1) / RESCORE_CHUNK);
     hipLaunchKernelGGL(range_pack_kernel, dim3(chunks, (unsigned)nq_block), dim3(256), 0, s, p, S, ldS, counts, offs, lims);
     return hipGetLastError();
 }

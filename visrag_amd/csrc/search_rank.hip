@@ -12,26 +12,19 @@
 //      filter index outside [-1, n_filters) (a device caller's: it cannot be seen before the launch) leaves the count at 0;
 //   3. rank_count_kernel, one workgroup per (column chunk of 4096, pair): lo = one_ulp_down(t - eps), hi = the next float above
 //      t + eps.  b > hi: counted from the bf16 score alone; b < lo: skipped; the columns in [lo, hi] are compacted into an LDS
-//      list (ballot + popcount, as range_rescore_kernel does) and re-scored one candidate per wave, the row's loads issued in
-//      front of dot_lane's fma chain (profiles/diverse_search_bench.txt): a rank compares keys (score descending, then lower id
+//      list (search_rescore.h: chunk_scan) and re-scored one candidate per wave, the row's loads issued in front of the fma
+//      chain (search_common.h: exact_row_score; profiles/diverse_search_bench.txt): a rank compares keys (score descending, then lower id
 //      first), a count compares floats (>= t, or > t when strict).  The target lies in its own band and compares equal: it never
 //      counts itself.  S is only read — several pairs share a score row.  The workgroup's total is added to the pair's 64-bit
 //      count: integer adds commute, the result does not depend on the order; no workgroup waits for another.
 // Pairs are laid along the grid's x dimension (chunk fastest), a launch holds at most 2^22 workgroups: no pair count is assumed
 // to fit a grid's y or z.  No kernel looks at or past column n_docs of a score row: the padded columns hold zeros.
 #include "kernels.h"
-#include "search_common.h"
+#include "search_rescore.h"
 
 namespace vr {
 
-constexpr int RANK_CHUNK = 4096;            // columns per workgroup (the range search's chunk)
 constexpr int64_t RANK_MAX_WGS = (int64_t)1 << 22;   // workgroups per launch of the counting kernel
-
-struct RankLds {
-    int cand[RANK_CHUNK];                   // columns inside the band, any order
-    int n_cand;
-    unsigned ahead;                         // rows of this chunk ahead of the bar
-};
 
 __global__ __launch_bounds__(256) void rank_bar_kernel(RankSearchArgs p, int n_pairs) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -43,8 +36,8 @@ __global__ __launch_bounds__(256) void rank_bar_kernel(RankSearchArgs p, int n_p
     f32x4 qv[MERGE_MAXV];
     load_query_regs(qv, a.q_f32 + (size_t)q * a.dim, nv, lane);
     float eps = query_eps(a, qv);
-    const int f = p.filter_of_query ? p.filter_of_query[q] : -1;
-    if (!(f == -1 || (unsigned)f < (unsigned)p.n_filters)) eps = __builtin_nanf("");   // nothing is allowed: the count stays 0
+    // a filter index out of range: nothing is allowed, the count stays 0
+    if (!filter_index_ok(p.filter_of_query ? p.filter_of_query[q] : -1, p.n_filters)) eps = __builtin_nanf("");
     unsigned long long bar;
     if (p.pair_id) {
         const uint32_t id = (uint32_t)p.pair_id[pair];                     // (in [0, n_docs): the host checked it)
@@ -64,32 +57,20 @@ __global__ __launch_bounds__(256) void rank_bar_kernel(RankSearchArgs p, int n_p
 
 __global__ __launch_bounds__(256) void rank_count_kernel(RankSearchArgs p, const float* __restrict__ S, size_t ldS, int pair0,
                                                          int chunks) {
-    __shared__ RankLds L;
+    __shared__ ChunkLds L;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const SearchArgs& a = p.a;
     const int pair = pair0 + (int)(blockIdx.x / (unsigned)chunks), chunk = (int)(blockIdx.x % (unsigned)chunks);
     const float eps = p.bar_eps[pair];
     if (eps != eps) return;                                                // (workgroup-uniform) a filter index out of range
     const int q = p.pair_query[pair], n_docs = (int)a.n_docs, nv = a.dim >> 2;
-    const int c0 = chunk * RANK_CHUNK, c1 = min(c0 + RANK_CHUNK, n_docs);
+    const int c0 = chunk * RESCORE_CHUNK, c1 = min(c0 + RESCORE_CHUNK, n_docs);
     const unsigned long long bar = p.bars[pair];
     const bool by_key = p.pair_id != nullptr;
     const float t = by_key ? key_score(bar) : __uint_as_float((uint32_t)bar);
     const float lo = one_ulp_down(t - eps), hi = one_ulp_up(t + eps);
-    if (tid == 0) { L.n_cand = 0; L.ahead = 0u; }
-    __syncthreads();
     // ---- certainly ahead: b > hi; the band: lo <= b <= hi (a masked column is -inf, lo is finite)
-    const float* row = S + (size_t)q * ldS;
-    unsigned mine = 0;                      // rows ahead of the bar this wave found (complete in lane 0: it leaves the loop last)
-    for (int i0 = c0 + tid * 4; i0 < c1; i0 += 256 * 4) {                  // (c0 and ldS are multiples of 4: aligned; < ldS)
-        const f32x4 b = *reinterpret_cast<const f32x4*>(row + i0);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const bool valid = i0 + e < c1;
-            mine += (unsigned)__popcll(__ballot(valid && b[e] > hi));
-            band_append(valid && b[e] >= lo && b[e] <= hi, i0 + e, L.cand, &L.n_cand);  // (< RANK_CHUNK: one slot per column)
-        }
-    }
+    unsigned mine = chunk_scan<4, false>(S + (size_t)q * ldS, c0, c1, lo, hi, L);   // rows ahead of the bar this wave found
     __syncthreads();
     // ---- fp32 re-scoring of the band, one candidate per wave
     const int m = L.n_cand;
@@ -98,9 +79,7 @@ __global__ __launch_bounds__(256) void rank_count_kernel(RankSearchArgs p, const
         load_query_regs(qv, a.q_f32 + (size_t)q * a.dim, nv, lane);
         for (int c = wave; c < m; c += 4) {
             const int id = L.cand[c];
-            f32x4 dv[MERGE_MAXV];
-            load_row_regs(dv, a.index_f32 + (size_t)id * a.dim, nv, lane);
-            const float s = wave_sum(dot_regs(qv, dv, nv, lane));
+            const float s = exact_row_score(a, qv, id, nv, lane);
             const bool ahead = by_key ? make_key(s, (uint32_t)id) > bar : (p.strict ? s > t : s >= t);
             mine += ahead ? 1u : 0u;                                       // (every lane holds the same s)
         }
@@ -118,11 +97,9 @@ __global__ __launch_bounds__(256) void rank_count_kernel(RankSearchArgs p, const
 }
 
 static bool rank_args_ok(const RankSearchArgs& p, size_t ldS, int nq_block, int64_t n_pairs) {
-    const SearchArgs& a = p.a;
-    return nq_block >= 1 && nq_block <= 256 && n_pairs >= 1 && n_pairs < ((int64_t)1 << 31) && a.n_docs >= 1 &&
-           a.n_docs < ((int64_t)1 << 31) && range_dim_ok(a.dim) && a.index_f32 && a.q_f32 && a.dmax && (a.eps_data || a.eps_rel >= 0.f) &&
-           p.pair_query && ((p.pair_id != nullptr) != (p.pair_thr != nullptr)) && (!p.pair_id || p.out_scores) && p.bars && p.bar_eps &&
-           p.out_counts && p.stats && ldS % 4 == 0 && (int64_t)ldS >= a.n_docs && (!p.filter_of_query || p.n_filters >= 1);
+    return rescore_args_ok(p.a, nq_block) && n_pairs >= 1 && n_pairs < ((int64_t)1 << 31) && p.pair_query &&
+           ((p.pair_id != nullptr) != (p.pair_thr != nullptr)) && (!p.pair_id || p.out_scores) && p.bars && p.bar_eps &&
+           p.out_counts && p.stats && ldS % 4 == 0 && (int64_t)ldS >= p.a.n_docs && (!p.filter_of_query || p.n_filters >= 1);
 }
 
 hipError_t launch_rank_bars(const RankSearchArgs& p, size_t ldS, int nq_block, int64_t n_pairs, hipStream_t s) {
@@ -133,7 +110,7 @@ hipError_t launch_rank_bars(const RankSearchArgs& p, size_t ldS, int nq_block, i
 
 hipError_t launch_rank_count(const RankSearchArgs& p, const float* S, size_t ldS, int nq_block, int64_t n_pairs, hipStream_t s) {
     if (!rank_args_ok(p, ldS, nq_block, n_pairs) || !S) return hipErrorInvalidValue;
-    const int64_t chunks = (p.a.n_docs + RANK_CHUNK - 1) / RANK_CHUNK;
+    const int64_t chunks = (p.a.n_docs + RESCORE_CHUNK - 1) / RESCORE_CHUNK;
     const int64_t per_launch = RANK_MAX_WGS / chunks;                      // (chunks < 2^19: at least 8 pairs)
     for (int64_t p0 = 0; p0 < n_pairs; p0 += per_launch) {
         const int64_t np = n_pairs - p0 < per_launch ? n_pairs - p0 : per_launch;

@@ -6,7 +6,10 @@
 //                   among the keys equal to it — the one place where "lowest ids first at the threshold" is decided;
 //   gather_window   the positions at ranks [o, kz) between two such keys, the same tie rule at both edges (search_window.hip:
 //                   values = a rewritten score row; search_group_window.hip: values = rewritten group maxima).
-// What is done with the candidates (re-scoring, certification, output) is the kernels' own.
+//   top_positions / window_positions / sort_gathered   the select-and-gather fronts and the sorting tail of the kernels that
+//                   select from a row of final fp32 scores;
+//   certified_select  the deep path's flow over a row of bf16 scores: K' best, re-score, tau, gather again or flag.
+// What a candidate's exact key is, and the output, are the kernels' own.
 // Also here: flag_slots, the part of a flag list that one launch of a fallback kernel walks.
 #pragma once
 #include "kernels.h"
@@ -170,6 +173,91 @@ __device__ __forceinline__ int gather_window(const float* __restrict__ vals, int
         __syncthreads();
     }
     return L.run[2];
+}
+
+// ---- what the selecting kernels do with the two gathers: each is called by the whole workgroup, the LDS free (barrier) ----
+// the positions at ranks [0, kz) of vals[0, n) into L.cand, ascending (1 <= kz <= n); returns the kz-th largest key
+template <bool NAN_LOW = false>
+__device__ __forceinline__ KthKey top_positions(const float* __restrict__ vals, int n, int kz, SelectLds& L) {
+    const KthKey kth = select_kth<NAN_LOW>(vals, n, kz, L);
+    gather_ordered<NAN_LOW>(vals, n, kth.T, kz - kth.need_eq, kth.need_eq, SEL_CAND, L);
+    return kth;
+}
+
+// the positions at ranks [o, kz) of vals[0, n) into L.s.cand, ascending (0 <= o < kz <= n); returns how many were stored
+__device__ __forceinline__ int window_positions(const float* __restrict__ vals, int n, int o, int kz, WindowSelectLds& L) {
+    KthKey ka{0xFFFFFFFFu, 0};
+    if (o > 0) {
+        ka = select_kth(vals, n, o, L.s);
+        __syncthreads();
+    }
+    const KthKey kzk = select_kth(vals, n, kz, L.s);
+    __syncthreads();
+    return min(gather_window(vals, n, ka, o > 0, kzk, L), SEL_CAND);
+}
+
+// keys make_key(vals[i], i) of the n_sel gathered positions, padded to n_sort (a power of two) and sorted: L.keys[0, n_sort)
+__device__ __forceinline__ void sort_gathered(const float* __restrict__ vals, int n_sel, int n_sort, SelectLds& L) {
+    const int tid = threadIdx.x;
+    for (int c = tid; c < n_sort; c += 256) {
+        uint64_t key = KEY_NONE;
+        if (c < n_sel) { const int i = L.cand[c]; key = make_key(vals[i], (uint32_t)i); }
+        L.keys[c] = key;
+    }
+    __syncthreads();
+    block_bitonic_desc(L.keys, n_sort, tid, 256);
+}
+
+// n_sort of a launch: the power of two (>= 64) that holds k keys
+inline int sort_width(int k) {
+    int n_sort = 64;
+    while (n_sort < k) n_sort <<= 1;
+    return n_sort;
+}
+
+// ---- the certifying select (search_bigk.hip has the why; search_filter.hip and search_group.hip run it on their own rows) ----
+// The kp best of vals[0, n), gathered by top_positions<NAN_LOW> (T: the key it returned; the kernel loads its query between the
+// two, so that the select runs without it), are re-scored (key_of(c): the exact key of candidate position c, called by a whole
+// wave, wave-uniform) and sorted into L.keys.  universe = how many positions can rank at all.  With `certify`, and candidates
+// left outside (kp < universe): tau = (k-th exact score) - eps_of(), lowered by one ulp with TAU_DOWN; a candidate
+// outside has a value <= the kp-th; if that does not lie below tau, EVERY position with a value >= tau is gathered and
+// re-scored instead (up to SEL_CAND), else the query is to be flagged.  Returns how many keys of L.keys stand; *what: 0 certified
+// as it stood, 1 after the second gather, 2 to be flagged; *tau: -inf where none was taken.
+// NAN_LOW (the plain search: ranked keys): a NaN value is selected last, and with fewer than k numbers among the re-scored —
+// the candidates then hold EVERY position that ranks: a NaN query, or fewer than k rows free of NaN — the result stands as it is.
+// Called by the whole workgroup, the LDS free (barrier).
+template <bool NAN_LOW, bool TAU_DOWN, typename KeyOf, typename EpsOf>
+__device__ __forceinline__ int certified_select(const float* __restrict__ vals, int n, int universe, int kp, unsigned T, int k,
+                                                bool certify, KeyOf key_of, EpsOf eps_of, SelectLds& L, int* what, float* tau) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    auto rescore_sort = [&](int m) {
+        int n2 = 1;
+        while (n2 < m) n2 <<= 1;
+        for (int c = m + tid; c < n2; c += 256) L.keys[c] = KEY_NONE;
+        for (int c = wave; c < m; c += 4) {
+            const uint64_t key = key_of(L.cand[c]);
+            if (lane == 0) L.keys[c] = key;
+        }
+        __syncthreads();
+        block_bitonic_desc(L.keys, n2, tid, 256);
+    };
+    rescore_sort(kp);
+    *what = 0;
+    *tau = -INFINITY;
+    if (certify && kp < universe && (!NAN_LOW || L.keys[k - 1] != KEY_NONE)) {      // kp >= k here (kp < universe => kp = k + margin)
+        const float t = key_score(L.keys[k - 1]) - eps_of();
+        *tau = TAU_DOWN ? one_ulp_down(t) : t;
+        if (!(orderable_f32(T) < *tau)) {
+            // every position whose value is >= tau (strictly above the key just below tau's)
+            __syncthreads();
+            const unsigned tk = f32_orderable(*tau);
+            const int m = gather_ordered<NAN_LOW>(vals, n, tk ? tk - 1u : 0u, 0, 0, SEL_CAND, L);
+            __syncthreads();
+            if (m <= SEL_CAND && m >= kp) { rescore_sort(m); kp = m; *what = 1; }
+            else *what = 2;
+        }
+    }
+    return kp;
 }
 
 }  // namespace vr

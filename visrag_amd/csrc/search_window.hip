@@ -19,8 +19,8 @@
 //      float above v_a + 2 eps;
 //   3. window_rescore_kernel, grid (column chunk of 4096, query): the row is REWRITTEN in place so that it alone defines the
 //      answer: +inf for b > hi (certainly ahead), -inf for b < lo (certainly behind, or masked), and for the columns in
-//      [lo, hi] — compacted into an LDS list by ballot + popcount, re-scored one candidate per wave with the row's loads issued
-//      in front of the fma chain (profiles/diverse_search_bench.txt) — their fp32 score e.  The A rows of +inf then occupy
+//      [lo, hi] — compacted into an LDS list (search_rescore.h: chunk_scan), re-scored one candidate per wave with the row's loads
+//      issued in front of the fma chain (exact_row_score; profiles/diverse_search_bench.txt) — their fp32 score e.  The A rows of +inf then occupy
 //      ranks 0 .. A - 1 of the rewritten row (id order), every band row stands where its key puts it, and the window is ranks
 //      o .. o + k - 1 of the rewritten row: no per-query counter to subtract.  A column is written by one thread only;
 //   4. window_select_kernel, one workgroup per query: radix selects for rank o (when o > 0) and rank min(o + k, na) of the
@@ -31,17 +31,9 @@
 // No kernel waits for another workgroup; stream order between the launches is the only ordering.  No kernel reads a column at
 // or past n_docs as a value or writes one: the padded columns hold zeros.
 #include "kernels.h"
-#include "search_select.h"
+#include "search_rescore.h"
 
 namespace vr {
-
-constexpr int WIN_CHUNK = 4096;             // columns per workgroup of the re-scoring (the range and the rank search's chunk)
-
-struct WindowLds {
-    int cand[WIN_CHUNK];                    // columns inside the band, any order
-    int n_cand;
-    unsigned ahead;                         // rows of this chunk certainly ahead of the window
-};
 
 __global__ __launch_bounds__(256) void window_edge_kernel(WindowSearchArgs p, const float* __restrict__ S, size_t ldS) {
     __shared__ SelectLds L;
@@ -60,52 +52,21 @@ __global__ __launch_bounds__(256) void window_edge_kernel(WindowSearchArgs p, co
     const float eps = query_eps(a, qv);                                    // (every wave computes the same value)
     const float* row = S + (size_t)q * ldS;
     const int kz = (int)min(o + (int64_t)a.k, (int64_t)na);                // 1 <= o + 1 <= kz <= na
-    const KthKey ka = select_kth(row, n_docs, (int)o + 1, L);
-    __syncthreads();
-    const KthKey kz_key = select_kth(row, n_docs, kz, L);
-    if (tid == 0) {
-        const float va = orderable_f32(ka.T), vz = orderable_f32(kz_key.T);
-        p.edges[2 * q] = one_ulp_down(vz - 2.f * eps);
-        p.edges[2 * q + 1] = one_ulp_up(va + 2.f * eps);
-    }
+    const BandEdges e = window_edges(row, n_docs, (int)o, kz, eps, L);
+    if (tid == 0) { p.edges[2 * q] = e.lo; p.edges[2 * q + 1] = e.hi; }
 }
 
 __global__ __launch_bounds__(256) void window_rescore_kernel(WindowSearchArgs p, float* __restrict__ S, size_t ldS) {
-    __shared__ WindowLds L;
+    __shared__ ChunkLds L;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const SearchArgs& a = p.a;
     const int q = blockIdx.y, n_docs = (int)a.n_docs, nv = a.dim >> 2;
     const float lo = p.edges[2 * q], hi = p.edges[2 * q + 1];
     if (lo != lo) return;                                                  // (workgroup-uniform) an empty window
-    const int c0 = blockIdx.x * WIN_CHUNK, c1 = min(c0 + WIN_CHUNK, n_docs);
-    if (tid == 0) { L.n_cand = 0; L.ahead = 0u; }
-    __syncthreads();
+    const int c0 = blockIdx.x * RESCORE_CHUNK, c1 = min(c0 + RESCORE_CHUNK, n_docs);
     // ---- certainly ahead: b > hi -> +inf; certainly behind or masked: b < lo -> -inf; the band lo <= b <= hi: listed
     float* row = S + (size_t)q * ldS;
-    unsigned mine = 0;                      // rows certainly ahead this wave found (complete in lane 0: it leaves the loop last)
-    for (int i0 = c0 + tid * 4; i0 < c1; i0 += 256 * 4) {                  // (c0 and ldS are multiples of 4: aligned; < ldS)
-        const f32x4 b = *reinterpret_cast<const f32x4*>(row + i0);
-        f32x4 w;
-        bool any_band = false;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const bool valid = i0 + e < c1;
-            const bool up = valid && b[e] > hi;
-            const bool in = valid && b[e] >= lo && b[e] <= hi;
-            w[e] = up ? INFINITY : -INFINITY;
-            any_band |= in;
-            mine += (unsigned)__popcll(__ballot(up));
-            band_append(in, i0 + e, L.cand, &L.n_cand);                    // (< WIN_CHUNK: one slot per column)
-        }
-        // a band column is written by the wave that re-scores it, a column at or past n_docs by nobody
-        if (i0 + 4 <= c1 && !any_band) {
-            *reinterpret_cast<f32x4*>(row + i0) = w;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (i0 + e < c1 && !(b[e] >= lo && b[e] <= hi)) row[i0 + e] = w[e];
-        }
-    }
+    const unsigned mine = chunk_scan<4, true>(row, c0, c1, lo, hi, L);     // rows certainly ahead this wave found
     if (lane == 0 && mine) atomicAdd(&L.ahead, mine);
     __syncthreads();
     // ---- fp32 re-scoring of the band, one candidate per wave
@@ -115,9 +76,7 @@ __global__ __launch_bounds__(256) void window_rescore_kernel(WindowSearchArgs p,
         load_query_regs(qv, a.q_f32 + (size_t)q * a.dim, nv, lane);
         for (int c = wave; c < m; c += 4) {
             const int id = L.cand[c];
-            f32x4 dv[MERGE_MAXV];
-            load_row_regs(dv, a.index_f32 + (size_t)id * a.dim, nv, lane);
-            const float s = wave_sum(dot_regs(qv, dv, nv, lane));
+            const float s = exact_row_score(a, qv, id, nv, lane);
             if (lane == 0) row[id] = s;
         }
     }
@@ -142,30 +101,13 @@ __global__ __launch_bounds__(256) void window_select_kernel(WindowSearchArgs p, 
     const int o = (int)p.offsets[q];                                       // (< na: the edge kernel saw it)
     const int kz = (int)min((int64_t)o + k, (int64_t)na);
     const float* row = S + (size_t)q * ldS;
-    KthKey ka{0xFFFFFFFFu, 0};
-    if (o > 0) {
-        ka = select_kth(row, n_docs, o, L.s);
-        __syncthreads();
-    }
-    const KthKey kzk = select_kth(row, n_docs, kz, L.s);
-    __syncthreads();
-    const int n_sel = min(gather_window(row, n_docs, ka, o > 0, kzk, L), SEL_CAND);
-    for (int c = tid; c < n_sort; c += 256) {
-        uint64_t key = KEY_NONE;
-        if (c < n_sel) { const int i = L.s.cand[c]; key = make_key(row[i], (uint32_t)i); }
-        L.s.keys[c] = key;
-    }
-    __syncthreads();
-    block_bitonic_desc(L.s.keys, n_sort, tid, 256);
+    sort_gathered(row, window_positions(row, n_docs, o, kz, L), n_sort, L.s);
     for (int c = tid; c < k; c += 256) emit_slot(a, q, c, L.s.keys[c]);
 }
 
 static bool window_args_ok(const WindowSearchArgs& p, size_t ldS, int nq_block) {
-    const SearchArgs& a = p.a;
-    return nq_block >= 1 && nq_block <= 256 && a.n_docs >= 1 && a.n_docs < ((int64_t)1 << 31) && range_dim_ok(a.dim) && a.index_f32 &&
-           a.q_f32 && a.dmax && (a.eps_data || a.eps_rel >= 0.f) && a.k >= 1 && a.k <= SEL_CAND - SEL_MARGIN && a.out_scores &&
-           a.out_ids && !a.out_keys && p.offsets && p.edges && p.stats && ldS % 4 == 0 && (int64_t)ldS >= a.n_docs &&
-           (!p.filter_of_query || (p.n_filters >= 1 && p.allowed));
+    return rescore_args_ok(p.a, nq_block) && topk_out_ok(p.a) && p.offsets && p.edges && p.stats && ldS % 4 == 0 &&
+           (int64_t)ldS >= p.a.n_docs && (!p.filter_of_query || (p.n_filters >= 1 && p.allowed));
 }
 
 hipError_t launch_window_edges(const WindowSearchArgs& p, const float* S, size_t ldS, int nq_block, hipStream_t s) {
@@ -176,16 +118,14 @@ hipError_t launch_window_edges(const WindowSearchArgs& p, const float* S, size_t
 
 hipError_t launch_window_rescore(const WindowSearchArgs& p, float* S, size_t ldS, int nq_block, hipStream_t s) {
     if (!window_args_ok(p, ldS, nq_block) || !S) return hipErrorInvalidValue;
-    const unsigned chunks = (unsigned)((p.a.n_docs + WIN_CHUNK - 1) / WIN_CHUNK);
+    const unsigned chunks = (unsigned)((p.a.n_docs + RESCORE_CHUNK - 1) / RESCORE_CHUNK);
     hipLaunchKernelGGL(window_rescore_kernel, dim3(chunks, (unsigned)nq_block), dim3(256), 0, s, p, S, ldS);
     return hipGetLastError();
 }
 
 hipError_t launch_window_select(const WindowSearchArgs& p, const float* S, size_t ldS, int nq_block, hipStream_t s) {
     if (!window_args_ok(p, ldS, nq_block) || !S) return hipErrorInvalidValue;
-    int n_sort = 64;                                                       // the power of two that holds k keys
-    while (n_sort < p.a.k) n_sort <<= 1;
-    hipLaunchKernelGGL(window_select_kernel, dim3((unsigned)nq_block), dim3(256), 0, s, p, S, ldS, n_sort);
+    hipLaunchKernelGGL(window_select_kernel, dim3((unsigned)nq_block), dim3(256), 0, s, p, S, ldS, sort_width(p.a.k));
     return hipGetLastError();
 }
 
