@@ -288,6 +288,46 @@ int vr_chat_score(vr_chat_t ch, int32_t B, const uint8_t* const* slices, const i
                   int32_t slices_on_device, const int32_t* input_ids, const int32_t* seq_offsets, const int32_t* vision_rows,
                   const int32_t* cont_len, float* out_logit, float* out_lse, float* out_top_logit, int32_t* out_top_token,
                   void* stream);
+/* Several GIVEN tokens appended to prompts that are already cached, in ONE packed decoder pass on the bf16 route: tokens
+ * [tok_offsets[b], tok_offsets[b + 1]) go to row rows[b] of slot slots[b].  Binding as in vr_chat_step: a row with an empty
+ * tail may start on any slot that holds a prompt, a row with a tail continues its slot; several rows may share a slot and
+ * need not be adjacent.  Token j of a row whose tail holds t0 tokens sits at tail index t0 + j and position plen + t0 + j (the
+ * chat's own RoPE table); every layer's rope'd K / V rows go to the row's tail, and the attention reads the slot's prompt
+ * keys, then the row's tail keys up to the token's own (csrc/chat_extend.hip).  Afterwards the row's tail holds t0 + n
+ * tokens, its current logits are those after its last appended token (vr_chat_select / vr_chat_sample / vr_chat_step /
+ * vr_chat_row_score continue from there); the logits of rows the call does not name stay readable.
+ *   seen_mode 0 leaves the row's seen set alone, 1 adds the appended ids (forced tokens that count as generated), 2 clears
+ * it (a new turn); a row that starts on a slot starts with an empty set in every mode.
+ *   targets NULL: nothing is scored, the stream is not synchronised.  Otherwise targets [sum n] (-1 = none): entry t is the
+ * distribution AFTER packed token t evaluated at targets[t], the four numbers of vr_chat_score; entries whose target is -1
+ * are left untouched.  Synchronises the stream.
+ *   Checked before any state changes, state and outputs untouched: a NULL pointer, B < 1, an empty token list, a token or
+ * target id out of range, a slot without a prompt, a repeated row, a row that continues another slot: VR_ERR_INVALID;
+ * B > max_rows, t0 + n > max_new, plen + t0 + n > max_len, sum n > the model's max_tokens, B > its max_seqs:
+ * VR_ERR_CAPACITY; no head loaded: VR_ERR_STATE. */
+int vr_chat_extend(vr_chat_t ch, int32_t B, const int32_t* slots, const int32_t* rows, const int32_t* tok_offsets,
+                   const int32_t* tokens, const int32_t* targets, int32_t seen_mode, float* out_logit, float* out_lse,
+                   float* out_top_logit, int32_t* out_top_token, void* stream);
+/* The four numbers of vr_chat_score from the CURRENT logits of rows[i] at targets[i] (host arrays [n]; rows may repeat: the
+ * first tokens of several continuations of one prefilled row are one call).  One workgroup per entry over the fp32 logits
+ * row; the lowest id wins among tied maxima.  An id or row out of range: VR_ERR_INVALID; a row without logits:
+ * VR_ERR_STATE.  Synchronises the stream. */
+int vr_chat_row_score(vr_chat_t ch, int32_t n, const int32_t* rows, const int32_t* targets, float* out_logit, float* out_lse,
+                      float* out_top_logit, int32_t* out_top_token, void* stream);
+/* vr_chat_row_score from the logits of a slot's PROMPT, its last position (what a prefill leaves on its row): they outlive the
+ * decode steps of a generation on that slot (steps write other lines) and are lost when a prefill or a vr_chat_extend writes
+ * the logits of the row the prefill named.  slots may repeat.  A slot without a prompt or whose prompt logits are gone:
+ * VR_ERR_STATE; otherwise as vr_chat_row_score.  This is how the first token of a continuation is scored on a prompt that a
+ * finished generation left resident. */
+int vr_chat_slot_score(vr_chat_t ch, int32_t n, const int32_t* slots, const int32_t* targets, float* out_logit, float* out_lse,
+                       float* out_top_logit, int32_t* out_top_token, void* stream);
+/* The prompt tokens `slot` holds (0: none), whether vr_chat_slot_score can still read the prompt's logits, and how often the
+ * slot has been prefilled (vr_chat_prefill / vr_chat_prefill_batch, whoever called them): a caller that keeps a prompt in a slot
+ * compares the count with the one it saw after its own prefill. */
+int vr_chat_slot_state(vr_chat_t ch, int32_t slot, int32_t* prompt_len, int32_t* has_prompt_logits, int32_t* generation);
+/* Shortens the tail of `row` to `length` tokens (0 <= length <= its current length, else VR_ERR_INVALID).  The row loses its
+ * logits, its seen set stays; host state only. */
+int vr_chat_row_truncate(vr_chat_t ch, int32_t row, int32_t length);
 
 /* ---- index: replaces torch.matmul + torch.topk over pickle shards -------------------- */
 /* Reference: _retrieve_one_shard / distributed_parallel_retrieve
@@ -1149,6 +1189,18 @@ int vr_op_chat_attention(int device_id, const void* q, const void* prompt, const
                          int32_t E, int32_t slots, int32_t max_len, int32_t rows, int32_t max_new, int32_t n,
                          const int32_t* step_row, const int32_t* step_slot, const int32_t* step_tail,
                          const int32_t* slot_plen, int32_t force_splits, void* att, void* stream);
+/* vr_chat_extend's two-segment attention (chat_extend.hip) on the caller's buffers, head_dim 64, scale 1/8, `heads` heads
+ * (heads * 64 <= E): q bf16 [seq_off[B]][ldq], head h at column h * 64; caches as vr_op_chat_attention's; layer l.  Sequence b
+ * owns the packed rows [seq_off[b], seq_off[b + 1]) (n_b >= 1 of them): query j sees the prompt keys [0, seq_plen[b]) of slot
+ * seq_slot[b] and the tail keys [0, seq_t0[b] + j] of cache row seq_row[b], which already hold the new tokens' K / V.  out bf16
+ * [seq_off[B]][ldo].  No plane row outside [0, plen) / [0, t0 + n) is read, nothing but the sequence's own out rows is
+ * written.  seq_* are host arrays; 1 <= B <= 16, rows distinct, 1 <= plen <= max_len, t0 >= 0, t0 + n <= max_new, ldq a
+ * multiple of 8, ldo of 4, both >= heads * 64, pointers 16-byte aligned — every check comes before the launch
+ * (VR_ERR_INVALID; B > 16, plen > max_len or t0 + n > max_new: VR_ERR_CAPACITY).  Synchronises the stream. */
+int vr_op_chat_extend_attention(int device_id, const void* q, int32_t ldq, const void* prompt, const void* tails, int32_t layers,
+                                int32_t l, int32_t E, int32_t heads, int32_t slots, int32_t max_len, int32_t rows, int32_t max_new,
+                                int32_t B, const int32_t* seq_row, const int32_t* seq_slot, const int32_t* seq_plen,
+                                const int32_t* seq_t0, const int32_t* seq_off, void* out, int32_t ldo, void* stream);
 /* vr_chat_select's kernels on the caller's logits: logits f32 [n][ld] and seen bit sets u32 [n][words] on the device (row i of
  * both belongs to selected row i), group_offsets [n_groups + 1] and beam_scores [n] (or NULL) on the host.  mode VR_CHAT_*;
  * K candidates are ranked (the sampler draws among them), kout are returned per group: out_* [n_groups][kout] on the host,

@@ -199,6 +199,17 @@ SIGNATURES = {
     "vr_chat_row_len": (C.c_int, [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
     "vr_chat_score": (C.c_int, [_vp, _i32, C.POINTER(_vp), C.POINTER(_i32), _i32, _i32, C.POINTER(_i32), C.POINTER(_i32),
                                 C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_i32), _vp]),
+    "vr_chat_extend": (C.c_int, [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _i32,
+                                 C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_i32), _vp]),
+    "vr_chat_row_score": (C.c_int, [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32),
+                                    C.POINTER(_i32), _vp]),
+    "vr_chat_row_truncate": (C.c_int, [_vp, _i32, _i32]),
+    "vr_chat_slot_score": (C.c_int, [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32),
+                                     C.POINTER(_i32), _vp]),
+    "vr_chat_slot_state": (C.c_int, [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "vr_op_chat_extend_attention": (C.c_int, [C.c_int, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                              C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp,
+                                              _i32, _vp]),
     "vr_op_head_score": (C.c_int, [C.c_int, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 # every symbol include/visrag_gen.h declares (the EVisRAG generator's language model)

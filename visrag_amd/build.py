@@ -19,13 +19,15 @@ from typing import Iterable, List, Optional
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["gemm.hip", "gemm192.hip", "gemm256w.hip", "gemm128w.hip", "gemm_skinny.hip", "norm.hip", "attention.hip", "attention_w.hip", "attention_small.hip", "patch_embed.hip", "misc.hip", "search.hip", "search256.hip", "search256w.hip",
-           "search_small.hip", "search_bigk.hip", "search_exact.hip", "search_band.hip", "search_group.hip", "search_filter.hip", "search_range.hip", "search_rank.hip", "search_window.hip", "search_group_window.hip", "search_group_rank.hip", "search_group_range.hip", "search_multi.hip", "search_multi_group.hip", "search_diverse.hip", "search_rrf.hip", "index_edit.hip", "hp_text.hip", "resize.hip", "synth.hip", "pack.hip", "model.hip", "encode.hip", "index.hip", "index_searches.hip", "index_rows.hip", "ops.hip", "chat.hip", "chat_kernels.hip", "chat_sample.hip", "head_score.hip", "gen_kernels.hip", "gen.hip", "gen_vision.hip"]
+           "search_small.hip", "search_bigk.hip", "search_exact.hip", "search_band.hip", "search_group.hip", "search_filter.hip", "search_range.hip", "search_rank.hip", "search_window.hip", "search_group_window.hip", "search_group_rank.hip", "search_group_range.hip", "search_multi.hip", "search_multi_group.hip", "search_diverse.hip", "search_rrf.hip", "index_edit.hip", "hp_text.hip", "resize.hip", "synth.hip", "pack.hip", "model.hip", "encode.hip", "index.hip", "index_searches.hip", "index_rows.hip", "ops.hip", "chat.hip", "chat_kernels.hip", "chat_sample.hip", "chat_extend.hip", "head_score.hip", "gen_kernels.hip", "gen.hip", "gen_vision.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # attention.hip: relaxed NaN handling only (infinities are honoured: masked scores are -inf).  Without it
 # every fmaxf of an MFMA result is preceded by a canonicalising v_max_f32 x, x (32 extra VALU per tile);
 # same for the clamp of the GELU epilogue (gemm*.hip: one v_max per output value).
 FILE_FLAGS = {"attention.hip": ["-fno-honor-nans"], "attention_w.hip": ["-fno-honor-nans"], "attention_small.hip": ["-fno-honor-nans"], "gemm.hip": ["-fno-honor-nans"], "gemm192.hip": ["-fno-honor-nans"],
               "gemm256w.hip": ["-fno-honor-nans"], "gemm128w.hip": ["-fno-honor-nans"]}
+# chat_extend.hip is deliberately NOT in this table: its two-segment mask selects -inf over scores of masked tail rows that may
+# hold anything finite, on few rows (sum n <= 16 * max_new) where the canonicalising v_max costs nothing measurable.
 # gemm256w.hip hand-allocates the accumulation registers inside asm statements; hipcc only sees them as clobbers,
 # so if it ever runs out of VGPRs there it parks the overflow in registers that hold results.  The build checks
 # the generated code: outside the kernel's own asm there must be no accumulation-register traffic at all.

@@ -28,10 +28,21 @@ struct vr_chat_s {
     std::vector<int> plen;                // per slot: prompt tokens (0 = none)
     std::vector<int> row_slot, row_len;   // per row: its prompt slot (-1 = unbound), generated tokens in its tail
     std::vector<int> lpos;                // per row: its logits row in w_logits (-1 = none)
+    // per slot: the line of w_logits that still holds the logits of the prompt's LAST position (-1 = gone).  A prefill writes
+    // them to line max_rows + row; decode steps write the lower half only, so the line survives a generation and is lost
+    // when a prefill or an extend writes that line again
+    std::vector<int> slot_lrow;
+    std::vector<int> slot_gen;            // per slot: prefills so far (a caller that keeps a slot asks whether it is still its own)
 };
 
 static size_t chat_prompt_off(const vr_chat_s* ch, int l, int kv, int slot) {      // bytes
     return ((((size_t)l * 2 + kv) * ch->c.max_slots + slot) * (size_t)ch->c.max_len * ch->E) * 2;
+}
+
+// logits line `line` is about to be rewritten: no slot's prompt logits live there any more
+static void chat_release_line(vr_chat_s* ch, int line) {
+    for (int& l : ch->slot_lrow)
+        if (l == line) l = -1;
 }
 
 extern "C" int vr_chat_create(vr_model_t m, const vr_chat_config_t* cfg, vr_chat_t* out) {
@@ -87,6 +98,8 @@ extern "C" int vr_chat_create(vr_model_t m, const vr_chat_config_t* cfg, vr_chat
     ch->row_slot.assign(R, -1);
     ch->row_len.assign(R, 0);
     ch->lpos.assign(R, -1);
+    ch->slot_lrow.assign(cfg->max_slots, -1);
+    ch->slot_gen.assign(cfg->max_slots, 0);
     *out = ch;
     return VR_OK;
 }
@@ -140,6 +153,8 @@ extern "C" int vr_chat_prefill(vr_chat_t ch, int32_t slot, int32_t row, const ui
     hipStream_t s = (hipStream_t)stream;
     vr_model_s* w = ch->work;
     ch->plen[slot] = 0;                                  // the slot's cache is rewritten from here on
+    ch->slot_lrow[slot] = -1;
+    ch->slot_gen[slot]++;
     for (int r = 0; r < ch->c.max_rows; ++r)
         if (ch->row_slot[r] == slot) { ch->row_slot[r] = -1; ch->row_len[r] = 0; ch->lpos[r] = -1; }
     ChatPrefillCtx ctx{ch, slot};
@@ -158,12 +173,14 @@ extern "C" int vr_chat_prefill(vr_chat_t ch, int32_t slot, int32_t row, const ui
     HIPCHK(launch_rmsnorm(w->w_h.as<float>() + (size_t)(T - 1) * ch->E, 1, ch->E, ch->E, ch->norm_w.as<float>(), c.rms_norm_eps, ch->w_xn.p,
                           ch->E, s));
     const int lrow = ch->c.max_rows + row;               // prefill logits live in the upper half of w_logits
+    chat_release_line(ch, lrow);
     VRCHK(chat_head(ch, 1, lrow, s));
     HIPCHK(hipMemsetAsync((unsigned*)ch->seen.p + (size_t)row * ch->words, 0, (size_t)ch->words * 4, s));
     ch->plen[slot] = T;
     ch->row_slot[row] = slot;
     ch->row_len[row] = 0;
     ch->lpos[row] = lrow;
+    ch->slot_lrow[slot] = lrow;
     return VR_OK;
 }
 
@@ -207,7 +224,7 @@ extern "C" int vr_chat_prefill_batch(vr_chat_t ch, int32_t B, const int32_t* slo
     hipStream_t s = (hipStream_t)stream;
     // the slots' caches are rewritten from here on: rows that continued them lose their tails
     auto unbind = [&]() {
-        for (int b = 0; b < B; ++b) ch->plen[slots[b]] = 0;
+        for (int b = 0; b < B; ++b) { ch->plen[slots[b]] = 0; ch->slot_lrow[slots[b]] = -1; ch->slot_gen[slots[b]]++; }
         for (int r = 0; r < R; ++r)
             if (ch->row_slot[r] >= 0 && slot_used[ch->row_slot[r]]) { ch->row_slot[r] = -1; ch->row_len[r] = 0; ch->lpos[r] = -1; }
     };
@@ -241,9 +258,11 @@ extern "C" int vr_chat_prefill_batch(vr_chat_t ch, int32_t B, const int32_t* slo
         HIPCHK(launch_gemm_skinny(a, s));
         j += n;
     }
+    for (int b = 0; b < B; ++b) chat_release_line(ch, R + rows[b]);
     for (int b = 0; b < B; ++b) {
         const int r = rows[b];
         HIPCHK(hipMemsetAsync((unsigned*)ch->seen.p + (size_t)r * ch->words, 0, (size_t)ch->words * 4, s));
+        ch->slot_lrow[slots[b]] = R + r;
         ch->plen[slots[b]] = seq_offsets[b + 1] - seq_offsets[b];
         ch->row_slot[r] = slots[b];
         ch->row_len[r] = 0;
@@ -473,6 +492,20 @@ extern "C" int vr_chat_logits(vr_chat_t ch, int32_t row, float* out, void* strea
     return VR_OK;
 }
 
+// the scoring head's buffers (s_*), allocated at the first call that scores
+static int chat_score_scratch(vr_chat_s* ch) {
+    if (ch->s_xn.p) return VR_OK;
+    const int cap = ch->work->c.max_tokens;
+    int rc;
+    if ((rc = ch->s_xn.alloc((size_t)pad256(cap) * ch->head.k_pad * 2)) || (rc = ch->s_part.alloc(head_score_part_words(cap, ch->V) * 4)) ||
+        (rc = ch->s_tgt.alloc((size_t)cap * 4)) || (rc = ch->s_out.alloc((size_t)4 * cap * 4)) ||
+        (rc = ch->s_reps.alloc((size_t)ch->work->c.max_seqs * ch->E * 4))) {
+        ch->s_xn.free();
+        return rc;
+    }
+    return VR_OK;
+}
+
 // ---- teacher-forced scoring: the packed pass of a prefill without its cache side, every continuation position through the
 // fused head (head_score.hip).  Touches none of the generation state: its rows, targets and results live in buffers of its own.
 extern "C" int vr_chat_score(vr_chat_t ch, int32_t B, const uint8_t* const* slices, const int32_t* slice_hw, int32_t n_slices,
@@ -503,15 +536,7 @@ extern "C" int vr_chat_score(vr_chat_t ch, int32_t B, const uint8_t* const* slic
     VRCHK(set_dev(ch->model->device));
     hipStream_t s = (hipStream_t)stream;
     const int E = ch->E, Kp = ch->head.k_pad, cap = w->c.max_tokens;
-    if (!ch->s_xn.p) {
-        int rc;
-        if ((rc = ch->s_xn.alloc((size_t)pad256(cap) * Kp * 2)) || (rc = ch->s_part.alloc(head_score_part_words(cap, ch->V) * 4)) ||
-            (rc = ch->s_tgt.alloc((size_t)cap * 4)) || (rc = ch->s_out.alloc((size_t)4 * cap * 4)) ||
-            (rc = ch->s_reps.alloc((size_t)w->c.max_seqs * E * 4))) {
-            ch->s_xn.free();
-            return rc;
-        }
-    }
+    VRCHK(chat_score_scratch(ch));
     EncodeHook hook;
     hook.bf16_route = true;                              // the route of the prefill; no layer hook: nothing is cached
     w->arena_open = false;
@@ -547,5 +572,207 @@ extern "C" int vr_chat_row_len(vr_chat_t ch, int32_t row, int32_t* slot, int32_t
     if (row < 0 || row >= ch->c.max_rows) return fail(VR_ERR_INVALID, "row %d out of range", row);
     *slot = ch->row_slot[row];
     *generated = ch->row_len[row];
+    return VR_OK;
+}
+
+// ---- several given tokens appended to rows whose prompts are cached: ONE packed decoder pass (the encode pass on the bf16
+// route) whose positions continue the rows, whose per-layer hook stores the rope'd K / V rows in the rows' tails and whose
+// attention reads "prompt plane, then tail plane" (chat_extend.hip)
+struct ChatExtendCtx { vr_chat_s* ch; ChatExtend ex; };
+static int chat_extend_layer(void* ctx, int l, const void* qkv, int ldqkv, int T, hipStream_t s) {
+    const ChatExtendCtx* p = (const ChatExtendCtx*)ctx;
+    vr_chat_s* ch = p->ch;
+    if (T != p->ex.off[p->ex.n]) return fail(VR_ERR_STATE, "extend hook: %d rows, expected %d", T, p->ex.off[p->ex.n]);
+    const size_t plane = (size_t)ch->c.max_rows * ch->c.max_new * ch->E * 2;      // bytes of one (layer, K|V) tail plane
+    HIPCHK(launch_chat_tail_scatter(p->ex, qkv, ldqkv, ch->E, ch->c.max_new, (char*)ch->tails.p + ((size_t)l * 2) * plane,
+                                    (char*)ch->tails.p + ((size_t)l * 2 + 1) * plane, s));
+    return VR_OK;
+}
+static int chat_extend_attn(void* ctx, int l, const void* qkv, int ldqkv, int T, void* out, int ldo, hipStream_t s) {
+    const ChatExtendCtx* p = (const ChatExtendCtx*)ctx;
+    vr_chat_s* ch = p->ch;
+    (void)T;
+    const ChatCaps caps{ch->c.max_slots, ch->c.max_len, ch->c.max_rows, ch->c.max_new};
+    HIPCHK(launch_chat_extend_attn(p->ex, qkv, ldqkv, ch->prompt.p, ch->tails.p, l, ch->E, ch->H, caps, out, ldo, s));
+    return VR_OK;
+}
+
+extern "C" int vr_chat_extend(vr_chat_t ch, int32_t B, const int32_t* slots, const int32_t* rows, const int32_t* tok_offsets,
+                              const int32_t* tokens, const int32_t* targets, int32_t seen_mode, float* out_logit, float* out_lse,
+                              float* out_top_logit, int32_t* out_top_token, void* stream) {
+    if (!ch || !slots || !rows || !tok_offsets || !tokens) return fail(VR_ERR_INVALID, "NULL argument");
+    if (targets && (!out_logit || !out_lse || !out_top_logit || !out_top_token)) return fail(VR_ERR_INVALID, "targets without outputs");
+    if (!ch->head.has_w) return fail(VR_ERR_STATE, "vr_chat_load_head has not run");
+    if (seen_mode < 0 || seen_mode > 2) return fail(VR_ERR_INVALID, "seen_mode %d: 0 (keep), 1 (join), 2 (clear)", seen_mode);
+    if (B < 1) return fail(VR_ERR_INVALID, "B must be positive");
+    const int R = ch->c.max_rows;
+    vr_model_s* w = ch->work;
+    // ---- every check before any state changes
+    if (B > R) return fail(VR_ERR_CAPACITY, "%d rows exceed max_rows=%d", B, R);
+    if (B > w->c.max_seqs) return fail(VR_ERR_CAPACITY, "%d rows exceed the model's max_seqs=%d", B, w->c.max_seqs);
+    if (tok_offsets[0] != 0) return fail(VR_ERR_INVALID, "tok_offsets[0] must be 0");
+    ChatExtendCtx ctx{ch, {}};
+    ChatExtend& ex = ctx.ex;
+    ex.n = B;
+    std::vector<char> used(R, 0);
+    int32_t base_pos[CHAT_MAX_ROWS];
+    for (int b = 0; b < B; ++b) {
+        const int sl = slots[b], r = rows[b], n = tok_offsets[b + 1] - tok_offsets[b];
+        if (n < 1) return fail(VR_ERR_INVALID, "extend row %d: empty token list", b);
+        if (sl < 0 || sl >= ch->c.max_slots || ch->plen[sl] <= 0) return fail(VR_ERR_INVALID, "extend row %d: slot %d holds no prompt", b, sl);
+        if (r < 0 || r >= R || used[r]) return fail(VR_ERR_INVALID, "extend row %d: row %d out of range or repeated", b, r);
+        used[r] = 1;
+        if (ch->row_slot[r] != sl && ch->row_len[r] > 0) return fail(VR_ERR_INVALID, "row %d continues slot %d, not %d", r, ch->row_slot[r], sl);
+        const int t0 = ch->row_slot[r] == sl ? ch->row_len[r] : 0;
+        if (t0 + n > ch->c.max_new || ch->plen[sl] + t0 + n > ch->c.max_len)
+            return fail(VR_ERR_CAPACITY, "row %d would exceed max_len=%d / max_new=%d", r, ch->c.max_len, ch->c.max_new);
+        ex.row[b] = r; ex.slot[b] = sl; ex.plen[b] = ch->plen[sl]; ex.t0[b] = t0; ex.off[b] = tok_offsets[b];
+        base_pos[b] = ch->plen[sl] + t0;
+    }
+    const int T = tok_offsets[B];
+    ex.off[B] = T;
+    if (T > w->c.max_tokens) return fail(VR_ERR_CAPACITY, "%d appended tokens exceed the model's max_tokens=%d", T, w->c.max_tokens);
+    for (int t = 0; t < T; ++t) {
+        if (tokens[t] < 0 || tokens[t] >= ch->V) return fail(VR_ERR_INVALID, "token id %d out of range at %d", tokens[t], t);
+        if (targets && (targets[t] < -1 || targets[t] >= ch->V)) return fail(VR_ERR_INVALID, "target id %d out of range at %d", targets[t], t);
+    }
+    VRCHK(set_dev(ch->model->device));
+    if (targets) VRCHK(chat_score_scratch(ch));
+    hipStream_t s = (hipStream_t)stream;
+    const int E = ch->E;
+    EncodeHook hook;
+    hook.bf16_route = true;
+    hook.layer = chat_extend_layer;
+    hook.attn = chat_extend_attn;
+    hook.ctx = &ctx;
+    hook.base_pos = base_pos;
+    hook.rope_table = ch->rope.as<float>();              // max_len positions (the work model's table stops at max_tokens)
+    hook.rope_len = ch->c.max_len;
+    w->arena_open = false;
+    int rc = encode_impl(w, nullptr, nullptr, 0, 0, tokens, tok_offsets, B, nullptr, ch->w_reps.as<float>(), 1, stream, nullptr, 0, &hook);
+    arena_close(w, stream);
+    if (rc) return rc;
+    // the rows' last tokens -> final RMSNorm (scaled weight) -> the head, one pass per run of adjacent logits rows (as the
+    // batched prefill): the logits of rows this call does not name stay where they are
+    std::vector<int> order(B);
+    for (int b = 0; b < B; ++b) order[b] = b;
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return rows[a] < rows[b]; });
+    // the head rewrites the rows' logits lines from here on: whatever they held (a row's logits, a prompt's) is gone even if a
+    // launch below fails
+    for (int b = 0; b < B; ++b) { chat_release_line(ch, R + rows[b]); ch->lpos[rows[b]] = -1; }
+    ChatBatch lr{};
+    lr.n = B;
+    for (int b = 0; b <= B; ++b) lr.off[b] = tok_offsets[b];
+    for (int j = 0; j < B; ++j) lr.idx[order[j]] = j;
+    HIPCHK(launch_chat_last_rows(lr, w->w_h.as<float>(), E, ch->norm_w.as<float>(), w->c.rms_norm_eps, ch->w_pxn.p, s));
+    for (int j = 0; j < B;) {
+        int n = 1;
+        while (j + n < B && rows[order[j + n]] == rows[order[j]] + n) ++n;
+        GemmArgs a = gemm_args((const char*)ch->w_pxn.p + (size_t)j * E * 2, E, ch->head, n,
+                               ch->w_logits.as<float>() + (size_t)(R + rows[order[j]]) * ch->Vpad, ch->Vpad);
+        HIPCHK(launch_gemm_skinny(a, s));
+        j += n;
+    }
+    for (int b = 0; b < B; ++b) {
+        unsigned* seen = (unsigned*)ch->seen.p + (size_t)rows[b] * ch->words;
+        // (a row that starts on a slot starts with an empty seen set, as in vr_chat_step)
+        if (seen_mode == 2 || ch->row_slot[rows[b]] != slots[b]) HIPCHK(hipMemsetAsync(seen, 0, (size_t)ch->words * 4, s));
+        if (seen_mode == 1) HIPCHK(launch_mark_seen(w->w_ids.as<int>() + tok_offsets[b], tok_offsets[b + 1] - tok_offsets[b], seen, ch->V, s));
+    }
+    if (targets) {
+        // entry t: the distribution after packed token t = its hidden row through the final norm and the fused head
+        const int Kp = ch->head.k_pad, cap = w->c.max_tokens;
+        HIPCHK(launch_rmsnorm(w->w_h.as<float>(), T, E, E, ch->norm_w.as<float>(), w->c.rms_norm_eps, ch->s_xn.p, Kp, s));
+        HIPCHK(hipMemcpyAsync(ch->s_tgt.p, targets, (size_t)T * 4, hipMemcpyHostToDevice, s));
+        float* o = ch->s_out.as<float>();
+        HIPCHK(launch_head_score(ch->s_xn.p, Kp, ch->head.w.p, Kp, T, ch->V, Kp, ch->s_tgt.as<int>(), ch->s_part.p, o, o + cap, o + 2 * (size_t)cap,
+                                 (int*)(o + 3 * (size_t)cap), s));
+        std::vector<int32_t> host((size_t)4 * T);
+        for (int a = 0; a < 4; ++a) HIPCHK(hipMemcpyAsync(host.data() + (size_t)a * T, o + (size_t)a * cap, (size_t)T * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (int t = 0; t < T; ++t) {
+            if (targets[t] < 0) continue;
+            memcpy(out_logit + t, &host[t], 4);
+            memcpy(out_lse + t, &host[(size_t)T + t], 4);
+            memcpy(out_top_logit + t, &host[2 * (size_t)T + t], 4);
+            out_top_token[t] = host[3 * (size_t)T + t];
+        }
+    }
+    for (int b = 0; b < B; ++b) {
+        const int r = rows[b];
+        ch->row_slot[r] = slots[b];
+        ch->row_len[r] = ex.t0[b] + (tok_offsets[b + 1] - tok_offsets[b]);
+        ch->lpos[r] = R + r;
+    }
+    return VR_OK;
+}
+
+// the four numbers of the scoring head from finished logits lines (chat_row_score_kernel), CHAT_ROW_SCORE_MAX entries per launch
+static int chat_score_lines(vr_chat_s* ch, int n, const std::vector<int>& lines, const int32_t* targets, float* out_logit, float* out_lse,
+                            float* out_top_logit, int32_t* out_top_token, void* stream) {
+    VRCHK(set_dev(ch->model->device));
+    hipStream_t s = (hipStream_t)stream;
+    float* o = ch->w_out.as<float>();                         // (w_out holds 3072 words: four runs of CHAT_ROW_SCORE_MAX fit)
+    static_assert(4 * CHAT_ROW_SCORE_MAX <= CHAT_MAX_ROWS * CHAT_TOPK_MAX * 3, "w_out holds the four runs");
+    for (int i0 = 0; i0 < n; i0 += CHAT_ROW_SCORE_MAX) {
+        ChatRowScore sc{};
+        sc.n = std::min(CHAT_ROW_SCORE_MAX, n - i0);
+        for (int i = 0; i < sc.n; ++i) { sc.lrow[i] = lines[i0 + i]; sc.target[i] = targets[i0 + i]; }
+        HIPCHK(launch_chat_row_score(sc, ch->w_logits.as<float>(), ch->Vpad, ch->V, o, o + CHAT_ROW_SCORE_MAX, o + 2 * CHAT_ROW_SCORE_MAX,
+                                     (int*)(o + 3 * CHAT_ROW_SCORE_MAX), s));
+        int32_t host[4 * CHAT_ROW_SCORE_MAX];
+        HIPCHK(hipMemcpyAsync(host, o, sizeof(host), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        memcpy(out_logit + i0, host, (size_t)sc.n * 4);
+        memcpy(out_lse + i0, host + CHAT_ROW_SCORE_MAX, (size_t)sc.n * 4);
+        memcpy(out_top_logit + i0, host + 2 * CHAT_ROW_SCORE_MAX, (size_t)sc.n * 4);
+        memcpy(out_top_token + i0, host + 3 * CHAT_ROW_SCORE_MAX, (size_t)sc.n * 4);
+    }
+    return VR_OK;
+}
+
+extern "C" int vr_chat_row_score(vr_chat_t ch, int32_t n, const int32_t* rows, const int32_t* targets, float* out_logit, float* out_lse,
+                                 float* out_top_logit, int32_t* out_top_token, void* stream) {
+    if (!ch || !rows || !targets || !out_logit || !out_lse || !out_top_logit || !out_top_token) return fail(VR_ERR_INVALID, "NULL argument");
+    if (n < 1) return fail(VR_ERR_INVALID, "n must be positive");
+    std::vector<int> lines(n);
+    for (int i = 0; i < n; ++i) {
+        if (rows[i] < 0 || rows[i] >= ch->c.max_rows) return fail(VR_ERR_INVALID, "entry %d: row %d out of range", i, rows[i]);
+        if (targets[i] < 0 || targets[i] >= ch->V) return fail(VR_ERR_INVALID, "entry %d: target id %d out of range", i, targets[i]);
+        if (ch->lpos[rows[i]] < 0) return fail(VR_ERR_STATE, "row %d has no logits", rows[i]);
+        lines[i] = ch->lpos[rows[i]];
+    }
+    return chat_score_lines(ch, n, lines, targets, out_logit, out_lse, out_top_logit, out_top_token, stream);
+}
+
+extern "C" int vr_chat_slot_score(vr_chat_t ch, int32_t n, const int32_t* slots, const int32_t* targets, float* out_logit, float* out_lse,
+                                  float* out_top_logit, int32_t* out_top_token, void* stream) {
+    if (!ch || !slots || !targets || !out_logit || !out_lse || !out_top_logit || !out_top_token) return fail(VR_ERR_INVALID, "NULL argument");
+    if (n < 1) return fail(VR_ERR_INVALID, "n must be positive");
+    std::vector<int> lines(n);
+    for (int i = 0; i < n; ++i) {
+        if (slots[i] < 0 || slots[i] >= ch->c.max_slots) return fail(VR_ERR_INVALID, "entry %d: slot %d out of range", i, slots[i]);
+        if (targets[i] < 0 || targets[i] >= ch->V) return fail(VR_ERR_INVALID, "entry %d: target id %d out of range", i, targets[i]);
+        if (ch->plen[slots[i]] <= 0 || ch->slot_lrow[slots[i]] < 0) return fail(VR_ERR_STATE, "slot %d: the prompt's logits are gone", slots[i]);
+        lines[i] = ch->slot_lrow[slots[i]];
+    }
+    return chat_score_lines(ch, n, lines, targets, out_logit, out_lse, out_top_logit, out_top_token, stream);
+}
+
+extern "C" int vr_chat_slot_state(vr_chat_t ch, int32_t slot, int32_t* prompt_len, int32_t* has_prompt_logits, int32_t* generation) {
+    if (!ch || !prompt_len || !has_prompt_logits || !generation) return fail(VR_ERR_INVALID, "NULL argument");
+    if (slot < 0 || slot >= ch->c.max_slots) return fail(VR_ERR_INVALID, "slot %d out of range", slot);
+    *prompt_len = ch->plen[slot];
+    *has_prompt_logits = ch->plen[slot] > 0 && ch->slot_lrow[slot] >= 0;
+    *generation = ch->slot_gen[slot];
+    return VR_OK;
+}
+
+extern "C" int vr_chat_row_truncate(vr_chat_t ch, int32_t row, int32_t length) {
+    if (!ch) return fail(VR_ERR_INVALID, "NULL argument");
+    if (row < 0 || row >= ch->c.max_rows) return fail(VR_ERR_INVALID, "row %d out of range", row);
+    if (length < 0 || length > ch->row_len[row]) return fail(VR_ERR_INVALID, "length %d outside 0..%d", length, ch->row_len[row]);
+    ch->row_len[row] = length;                           // host state only: the tail's rows stay, the next append overwrites them
+    ch->lpos[row] = -1;
     return VR_OK;
 }

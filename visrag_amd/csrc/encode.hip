@@ -318,7 +318,8 @@ int encode_impl(vr_model_t m, const uint8_t* const* slices, const int32_t* slice
         if (vision_rows[i] >= T) return fail(VR_ERR_INVALID, "vision row %d out of range", vision_rows[i]);
 
     // ---- K13: token embeddings * scale_emb into the fp32 stream
-    VRCHK(arena_begin(m, (size_t)T * 4 + (size_t)(B + 1) * 4 + (size_t)n_slices * (Q * 4 + 8 + 64 * 3) + 4096));
+    const int32_t* base_pos = hook ? hook->base_pos : nullptr;        // (vr_chat_extend: sequences that continue a cache)
+    VRCHK(arena_begin(m, (size_t)T * 4 * (base_pos ? 2 : 1) + (size_t)(B + 1) * 4 + (size_t)n_slices * (Q * 4 + 8 + 64 * 3) + 4096));
     {
         int* a_ids = (int*)arena_take(m, (size_t)T * 4);
         int* a_seq = (int*)arena_take(m, (size_t)(B + 1) * 4);
@@ -341,7 +342,14 @@ int encode_impl(vr_model_t m, const uint8_t* const* slices, const int32_t* slice
         HIPCHK(launch_embed_gather_hp(m->w_ids.as<int>(), T, m->embed.p, m->embed_lo.p, E, c.scale_emb, m->w_h.as<float>(), s));
     else
         HIPCHK(launch_embed_gather(m->w_ids.as<int>(), T, m->embed.p, E, c.scale_emb, m->w_h.as<float>(), s));
-    HIPCHK(launch_iota_pos(m->w_seq.as<int>(), B, m->w_pos.as<int>(), s));
+    if (base_pos) {                      // positions that do not start at 0: built here, uploaded like the ids
+        int* a_pos = (int*)arena_take(m, (size_t)T * 4);
+        for (int i = 0; i < B; ++i)
+            for (int t = seq_offsets[i]; t < seq_offsets[i + 1]; ++t) a_pos[t] = base_pos[i] + (t - seq_offsets[i]);
+        HIPCHK(hipMemcpyAsync(m->w_pos.p, a_pos, (size_t)T * 4, hipMemcpyHostToDevice, s));
+    } else {
+        HIPCHK(launch_iota_pos(m->w_seq.as<int>(), B, m->w_pos.as<int>(), s));
+    }
 
     // ---- vision: group slices by shape, chunk to the workspace
     if (n_slices > 0) {
@@ -395,7 +403,16 @@ int encode_impl(vr_model_t m, const uint8_t* const* slices, const int32_t* slice
     // ---- decoder (modeling_minicpm.py:939-1004, 1147-1304), packed ragged sequences
     float* h = m->w_h.as<float>();
     const int* seq = m->w_seq.as<int>();
-    if (max_len > m->rope_len) return fail(VR_ERR_CAPACITY, "sequence of %d tokens exceeds the RoPE table", max_len);
+    const float* rope_table = hook && hook->rope_table ? hook->rope_table : m->rope.as<float>();
+    {
+        const int rope_len = hook && hook->rope_table ? hook->rope_len : m->rope_len;
+        int last = max_len;              // one past the largest position of the batch
+        if (base_pos) {
+            last = 0;
+            for (int i = 0; i < B; ++i) last = std::max(last, base_pos[i] + seq_offsets[i + 1] - seq_offsets[i]);
+        }
+        if (last > rope_len) return fail(VR_ERR_CAPACITY, "sequence of %d tokens exceeds the RoPE table", last);
+    }
     VRCHK(prof_begin(m, VR_PROF_DECODER, s));
     if (hp) {
         VRCHK(run_decoder_hp(m, T, B, max_len, s));
@@ -448,14 +465,18 @@ int encode_impl(vr_model_t m, const uint8_t* const* slices, const int32_t* slice
         VRCHK(norm(L.ln1.v.as<float>()));
         {
             GemmArgs a = gemm_args(m->w_dxn.p, E, L.qkv, T, m->w_dqkv.p, 3 * E);
-            a.rope_pos = m->w_pos.as<int>(); a.rope_table = m->rope.as<float>(); a.rope_cols = 2 * E;
+            a.rope_pos = m->w_pos.as<int>(); a.rope_table = rope_table; a.rope_cols = 2 * E;
             warm_for(a, EPI_ROPE, L.o);
             VRCHK(prof_begin(m, VR_PROF_DEC_QKV, s));
             HIPCHK(launch_gemm(a, EPI_ROPE, GEMM_VARIANT_AUTO, s));
             VRCHK(prof_end(m, VR_PROF_DEC_QKV, 6.0 * T * (double)E * E, s));
         }
         if (hook && hook->layer) VRCHK(hook->layer(hook->ctx, l, m->w_dqkv.p, 3 * E, T, s));
-        {
+        if (hook && hook->attn) {
+            VRCHK(prof_begin(m, VR_PROF_DEC_ATTN, s));
+            VRCHK(hook->attn(hook->ctx, l, m->w_dqkv.p, 3 * E, T, m->w_datt.p, E, s));
+            VRCHK(prof_end(m, VR_PROF_DEC_ATTN, 0.0, s));     // (its keys are the hook's business: time is booked, FLOPs are not)
+        } else {
             VRCHK(prof_begin(m, VR_PROF_DEC_ATTN, s));
             AttnArgs a{};
             a.q = m->w_dqkv.p; a.ldq = 3 * E; a.k = (const char*)m->w_dqkv.p + (size_t)E * 2; a.ldk = 3 * E;

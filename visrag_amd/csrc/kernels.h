@@ -188,6 +188,28 @@ hipError_t launch_chat_select(const ChatSel& sel, int mode, const float* logits,
 hipError_t launch_chat_sample(const ChatSel& sel, const float* logits, int ld, int V, const unsigned* seen, int words, float pen,
                               float temperature, int top_k, double top_p, unsigned long long seed, unsigned step, float* o_score,
                               int* o_tok, int* o_kept, int* o_cut, hipStream_t s);
+// ---- several given tokens appended to cached prompts in one packed pass (chat_extend.hip; host side vr_chat_extend) ----
+// passed by value: sequence b appends the packed rows [off[b], off[b + 1]) to tail row row[b] at tail index t0[b]; its prompt
+// is the first plen[b] keys of slot slot[b]
+struct ChatExtend { int n; int row[CHAT_MAX_ROWS], slot[CHAT_MAX_ROWS], plen[CHAT_MAX_ROWS], t0[CHAT_MAX_ROWS], off[CHAT_MAX_ROWS + 1]; };
+constexpr int CHAT_EXT_QT = 64;     // query rows per workgroup of the two-segment attention
+// one layer's rope'd K / V rows of the packed q | k | v rows [off[n]][ld] -> tail index t0[b] + t - off[b] of row[b] in the
+// layer's K / V tail planes [rows][max_new][E]; the caller has checked row[b] < rows and t0[b] + n_b <= max_new
+hipError_t launch_chat_tail_scatter(const ChatExtend& ex, const void* qkv, int ld, int E, int max_new, void* kplane, void* vplane,
+                                    hipStream_t s);
+// Two-segment causal attention, head_dim 64, scale 1/8: query j of sequence b (packed row off[b] + j of q [rows][ldq], head h at
+// column h * 64) sees keys [0, plen[b]) of its slot's prompt planes and keys [0, t0[b] + j] of its row's tail planes (layer l of
+// prompt [layers][K|V][slots][len][E] / tails [layers][K|V][rows][tail][E]); out bf16 [rows][ldo].  One workgroup per (64-query
+// tile, head, sequence); reads no plane row outside [0, plen) / [0, t0 + n), writes its own output rows only.  The caller has
+// checked every index against `cap`; q and the planes 16-byte aligned, ldq % 8 == 0, E % 8 == 0, ldo % 4 == 0.
+hipError_t launch_chat_extend_attn(const ChatExtend& ex, const void* q, int ldq, const void* prompt, const void* tails, int l, int E,
+                                   int heads, const ChatCaps& cap, void* out, int ldo, hipStream_t s);
+// the four numbers of launch_head_score from fp32 logits rows already computed: entry i < sc.n reads logits row lrow[i] at
+// target[i] (outside [0, V): its x_t entry is left unwritten); one workgroup per entry, lowest id among tied maxima
+constexpr int CHAT_ROW_SCORE_MAX = 64;
+struct ChatRowScore { int n; int lrow[CHAT_ROW_SCORE_MAX], target[CHAT_ROW_SCORE_MAX]; };
+hipError_t launch_chat_row_score(const ChatRowScore& sc, const float* logits, int ld, int V, float* x_t, float* lse, float* top_x,
+                                 int* top_id, hipStream_t s);
 
 // ---- EVisRAG generator (gen_kernels.hip) ---------------------------------------------------
 constexpr int GEN_ATT_SPLITS = 16;  // most KV ranges one decode step's attention is cut into

@@ -142,10 +142,18 @@ static inline GemmArgs gemm_args(const void* A, int lda, const Linear& L, int M,
 // encode_impl's optional per-call extras (vr_chat_prefill): `bf16_route` keeps a token-only batch off the split-precision
 // text route; `layer` (when set) runs after every decoder layer's q|k|v projection + RoPE with the layer's bf16 rows
 // [T][ldqkv] (q | k | v) on the launch stream.  A null hook is the plain vr_encode pass.
+// vr_chat_extend's extras (each absent when null; a hook that sets none of them launches what a hook without them launches):
+// `base_pos` (host, [B]): token j of sequence b sits at position base_pos[b] + j instead of j; `rope_table` / `rope_len`: the
+// RoPE table those positions index (f32 [rope_len][64]) instead of the model's; `attn` replaces the layer's launch_attention:
+// it reads the q columns of qkv (and whatever `layer` stored) and writes bf16 out [T][ldo].
 struct EncodeHook {
     bool bf16_route = false;
     int (*layer)(void* ctx, int l, const void* qkv, int ldqkv, int T, hipStream_t s) = nullptr;
     void* ctx = nullptr;
+    const int32_t* base_pos = nullptr;
+    const float* rope_table = nullptr;
+    int rope_len = 0;
+    int (*attn)(void* ctx, int l, const void* qkv, int ldqkv, int T, void* out, int ldo, hipStream_t s) = nullptr;
 };
 
 // ---- defined in model.hip

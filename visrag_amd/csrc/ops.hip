@@ -371,6 +371,42 @@ extern "C" int vr_op_chat_attention(int device_id, const void* q, const void* pr
     return VR_OK;
 }
 
+extern "C" int vr_op_chat_extend_attention(int device_id, const void* q, int32_t ldq, const void* prompt, const void* tails, int32_t layers,
+                                           int32_t l, int32_t E, int32_t heads, int32_t slots, int32_t max_len, int32_t rows,
+                                           int32_t max_new, int32_t B, const int32_t* seq_row, const int32_t* seq_slot,
+                                           const int32_t* seq_plen, const int32_t* seq_t0, const int32_t* seq_off, void* out,
+                                           int32_t ldo, void* stream) {
+    if (!q || !prompt || !tails || !seq_row || !seq_slot || !seq_plen || !seq_t0 || !seq_off || !out) return fail(VR_ERR_INVALID, "NULL argument");
+    if (E < 64 || E % 8 || heads < 1 || heads * 64 > E) return fail(VR_ERR_INVALID, "need E %% 8 == 0 and 1 <= heads <= E / 64");
+    if (layers < 1 || l < 0 || l >= layers) return fail(VR_ERR_INVALID, "layer %d of %d", l, layers);
+    if (slots < 1 || max_len < 1 || rows < 1 || max_new < 1) return fail(VR_ERR_INVALID, "bad cache geometry");
+    if (ldq % 8 || ldq < heads * 64 || ldo % 4 || ldo < heads * 64) return fail(VR_ERR_INVALID, "ldq (multiple of 8) / ldo (of 4) must cover heads * 64");
+    if (B < 1) return fail(VR_ERR_INVALID, "B must be positive");
+    if (B > CHAT_MAX_ROWS) return fail(VR_ERR_CAPACITY, "%d sequences exceed %d", B, CHAT_MAX_ROWS);
+    if (((uintptr_t)q | (uintptr_t)prompt | (uintptr_t)tails | (uintptr_t)out) & 15) return fail(VR_ERR_INVALID, "pointers must be 16-byte aligned");
+    if (seq_off[0] != 0) return fail(VR_ERR_INVALID, "seq_off[0] must be 0");
+    ChatExtend ex{};
+    ex.n = B;
+    std::vector<char> used(rows, 0);
+    for (int b = 0; b < B; ++b) {
+        const int r = seq_row[b], sl = seq_slot[b], pl = seq_plen[b], t0 = seq_t0[b], n = seq_off[b + 1] - seq_off[b];
+        if (sl < 0 || sl >= slots || pl < 1) return fail(VR_ERR_INVALID, "sequence %d: slot %d out of range or without a prompt key", b, sl);
+        if (pl > max_len) return fail(VR_ERR_CAPACITY, "sequence %d: %d prompt keys exceed max_len=%d", b, pl, max_len);
+        if (r < 0 || r >= rows || used[r]) return fail(VR_ERR_INVALID, "sequence %d: row %d out of range or repeated", b, r);
+        if (t0 < 0 || n < 1) return fail(VR_ERR_INVALID, "sequence %d: negative tail index or no query row", b);
+        if ((int64_t)t0 + n > max_new) return fail(VR_ERR_CAPACITY, "sequence %d: tail of %lld rows exceeds max_new=%d", b, (long long)t0 + n, max_new);
+        used[r] = 1;
+        ex.row[b] = r; ex.slot[b] = sl; ex.plen[b] = pl; ex.t0[b] = t0; ex.off[b] = seq_off[b];
+    }
+    ex.off[B] = seq_off[B];
+    VRCHK(set_dev(device_id));
+    hipStream_t s = (hipStream_t)stream;
+    const ChatCaps caps{slots, max_len, rows, max_new};
+    HIPCHK(launch_chat_extend_attn(ex, q, ldq, prompt, tails, l, E, heads, caps, out, ldo, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return VR_OK;
+}
+
 extern "C" int vr_op_chat_select(int device_id, int32_t mode, const float* logits, int32_t ld, int32_t V, const uint32_t* seen,
                                  int32_t words, int32_t n_groups, const int32_t* group_offsets, const float* beam_scores, int32_t K,
                                  int32_t kout, float repetition_penalty, float temperature, uint64_t seed, int32_t step,

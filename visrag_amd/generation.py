@@ -248,6 +248,8 @@ class HipChat:
         self.V = encoder.cfg.vocab_size
         c = _lib.VRChatConfig(max_len=self.max_len, max_rows=self.max_rows, dim_model_base=float(dim_model_base),
                               max_slots=self.max_slots, max_new=self.max_new)
+        self.prefills = 0                 # prefill / prefill_batch calls so far (a statistic: tests count them)
+        self._slot_item = {}              # slot -> (ids, slices) of the item this wrapper prefilled there, with the slot's generation
         self._h = C.c_void_p()
         _lib.check(self.lib.vr_chat_create(encoder._h, C.byref(c), C.byref(self._h)), "vr_chat_create")
 
@@ -288,8 +290,10 @@ class HipChat:
             rp = rows.ctypes.data_as(C.POINTER(C.c_int32))
         else:
             ptrs, hw, rp = None, None, None
+        self.prefills += 1
         _lib.check(self.lib.vr_chat_prefill(self._h, int(slot), int(row), ptrs, hw, n, 0, ids.ctypes.data_as(C.POINTER(C.c_int32)),
                                             len(ids), rp, self._stream()), "vr_chat_prefill")
+        self._remember(slot, item)
 
     def prefill_batch(self, slots: Sequence[int], rows: Sequence[int], items: Sequence) -> None:
         """PreparedItems in ONE packed pass: item b into prompt slot slots[b], its logits on row rows[b] (vr_chat_prefill_batch).
@@ -319,8 +323,11 @@ class HipChat:
             ptrs, hw, rp = None, None, None
         a = lambda v: (C.c_int32 * B)(*[int(x) for x in v])
         p32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_int32))
+        self.prefills += 1
         _lib.check(self.lib.vr_chat_prefill_batch(self._h, B, a(slots), a(rows), ptrs, hw, n, 0, p32(ids), p32(off), rp, self._stream()),
                    "vr_chat_prefill_batch")
+        for sl, it in zip(slots, items):
+            self._remember(sl, it)
 
     def step(self, slots: Sequence[int], rows: Sequence[int], tokens: Sequence[int]) -> None:
         n = len(rows)
@@ -414,6 +421,106 @@ class HipChat:
             m += c
         return out
 
+    _SEEN_MODES = {"keep": 0, "join": 1, "clear": 2}
+
+    def extend(self, slots: Sequence[int], rows: Sequence[int], token_lists: Sequence[Sequence[int]],
+               targets: Optional[Sequence[Sequence[int]]] = None, seen: str = "keep") -> Optional[List[Dict[str, np.ndarray]]]:
+        """Append token_lists[b] to row rows[b] of the cached prompt slots[b], all rows in ONE packed decoder pass
+        (vr_chat_extend).  Afterwards a row's logits are those after its last appended token.  seen: "keep" leaves the rows'
+        seen sets alone, "join" adds the appended ids, "clear" empties them (a new turn).  targets (one list per row, as long
+        as its tokens, -1 = none): entry j is the distribution AFTER token j evaluated at targets[b][j] -> per row
+        dict(logit, lse, top_logit, top_token), numpy [len(tokens)]; entries without a target hold (nan, nan, nan, -1).
+        Without targets nothing is returned and the stream is not synchronised."""
+        if seen not in self._SEEN_MODES:
+            raise ValueError(f"seen={seen!r}: 'keep', 'join' or 'clear'")
+        B = len(token_lists)
+        if B < 1 or not (B == len(slots) == len(rows)):
+            raise ValueError("extend needs one slot, one row and one token list per sequence, and at least one")
+        lens = [len(t) for t in token_lists]
+        off = np.zeros(B + 1, dtype=np.int32)
+        off[1:] = np.cumsum(lens)
+        M = int(off[B])
+        toks = np.ascontiguousarray(np.asarray([int(t) for tl in token_lists for t in tl], dtype=np.int32))
+        p32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_int32))
+        pf = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))
+        a = lambda v: (C.c_int32 * B)(*[int(x) for x in v])
+        tp = lo = ls = tl_ = tt = None
+        if targets is not None:
+            if len(targets) != B or any(len(t) != n for t, n in zip(targets, lens)):
+                raise ValueError("extend needs one target per appended token (-1 = none)")
+            tg = np.ascontiguousarray(np.asarray([int(t) for tl in targets for t in tl], dtype=np.int32))
+            logit, lse, top = (np.full(max(M, 1), np.nan, dtype=np.float32) for _ in range(3))
+            tok = np.full(max(M, 1), -1, dtype=np.int32)
+            tp, lo, ls, tl_, tt = p32(tg), pf(logit), pf(lse), pf(top), p32(tok)
+        _lib.check(self.lib.vr_chat_extend(self._h, B, a(slots), a(rows), p32(off), p32(toks) if M else None, tp,
+                                           self._SEEN_MODES[seen], lo, ls, tl_, tt, self._stream()), "vr_chat_extend")
+        if targets is None:
+            return None
+        return [{"logit": logit[off[b]:off[b + 1]].copy(), "lse": lse[off[b]:off[b + 1]].copy(),
+                 "top_logit": top[off[b]:off[b + 1]].copy(), "top_token": tok[off[b]:off[b + 1]].copy()} for b in range(B)]
+
+    def row_score(self, rows: Sequence[int], targets: Sequence[int]) -> Dict[str, np.ndarray]:
+        """The four numbers of `score` from the CURRENT logits of rows[i] at targets[i] (vr_chat_row_score; rows may repeat)
+        -> dict(logit, lse, top_logit, top_token), numpy [len(rows)]."""
+        n = len(rows)
+        if n < 1 or n != len(targets):
+            raise ValueError("row_score needs at least one row and one target per row")
+        logit, lse, top = (np.zeros(n, dtype=np.float32) for _ in range(3))
+        tok = np.zeros(n, dtype=np.int32)
+        a = lambda v: (C.c_int32 * n)(*[int(x) for x in v])
+        p32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_int32))
+        pf = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))
+        _lib.check(self.lib.vr_chat_row_score(self._h, n, a(rows), a(targets), pf(logit), pf(lse), pf(top), p32(tok), self._stream()),
+                   "vr_chat_row_score")
+        return {"logit": logit, "lse": lse, "top_logit": top, "top_token": tok}
+
+    def slot_score(self, slots: Sequence[int], targets: Sequence[int]) -> Dict[str, np.ndarray]:
+        """`row_score` from the logits of the slots' PROMPTS (their last position): they outlive a generation on the slot and
+        are lost when the row the prefill named is prefilled or extended again (vr_chat_slot_score)."""
+        n = len(slots)
+        if n < 1 or n != len(targets):
+            raise ValueError("slot_score needs at least one slot and one target per slot")
+        logit, lse, top = (np.zeros(n, dtype=np.float32) for _ in range(3))
+        tok = np.zeros(n, dtype=np.int32)
+        a = lambda v: (C.c_int32 * n)(*[int(x) for x in v])
+        p32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_int32))
+        pf = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))
+        _lib.check(self.lib.vr_chat_slot_score(self._h, n, a(slots), a(targets), pf(logit), pf(lse), pf(top), p32(tok), self._stream()),
+                   "vr_chat_slot_score")
+        return {"logit": logit, "lse": lse, "top_logit": top, "top_token": tok}
+
+    def _slot_state(self, slot: int) -> Tuple[int, bool, int]:
+        n, ok, gen = C.c_int32(), C.c_int32(), C.c_int32()
+        _lib.check(self.lib.vr_chat_slot_state(self._h, int(slot), C.byref(n), C.byref(ok), C.byref(gen)), "vr_chat_slot_state")
+        return int(n.value), bool(ok.value), int(gen.value)
+
+    def slot_state(self, slot: int) -> Tuple[int, bool]:
+        """-> (prompt tokens the slot holds, whether `slot_score` can still read the prompt's logits)"""
+        return self._slot_state(slot)[:2]
+
+    def slot_generation(self, slot: int) -> int:
+        """How often the slot has been prefilled, counted by the library whoever called it: a caller that keeps a prompt in
+        a slot compares it with the count it saw after its own prefill."""
+        return self._slot_state(slot)[2]
+
+    def _remember(self, slot: int, item) -> None:
+        self._slot_item[int(slot)] = ([int(t) for t in item.input_ids], [np.asarray(s) for s in item.slices],
+                                      self.slot_generation(slot))
+
+    def slot_holds(self, slot: int, item) -> bool:
+        """Does `slot` hold exactly this item's prompt — the ids and slices this wrapper prefilled there, and nobody (this
+        wrapper, another one of the same handle, the C API) has prefilled the slot since?"""
+        rec = self._slot_item.get(int(slot))
+        if rec is None or rec[2] != self.slot_generation(slot):
+            return False
+        ids, slices, _ = rec
+        return (ids == [int(t) for t in item.input_ids] and len(slices) == len(item.slices) and
+                all(a.shape == np.asarray(b).shape and np.array_equal(a, b) for a, b in zip(slices, item.slices)))
+
+    def truncate(self, row: int, length: int) -> None:
+        """Shorten the tail of `row` to `length` tokens; the row loses its logits, its seen set stays (vr_chat_row_truncate)."""
+        _lib.check(self.lib.vr_chat_row_truncate(self._h, int(row), int(length)), "vr_chat_row_truncate")
+
 
 # what HF generate would accept but this generator does not implement: refused rather than silently dropped
 _NEUTRAL = {"top_p": 1.0, "length_penalty": 1.0, "min_new_tokens": 0, "no_repeat_ngram_size": 0,
@@ -500,7 +607,9 @@ def prefill_groups(lengths: Sequence[int], max_tokens: int, max_seqs: int) -> Li
 
 def _generate_chunk(chat, items, max_new, nb, do_sample, pen, temp, top_k, seed, eos, prefill="single", nucleus=None):
     """Every item's rule is a generator of select / advance requests; each round serves all pending requests of one kind in
-    ONE device call (advances first: a select must see the appended token), so the items advance in lockstep."""
+    ONE device call (advances first: a select must see the appended token), so the items advance in lockstep.
+    prefill="resident": item i's prompt (and whatever its row already appended) sits in slot i with its logits on row i * nb
+    (ChatSession); nothing is prefilled."""
     rules, rows, reqs, results = [], [], [], [None] * len(items)
     if prefill == "batched":
         for g in prefill_groups([len(it.input_ids) for it in items], chat.enc.max_tokens, chat.enc.max_seqs):
@@ -598,6 +707,202 @@ def score_items(chat, items: Sequence, continuations: Sequence[Sequence[int]], r
             out.append({"token_logprobs": lp, "sum": total, "score": score,
                         "greedy_match": top == np.asarray(conts[i], dtype=np.int64), "top_tokens": top})
     return out
+
+
+def _score_on_slot(chat, slot: int, prow: int, conts: List[List[int]], repetition_penalty: float, length_penalty: float) -> List[Dict]:
+    """The continuations of ONE resident prompt: token 0 of every continuation from the prompt's logits (one `row_score`
+    call on the prompt's row, or — prow None: a generation has moved the row on — one `slot_score` call), tokens 1.. from
+    `extend` on rows of that slot, at most max_rows of them per call."""
+    if prow is None:
+        first = chat.slot_score([slot] * len(conts), [c[0] for c in conts])
+    else:
+        first = chat.row_score([prow] * len(conts), [c[0] for c in conts])
+    logit = [[float(first["logit"][a])] for a in range(len(conts))]
+    lse = [[float(first["lse"][a])] for a in range(len(conts))]
+    top = [[int(first["top_token"][a])] for a in range(len(conts))]
+    # rows free for the tails: unbound ones and those of this slot (rows of other slots — other items of the pack, a generation
+    # in progress — are left alone); the prompt's own row only when there is no other
+    cands = [r for r in range(chat.max_rows) if r != prow and chat.row_state(r)[0] in (-1, slot)] or [prow]
+    if cands == [None]:
+        raise ValueError(f"no row is free for the continuations of slot {slot}")
+    longer = [a for a, c in enumerate(conts) if len(c) > 1]
+    per = max(1, min(len(cands), chat.enc.max_seqs))
+    lo = 0
+    while lo < len(longer):
+        chunk, tok = [], 0
+        while lo + len(chunk) < len(longer) and len(chunk) < per:
+            n = len(conts[longer[lo + len(chunk)]]) - 1
+            if chunk and tok + n > chat.enc.max_tokens:
+                break
+            chunk.append(longer[lo + len(chunk)])
+            tok += n
+        lo += len(chunk)
+        rows = cands[:len(chunk)]
+        for r in rows:                                   # a row that carried an earlier chunk starts over
+            if chat.row_state(r) != (slot, 0) and chat.row_state(r)[0] == slot:
+                chat.truncate(r, 0)
+        res = chat.extend([slot] * len(chunk), rows, [conts[a][:-1] for a in chunk], targets=[conts[a][1:] for a in chunk])
+        for a, r in zip(chunk, res):
+            logit[a] += [float(x) for x in r["logit"]]
+            lse[a] += [float(x) for x in r["lse"]]
+            top[a] += [int(x) for x in r["top_token"]]
+    out = []
+    for a, c in enumerate(conts):
+        lp = np.asarray(logit[a], dtype=np.float64) - np.asarray(lse[a], dtype=np.float64)
+        score, total = sequence_score(lp, c, repetition_penalty, length_penalty, return_sum=True)
+        t = np.asarray(top[a], dtype=np.int64)
+        out.append({"token_logprobs": lp, "sum": total, "score": score, "greedy_match": t == np.asarray(c, dtype=np.int64),
+                    "top_tokens": t})
+    return out
+
+
+def score_items_shared(chat, items: Sequence, continuations_of_item: Sequence[Sequence[Sequence[int]]],
+                       repetition_penalty: float = 1.0, length_penalty: float = 1.0,
+                       prefilled: Optional[Dict[int, Tuple[int, int]]] = None) -> List[List[Dict]]:
+    """`score_items` for SEVERAL continuations per prompt over ONE prefill per prompt: item i is prefilled once
+    (`prefill_batch`, the items in `prefill_groups` packs), the first token of each of its continuations is read off the
+    prompt row's logits (`row_score`), the others come from `extend` with tokens c[0..n-2] and targets c[1..n-1] on rows of
+    that slot, at most max_rows rows per call (a one-token continuation needs no extend).  -> per item, per continuation, the
+    dict of `score_items`; the two routes agree to bf16 accuracy.
+
+    prefilled: {item index: (slot, row)} for prompts already resident — `row` holds the prompt's logits and an empty tail on
+    `slot`, or row is None: the slot's prompt logits are still readable (`slot_state`) although a generation has moved its
+    rows on, which are then overwritten; those items are not prefilled again.  With a row the caller vouches that the slot
+    holds THIS item's prompt (only the row's binding is checked); with None the handle checks it (`slot_holds`: the ids and
+    slices it prefilled there, the slot not prefilled since) and anything else raises ValueError.  The other items use the slots and rows `prefilled` does not name; rows bound
+    to a scored slot (other than the prompt's row) are overwritten.  A continuation longer than max_new raises ValueError."""
+    items = list(items)
+    conts = [[[int(t) for t in c] for c in cs] for cs in continuations_of_item]
+    if len(items) != len(conts):
+        raise ValueError(f"{len(items)} items but {len(conts)} continuation lists")
+    for i, cs in enumerate(conts):
+        if not cs:
+            raise ValueError(f"item {i} has no continuation")
+        for a, c in enumerate(cs):
+            if not c:
+                raise ValueError(f"continuation {a} of item {i} is empty")
+            if len(c) > chat.max_new:
+                raise ValueError(f"continuation {a} of item {i}: {len(c)} tokens exceed the chat handle's max_new={chat.max_new}")
+    prefilled = {int(i): (int(s), None if r is None else int(r)) for i, (s, r) in (prefilled or {}).items()}
+    for i, (s, r) in prefilled.items():
+        if not 0 <= i < len(items):
+            raise ValueError(f"prefilled names item {i} of {len(items)}")
+        if r is None:
+            if not chat.slot_holds(s, items[i]) or chat.slot_state(s) != (len(items[i].input_ids), True):
+                raise ValueError(f"prefilled item {i}: slot {s} does not hold its prompt with readable logits")
+        elif chat.row_state(r) != (s, 0):
+            raise ValueError(f"prefilled item {i}: row {r} does not hold the prompt of slot {s} with an empty tail")
+    out: List[Optional[List[Dict]]] = [None] * len(items)
+    for i, (s, r) in prefilled.items():
+        out[i] = _score_on_slot(chat, s, r, conts[i], repetition_penalty, length_penalty)
+    todo = [i for i in range(len(items)) if i not in prefilled]
+    if todo:
+        free_slots = [s for s in range(chat.max_slots) if s not in {s_ for s_, _ in prefilled.values()}]
+        free_rows = [r for r in range(chat.max_rows) if r not in {r_ for _, r_ in prefilled.values()} and
+                     chat.row_state(r)[0] not in {s_ for s_, _ in prefilled.values()}]
+        if not free_slots or not free_rows:
+            raise ValueError("prefilled leaves no slot or row for the other items")
+        # a pack keeps half its rows for the tails (one row per prompt, the rest for the continuations of the prompt at hand)
+        per = max(1, min(len(free_slots), len(free_rows) // 2))
+        for lo in range(0, len(todo), per):
+            pack = todo[lo:lo + per]
+            for g in prefill_groups([len(items[i].input_ids) for i in pack], chat.enc.max_tokens, chat.enc.max_seqs):
+                chat.prefill_batch([free_slots[j] for j in g], [free_rows[j] for j in g], [items[pack[j]] for j in g])
+            for j, i in enumerate(pack):
+                out[i] = _score_on_slot(chat, free_slots[j], free_rows[j], conts[i], repetition_penalty, length_penalty)
+    return out
+
+
+def resident_after_generation(chat, items: Sequence, num_beams: int) -> Dict[int, Tuple[int, None]]:
+    """Which items does `generate_items(chat, items, num_beams=...)` leave resident for `score_items_shared(prefilled=...)`?
+    It cuts the items into chunks of max_rows // num_beams (at most max_slots) and puts item i of a chunk in slot i, so only
+    a generation of ONE chunk leaves item i in slot i; of those, the slots that hold exactly the item's prompt (`slot_holds`:
+    ids and slices, not prefilled since) with readable prompt logits.  -> {item index: (slot, None)}."""
+    n = len(items)
+    if n > max(1, min(chat.max_rows // max(1, int(num_beams)), chat.max_slots)):
+        return {}
+    return {i: (i, None) for i in range(n)
+            if chat.slot_holds(i, items[i]) and chat.slot_state(i) == (len(items[i].input_ids), True)}
+
+
+class ChatSession:
+    """Several turns about one page over ONE cached prompt: slot 0 and rows [0, num_beams) of `chat`.  `make_item(msgs)`
+    builds the PreparedItem of the whole history as chat(assistant_turn=True) does.  The session keeps the ids it has fed
+    (prompt, then the row's tail).  `ask`: if the fed ids are a prefix of the new ids it appends the remainder (`extend`,
+    seen="clear": HF penalises only ids generated in the current generate); if the two part inside the tail it truncates
+    the tail to the common prefix and appends; if they part inside the prompt, the slices differ or the tail would not fit,
+    it prefills afresh.  Then it decodes with the rules of `generate_items`.  The contract is on id lists — a turn equals a
+    fresh prefill of the same ids to bf16 accuracy; whether a tokenizer splits concatenated text alike only decides which
+    path is taken.  `counts` / `last_path` ("prefill", "extend", "truncate") say which.  Slot 0 and rows [0, num_beams) of
+    the handle belong to the session: before it extends, it checks that row 0 still continues slot 0 with the tail it fed and
+    that slot 0 has not been prefilled since its own prefill (`slot_generation`: the library counts the prefills of a slot,
+    whoever called them); otherwise, or when the remainder exceeds the encoder's max_tokens, it prefills afresh."""
+
+    def __init__(self, chat, make_item, eos: int = EOS_ID, max_new_tokens: int = 20, num_beams: int = 1, do_sample: bool = False,
+                 repetition_penalty: float = 1.0, temperature: float = 1.0, top_k: int = 50, seed: int = 0,
+                 nucleus: Optional[NucleusSampling] = None):
+        nb = int(num_beams)
+        if nb < 1 or nb > chat.max_rows:
+            raise ValueError(f"num_beams={num_beams} outside 1..max_rows={chat.max_rows}")
+        if do_sample and nb > 1:
+            raise NotImplementedError("beam sampling (do_sample=True with num_beams > 1) is not supported")
+        if max_new_tokens < 1 or max_new_tokens > chat.max_new:
+            raise ValueError(f"max_new_tokens={max_new_tokens} outside 1..max_new={chat.max_new}")
+        self.chat, self.make_item, self.eos = chat, make_item, int(eos)
+        self.max_new_tokens, self.nb, self.do_sample = int(max_new_tokens), nb, bool(do_sample)
+        self.pen, self.temp, self.top_k, self.seed, self.nucleus = repetition_penalty, temperature, top_k, seed, nucleus
+        self.fed: List[int] = []          # ids the cache of row 0 holds: the prompt, then the tail
+        self.plen = 0
+        self.slices: List[np.ndarray] = []
+        self.counts = {"prefill": 0, "extend": 0, "truncate": 0}
+        self.last_path: Optional[str] = None
+        self._stamp = None                # slot 0's generation after the session's own prefill
+
+    def _intact(self) -> bool:
+        """row 0 still continues slot 0 with the tail the session fed, and nobody has prefilled slot 0 since"""
+        return self._stamp == self.chat.slot_generation(0) and self.chat.row_state(0) == (0, len(self.fed) - self.plen)
+
+    def _same_slices(self, slices) -> bool:
+        return len(slices) == len(self.slices) and all(a.shape == b.shape and np.array_equal(a, b) for a, b in zip(slices, self.slices))
+
+    def feed(self, item) -> str:
+        """Bring row 0 to `item.input_ids` with its logits current -> the path taken."""
+        ids = [int(t) for t in item.input_ids]
+        slices = [np.asarray(s) for s in item.slices]
+        common = 0
+        while common < min(len(ids), len(self.fed)) and ids[common] == self.fed[common]:
+            common += 1
+        common = min(common, len(ids) - 1)               # at least one token is appended: the logits are those after it
+        fits = (len(ids) - self.plen + self.max_new_tokens <= self.chat.max_new and len(ids) + self.max_new_tokens <= self.chat.max_len and
+                len(ids) - common <= self.chat.enc.max_tokens)
+        if not self.fed or common < self.plen or not self._same_slices(slices) or not fits or not self._intact():
+            self.chat.prefill(0, 0, item)
+            self._stamp = self.chat.slot_generation(0)
+            self.fed, self.plen, self.slices, path = ids, len(ids), slices, "prefill"
+        else:
+            path = "extend"
+            if common < len(self.fed):
+                self.chat.truncate(0, common - self.plen)
+                path = "truncate"
+            self.chat.extend([0], [0], [ids[common:]], seen="clear")
+            self.fed = ids
+        self.counts[path] += 1
+        self.last_path = path
+        return path
+
+    def ask_ids(self, msgs) -> List[int]:
+        """One turn -> the output ids (as generate_items returns them)."""
+        self.feed(self.make_item(msgs))
+        base = len(self.fed) - self.plen                 # the tail before this turn's generation
+        res = _generate_chunk(self.chat, [None], self.max_new_tokens, self.nb, self.do_sample, self.pen, self.temp, self.top_k,
+                              self.seed, self.eos, prefill="resident", nucleus=self.nucleus)[0]
+        tokens = [int(t) for t in res["tokens"]]
+        if self.nb == 1:                                 # row 0 holds the tokens it was stepped with: they count as fed
+            kept = self.chat.row_state(0)[1] - base
+            self.fed = self.fed + tokens[:kept]
+        else:                                            # which beam ended on row 0 is the rule's business: keep the fed ids only
+            self.chat.truncate(0, base)
+        return tokens
 
 
 def marginal_weights(S, doc_scores):

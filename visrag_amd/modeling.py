@@ -390,17 +390,34 @@ class VisRAGRet:
         return self._chat
 
     def score_answers(self, image_list, msgs_list, answers_list, tokenizer, max_inp_length: int = 2048, append_eos: bool = True,
-                      repetition_penalty: float = 1.0, length_penalty: float = 1.0):
+                      repetition_penalty: float = 1.0, length_penalty: float = 1.0, shared_prefill: bool = False):
         """How likely is each given answer after (page, question)?  Prompts are built as chat(assistant_turn=True) builds
         them; every answer of answers_list[i] is tokenised without BOS (append_eos: followed by the eos the generator would
         close it with) and scored on item i in a packed teacher-forced pass.  Returns per item the list of
         `generation.score_items` dicts of its answers (token_logprobs, sum, score, greedy_match, top_tokens).  The
-        penalties are those of `generation.sequence_score`; sampling warpers have no part in it."""
-        from .generation import score_items
+        penalties are those of `generation.sequence_score`; sampling warpers have no part in it.
+        shared_prefill=True prefills every item ONCE and appends its answers to that cached prompt
+        (`generation.score_items_shared`: the tower and the prompt's decoder rows run once per item instead of once per
+        answer); the result agrees with the default route to bf16 accuracy.  It uses the chat handle's slots and rows: a
+        generation in progress on the same handle does not survive it."""
+        from .generation import score_items, score_items_shared
         chat = self._scoring_chat("score_answers")
         image_list, msgs_list, answers_list = list(image_list), list(msgs_list), [list(a) for a in answers_list]
         if not (len(image_list) == len(msgs_list) == len(answers_list)):
             raise ValueError(f"{len(image_list)} images, {len(msgs_list)} message lists and {len(answers_list)} answer lists")
+        if shared_prefill:
+            uniq, cont_lists, owner = [], [], []
+            for i, (msgs, image, answers) in enumerate(zip(msgs_list, image_list, answers_list)):
+                if not answers:
+                    continue
+                p, imgs = chat_prompt(msgs, image, tokenizer, self.config)
+                uniq.append(_prompt_item(p + "<AI>", imgs, tokenizer, max_inp_length))
+                cont_lists.append([answer_ids(a, tokenizer, append_eos) for a in answers]); owner.append(i)
+            out = [[] for _ in answers_list]
+            if uniq:
+                for i, rs in zip(owner, score_items_shared(chat, uniq, cont_lists, repetition_penalty, length_penalty)):
+                    out[i] = rs
+            return out
         items, conts, owner = [], [], []
         for i, (msgs, image, answers) in enumerate(zip(msgs_list, image_list, answers_list)):
             p, imgs = chat_prompt(msgs, image, tokenizer, self.config)
@@ -416,7 +433,8 @@ class VisRAGRet:
     def choose(self, image, msgs, options, tokenizer, normalise: bool = True, **kwargs):
         """Multiple choice: score every option as an answer to (image, msgs) and take the best -> (index, scores).  The
         argmax is over `score` (the length-normalised sum) when normalise is true, over `sum` otherwise; the first option wins
-        among equals.  kwargs: score_answers' (max_inp_length, append_eos, repetition_penalty, length_penalty)."""
+        among equals.  kwargs: score_answers' (max_inp_length, append_eos, repetition_penalty, length_penalty,
+        shared_prefill)."""
         options = list(options)
         if not options:
             raise ValueError("choose needs at least one option")
@@ -424,15 +442,20 @@ class VisRAGRet:
         keys = [float(s["score" if normalise else "sum"]) for s in scores]
         return keys.index(max(keys)), scores
 
-    def marginal_selection(self, image_list, msgs, doc_scores, tokenizer, normalise: bool = True, details: bool = False, **kwargs):
+    def marginal_selection(self, image_list, msgs, doc_scores, tokenizer, normalise: bool = True, details: bool = False,
+                           shared_prefill: bool = False, **kwargs):
         """Weighted selection in its RAG-Sequence form: weighted_selection's generation as it is, then every candidate answer
         (the distinct output id lists of the pages' best hypotheses, in first-seen order) is scored on EVERY page —
         S[a][i] = score_items of candidate a on page i under the beam's repetition_penalty (`score` when normalise is true,
         `sum` otherwise) — and weight[a] = sum_i softmax(doc_scores)_i * exp(S[a][i]) in fp64.  The answer is the first
         largest weight: two pages that agree reinforce each other where weighted selection lets them compete.
         details=True -> (answer, {"S", "weights", "candidates", "index", "doc_probs", "answers": per candidate,
-        "weighted_selection": (answer, details) of the plain selection}).  kwargs: weighted_selection's."""
-        from .generation import chat_generation_config, decode_text, marginal_weights, score_items
+        "weighted_selection": (answer, details) of the plain selection}).  kwargs: weighted_selection's.
+        shared_prefill=True scores the candidates on the cached prompts (`generation.score_items_shared`): the slots the
+        generation left behind are REUSED when they still hold the pages' prompts with readable prompt logits (all pages fit
+        one chunk of the generator's cache: no prefill at all), and are prefilled once per page otherwise."""
+        from .generation import (chat_generation_config, decode_text, marginal_weights, resident_after_generation, score_items,
+                                 score_items_shared)
         chat = self._scoring_chat("marginal_selection")
         image_list = list(image_list)
         ws_answer, ws = self.weighted_selection(image_list, msgs, doc_scores, tokenizer, details=True, **kwargs)
@@ -446,15 +469,70 @@ class VisRAGRet:
             items.append(_prompt_item(p + "<AI>", imgs, tokenizer, kwargs.get("max_inp_length", 2048)))
         pen = chat_generation_config(False, kwargs)["repetition_penalty"]
         n = len(items)
-        res = score_items(chat, [it for _ in candidates for it in items], [c for c in candidates for _ in items], pen, 1.0)
         key = "score" if normalise else "sum"
-        S = [[float(res[a * n + i][key]) for i in range(n)] for a in range(len(candidates))]
+        if shared_prefill:
+            # the pages the generation (one chunk, with the num_beams it actually ran) left in their slots, checked by content
+            resident = resident_after_generation(chat, items, chat_generation_config(False, kwargs)["num_beams"])
+            per_page = score_items_shared(chat, items, [candidates] * n, pen, 1.0, prefilled=resident)
+            S = [[float(per_page[i][a][key]) for i in range(n)] for a in range(len(candidates))]
+        else:
+            res = score_items(chat, [it for _ in candidates for it in items], [c for c in candidates for _ in items], pen, 1.0)
+            S = [[float(res[a * n + i][key]) for i in range(n)] for a in range(len(candidates))]
         index, weights, p = marginal_weights(S, [float(x) for x in doc_scores])
         answers = decode_text(candidates, tokenizer)
         if not details:
             return answers[index]
         return answers[index], {"S": S, "weights": weights, "candidates": candidates, "index": index, "doc_probs": p,
                                 "answers": answers, "weighted_selection": (ws_answer, ws)}
+
+    def chat_session(self, image, tokenizer, **kwargs) -> "PageChatSession":
+        """Several questions about ONE page over one cached prompt (generation.ChatSession on slot 0, rows [0, num_beams) of
+        the generator's cache): session.ask(msgs) answers the whole ChatML history `msgs` as chat(assistant_turn=True)
+        would, feeding only the ids the cache does not hold yet.  kwargs: chat()'s (max_new_tokens, sampling,
+        max_inp_length, seed, answer_defaults and the generation options of the mode); max_new_tokens defaults to chat()'s
+        1024 or the generator's max_new, whichever is smaller.  Slot 0 and rows [0, num_beams) of the generator's cache
+        belong to the session; another call that prefills the generator in between is noticed and costs the session a fresh
+        prefill, never a wrong answer."""
+        return _chat_session(self, image, tokenizer, **kwargs)
+
+
+class PageChatSession:
+    """VisRAGRet.chat_session's handle: `ask(msgs)` -> the answer to the whole ChatML history `msgs` about the session's
+    page; `session` is the generation.ChatSession underneath (counts, last_path, fed).  ask(msgs, image=other) moves the
+    session to another page: its slices differ, so the prompt is prefilled afresh."""
+
+    def __init__(self, session, tokenizer, page):
+        self.session, self.tokenizer, self._page = session, tokenizer, page
+
+    def ask(self, msgs, image=None) -> str:
+        from .generation import decode_text
+        if image is not None:
+            self._page["image"] = image
+        return decode_text([self.session.ask_ids(msgs)], self.tokenizer)[0]
+
+
+def _chat_session(model: "VisRAGRet", image, tokenizer, max_new_tokens: Optional[int] = None, sampling: bool = True,
+                  max_inp_length: int = 2048, seed: int = 0, answer_defaults: bool = False, **kwargs) -> PageChatSession:
+    from .generation import ChatSession, NucleusSampling, answer_chat_generation_config, chat_generation_config
+    if getattr(model, "_chat", None) is None:
+        raise RuntimeError("chat_session() needs an LM head: call attach_generator() first (or load_generator())")
+    if max_new_tokens is None:            # chat()'s 1024, or what the attached generator's rows hold
+        max_new_tokens = min(1024, model._chat.max_new)
+    if answer_defaults:
+        gen = answer_chat_generation_config(sampling, kwargs)
+        if sampling:
+            gen["nucleus"] = NucleusSampling(gen.pop("top_p"), gen.pop("top_k"))
+    else:
+        gen = chat_generation_config(sampling, kwargs)
+
+    page = {"image": image}
+
+    def make_item(msgs):
+        p, imgs = chat_prompt(msgs, page["image"], tokenizer, model.config)
+        return _prompt_item(p + "<AI>", imgs, tokenizer, max_inp_length)
+
+    return PageChatSession(ChatSession(model._chat, make_item, eos=tokenizer.eos_id, max_new_tokens=max_new_tokens, seed=seed, **gen),
+                           tokenizer, page)
 
 
 def select_weighted(seq_scores, doc_scores):
